@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the brickmap path-trace hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline, the configuration and what the HIP events of
+the timed launches say.  `--full` adds everything that takes work of its own after the timed region: the algorithmic-byte roofline
+(an instrumented re-run of the timed steps) with the committed counter figures, the untimed extra shapes of the N = 1 line (one
+launch per frame, the 4-spp north-star shape, the multi-GPU job and its shard predictions; `--no-extras` leaves them out again) and
+the CPU baseline (`--no-cpu-baseline` leaves it out again).  `--dump-outputs DIR` writes what the timed steps left in the
+accumulation buffer (what a caller of the path receives: RGB sums and terminated-path counts) as DIR/accum.npy.
 
 A "step" is one FRAME of the path-trace kernel over this rank's shard of the workload: `spp` complete paths (primary + up to
 max_bounces bounces, one shadow ray per hit) for every pixel of the shard, with its own constants (sample_base) and its own
@@ -31,8 +38,9 @@ scaling efficiency must not be computed against it: every N > 1 line carries `sa
 last step -- the buffers are additive), `--scaling weak` makes the job grow with N (N spp in total).
 
 metric: Mrays/s = width * height * spp_total * segments / seconds  (nominal rays).
-The line also carries `roofline` (algorithmic bytes of the timed launches / their HIP-event duration against the 8 TB/s HBM
-peak) and, on rank 0 at N = 1, `cpu_baseline` (the oracle's scalar C port of the same path timed on the host cores).
+The line also carries `roofline` (the kernel, its launches and their HIP-event durations; with --full the algorithmic bytes of the
+timed launches / that duration against the 8 TB/s HBM peak) and, with --full on rank 0 at N = 1, `cpu_baseline` (the oracle's
+scalar C port of the same path timed on the host cores).
 """
 import argparse
 import json
@@ -58,6 +66,7 @@ LIMITER = {
 PROFILE_ROUNDS = ("r06", "r05", "r04", "r03")  # profiles/<round>_pmc_summary_<workload>.json is where roofline.traffic comes from (newest first)
 TUNING_VARIABLES = ("BM_REFILL_MIN", "BM_XCD_HANDOUT", "BM_HELPERS", "BM_TRACE_BLOCKS_PER_CU")  # what bm_tuning_overrides reports: the library's A/B knobs
 MULTI_FRAMES_PER_LAUNCH = 5  # N > 1: steps per launch and per exchange (the last batch's gather is not hidden by a next batch: keep it short)
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together
 
 
 def workload(name):
@@ -89,13 +98,34 @@ def batches(first, count, per_launch):
     return out
 
 
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array of {name: array} as <directory>/<name>.npy in float32, DUMP_LIMIT_BYTES in all.  An array over
+    its share is cut to a sample of its pixels (the array as [pixels, channels]): a fixed number of rows drawn by a generator with
+    a fixed seed, in order, so that two runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 4096  # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = share // (rows.itemsize * rows.shape[1])
+            a = rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="config2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the algorithmic-byte roofline, the untimed extra shapes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the accumulation buffer the timed steps left (rank 0: the gathered / reduced frame) as DIR/accum.npy, float32; "
+                         "an output larger than %d bytes is cut to a fixed, seeded sample of its pixels" % DUMP_LIMIT_BYTES)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--decomposition", choices=["rows", "samples"], default="rows",
                     help="N > 1: rows = interleaved row bands + RCCL gather (north-star); samples = full frame per rank, one sum-reduction at the end")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
@@ -112,8 +142,7 @@ def main():
     ap.add_argument("--verify", action="store_true",
                     help="N > 1: after the timed region rank 0 renders every step unsharded and compares it with the gathered / reduced frame")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extra measurements of the N = 1 line (one launch per frame, the 4-spp north-star shape, the shard predictions): "
-                         "used when the run is profiled, so that rocprofv3's per-kernel averages cover the timed launches")
+                    help="--full: skip the untimed extra measurements of the N = 1 line (one launch per frame, the 4-spp north-star shape, the shard predictions)")
     ap.add_argument("--streaming-mode", choices=["overlapped", "blocking"], default="overlapped",
                     help="streaming workloads: overlapped = two request rings, the host never waits for the GPU; blocking = the reference's order")
     ap.add_argument("--schedule", choices=["fused", "wavefront"], default="fused",
@@ -319,8 +348,10 @@ def main():
     t_start = time.perf_counter()
     for first, count in timed:
         issue(first, count)
+    last_batch = None
     if gatherer is not None:
-        keep(gatherer.finish())  # the last batch's gather is inside the timed region
+        last_batch = gatherer.finish()  # the last batch's gather is inside the timed region
+        keep(last_batch)
     if reducer is not None:
         reducer.start(accum)
         reduced = reducer.finish()
@@ -352,6 +383,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        # what a caller holds after the last timed step: the accumulation buffer (rows: the slots of the last gathered batch together
+        # hold every step; samples: the reduced frame)
+        if by_rows:
+            frame = last_batch.sum(dim=0) if last_batch.dim() == 4 else last_batch
+        else:
+            frame = reduced if reducer is not None else accum
+        dump_outputs(args.dump_outputs, {"accum": frame.float().cpu().numpy()})
+
     # ---- --verify: the frames rank 0 holds now must be the frames of one GPU rendering every sample of every step
     verified = None
     if args.verify and multi and rank == 0:
@@ -380,26 +420,26 @@ def main():
         elif not err < 1e-5:  # bit-identical paths; only the order of the float additions differs
             raise SystemExit(f"--verify: the {world}-rank frame differs from the single-GPU frame (relative error {err:g})")
 
-    # ---- algorithmic bytes of exactly the timed steps, from the instrumented kernel variant (not timed; same launches, same scheduling)
-    scene.counters_reset()
-    scratch = torch.zeros_like(accum)
-    for first, count in timed:
-        ps = [params(first + i, flags=bm.BM_FLAG_COUNTERS) for i in range(count)]
-        if count == 1:
-            scene.render(cam, ps[0], scratch)
-        else:
-            scene.render_frames(cam, ps, scratch)
-    cnt = scene.counters()
-    local_rows = state.local_rows
-    alg_bytes = 4 * cnt["index_loads"] + 64 * cnt["brick_tests"] + 16 * W * local_rows * args.steps
-    kernel_s = float(np.sum(launch_ms)) * 1e-3  # all timed launches
-    achieved_gbs = alg_bytes / kernel_s / 1e9
-    actual_rays = cnt["extend_rays"] + cnt["shadow_rays"]
-    bytes_per_step = alg_bytes / args.steps
-
     nominal_rays_per_step = W * H * spp_total * segments
     value = nominal_rays_per_step * args.steps / elapsed / 1e6
-    extras = not args.no_extras
+    kernel_s = float(np.sum(launch_ms)) * 1e-3  # all timed launches
+    extras = args.full and not args.no_extras
+
+    if args.full:
+        # ---- algorithmic bytes of exactly the timed steps, from the instrumented kernel variant (not timed; same launches, same scheduling)
+        scene.counters_reset()
+        scratch = torch.zeros_like(accum)
+        for first, count in timed:
+            ps = [params(first + i, flags=bm.BM_FLAG_COUNTERS) for i in range(count)]
+            if count == 1:
+                scene.render(cam, ps[0], scratch)
+            else:
+                scene.render_frames(cam, ps, scratch)
+        cnt = scene.counters()
+        alg_bytes = 4 * cnt["index_loads"] + 64 * cnt["brick_tests"] + 16 * W * state.local_rows * args.steps
+        achieved_gbs = alg_bytes / kernel_s / 1e9
+        actual_rays = cnt["extend_rays"] + cnt["shadow_rays"]
+        bytes_per_step = alg_bytes / args.steps
 
     def measure(render_one, frames, reps=2):
         """wall seconds per frame of `frames` frames issued by render_one(i), best of `reps` (after one untimed pass)"""
@@ -567,10 +607,23 @@ def main():
             "camera": {"position": list(cam.position), "angles": [0.8, -0.5]},
             "world_build_s": round(build_s, 2),
         },
-        "rays": {"nominal_per_step": nominal_rays_per_step, "actual_per_step_rank0": actual_rays / args.steps,
-                 "actual_Mrays_s_rank0_kernel": round(actual_rays / kernel_s / 1e6, 2)},
+        "rays": {"nominal_per_step": nominal_rays_per_step},
         "roofline": {
             "bound": "hbm",
+            "kernel": kernel_name,
+            "waves_per_simd": waves,
+            "launches": len(timed), "frames_per_launch": [c for _, c in timed],
+            "kernel_ms_avg": round(float(np.mean(launch_ms)), 4),   # average duration of one timed LAUNCH of `kernel` (what rocprofv3 --stats reports for it)
+            "kernel_ms_per_step": round(kernel_ms_per_step, 4),
+            # every launch of `kernel` this process made up to the end of the timed region (spin-up, warm-up, timed), so that the
+            # per-kernel average of `rocprofv3 --stats` over a --no-extras run can be re-derived: it averages launches of different frame
+            # counts; sum(frames) x algorithmic_bytes_per_step / sum(ms) is the rate over all of them, the last `launches` entries are the timed ones
+            "launch_log": ({"frames": launch_frames_log, "ms": [round(float(t), 4) for t in launch_ms_log]} if launch_ms_log is not None else None),
+        },
+    }
+    if args.full:
+        out["rays"].update(actual_per_step_rank0=actual_rays / args.steps, actual_Mrays_s_rank0_kernel=round(actual_rays / kernel_s / 1e6, 2))
+        out["roofline"].update({
             # what `achieved` is: SURVEY.md 8(d)'s ALGORITHMIC bytes -- the traffic of the REFERENCE's walk over the same rays
             # (4 B per cell it would load + 64 B per brick test + 16 B per pixel) -- of the timed launches, divided by their
             # duration (HIP events on the launch stream).  The kernel itself reads far less (one cube-field byte per STOP of the walk,
@@ -582,21 +635,11 @@ def main():
             "unit": "GB/s",
             "frac": round(achieved_gbs / HBM_PEAK_GBS, 5),
             **counter_figures(args.workload, kernel_ms_per_step * 1e-3, args.steps / len(timed)),
-            "kernel": kernel_name,
-            "waves_per_simd": waves,
-            "launches": len(timed), "frames_per_launch": [c for _, c in timed],
-            "kernel_ms_avg": round(float(np.mean(launch_ms)), 4),   # average duration of one timed LAUNCH of `kernel` (what rocprofv3 --stats reports for it)
-            "kernel_ms_per_step": round(kernel_ms_per_step, 4),
-            # every launch of `kernel` this process made up to the end of the timed region (spin-up, warm-up, timed), so that the
-            # per-kernel average of `rocprofv3 --stats` over a --no-extras run can be re-derived: it averages launches of different frame
-            # counts; sum(frames) x algorithmic_bytes_per_step / sum(ms) is the rate over all of them, the last `launches` entries are the timed ones
-            "launch_log": ({"frames": launch_frames_log, "ms": [round(float(t), 4) for t in launch_ms_log]} if launch_ms_log is not None else None),
             "algorithmic_bytes_per_launch": alg_bytes / len(timed),
             "algorithmic_bytes_per_step": bytes_per_step,
             "bytes_per_actual_ray": round(alg_bytes / max(actual_rays, 1), 1),
             "counts_per_step": {k: v / args.steps for k, v in cnt.items()},
-        },
-    }
+        })
     if single is not None:
         out["one_frame_per_launch"] = single
     if target4 is not None:
@@ -609,7 +652,7 @@ def main():
         out["same_job_single_gpu" if multi else "multi_gpu_job_on_one_gpu"] = same_job
     if shard_pred is not None:
         out["multi_gpu_prediction"] = shard_pred
-    if not multi and not args.no_cpu_baseline:
+    if args.full and not multi and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(W, H, max_bounces, G, cam)
     print(json.dumps(out), flush=True)
     if multi:
@@ -664,22 +707,8 @@ def bench_wavefront(args, bm, torch, np, scene, cam, accum, W, H, max_bounces, n
     elapsed = time.perf_counter() - t_start
     retired = float(accum[..., 3].sum(dtype=torch.float64).item()) - retired0
     value = retired * segments / elapsed / 1e6
-    # ---- per-kernel durations and algorithmic bytes of the same steady state (separate, untimed frames)
-    pc = bm.FrameParams(W, H, max_bounces=max_bounces, flags=bm.BM_FLAG_COUNTERS)
-    wf.counters_reset()
-    for _ in range(args.steps):
-        wf.frame(cam, pc, accum)
-    ce, cc = wf.counters("extend"), wf.counters("connect")
-    times = []
-    for _ in range(args.steps):
-        wf.frame(cam, p, accum)
-        times.append(wf.times())
-    ms = {k: float(np.mean([t[k] for t in times])) for k in times[0]}
-    # extend kernel: index words + bricks + its queue traffic: 48 B read (origin, direction, normal) and
-    # 16 B written (normal, distance) per slot
-    ext_bytes = (4 * ce["index_loads"] + 64 * ce["brick_tests"]) / args.steps + Q * (48 + 16)
-    achieved = ext_bytes / (ms["extend"] * 1e-3) / 1e9
-    actual = (ce["extend_rays"] + cc["shadow_rays"]) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accum": accum.float().cpu().numpy()})
     out = {
         "metric": "Mrays/sec (primary x spp x bounces) at 1080p 4-bounce",
         "value": round(value, 3), "unit": "Mrays/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -693,16 +722,33 @@ def bench_wavefront(args, bm, torch, np, scene, cam, accum, W, H, max_bounces, n
             "schedule": "wavefront", "width": W, "height": H, "queue_size": Q, "segments": segments, "world_voxels": G,
             "sharding": "single GPU (the queue schedule does not shard: replicas only)", "world_build_s": round(build_s, 2),
         },
-        "rays": {"nominal_per_step": retired * segments / args.steps, "paths_retired_per_step": retired / args.steps,
-                 "actual_per_step": actual, "actual_Mrays_s_frame": round(actual / (ms["total"] * 1e-3) / 1e6, 2)},
-        "frame_ms": {k: round(v, 4) for k, v in ms.items()},
-        "roofline": {
+        "rays": {"nominal_per_step": retired * segments / args.steps, "paths_retired_per_step": retired / args.steps},
+    }
+    if args.full:
+        # ---- per-kernel durations and algorithmic bytes of the same steady state (separate, untimed frames)
+        pc = bm.FrameParams(W, H, max_bounces=max_bounces, flags=bm.BM_FLAG_COUNTERS)
+        wf.counters_reset()
+        for _ in range(args.steps):
+            wf.frame(cam, pc, accum)
+        ce, cc = wf.counters("extend"), wf.counters("connect")
+        times = []
+        for _ in range(args.steps):
+            wf.frame(cam, p, accum)
+            times.append(wf.times())
+        ms = {k: float(np.mean([t[k] for t in times])) for k in times[0]}
+        # extend kernel: index words + bricks + its queue traffic: 48 B read (origin, direction, normal) and
+        # 16 B written (normal, distance) per slot
+        ext_bytes = (4 * ce["index_loads"] + 64 * ce["brick_tests"]) / args.steps + Q * (48 + 16)
+        achieved = ext_bytes / (ms["extend"] * 1e-3) / 1e9
+        actual = (ce["extend_rays"] + cc["shadow_rays"]) / args.steps
+        out["rays"].update(actual_per_step=actual, actual_Mrays_s_frame=round(actual / (ms["total"] * 1e-3) / 1e6, 2))
+        out["frame_ms"] = {k: round(v, 4) for k, v in ms.items()}
+        out["roofline"] = {
             "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
             "traffic": None, "kernel": "bm::wf_trace<false, false> (extend)", "kernel_ms_avg": round(ms["extend"], 4),
             "algorithmic_bytes_per_launch": ext_bytes,
             "counts_per_launch": {k: v / args.steps for k, v in ce.items()},
-        },
-    }
+        }
     print(json.dumps(out), flush=True)
 
 

@@ -100,7 +100,7 @@ def test_bench_multi_gpu_code_path_on_nccl_with_one_rank(extra):
     WORLD_SIZE = 1."""
     env = dict(os.environ, BM_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()),
                HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--workload", "config1", "--verify"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--workload", "config1", "--verify", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -184,7 +184,7 @@ def test_default_bench_line_schema():
     env = dict(os.environ, OMP_NUM_THREADS="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "BM_BENCH_FORCE_DIST"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -216,6 +216,29 @@ def test_default_bench_line_schema():
     assert set(pred["shard_ms_per_step"]) == {"2", "4", "8"} and all(v > 0 for v in pred["shard_ms_per_step"].values())
     assert [len(pred["per_rank_ms_per_step"][k]) for k in ("2", "4", "8")] == [2, 4, 8]
     assert 1.0 < pred["predicted_speedup"]["2"] < pred["predicted_speedup"]["4"] < pred["predicted_speedup"]["8"] <= 8.5
+
+
+def test_plain_bench_run_times_and_dumps_only(tmp_path):
+    """A run without --full sets up, warms up, times its steps and prints the line: no instrumented re-run, no extra shapes, no CPU
+    baseline.  --dump-outputs writes what the timed steps left in the accumulation buffer: every path of every frame (warm-up and
+    timed) ended exactly once in every pixel."""
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "BM_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--workload", "config1", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1
+    out = json.loads(line[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["roofline"]["frames_per_launch"] == [3]
+    assert not {"cpu_baseline", "one_frame_per_launch", "north_star_4spp", "multi_gpu_job_on_one_gpu", "multi_gpu_prediction"} & set(out)
+    assert "achieved" not in out["roofline"] and "counts_per_step" not in out["roofline"]
+    assert os.listdir(tmp_path / "out") == ["accum.npy"]
+    acc = np.load(tmp_path / "out" / "accum.npy")
+    assert acc.dtype == np.float32 and acc.shape == (256, 256, 4) and np.isfinite(acc).all()
+    assert np.all(acc[..., 3] == 5) and acc[..., :3].max() > 0  # 1 spp x (2 warm-up + 3 timed) frames
 
 
 def test_bench_refuses_tuning_overrides_when_strict():

@@ -165,6 +165,28 @@ def test_bench_helpers_run_without_a_gpu():
     assert b.batches(3, 20, 20) == [(3, 20)] and b.batches(0, 7, 5) == [(0, 4), (4, 3)] and b.batches(0, 0, 5) == [] and b.batches(0, 300, 256) == [(0, 150), (150, 150)]
 
 
+def test_bench_dump_outputs_stays_within_its_limit(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, all of them within the size limit; an output over its share becomes a sample
+    of its pixels that is the same on every call (two builds are compared element for element)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    b.DUMP_LIMIT_BYTES = 20000
+    small = np.arange(12, dtype=np.float64).reshape(3, 1, 4)
+    big = np.random.default_rng(1).random((64, 64, 4))
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 20000
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.astype(np.float32))
+    got, again = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    pixels = big.astype(np.float32).reshape(-1, 4)
+    assert got.dtype == np.float32 and got.shape[1] == 4 and 100 < len(got) < len(pixels) and np.array_equal(got, again)
+    assert all((pixels == p).all(axis=1).any() for p in got)
+
+
 def test_frame_plan_and_ticket_limits():
     """bm_frame_plan_of (host only): what the library decides for a frame.  ADVICE r05: (chunk, sample) items are the library's own choice
     only where their tickets fit the 32-bit hand-out -- a default-flag frame at very high spp falls back to pixel items (which carry no

@@ -45,9 +45,9 @@ def main():
     env = dict(os.environ, TMPDIR="/tmp")
     bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload] + extra
     steps = ["--steps", "5", "--warmup", "2"] if "--steps" not in extra else []
-    # 1. a first bench line: the kernel duration the derived figures of the PMC summary are priced with
+    # 1. a first bench line (--full: with the algorithmic-byte roofline): the kernel duration the derived figures of the PMC summary are priced with
     def bench_line():
-        r = subprocess.run(bench + steps, capture_output=True, text=True, cwd="/tmp", env=env)
+        r = subprocess.run(bench + steps + ["--full"], capture_output=True, text=True, cwd="/tmp", env=env)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if not line:
             print(r.stdout[-2000:], r.stderr[-4000:])
