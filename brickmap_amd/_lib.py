@@ -44,6 +44,17 @@ class bm_frame_plan(C.Structure):
                 ("refill_min", C.c_int32), ("refill_min_in_ring", C.c_int32), ("instrumented", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("local_rows", C.c_int32)]
 
 
+BM_EDIT_SET = 1
+BM_EDIT_CLEAR = 2
+BM_EDIT_BOX = 1
+BM_EDIT_SPHERE = 2
+
+
+class bm_edit(C.Structure):
+    _fields_ = [("op", C.c_int32), ("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3),
+                ("radius", C.c_int32)]
+
+
 class bm_scene_info(C.Structure):
     _fields_ = [("grid_size", C.c_int32), ("grid_height", C.c_int32), ("supergrid_xy", C.c_int32),
                 ("supergrid_z", C.c_int32), ("supercells", C.c_int32), ("queue_capacity", C.c_int32),
@@ -97,8 +108,14 @@ SIGNATURES = {
     "bm_scene_device_indices": (_i, [_vp, _i, _vp]),
     "bm_scene_device_brick": (_i, [_vp, _i, C.c_uint32, _vp]),
     "bm_scene_column_heights": (_i, [_vp, _i, _i, _vp]),
+    "bm_scene_edit": (_i, [_vp, _i, C.POINTER(bm_edit), _vp]),
+    "bm_scene_set_voxels": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "bm_scene_device_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bm_scene_host_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bm_scene_last_edit_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bm_host_column_heights": (_i, [_i, _i, _i, _i, _vp]),
     "bm_host_generate_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32]),
+    "bm_host_edit_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32, _i, C.POINTER(bm_edit)]),
     "bm_host_cube_field": (_i, [_i, _i, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_buffer_alloc": (_i, [_i, C.c_size_t, C.POINTER(_vp)]),
     "bm_buffer_free": (_i, [_i, _vp]),

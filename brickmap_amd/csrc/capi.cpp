@@ -1,4 +1,5 @@
 // capi.cpp -- extern "C" surface of libbrickmap_hip.so (declared in include/brickmap.h).
+#include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -94,6 +95,32 @@ int bm_scene_device_indices(bm_scene* scene, int supercell, uint32_t* indices409
 
 int bm_scene_device_brick(bm_scene* scene, int supercell, uint32_t device_slot, uint32_t* out16) { BM_NEED(scene); return scene->impl.device_brick(supercell, device_slot, out16); }
 
+int bm_scene_edit(bm_scene* scene, int count, const bm_edit* edits, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.edit(count, edits, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_scene_set_voxels(bm_scene* scene, int n, const int32_t* xyz, const uint8_t* values, void* hip_stream) {
+	BM_NEED(scene);
+	if (n < 0 || (n > 0 && (!xyz || !values))) { set_error("bm_scene_set_voxels: bad count or null argument"); return BM_EINVAL; }
+	std::vector<bm_edit> edits;
+	edits.reserve(static_cast<size_t>(n));
+	for (int i = 0; i < n; ++i) {
+		const int32_t* v = xyz + 3 * static_cast<size_t>(i);
+		if (v[0] < 0 || v[1] < 0 || v[2] < 0 || v[0] == INT32_MAX || v[1] == INT32_MAX || v[2] == INT32_MAX) continue; // outside the world: a no-op
+		bm_edit e{};
+		e.op = values[i] ? BM_EDIT_SET : BM_EDIT_CLEAR;
+		e.shape = BM_EDIT_BOX;
+		for (int k = 0; k < 3; ++k) { e.lo[k] = v[k]; e.hi[k] = v[k] + 1; }
+		edits.push_back(e);
+	}
+	return scene->impl.edit(static_cast<int>(edits.size()), edits.data(), static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.device_cube_field(dst, capacity, bytes); }
+int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.host_cube_field(dst, capacity, bytes); }
+int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms) { BM_NEED(scene); return scene->impl.last_edit_ms(scatter_ms, field_ms); }
+
 int bm_scene_column_heights(bm_scene* scene, int sx, int sy, float* heights) {
 	BM_NEED(scene);
 	const bm::WorldDims& d = scene->impl.world.dims;
@@ -128,6 +155,40 @@ int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, i
 		const size_t n = c.bricks.size() < brick_capacity ? c.bricks.size() : brick_capacity;
 		std::memcpy(bricks, c.bricks.data(), n * sizeof(bm::Brick));
 	}
+	return 0;
+}
+
+int bm_host_edit_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096, uint32_t* brick_count,
+						   uint32_t* bricks, uint32_t brick_capacity, int count, const bm_edit* edits) {
+	bm::World w;
+	if (!w.dims.set(grid_size, grid_height) || sx < 0 || sy < 0 || sz < 0 || sx >= w.dims.supergrid_xy || sy >= w.dims.supergrid_xy ||
+		sz >= w.dims.supergrid_z) {
+		set_error("bad world dimensions or supercell");
+		return BM_EINVAL;
+	}
+	if (!indices4096 || !brick_count || (!bricks && *brick_count > 0) || *brick_count > 4096u || *brick_count > brick_capacity) {
+		set_error("bad supercell arrays");
+		return BM_EINVAL;
+	}
+	std::string why;
+	if (!bm::World::validate_edits(edits, count, &why)) { set_error("bm_host_edit_supercell: " + why); return BM_EINVAL; }
+	bm::HostSupercell c;
+	c.indices.assign(indices4096, indices4096 + bm::kCellsPerSupercell);
+	c.bricks.resize(*brick_count);
+	if (*brick_count) std::memcpy(c.bricks.data(), bricks, *brick_count * sizeof(bm::Brick));
+	std::vector<uint8_t> used(*brick_count, 0);
+	for (uint32_t word : c.indices) {
+		if (!word) continue;
+		if (!(word & BM_BRICK_LOADED_BIT) || (word & BM_BRICK_INDEX_BITS) >= *brick_count) { set_error("an index word names no brick"); return BM_EINVAL; }
+		used[word & BM_BRICK_INDEX_BITS] = 1;
+	}
+	for (uint32_t s = *brick_count; s-- > 0;) // slots no word names are free; the lowest is reused first
+		if (!used[s]) c.free_slots.push_back(s);
+	bm::World::edit_supercell(w.dims, c, sx, sy, sz, edits, count, nullptr);
+	if (c.bricks.size() > brick_capacity) { set_error("brick buffer too small for the edited supercell"); return BM_EINVAL; }
+	std::memcpy(indices4096, c.indices.data(), bm::kCellsPerSupercell * sizeof(uint32_t));
+	if (!c.bricks.empty()) std::memcpy(bricks, c.bricks.data(), c.bricks.size() * sizeof(bm::Brick));
+	*brick_count = static_cast<uint32_t>(c.bricks.size());
 	return 0;
 }
 

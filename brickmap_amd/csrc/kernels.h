@@ -20,6 +20,22 @@ void launch_resolve(const float* accum, float* out, long long n, hipStream_t str
 void launch_debug_sincos(int n, const float* x, float* s, float* c, hipStream_t stream);
 void launch_debug_sky(const FrameConstants& fc, int n, const float* v, float* sun, float* sky, float* sunsky, hipStream_t stream);
 
+// voxel edits (edit.hip).  FieldUpdate: the box of the octant cube field an edit batch recomputes, in bordered cell coordinates
+// (1 ... cells, half-open ranges): r* = the cells written (the changed cells' bounding box grown by 254, clipped); ay = the rows the x
+// pass covers for the y pass, bz = the slices the x and y passes cover for the z pass (the r ranges grown by 254, clipped)
+struct FieldUpdate {
+	int rx0, rx1, ry0, ry1, rz0, rz1;
+	int ay0, ay1, bz0, bz1;
+	int cells, cells_height, sg_xy, sg_xy2;
+	int cf_shift;
+	uint32_t cf_pxy, cf_plane;
+};
+size_t field_update_tmp_bytes(const FieldUpdate& u); // intermediate planes of the passes
+// dirty cell i: index word words[i] at index_grid[cells[i]]; brick bricks[16 i ...] at arena slot slots[i] unless that is 0xFFFFFFFF
+void launch_edit_scatter(const uint32_t* cells, const uint32_t* words, const uint32_t* slots, const uint32_t* bricks, uint32_t count,
+						 uint32_t* index_grid, uint32_t* arena, hipStream_t stream);
+void launch_field_update(const uint32_t* index_grid, uint8_t* field, uint8_t* tmp, const FieldUpdate& u, hipStream_t stream);
+
 // wavefront mode (wavefront.hip)
 int wavefront_blocks_per_cu(bool connect, bool instrumented);
 void launch_wf_primary(WfState* st, WfRay* work, const FrameConstants* fc_dev, uint32_t queue_size, uint32_t pixels, hipStream_t stream);

@@ -221,6 +221,13 @@ Scene::~Scene() {
 	if (d_moves_) hipFree(d_moves_);
 	if (d_bricks_queue_) hipFree(d_bricks_queue_);
 	if (d_indices_queue_) hipFree(d_indices_queue_);
+	if (d_positions_) hipFree(d_positions_);
+	if (h_edit_) hipHostFree(h_edit_);
+	if (d_edit_) hipFree(d_edit_);
+	if (d_cf_tmp_) hipFree(d_cf_tmp_);
+	if (ev_edit_) hipEventDestroy(ev_edit_);
+	if (ev_edit_caller_) hipEventDestroy(ev_edit_caller_);
+	for (hipEvent_t e : ev_edit_time_) if (e) hipEventDestroy(e);
 	if (d_counters_) hipFree(d_counters_);
 	if (d_work_counter_) hipFree(d_work_counter_);
 	if (d_frame_constants_) hipFree(d_frame_constants_);
@@ -263,6 +270,9 @@ int Scene::init(int grid_size, int grid_height) {
 	}
 	BM_HIP(hipEventCreateWithFlags(&ev_upload_, hipEventDisableTiming));
 	BM_HIP(hipEventCreateWithFlags(&ev_snapshot_, hipEventDisableTiming));
+	BM_HIP(hipEventCreateWithFlags(&ev_edit_, hipEventDisableTiming));
+	BM_HIP(hipEventCreateWithFlags(&ev_edit_caller_, hipEventDisableTiming));
+	for (int i = 0; i < 3; ++i) BM_HIP(hipEventCreate(&ev_edit_time_[i]));
 	for (int r = 0; r < 2; ++r) {
 		BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_count_[r]), sizeof(uint32_t), hipHostMallocDefault));
 		BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_load_count_[r]), sizeof(uint32_t)));
@@ -289,6 +299,7 @@ int Scene::alloc_queue() {
 	if (h_indices_) { hipHostFree(h_indices_); h_indices_ = nullptr; }
 	if (d_bricks_queue_) { hipFree(d_bricks_queue_); d_bricks_queue_ = nullptr; }
 	if (d_indices_queue_) { hipFree(d_indices_queue_); d_indices_queue_ = nullptr; }
+	if (d_positions_) { hipFree(d_positions_); d_positions_ = nullptr; }
 	const size_t n = static_cast<size_t>(queue_cap_);
 	for (int r = 0; r < 2; ++r) {
 		if (h_positions_[r]) { hipHostFree(h_positions_[r]); h_positions_[r] = nullptr; }
@@ -302,6 +313,7 @@ int Scene::alloc_queue() {
 	BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_indices_), n * sizeof(uint32_t), hipHostMallocDefault));  // Scene.cpp:32
 	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_bricks_queue_), n * sizeof(Brick)));                          // Scene.cpp:189
 	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_indices_queue_), n * sizeof(uint32_t)));                      // Scene.cpp:190
+	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_positions_), n * 3 * sizeof(int)));
 	// a batch of n requests can make at most n pools grow
 	if (h_moves_) { hipHostFree(h_moves_); h_moves_ = nullptr; }
 	if (d_moves_) { hipFree(d_moves_); d_moves_ = nullptr; }
@@ -323,7 +335,7 @@ int Scene::set_streaming_mode(int overlapped) {
 		snapshot_pending_ = false;
 		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[ring_snapshot_]);
 		if (count > 0) {
-			if (int e = service_ring(ring_snapshot_, count)) return e;
+			if (int e = service_ring(ring_snapshot_, count, nullptr)) return e;
 		}
 		BM_HIP(hipDeviceSynchronize());
 	}
@@ -645,6 +657,8 @@ int Scene::reset_residency() {
 		c.resident = 0;
 		c.pool_capacity = 0;
 		c.pool_base = 0;
+		c.dev_slot.assign(c.bricks.size(), kNoDeviceSlot);
+		c.pool_free.clear();
 		if (!c.bricks.empty()) {
 			if (int e = region_alloc(kStartingPool, &c.pool_base)) return e;
 			c.pool_capacity = kStartingPool;
@@ -662,6 +676,7 @@ int Scene::reset_residency() {
 	view_.load_queue = d_load_queue_[0];
 	view_.load_queue_count = d_load_count_[0];
 	resident_bricks_ = 0;
+	preloaded_ = false;
 	staging_busy_ = false;
 	failed_ = false;
 	stream_batches_ = stream_host_ns_ = 0;
@@ -678,7 +693,10 @@ int Scene::preload_all() {
 	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell);
 	std::vector<uint32_t> bases(d.supercells, 0u);
 	// "all bricks pre-loaded" (BASELINE configs 1-2): every pool is its supercell's full host brick vector, exact fit, and
-	// the device words are the host words (slot | loaded | lod, Scene.cpp:104)
+	// the device words are the host words (slot | loaded | lod, Scene.cpp:104).  Host slots that edits freed keep their place in the
+	// pool and are the pool's free slots.
+	total_bricks_ = 0;
+	for (int i = 0; i < d.supercells; ++i) total_bricks_ += world.supercells[i].bricks.size();
 	arena_reset();
 	if (int e = arena_reserve(std::max<uint64_t>(total_bricks_, 1), true)) return e;
 	for (int i = 0; i < d.supercells; ++i) {
@@ -689,6 +707,9 @@ int Scene::preload_all() {
 		bases[i] = c.pool_base;
 		std::memcpy(&words[static_cast<size_t>(i) * kCellsPerSupercell], c.indices.data(), kCellsPerSupercell * sizeof(uint32_t));
 		c.resident = static_cast<uint32_t>(c.bricks.size());
+		c.dev_slot.resize(c.bricks.size());
+		for (size_t s = 0; s < c.bricks.size(); ++s) c.dev_slot[s] = static_cast<uint16_t>(s);
+		c.pool_free = c.free_slots;
 		if (!c.bricks.empty())
 			BM_HIP(hipMemcpy(d_arena_ + static_cast<size_t>(c.pool_base) * kBrickWords, c.bricks.data(), c.bricks.size() * sizeof(Brick), hipMemcpyHostToDevice));
 	}
@@ -701,7 +722,8 @@ int Scene::preload_all() {
 	snapshot_pending_ = false;
 	view_.load_queue = d_load_queue_[0];
 	view_.load_queue_count = d_load_count_[0];
-	resident_bricks_ = total_bricks_;
+	resident_bricks_ = world.total_bricks();
+	preloaded_ = true;
 	staging_busy_ = false;
 	failed_ = false;
 	stream_batches_ = stream_host_ns_ = 0;
@@ -779,10 +801,12 @@ void Scene::drop_frame_streams() {
 // ---------------------------------------------------------------- streaming
 // Stage the first `count` requests of a ring (positions already in its pinned mirror), copy them up and scatter
 // them into the arena / index grid on the load stream (Scene.cpp:215-229 + the upload kernel, kernel.cu:141-151,412-413).
-int Scene::service_ring(int ring, uint32_t count) {
+// An entry is stale when an edit has emptied its brick since it was requested, or when its brick is resident already (a brick an
+// edit changed is asked for again, and may then stand in the ring twice): it is skipped and not counted in *serviced.
+int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 	const auto t_host0 = std::chrono::steady_clock::now();
 	const WorldDims& d = world.dims;
-	const int* pos = h_positions_[ring];
+	int* pos = h_positions_[ring];
 	// ---- pass 1: nothing is mutated before every entry has been checked (the positions come back from device memory:
 	// never index host arrays with an entry that cannot be a request)
 	for (uint32_t i = 0; i < count; ++i) {
@@ -796,8 +820,8 @@ int Scene::service_ring(int ring, uint32_t count) {
 		}
 		const HostSupercell& c = world.supercells[d.supercell_id(px / kSupercell, py / kSupercell, pz / kSupercell)];
 		const uint32_t word = c.indices[static_cast<uint32_t>((px % kSupercell) + (py % kSupercell) * kSupercell + (pz % kSupercell) * kSupercell * kSupercell)];
-		if (!(word & BM_BRICK_LOADED_BIT) || (word & BM_BRICK_INDEX_BITS) >= c.bricks.size()) {
-			set_error("brick request ring names an empty brick");
+		if (word != 0 && (!(word & BM_BRICK_LOADED_BIT) || (word & BM_BRICK_INDEX_BITS) >= c.bricks.size() || (word & BM_BRICK_INDEX_BITS) >= c.dev_slot.size())) {
+			set_error("brick request ring names a brick that does not exist");
 			failed_ = true;
 			return BM_ESTATE;
 		}
@@ -809,7 +833,7 @@ int Scene::service_ring(int ring, uint32_t count) {
 	// ---- pass 2: hand out slots, grow pools.  From here on host state changes entry by entry; the only thing that can
 	// still go wrong is running out of device memory while the arena grows, and that leaves the scene marked as failed
 	// (every later frame / batch is refused until the residency is reset) instead of half-updated and in use.
-	uint32_t n_moves = 0;
+	uint32_t n_moves = 0, kept = 0;
 	std::unordered_map<int, uint32_t> batch_first_resident, batch_move; // per supercell: bricks resident before this batch / its entry in h_moves_
 	for (uint32_t i = 0; i < count; ++i) {
 		const int px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
@@ -817,10 +841,20 @@ int Scene::service_ring(int ring, uint32_t count) {
 		HostSupercell& c = world.supercells[sci];
 		const uint32_t local = static_cast<uint32_t>((px % kSupercell) + (py % kSupercell) * kSupercell + (pz % kSupercell) * kSupercell * kSupercell);
 		const uint32_t word = c.indices[local];
-		std::memcpy(h_bricks_ + static_cast<size_t>(i) * kBrickWords, c.bricks[word & BM_BRICK_INDEX_BITS].data, sizeof(Brick));
+		if (word == 0 || c.dev_slot[word & BM_BRICK_INDEX_BITS] != kNoDeviceSlot) continue; // stale (above)
+		const uint32_t i_out = kept++;
+		if (i_out != i) { pos[3 * i_out] = px; pos[3 * i_out + 1] = py; pos[3 * i_out + 2] = pz; }
+		std::memcpy(h_bricks_ + static_cast<size_t>(i_out) * kBrickWords, c.bricks[word & BM_BRICK_INDEX_BITS].data, sizeof(Brick));
 		// slots are handed out in request order (gpu_index_highest++, Scene.cpp:224); a full pool doubles first
-		// (Scene.cpp:231-251: 2^ceil(log2(highest + 1))) -- here it moves to a larger region of the arena
+		// (Scene.cpp:231-251: 2^ceil(log2(highest + 1))) -- here it moves to a larger region of the arena.  A slot an edit freed is reused first.
 		const uint32_t resident_before_batch = batch_first_resident.emplace(sci, c.resident).first->second;
+		if (!c.pool_free.empty()) {
+			const uint32_t slot = c.pool_free.back();
+			c.pool_free.pop_back();
+			c.dev_slot[word & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(slot);
+			h_indices_[i_out] = slot | BM_BRICK_LOADED_BIT | (word & BM_BRICK_LOD_BITS);
+			continue;
+		}
 		if (c.resident >= c.pool_capacity) {
 			const uint32_t grown = std::max<uint32_t>(kStartingPool, c.pool_capacity * 2u);
 			uint32_t fresh = 0;
@@ -839,26 +873,29 @@ int Scene::service_ring(int ring, uint32_t count) {
 			c.pool_base = fresh;
 			c.pool_capacity = grown;
 		}
-		h_indices_[i] = c.resident | BM_BRICK_LOADED_BIT | (word & BM_BRICK_LOD_BITS);
+		c.dev_slot[word & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(c.resident);
+		h_indices_[i_out] = c.resident | BM_BRICK_LOADED_BIT | (word & BM_BRICK_LOD_BITS);
 		c.resident++;
 	}
+	const bool compacted = kept != count; // stale entries were dropped: the scatter reads the kept positions from d_positions_
 	auto queue = [&]() -> int {
-		BM_HIP(hipMemcpyAsync(d_bricks_queue_, h_bricks_, static_cast<size_t>(count) * sizeof(Brick), hipMemcpyHostToDevice, load_stream_));    // :228
-		BM_HIP(hipMemcpyAsync(d_indices_queue_, h_indices_, static_cast<size_t>(count) * sizeof(uint32_t), hipMemcpyHostToDevice, load_stream_)); // :229
+		BM_HIP(hipMemcpyAsync(d_bricks_queue_, h_bricks_, static_cast<size_t>(kept) * sizeof(Brick), hipMemcpyHostToDevice, load_stream_));    // :228
+		BM_HIP(hipMemcpyAsync(d_indices_queue_, h_indices_, static_cast<size_t>(kept) * sizeof(uint32_t), hipMemcpyHostToDevice, load_stream_)); // :229
+		if (compacted) BM_HIP(hipMemcpyAsync(d_positions_, pos, static_cast<size_t>(kept) * 3 * sizeof(int), hipMemcpyHostToDevice, load_stream_));
 		// The scatter kernel rewrites index words that a frame still in flight may be reading and requesting through
 		// (plain load + atomicOr): a word flipping to "loaded" between the two would be requested a second time; the move
 		// kernel rewrites pool bases such a frame addresses bricks with.  In overlapped mode both therefore run behind every
 		// frame in flight, whatever stream it is on; the copies above already overlap them.
 		if (overlapped_) { if (int e = order_load_stream_behind_frames()) return e; }
 		DeviceScene ring_view = view_;
-		ring_view.load_queue = d_load_queue_[ring];
+		ring_view.load_queue = compacted ? d_positions_ : d_load_queue_[ring];
 		ring_view.load_queue_count = d_load_count_[ring];
 		if (n_moves > 0) { // grown pools: copy their bricks to the new regions and publish the new bases, ahead of the scatter
 			BM_HIP(hipMemcpyAsync(d_moves_, h_moves_, static_cast<size_t>(n_moves) * sizeof(PoolMove), hipMemcpyHostToDevice, load_stream_));
 			launch_pool_moves(d_moves_, n_moves, d_arena_, d_pool_base_, load_stream_);
 			BM_HIP(hipGetLastError());
 		}
-		launch_upload(ring_view, d_bricks_queue_, d_indices_queue_, d_arena_, count, load_stream_); // kernel.cu:412
+		launch_upload(ring_view, d_bricks_queue_, d_indices_queue_, d_arena_, kept, load_stream_); // kernel.cu:412
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipMemsetAsync(d_load_count_[ring], 0, sizeof(uint32_t), load_stream_));             // kernel.cu:413
 		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
@@ -869,7 +906,8 @@ int Scene::service_ring(int ring, uint32_t count) {
 	freed_this_batch_.clear();
 	staging_busy_ = true;
 	upload_seq_++;
-	resident_bricks_ += count;
+	resident_bricks_ += kept;
+	if (serviced) *serviced = kept;
 	stream_batches_++;
 	stream_host_ns_ += static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_host0).count());
 	return 0;
@@ -890,9 +928,7 @@ int Scene::process_load_queue(uint32_t* serviced) {
 		if (count == 0) return 0;
 		BM_HIP(hipMemcpyAsync(h_positions_[0], d_load_queue_[0], static_cast<size_t>(count) * 3 * sizeof(int), hipMemcpyDeviceToHost, load_stream_)); // :209
 		BM_HIP(hipStreamSynchronize(load_stream_));
-		if (int e = service_ring(0, count)) return e;
-		if (serviced) *serviced = count;
-		return 0;
+		return service_ring(0, count, serviced);
 	}
 	// ---- overlapped mode: never wait for the GPU.  (1) service the ring that was copied out by the previous call,
 	// (2) start copying out the ring the last frame wrote, behind that frame, on the load stream, (3) hand the other
@@ -902,8 +938,7 @@ int Scene::process_load_queue(uint32_t* serviced) {
 		snapshot_pending_ = false;
 		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[ring_snapshot_]);
 		if (count > 0) {
-			if (int e = service_ring(ring_snapshot_, count)) return e;
-			if (serviced) *serviced = count;
+			if (int e = service_ring(ring_snapshot_, count, serviced)) return e;
 		}
 	}
 	if (int e = order_load_stream_behind_frames()) return e; // the ring is complete once every frame that may append to it has ended
@@ -977,6 +1012,236 @@ int Scene::device_brick(int supercell, uint32_t device_slot, uint32_t* out16) {
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
 	BM_HIP(hipMemcpy(out16, d_arena_ + (static_cast<size_t>(world.supercells[supercell].pool_base) + device_slot) * kBrickWords, sizeof(Brick), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+// ---------------------------------------------------------------- voxel edits
+// The host world first (World::edit_supercell on every supercell the batch reaches: bits, LoD masks, words, host slots), then the
+// device: per dirty cell its new device word -- slot | loaded | lod for a resident brick, which keeps its pool slot and gets its new
+// content; unloaded | lod for a brick that is not resident (requested bit clear: asked for again); 0 for an empty cell, whose pool
+// slot goes on the pool's free list.  A preloaded scene services no requests, so a new brick gets a pool slot at once (a freed one
+// first, else the pool grows through region_alloc and the move kernel).  On the load stream, behind every frame in flight: one copy
+// of the staged batch, the pool moves, one scatter kernel, and -- when some cell's occupancy changed -- the cube-field update
+// (edit.hip); recorded as an upload batch, so every frame issued later waits for it.
+int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
+	std::string why;
+	if (!World::validate_edits(edits, count, &why)) { set_error("bm_scene_edit: " + why); return BM_EINVAL; }
+	if (!on_device_) { set_error("bm_scene_edit: scene not generated"); return BM_ESTATE; }
+	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	const WorldDims& d = world.dims;
+	std::vector<int> reached;
+	{
+		std::vector<uint8_t> seen(static_cast<size_t>(d.supercells), 0);
+		for (int i = 0; i < count; ++i) {
+			int lo[3], hi[3];
+			if (!World::edit_bounds(d, edits[i], lo, hi)) continue;
+			for (int sz = lo[2] / kColumnSpan; sz <= (hi[2] - 1) / kColumnSpan; ++sz)
+				for (int sy = lo[1] / kColumnSpan; sy <= (hi[1] - 1) / kColumnSpan; ++sy)
+					for (int sx = lo[0] / kColumnSpan; sx <= (hi[0] - 1) / kColumnSpan; ++sx) {
+						const int sc = d.supercell_id(sx, sy, sz);
+						if (!seen[sc]) { seen[sc] = 1; reached.push_back(sc); }
+					}
+		}
+	}
+	if (reached.empty()) return 0;
+	std::sort(reached.begin(), reached.end());
+	BM_HIP(hipSetDevice(device_));
+	if (edit_busy_) { BM_HIP(hipEventSynchronize(ev_edit_)); edit_busy_ = false; } // the staging of the previous batch has been copied
+
+	// ---- host world, supercell by supercell (voxels of different supercells are independent: batch order is kept within each)
+	std::vector<uint32_t> cells, words, slots;
+	std::vector<Brick> bricks;
+	std::vector<PoolMove> moves;
+	int box_lo[3] = {1 << 30, 1 << 30, 1 << 30}, box_hi[3] = {-1, -1, -1}; // cells whose occupancy changed (unbordered, inclusive)
+	std::vector<uint32_t> old_words;
+	std::vector<uint16_t> old_dev;
+	std::vector<uint8_t> touched;
+	std::vector<int> fresh_cells;
+	for (const int sci : reached) {
+		HostSupercell& c = world.supercells[sci];
+		const int sx = sci % d.supergrid_xy, sy = (sci / d.supergrid_xy) % d.supergrid_xy, sz = sci / (d.supergrid_xy * d.supergrid_xy);
+		old_words = c.indices;
+		old_dev = c.dev_slot;
+		touched.assign(kCellsPerSupercell, 0);
+		World::edit_supercell(d, c, sx, sy, sz, edits, count, touched.data());
+		// device slots of the host slots after the batch: untouched cells keep theirs (their host slots did not move)
+		std::vector<uint16_t> dev(c.bricks.size(), kNoDeviceSlot);
+		for (int j = 0; j < kCellsPerSupercell; ++j)
+			if (c.indices[j] && !touched[j]) dev[c.indices[j] & BM_BRICK_INDEX_BITS] = old_dev[c.indices[j] & BM_BRICK_INDEX_BITS];
+		fresh_cells.clear();
+		for (int j = 0; j < kCellsPerSupercell; ++j) {
+			if (!touched[j]) continue;
+			const uint32_t ow = old_words[j], nw = c.indices[j];
+			const uint16_t ods = ow ? old_dev[ow & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
+			if (ods != kNoDeviceSlot) {
+				if (nw) dev[nw & BM_BRICK_INDEX_BITS] = ods; // resident stays resident, rewritten in place
+				else { c.pool_free.push_back(ods); resident_bricks_--; }
+			} else if (nw && preloaded_) {
+				fresh_cells.push_back(j);
+			}
+			if ((ow != 0) != (nw != 0)) {
+				const int g[3] = {sx * kSupercell + (j & 15), sy * kSupercell + ((j >> 4) & 15), sz * kSupercell + (j >> 8)};
+				for (int k = 0; k < 3; ++k) { box_lo[k] = std::min(box_lo[k], g[k]); box_hi[k] = std::max(box_hi[k], g[k]); }
+			}
+		}
+		if (!fresh_cells.empty()) { // preloaded scene: new bricks get pool slots now, freed ones first
+			const uint32_t reuse = static_cast<uint32_t>(std::min(fresh_cells.size(), c.pool_free.size()));
+			const uint32_t appends = static_cast<uint32_t>(fresh_cells.size()) - reuse;
+			if (c.resident + appends > c.pool_capacity) {
+				uint32_t grown = kStartingPool;
+				while (grown < c.resident + appends || grown < 2 * c.pool_capacity) grown *= 2;
+				uint32_t fresh = 0;
+				if (int e = region_alloc(grown, &fresh)) { failed_ = true; return e; }
+				moves.push_back(PoolMove{c.pool_capacity ? c.pool_base : fresh, fresh, c.pool_capacity ? c.resident : 0u, static_cast<uint32_t>(sci)});
+				if (c.pool_capacity > 0) { // (a preloaded pool is an exact fit: only its largest power of two is handed out again)
+					int cls = 0;
+					while ((2u << cls) <= c.pool_capacity) ++cls;
+					freed_this_batch_.emplace_back(cls, c.pool_base);
+					pool_bricks_ -= c.pool_capacity;
+				}
+				c.pool_base = fresh;
+				c.pool_capacity = grown;
+			}
+			for (const int j : fresh_cells) {
+				uint32_t ds;
+				if (!c.pool_free.empty()) { ds = c.pool_free.back(); c.pool_free.pop_back(); }
+				else ds = c.resident++;
+				dev[c.indices[j] & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(ds);
+				resident_bricks_++;
+			}
+		}
+		c.dev_slot.swap(dev);
+		for (int j = 0; j < kCellsPerSupercell; ++j) {
+			if (!touched[j]) continue;
+			const uint32_t nw = c.indices[j];
+			const uint16_t ds = nw ? c.dev_slot[nw & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
+			cells.push_back(static_cast<uint32_t>(sci) * kCellsPerSupercell + static_cast<uint32_t>(j));
+			if (!nw) words.push_back(0u);
+			else if (ds == kNoDeviceSlot) words.push_back(BM_BRICK_UNLOADED_BIT | (nw & BM_BRICK_LOD_BITS));
+			else words.push_back(ds | BM_BRICK_LOADED_BIT | (nw & BM_BRICK_LOD_BITS));
+			slots.push_back(ds == kNoDeviceSlot ? 0xFFFFFFFFu : c.pool_base + ds);
+			bricks.push_back(nw ? c.bricks[nw & BM_BRICK_INDEX_BITS] : Brick{});
+		}
+	}
+	const uint32_t n = static_cast<uint32_t>(cells.size());
+	if (n == 0) { // nothing inside the world changed a brick (e.g. clearing empty space)
+		for (const auto& f : freed_this_batch_) free_regions_[f.first].push_back(f.second);
+		freed_this_batch_.clear();
+		return 0;
+	}
+
+	// ---- staging: [pool moves][cells][words][slots][bricks], 64-byte aligned sections
+	auto up = [](size_t b) { return (b + 63) / 64 * 64; };
+	const size_t o_cells = up(moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
+				 o_bricks = o_slots + up(n * 4ull), bytes = o_bricks + n * sizeof(Brick);
+	const bool field = box_hi[0] >= 0;
+	FieldUpdate fu{};
+	if (field) {
+		const int lim[3] = {d.cells, d.cells, d.cells_height};
+		int r0[3], r1[3];
+		for (int k = 0; k < 3; ++k) { // bordered coordinates: interior cells are 1 ... lim
+			r0[k] = std::max(1, box_lo[k] + 1 - 254);
+			r1[k] = std::min(lim[k] + 1, box_hi[k] + 1 + 254 + 1);
+		}
+		fu.rx0 = r0[0]; fu.rx1 = r1[0]; fu.ry0 = r0[1]; fu.ry1 = r1[1]; fu.rz0 = r0[2]; fu.rz1 = r1[2];
+		fu.ay0 = std::max(1, fu.ry0 - 254); fu.ay1 = std::min(d.cells + 1, fu.ry1 + 254);
+		fu.bz0 = std::max(1, fu.rz0 - 254); fu.bz1 = std::min(d.cells_height + 1, fu.rz1 + 254);
+		fu.cells = d.cells; fu.cells_height = d.cells_height;
+		fu.sg_xy = d.supergrid_xy; fu.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
+		fu.cf_shift = view_.cf_shift; fu.cf_pxy = view_.cf_pxy; fu.cf_plane = view_.cf_plane;
+	}
+	auto queue = [&]() -> int {
+		if (bytes > edit_cap_) {
+			BM_HIP(hipStreamSynchronize(load_stream_)); // the previous batch's kernels may still read the device staging
+			if (h_edit_) { BM_HIP(hipHostFree(h_edit_)); h_edit_ = nullptr; }
+			if (d_edit_) { BM_HIP(hipFree(d_edit_)); d_edit_ = nullptr; }
+			edit_cap_ = 0;
+			const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
+			BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_edit_), cap, hipHostMallocDefault));
+			BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_edit_), cap));
+			edit_cap_ = cap;
+		}
+		if (field && field_update_tmp_bytes(fu) > cf_tmp_cap_) {
+			BM_HIP(hipStreamSynchronize(load_stream_));
+			if (d_cf_tmp_) { BM_HIP(hipFree(d_cf_tmp_)); d_cf_tmp_ = nullptr; }
+			cf_tmp_cap_ = 0;
+			BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cf_tmp_), field_update_tmp_bytes(fu)));
+			cf_tmp_cap_ = field_update_tmp_bytes(fu);
+		}
+		if (!moves.empty()) std::memcpy(h_edit_, moves.data(), moves.size() * sizeof(PoolMove));
+		std::memcpy(h_edit_ + o_cells, cells.data(), n * 4ull);
+		std::memcpy(h_edit_ + o_words, words.data(), n * 4ull);
+		std::memcpy(h_edit_ + o_slots, slots.data(), n * 4ull);
+		std::memcpy(h_edit_ + o_bricks, bricks.data(), n * sizeof(Brick));
+		// behind every frame in flight (they read the words, pool bases, bricks and field this rewrites) and the caller's queued work
+		if (int e = order_load_stream_behind_frames()) return e;
+		BM_HIP(hipEventRecord(ev_edit_caller_, stream));
+		BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
+		BM_HIP(hipMemcpyAsync(d_edit_, h_edit_, bytes, hipMemcpyHostToDevice, load_stream_));
+		BM_HIP(hipEventRecord(ev_edit_, load_stream_)); // the pinned staging is free again from here on
+		BM_HIP(hipEventRecord(ev_edit_time_[0], load_stream_));
+		if (!moves.empty()) {
+			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_), static_cast<uint32_t>(moves.size()), d_arena_, d_pool_base_, load_stream_);
+			BM_HIP(hipGetLastError());
+		}
+		launch_edit_scatter(reinterpret_cast<const uint32_t*>(d_edit_ + o_cells), reinterpret_cast<const uint32_t*>(d_edit_ + o_words),
+							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, d_index_grid_, d_arena_,
+							load_stream_);
+		BM_HIP(hipGetLastError());
+		BM_HIP(hipEventRecord(ev_edit_time_[1], load_stream_));
+		if (field) {
+			launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
+			BM_HIP(hipGetLastError());
+		}
+		BM_HIP(hipEventRecord(ev_edit_time_[2], load_stream_));
+		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
+		return 0;
+	};
+	if (int e = queue()) { failed_ = true; return e; } // the host world is ahead of the device: refuse to go on
+	for (const auto& f : freed_this_batch_) free_regions_[f.first].push_back(f.second); // reusable by the NEXT batch
+	freed_this_batch_.clear();
+	edit_busy_ = true;
+	edit_timed_ = true;
+	edit_field_timed_ = field;
+	upload_seq_++;
+	return 0;
+}
+
+int Scene::last_edit_ms(float* scatter_ms, float* field_ms) {
+	if (!scatter_ms || !field_ms) { set_error("null argument"); return BM_EINVAL; }
+	if (!edit_timed_) { set_error("no edit has changed the scene yet"); return BM_ESTATE; }
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipEventSynchronize(ev_edit_time_[2]));
+	BM_HIP(hipEventElapsedTime(scatter_ms, ev_edit_time_[0], ev_edit_time_[1]));
+	BM_HIP(hipEventElapsedTime(field_ms, ev_edit_time_[1], ev_edit_time_[2]));
+	if (!edit_field_timed_) *field_ms = 0.0f;
+	return 0;
+}
+
+int Scene::device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
+	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	const WorldDims& d = world.dims;
+	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = 8 * X * X * Z;
+	if (bytes) *bytes = need;
+	if (!dst) return 0;
+	if (capacity < need) { set_error("cube field buffer too small"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipDeviceSynchronize());
+	// every plane is Z slices of X rows padded to 2^cf_shift bytes, and the planes follow each other: 8 X Z rows in all
+	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_, static_cast<size_t>(1) << view_.cf_shift, X, 8 * X * Z, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int Scene::host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
+	const WorldDims& d = world.dims;
+	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = 8 * X * X * Z;
+	if (bytes) *bytes = need;
+	if (!dst) return 0;
+	if (!world.generated) { set_error("world not generated"); return BM_ESTATE; }
+	if (capacity < need) { set_error("cube field buffer too small"); return BM_EINVAL; }
+	std::vector<uint8_t> f;
+	world.build_cube_field(f, 8);
+	std::memcpy(dst, f.data(), need);
 	return 0;
 }
 

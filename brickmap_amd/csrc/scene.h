@@ -56,6 +56,11 @@ public:
 	int info(bm_scene_info* out);
 	int device_indices(int supercell, uint32_t* out4096);
 	int device_brick(int supercell, uint32_t device_slot, uint32_t* out16);
+	// voxel edits (edit.hip / scene.cpp "voxel edits"): host world first, then one scatter + the cube-field update on the load stream
+	int edit(int count, const bm_edit* edits, hipStream_t stream);
+	int device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
+	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
+	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
 	int render(const bm_camera* cam, const bm_frame_params* fp, float* accum, uint32_t* dbg, hipStream_t stream);
 	// `count` consecutive frames as one launch (the frame ring, trace.hip); dbgs may be null, and so may any of its entries
 	int render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream);
@@ -84,7 +89,7 @@ private:
 	int allocate_device();
 	void free_device();
 	int alloc_queue();
-	int service_ring(int ring, uint32_t count);
+	int service_ring(int ring, uint32_t count, uint32_t* serviced);
 
 	int device_;
 	bool on_device_ = false;
@@ -173,7 +178,20 @@ private:
 	PoolMove* h_moves_ = nullptr;                 // pinned staging of one batch's pool moves
 	PoolMove* d_moves_ = nullptr;
 	uint32_t moves_cap_ = 0;
-	uint64_t total_bricks_ = 0, resident_bricks_ = 0;
+	uint64_t total_bricks_ = 0, resident_bricks_ = 0; // host slots (what a full preload holds) / resident non-empty bricks
+	bool preloaded_ = false;                     // bm_scene_preload_all: an edit uploads new bricks at once (no requests are serviced)
+	int* d_positions_ = nullptr;                 // a ring's entries without the stale ones, when service_ring skips some
+	// edits: pinned + device staging of one batch (pool moves, dirty cells, their words, arena slots and bricks), grown on demand;
+	// the staging is free again once ev_edit_ has passed.  d_cf_tmp_: the intermediate planes of the cube-field update.
+	char* h_edit_ = nullptr;
+	char* d_edit_ = nullptr;
+	size_t edit_cap_ = 0;
+	hipEvent_t ev_edit_ = nullptr, ev_edit_caller_ = nullptr;
+	hipEvent_t ev_edit_time_[3] = {}; // around the scatter and the field update of the last batch
+	bool edit_timed_ = false, edit_field_timed_ = false;
+	bool edit_busy_ = false;
+	uint8_t* d_cf_tmp_ = nullptr;
+	size_t cf_tmp_cap_ = 0;
 	int queue_cap_ = 1024;                       // variables.h:35
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27
 	DeviceScene view_{};

@@ -116,6 +116,7 @@ void World::build_supercell(int sx, int sy, int sz, const float* heights) {
 	HostSupercell& cell = supercells[dims.supercell_id(sx, sy, sz)];
 	cell.indices.assign(kCellsPerSupercell, 0u);
 	cell.bricks.clear();
+	cell.free_slots.clear();
 	cell.resident = 0;
 
 	// per brick column: lowest / highest terrain height under its 8x8 footprint
@@ -197,8 +198,142 @@ void World::generate(int threads) {
 
 uint64_t World::total_bricks() const {
 	uint64_t n = 0;
-	for (const auto& c : supercells) n += c.bricks.size();
+	for (const auto& c : supercells) n += c.bricks.size() - c.free_slots.size();
 	return n;
+}
+
+// ---------------------------------------------------------------- voxel edits
+namespace {
+// bit positions of the 2x2x2 LoD octant q (bit 0: x >= 4, bit 1: y >= 4, bit 2: z >= 4) in a brick's 16 words (bit = x + 8y + 64z)
+struct LodMasks {
+	uint32_t m[8][kBrickWords] = {};
+	LodMasks() {
+		for (int bit = 0; bit < 512; ++bit) {
+			const int x = bit & 7, y = (bit >> 3) & 7, z = bit >> 6;
+			m[((x & 4) >> 2) + ((y & 4) >> 1) + (z & 4)][bit >> 5] |= 1u << (bit & 31);
+		}
+	}
+};
+const LodMasks kLodMasks;
+
+inline int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+} // namespace
+
+uint32_t World::brick_lod(const Brick& b) {
+	uint32_t lod = 0;
+	for (int q = 0; q < 8; ++q) {
+		uint32_t any = 0;
+		for (int w = 0; w < kBrickWords; ++w) any |= b.data[w] & kLodMasks.m[q][w];
+		if (any) lod |= 1u << q;
+	}
+	return lod;
+}
+
+bool World::validate_edits(const bm_edit* edits, int count, std::string* why) {
+	if (count < 0 || (count > 0 && !edits)) { *why = "bad edit count or null edit list"; return false; }
+	for (int i = 0; i < count; ++i) {
+		const bm_edit& e = edits[i];
+		const std::string at = "edit " + std::to_string(i) + ": ";
+		if (e.op != BM_EDIT_SET && e.op != BM_EDIT_CLEAR) { *why = at + "unknown op"; return false; }
+		if (e.shape == BM_EDIT_BOX) {
+			for (int k = 0; k < 3; ++k)
+				if (e.hi[k] < e.lo[k]) { *why = at + "box with hi < lo"; return false; }
+		} else if (e.shape == BM_EDIT_SPHERE) {
+			if (e.radius < 0) { *why = at + "sphere with a negative radius"; return false; }
+		} else {
+			*why = at + "unknown shape";
+			return false;
+		}
+	}
+	return true;
+}
+
+bool World::edit_bounds(const WorldDims& dims, const bm_edit& e, int lo[3], int hi[3]) {
+	const int64_t size[3] = {dims.grid_size, dims.grid_size, dims.grid_height};
+	for (int k = 0; k < 3; ++k) {
+		int64_t a, b; // half-open, 64-bit: centre +- radius may leave the int32 range
+		if (e.shape == BM_EDIT_BOX) { a = e.lo[k]; b = e.hi[k]; }
+		else { a = static_cast<int64_t>(e.center[k]) - e.radius; b = static_cast<int64_t>(e.center[k]) + e.radius + 1; }
+		a = clamp64(a, 0, size[k]);
+		b = clamp64(b, 0, size[k]);
+		if (a >= b) return false;
+		lo[k] = static_cast<int>(a);
+		hi[k] = static_cast<int>(b);
+	}
+	return true;
+}
+
+void World::edit_supercell(const WorldDims& dims, HostSupercell& c, int sx, int sy, int sz, const bm_edit* edits, int count, uint8_t* touched) {
+	const int org[3] = {sx * kColumnSpan, sy * kColumnSpan, sz * kColumnSpan}; // voxel origin of the supercell
+	for (int i = 0; i < count; ++i) {
+		const bm_edit& e = edits[i];
+		int lo[3], hi[3];
+		if (!edit_bounds(dims, e, lo, hi)) continue;
+		bool inside = true;
+		for (int k = 0; k < 3; ++k) {
+			lo[k] = std::max(lo[k], org[k]) - org[k];
+			hi[k] = std::min(hi[k], org[k] + kColumnSpan) - org[k];
+			inside = inside && lo[k] < hi[k];
+		}
+		if (!inside) continue;
+		const bool sphere = e.shape == BM_EDIT_SPHERE;
+		const __int128 r2 = static_cast<__int128>(e.radius) * e.radius;
+		for (int bz = lo[2] >> 3; bz <= (hi[2] - 1) >> 3; ++bz)
+			for (int by = lo[1] >> 3; by <= (hi[1] - 1) >> 3; ++by)
+				for (int bx = lo[0] >> 3; bx <= (hi[0] - 1) >> 3; ++bx) {
+					const int local = bx + by * kSupercell + bz * kSupercell * kSupercell;
+					uint32_t& word = c.indices[local];
+					if (e.op == BM_EDIT_CLEAR && word == 0) continue; // nothing to clear
+					// the edit's voxels in this brick (bit = x + 8y + 64z, Scene.cpp:91-93)
+					uint32_t mask[kBrickWords] = {};
+					bool any = false;
+					const int x0 = std::max(lo[0], bx * 8), x1 = std::min(hi[0], bx * 8 + 8);
+					const int y0 = std::max(lo[1], by * 8), y1 = std::min(hi[1], by * 8 + 8);
+					const int z0 = std::max(lo[2], bz * 8), z1 = std::min(hi[2], bz * 8 + 8);
+					for (int z = z0; z < z1; ++z)
+						for (int y = y0; y < y1; ++y)
+							for (int x = x0; x < x1; ++x) {
+								if (sphere) { // sum of squares in 64-bit integers (wider where a far-away centre would overflow them)
+									const __int128 dx = static_cast<int64_t>(org[0] + x) - e.center[0], dy = static_cast<int64_t>(org[1] + y) - e.center[1],
+												   dz = static_cast<int64_t>(org[2] + z) - e.center[2];
+									if (dx * dx + dy * dy + dz * dz > r2) continue;
+								}
+								const int bit = (x & 7) + (y & 7) * 8 + (z & 7) * 64;
+								mask[bit >> 5] |= 1u << (bit & 31);
+								any = true;
+							}
+					if (!any) continue;
+					if (touched) touched[local] = 1;
+					if (e.op == BM_EDIT_SET) {
+						if (word == 0) { // the cell gains a brick: a freed slot first, else a new one
+							uint32_t slot;
+							if (!c.free_slots.empty()) {
+								slot = c.free_slots.back();
+								c.free_slots.pop_back();
+							} else {
+								slot = static_cast<uint32_t>(c.bricks.size());
+								c.bricks.emplace_back();
+							}
+							std::memset(c.bricks[slot].data, 0, sizeof(Brick));
+							word = slot | 0x80000000u;
+						}
+						Brick& b = c.bricks[word & 0xFFFu];
+						for (int w = 0; w < kBrickWords; ++w) b.data[w] |= mask[w];
+						word = (word & 0xFFFu) | 0x80000000u | (brick_lod(b) << 12); // Scene.cpp:104
+					} else {
+						const uint32_t slot = word & 0xFFFu;
+						Brick& b = c.bricks[slot];
+						uint32_t left = 0;
+						for (int w = 0; w < kBrickWords; ++w) left |= (b.data[w] &= ~mask[w]);
+						if (left == 0) { // empty brick: word 0, slot free
+							c.free_slots.push_back(slot);
+							word = 0;
+						} else {
+							word = slot | 0x80000000u | (brick_lod(b) << 12);
+						}
+					}
+				}
+	}
 }
 
 // Largest empty cube per cell and octant: the classic "maximal square" recurrence in 3-D.  A cube of edge n anchored at

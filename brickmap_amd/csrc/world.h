@@ -3,7 +3,10 @@
 // (src/Scene.h:3-44, src/Scene.cpp:44-147), with the world dimensions made runtime.
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
+
+#include "../../include/brickmap.h"
 
 namespace bm {
 
@@ -20,12 +23,19 @@ static_assert(sizeof(Brick) == 64, "a brick is one 64-byte record");
 
 struct HostSupercell {               // Scene::Supercell, Scene.h:21-29 (host part)
 	std::vector<uint32_t> indices;   // 4096 words: slot | loaded | lod<<12, 0 = empty brick
-	std::vector<Brick> bricks;       // non-empty bricks in generation order
+	std::vector<Brick> bricks;       // bricks in generation order; slots in free_slots are empty and unused
+	std::vector<uint32_t> free_slots; // host slots emptied by edits, reused (last first) before bricks grows
 	uint32_t resident = 0;           // gpu_index_highest: next free slot of this supercell's pool
+	// device residency of the host bricks, kept by Scene: host slot -> slot in the device pool (kNoDeviceSlot = not resident),
+	// and the device slots that edits have freed (reused before the pool's high-water mark `resident` moves)
+	std::vector<uint16_t> dev_slot;
+	std::vector<uint32_t> pool_free;
 	// device pool of this supercell (Scene::Supercell gpu_count / gpu_index_highest, Scene.h:24-27), kept by Scene
 	uint32_t pool_capacity = 0;      // bricks the pool can hold (0 = no pool yet)
 	uint32_t pool_base = 0;          // first arena slot of the pool
 };
+
+constexpr uint16_t kNoDeviceSlot = 0xFFFF;
 
 struct WorldDims {
 	int grid_size = 0, grid_height = 0;         // voxels
@@ -53,12 +63,24 @@ public:
 	void generate_supercell(int sx, int sy, int sz);
 	// CPU half of Scene::generate (Scene.cpp:118-147)
 	void generate(int threads);
-	uint64_t total_bricks() const;
+	uint64_t total_bricks() const; // non-empty bricks (host slots minus freed ones)
 	// Octant cube field for the GPU walk (device_types.h DeviceScene::cube_field): 8 planes of
 	// (cells + 2)^2 * (cells_height + 2) bytes.  Plane o, cell c: edge (capped at 254) of the largest cube of empty
 	// cells inside the grid that has c as its near corner and extends towards -x / -y / -z where bit 0 / 1 / 2 of o is
 	// set, +x / +y / +z otherwise; 0 for a cell whose index word is non-zero, 255 for the border cells.
 	void build_cube_field(std::vector<uint8_t>& field, int threads) const;
+
+	// ---- voxel edits (bm_scene_edit): the host world stays authoritative; Scene carries the result to the device
+	// 2x2x2 LoD mask of a brick's bits (Scene.cpp:95)
+	static uint32_t brick_lod(const Brick& b);
+	// Check a whole batch before anything changes: known op and shape, hi >= lo, radius >= 0.  false + *why on the first bad edit.
+	static bool validate_edits(const bm_edit* edits, int count, std::string* why);
+	// Voxel bounds [lo, hi) of one (valid) edit clipped to a world of these dimensions; false = nothing of it inside the world.
+	static bool edit_bounds(const WorldDims& dims, const bm_edit& e, int lo[3], int hi[3]);
+	// Apply a batch, in order, to the supercell at supercell coordinates (sx, sy, sz): set / clear the voxels, recompute the LoD masks,
+	// give a cell that gains voxels a brick (a freed slot first) and a brick that becomes empty word 0 (its slot goes on free_slots).
+	// touched (4096 entries, may be null) is set to 1 for every cell whose word or brick the batch may have changed.
+	static void edit_supercell(const WorldDims& dims, HostSupercell& c, int sx, int sy, int sz, const bm_edit* edits, int count, uint8_t* touched);
 
 private:
 	void build_supercell(int sx, int sy, int sz, const float* heights);

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import bm_camera, bm_counters, bm_frame_params, bm_scene_info, check
+from ._lib import BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, bm_camera, bm_counters, bm_edit, bm_frame_params, bm_scene_info, check
 
 
 # The reference's fly-through presets (performance_measure.h:4-25): camera position + (horizontal, vertical) angle.
@@ -161,6 +161,48 @@ def host_generate_supercell(grid_size, grid_height, sx, sy, sz):
     return idx, bricks[: n.value].copy()
 
 
+def edit_box(op, lo, hi):
+    """One box edit (bm_edit): voxels lo <= v < hi on every axis; op is BM_EDIT_SET or BM_EDIT_CLEAR (or "set" / "clear")."""
+    e = bm_edit()
+    e.op, e.shape = _edit_op(op), BM_EDIT_BOX
+    e.lo[:] = [int(v) for v in lo]
+    e.hi[:] = [int(v) for v in hi]
+    return e
+
+
+def edit_sphere(op, center, radius):
+    """One sphere edit (bm_edit): voxels v with sum((v - center)^2) <= radius^2, in integers."""
+    e = bm_edit()
+    e.op, e.shape = _edit_op(op), BM_EDIT_SPHERE
+    e.center[:] = [int(v) for v in center]
+    e.radius = int(radius)
+    return e
+
+
+def _edit_op(op):
+    return {"set": BM_EDIT_SET, "clear": BM_EDIT_CLEAR}.get(op, op) if isinstance(op, str) else int(op)
+
+
+def _edit_array(edits):
+    edits = list(edits)
+    arr = (bm_edit * max(len(edits), 1))()
+    for i, e in enumerate(edits):
+        arr[i] = e
+    return arr, len(edits)
+
+
+def host_edit_supercell(grid_size, grid_height, sx, sy, sz, indices, bricks, edits):
+    """bm_host_edit_supercell: the host half of an edit batch on one supercell's arrays (no device needed).  indices: uint32[4096],
+    bricks: uint32[n, 16] as host_generate_supercell returns them; returns the edited (indices, bricks) -- new arrays."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).copy()
+    n = C.c_uint32(len(bricks))
+    buf = np.zeros((4096, 16), np.uint32)
+    buf[: len(bricks)] = np.asarray(bricks, np.uint32).reshape(-1, 16)
+    arr, count = _edit_array(edits)
+    check(_lib.load().bm_host_edit_supercell(grid_size, grid_height, sx, sy, sz, idx.ctypes.data, C.byref(n), buf.ctypes.data, 4096, count, arr))
+    return idx, buf[: n.value].copy()
+
+
 def probe_streams(count, device=0):
     """bm_probe_streams: `count` HIP streams (raw handles, ints) that demonstrably run side by side on `device` -- HIP maps streams
     onto a few hardware queues, and streams that share one do not overlap.  release_streams() gives them back."""
@@ -272,6 +314,66 @@ class Scene:
         out = np.zeros((128, 128), np.float32)
         check(self._L.bm_scene_column_heights(self.gpuScene, sx, sy, out.ctypes.data))
         return out
+
+    # ---- voxel edits (bm_scene_edit): ordered behind the frames in flight, seen by every frame issued after the call
+    def _stream(self, stream):
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        return C.c_void_p(stream)
+
+    def edit(self, edits, stream=None):
+        """Apply a list of edits (edit_box / edit_sphere) in order.  A malformed edit raises and leaves the scene unchanged."""
+        arr, count = _edit_array(edits)
+        check(self._L.bm_scene_edit(self.gpuScene, count, arr, self._stream(stream)))
+        return self
+
+    def fill_box(self, lo, hi, stream=None):
+        return self.edit([edit_box(BM_EDIT_SET, lo, hi)], stream)
+
+    def clear_box(self, lo, hi, stream=None):
+        return self.edit([edit_box(BM_EDIT_CLEAR, lo, hi)], stream)
+
+    def fill_sphere(self, center, radius, stream=None):
+        return self.edit([edit_sphere(BM_EDIT_SET, center, radius)], stream)
+
+    def carve_sphere(self, center, radius, stream=None):
+        return self.edit([edit_sphere(BM_EDIT_CLEAR, center, radius)], stream)
+
+    def set_voxels(self, coords, values, stream=None):
+        """coords: N x 3 int32 voxel coordinates (numpy array or CPU torch tensor); values: a scalar or N values (non-zero = solid)."""
+        if hasattr(coords, "detach"):
+            coords = coords.detach().cpu().numpy()
+        xyz = np.ascontiguousarray(np.asarray(coords).reshape(-1, 3), dtype=np.int32)
+        if hasattr(values, "detach"):
+            values = values.detach().cpu().numpy()
+        v = np.asarray(values)
+        v = np.full(len(xyz), 1 if v.item() else 0, np.uint8) if v.ndim == 0 else np.ascontiguousarray(v != 0, dtype=np.uint8)
+        assert len(v) == len(xyz), "values: a scalar or one per voxel"
+        check(self._L.bm_scene_set_voxels(self.gpuScene, len(xyz), xyz.ctypes.data, v.ctypes.data, self._stream(stream)))
+        return self
+
+    def _cube_field(self, fn):
+        n = C.c_size_t(0)
+        check(fn(self.gpuScene, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        check(fn(self.gpuScene, out.ctypes.data, out.size, C.byref(n)))
+        cx, cz = self.grid_size // 8 + 2, self.grid_height // 8 + 2
+        return out.reshape(8, cz, cx, cx)
+
+    def device_cube_field(self):
+        """bm_scene_device_cube_field: the device's octant cube field, uint8 [8, cells_height+2, cells+2, cells+2]."""
+        return self._cube_field(self._L.bm_scene_device_cube_field)
+
+    def host_cube_field(self):
+        """bm_scene_host_cube_field: the cube field of the scene's current host world (same layout)."""
+        return self._cube_field(self._L.bm_scene_host_cube_field)
+
+    def last_edit_ms(self):
+        """(scatter_ms, field_ms) of the last edit batch that changed the scene (hipEvents on the load stream)."""
+        a, b = C.c_float(0), C.c_float(0)
+        check(self._L.bm_scene_last_edit_ms(self.gpuScene, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
 
     def synchronize(self):
         check(self._L.bm_synchronize(self.gpuScene))

@@ -1,10 +1,12 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--dig x,y,z,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+// --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
 // With `wavefront` the frames are rendered with the reference's own queue schedule (one segment per call); with `ring` the
 // world is made resident first and all frames are ONE launch of the persistent kernel (launch_frames, the frame ring).
 #include <cstdint>
+#include <cstdio>
 #include <fstream>
 #include <iostream>
 #include <string>
@@ -14,7 +16,21 @@
 
 using namespace brickmap;
 
-int main(int argc, char** argv) {
+int main(int argc_in, char** argv_in) {
+	std::vector<char*> args;
+	int dig[4] = {0, 0, 0, -1};
+	for (int i = 0; i < argc_in; ++i) {
+		if (std::string(argv_in[i]) == "--dig" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d,%d,%d", &dig[0], &dig[1], &dig[2], &dig[3]) != 4 || dig[3] < 0) {
+				std::cerr << "--dig wants x,y,z,r (r >= 0)\n";
+				return 2;
+			}
+			continue;
+		}
+		args.push_back(argv_in[i]);
+	}
+	const int argc = static_cast<int>(args.size());
+	char** argv = args.data();
 	const int grid_size = argc > 1 ? std::atoi(argv[1]) : 1024, grid_height = argc > 2 ? std::atoi(argv[2]) : 1024;
 	const size_t width = argc > 3 ? std::atoi(argv[3]) : 1920, height = argc > 4 ? std::atoi(argv[4]) : 1080;
 	const int frames = argc > 5 ? std::atoi(argv[5]) : 64;
@@ -24,6 +40,7 @@ int main(int argc, char** argv) {
 	State state(width, height);                 // main.cpp:102
 	Scene scene(grid_size, grid_height);        // main.cpp:104
 	scene.generate();                           // main.cpp:105 -- nothing resident yet: bricks stream in on demand
+	if (dig[3] >= 0) scene.carve_sphere(dig, dig[3]);
 	camera.position = {grid_size / 2.f, grid_size / 8.f, 0.8f * grid_height};
 	camera.horizontal_angle = 0.8;
 	camera.vertical_angle = -0.5;

@@ -117,6 +117,20 @@ typedef struct bm_scene_info {
 	uint64_t stream_host_ns;        /* host time spent staging them (validate, copy bricks to pinned memory, hand out slots, queue) */
 } bm_scene_info;
 
+/* one voxel edit (bm_scene_edit).  Voxel coordinates are integers; a batch applies its edits in order. */
+#define BM_EDIT_SET 1    /* the shape's voxels become solid */
+#define BM_EDIT_CLEAR 2  /* the shape's voxels become empty */
+#define BM_EDIT_BOX 1    /* voxels v with lo <= v < hi on every axis (half-open)                          */
+#define BM_EDIT_SPHERE 2 /* voxels v with sum over the axes of (v - center)^2 <= radius^2 (64-bit integers) */
+typedef struct bm_edit {
+	int32_t op;         /* BM_EDIT_SET / BM_EDIT_CLEAR     */
+	int32_t shape;      /* BM_EDIT_BOX / BM_EDIT_SPHERE    */
+	int32_t lo[3];      /* box: first voxel                */
+	int32_t hi[3];      /* box: one past the last voxel    */
+	int32_t center[3];  /* sphere: centre voxel            */
+	int32_t radius;     /* sphere: radius in voxels, >= 0  */
+} bm_edit;
+
 /* traversal counters (BM_FLAG_COUNTERS); same order as oracle/oracle.c orc_counters */
 typedef struct bm_counters {
 	uint64_t index_loads, brick_tests, byte_tests, voxel_steps, extend_rays, shadow_rays, requests, paths;
@@ -181,10 +195,39 @@ BM_API int bm_scene_device_indices(bm_scene* scene, int supercell, uint32_t* ind
 BM_API int bm_scene_device_brick(bm_scene* scene, int supercell, uint32_t device_slot, uint32_t* brick16);
 BM_API int bm_scene_column_heights(bm_scene* scene, int sx, int sy, float* heights128x128);
 
+/* ---- voxel edits of a live scene (no reference counterpart: the reference builds its world once, Scene.cpp:118-147).
+ * Apply `count` edits, in order, to a scene after bm_scene_generate.  Shapes are clipped to the world (one wholly outside is a
+ * no-op); a malformed edit (unknown op or shape, hi < lo, radius < 0) is BM_EINVAL and the scene is left unchanged -- the whole
+ * batch is checked first.  The host world stays authoritative: every brick's bits, LoD mask (Scene.cpp:95) and index word
+ * (slot | loaded | lod << 12, Scene.cpp:104) are what the generator would store for that content, a brick that becomes empty gets
+ * word 0 and frees its slot, a cell that gains voxels gets a brick (freed slots first: slots stay below 4096).  On the device a
+ * resident brick is rewritten in place; a new brick is uploaded at once in a preloaded scene (bm_scene_preload_all) and becomes
+ * unloaded | lod in a streaming one (requested again, like a changed brick that is not resident).  The octant cube field is
+ * recomputed on the GPU where the batch can change it and equals bm_scene_host_cube_field byte for byte.  The edit runs on the
+ * scene's load stream behind every frame in flight and behind the work queued on `hip_stream` so far; frames issued before it
+ * see the old world, frames issued after it the new one.  A request for a brick that an edit emptied is skipped. */
+BM_API int bm_scene_edit(bm_scene* scene, int count, const bm_edit* edits, void* hip_stream);
+/* single voxels: xyz[n][3] voxel coordinates, values[n] != 0 -> solid, 0 -> empty; otherwise as bm_scene_edit (a voxel outside the
+ * world is a no-op) */
+BM_API int bm_scene_set_voxels(bm_scene* scene, int n, const int32_t* xyz, const uint8_t* values, void* hip_stream);
+/* the device's octant cube field, read back in the tight layout of bm_host_cube_field (waits for the device); *bytes = size
+ * needed (dst = NULL to query) */
+BM_API int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes);
+/* the cube field built on the host from the scene's current host world (bm_host_cube_field's layout) */
+BM_API int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes);
+/* device time of the last batch that changed the scene (hipEvents on the load stream): the scatter (pool moves, bricks, words)
+ * and the cube-field update (0 when no cell's occupancy changed); waits for that batch */
+BM_API int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,
                                       uint32_t* brick_count, uint32_t* bricks, uint32_t brick_capacity);
+/* the host half of bm_scene_edit on one supercell's arrays, in place (no device needed): indices4096 and bricks[*brick_count][16]
+ * as bm_host_generate_supercell returns them; a slot that no index word names is free and reused first.  *brick_count may grow
+ * (up to brick_capacity, else BM_EINVAL); on any error the arrays are left unchanged. */
+BM_API int bm_host_edit_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,
+                                  uint32_t* brick_count, uint32_t* bricks, uint32_t brick_capacity, int count, const bm_edit* edits);
 
 /* test door: the constants with which the walk divides a cube-field offset by the slice pitch (floor(n / divisor) ==
  * (uint64(n) * magic >> 32) >> shift for every n < 2^30; 3 <= divisor < 2^23) */

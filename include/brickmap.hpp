@@ -75,6 +75,28 @@ public:
 	void dump() { BM_CHECKED(bm_scene_dump(gpuScene.handle, "dump.txt")); }
 	// BASELINE configs 1-2: everything resident up front (no counterpart in the reference)
 	void preload_all() { BM_CHECKED(bm_scene_preload_all(gpuScene.handle)); }
+
+	// voxel edits of the live world (no counterpart in the reference; bm_scene_edit): applied in order, behind the frames in flight,
+	// seen by every frame issued afterwards.  Integer voxel coordinates; boxes are half-open [lo, hi), spheres hold |v - c|^2 <= r^2.
+	void edit(const std::vector<bm_edit>& edits, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_edit(gpuScene.handle, static_cast<int>(edits.size()), edits.data(), hip_stream));
+	}
+	static bm_edit box(int op, const int lo[3], const int hi[3]) {
+		bm_edit e{};
+		e.op = op; e.shape = BM_EDIT_BOX;
+		for (int k = 0; k < 3; ++k) { e.lo[k] = lo[k]; e.hi[k] = hi[k]; }
+		return e;
+	}
+	static bm_edit sphere(int op, const int center[3], int radius) {
+		bm_edit e{};
+		e.op = op; e.shape = BM_EDIT_SPHERE; e.radius = radius;
+		for (int k = 0; k < 3; ++k) e.center[k] = center[k];
+		return e;
+	}
+	void fill_box(const int lo[3], const int hi[3]) { edit({box(BM_EDIT_SET, lo, hi)}); }
+	void clear_box(const int lo[3], const int hi[3]) { edit({box(BM_EDIT_CLEAR, lo, hi)}); }
+	void fill_sphere(const int center[3], int radius) { edit({sphere(BM_EDIT_SET, center, radius)}); }
+	void carve_sphere(const int center[3], int radius) { edit({sphere(BM_EDIT_CLEAR, center, radius)}); }
 };
 
 // Which part of the frame this process renders (no counterpart in the reference, which is single-GPU: main.cpp:89 computes
