@@ -16,6 +16,8 @@ BM_FLAG_SAMPLE_ITEMS = 4
 BM_FLAG_COUNTERS = 2
 BM_FLAG_ORDERED = 16
 BM_FLAG_RAY_DIGEST = 32
+BM_QUERY_LOD = 1
+BM_QUERY_NO_REQUESTS = 2
 BRICK_INDEX_BITS = 0x00000FFF
 BRICK_LOD_BITS = 0x000FF000
 BRICK_REQUESTED_BIT = 0x20000000
@@ -53,6 +55,14 @@ BM_EDIT_SPHERE = 2
 class bm_edit(C.Structure):
     _fields_ = [("op", C.c_int32), ("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3),
                 ("radius", C.c_int32)]
+
+
+class bm_ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("tmax", C.c_float), ("reserved", C.c_uint32)]
+
+
+class bm_ray_hit(C.Structure):
+    _fields_ = [("distance", C.c_float), ("normal", C.c_float * 3), ("voxel", C.c_int32 * 3), ("level", C.c_int32)]
 
 
 class bm_scene_info(C.Structure):
@@ -113,6 +123,8 @@ SIGNATURES = {
     "bm_scene_device_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_scene_host_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_scene_last_edit_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "bm_scene_cast_rays": (_i, [_vp, C.c_int64, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_host_column_heights": (_i, [_i, _i, _i, _i, _vp]),
     "bm_host_generate_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32]),
     "bm_host_edit_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32, _i, C.POINTER(bm_edit)]),

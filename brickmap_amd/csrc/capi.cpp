@@ -1,6 +1,8 @@
 // capi.cpp -- extern "C" surface of libbrickmap_hip.so (declared in include/brickmap.h).
+#include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 #include <new>
@@ -20,6 +22,8 @@ struct bm_wavefront {
 };
 
 using bm::set_error;
+
+static_assert(sizeof(bm_ray) == 32 && sizeof(bm_ray_hit) == 32, "the query kernel reads and writes 32-byte records");
 
 #define BM_NEED(scene)                                   \
 	do {                                                 \
@@ -120,6 +124,41 @@ int bm_scene_set_voxels(bm_scene* scene, int n, const int32_t* xyz, const uint8_
 int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.device_cube_field(dst, capacity, bytes); }
 int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.host_cube_field(dst, capacity, bytes); }
 int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms) { BM_NEED(scene); return scene->impl.last_edit_ms(scatter_ms, field_ms); }
+
+int bm_scene_cast_rays(bm_scene* scene, int64_t n, const bm_ray* rays_dev, bm_ray_hit* hits_dev, uint32_t flags, const float lod_origin[3], void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.cast_rays(n, rays_dev, hits_dev, flags, lod_origin, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t n, const float* px, const float* py, bm_ray* out) {
+	if (!camera || width <= 0 || height <= 0 || width > 65535 || height > 65535 || n < 0 || (n > 0 && (!px || !py || !out))) {
+		set_error("bm_camera_pixel_rays: bad argument");
+		return BM_EINVAL;
+	}
+	// the camera basis of the frames (Scene::fill_frame_constants, this translation unit is built with -ffp-contract=off like it)
+	bm_frame_params p{};
+	p.width = width; p.height = height; p.spp = 1; p.band_rows = height; p.shard_count = 1;
+	bm::FrameConstants fc;
+	if (int e = bm::Scene::fill_frame_constants(camera, &p, &fc)) return e;
+	const float W = static_cast<float>(width), H = static_cast<float>(height);
+	for (int64_t i = 0; i < n; ++i) {
+		// primary_ray (csrc/traverse.h) with the jitter (jx, jy) replaced: pixel x covers ppx in (x - 1, x], so ppx = px - 1
+		const float ppx = px[i] - 1.f, ppy = py[i] - 1.f;
+		const float ni = (ppx / W) - 0.5f;
+		const float nj = ((H - ppy) / H) - 0.5f;
+		float v[3];
+		for (int k = 0; k < 3; ++k) v[k] = (fc.dir[k] + fc.right[k] * ni) + fc.up[k] * nj;
+		const float inv = 1.0f / std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+		bm_ray& r = out[i];
+		for (int k = 0; k < 3; ++k) {
+			r.origin[k] = fc.origin[k];
+			r.direction[k] = v[k] * inv;
+		}
+		r.tmax = std::numeric_limits<float>::infinity();
+		r.reserved = 0;
+	}
+	return 0;
+}
 
 int bm_scene_column_heights(bm_scene* scene, int sx, int sy, float* heights) {
 	BM_NEED(scene);

@@ -36,6 +36,11 @@ void launch_edit_scatter(const uint32_t* cells, const uint32_t* words, const uin
 						 uint32_t* index_grid, uint32_t* arena, hipStream_t stream);
 void launch_field_update(const uint32_t* index_grid, uint8_t* field, uint8_t* tmp, const FieldUpdate& u, hipStream_t stream);
 
+// ray queries (query.hip): n bm_ray records in, n bm_ray_hit records out; ticket = a zeroed word; campos = the LoD centre in brick cells
+int query_blocks_per_cu(bool request);
+void launch_query(const DeviceScene& sc, const int campos[3], const void* rays, void* hits, uint32_t n, uint32_t* ticket, int resident_blocks,
+				  bool request, hipStream_t stream);
+
 // wavefront mode (wavefront.hip)
 int wavefront_blocks_per_cu(bool connect, bool instrumented);
 void launch_wf_primary(WfState* st, WfRay* work, const FrameConstants* fc_dev, uint32_t queue_size, uint32_t pixels, hipStream_t stream);

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -230,6 +231,8 @@ Scene::~Scene() {
 	for (hipEvent_t e : ev_edit_time_) if (e) hipEventDestroy(e);
 	if (d_counters_) hipFree(d_counters_);
 	if (d_work_counter_) hipFree(d_work_counter_);
+	if (d_query_tickets_) hipFree(d_query_tickets_);
+	for (hipEvent_t e : ev_query_) if (e) hipEventDestroy(e);
 	if (d_frame_constants_) hipFree(d_frame_constants_);
 	if (h_frame_constants_) hipHostFree(h_frame_constants_);
 	for (int i = 0; i < kTimingRing; ++i) {
@@ -1395,6 +1398,47 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 	for (int e = first; e < first + count; ++e) ring_owner_[e] = launches_;
 	ring_next_ = first + count;
 	launches_++;
+	return 0;
+}
+
+// ---- ray queries (bm_scene_cast_rays).  Issued through the frames' bookkeeping: the stream is ordered behind pending uploads and
+// edits (begin_frame), and process_load_queue orders itself behind the query (end_frame).  The kernel only reads the world, apart
+// from the request atomics, so it may run beside frames.
+int Scene::cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream) {
+	if (flags & ~(BM_QUERY_LOD | BM_QUERY_NO_REQUESTS)) { set_error("bm_scene_cast_rays: unknown flag"); return BM_EINVAL; }
+	if (n < 0 || n > (int64_t{1} << 28)) { set_error("bm_scene_cast_rays: n must be 0 ... 2^28"); return BM_EINVAL; }
+	if (n == 0) return 0;
+	if (!rays || !hits) { set_error("bm_scene_cast_rays: null ray or hit buffer"); return BM_EINVAL; }
+	int campos[3] = {0, 0, 0};
+	if (flags & BM_QUERY_LOD) {
+		if (!lod_origin) { set_error("bm_scene_cast_rays: BM_QUERY_LOD needs lod_origin"); return BM_EINVAL; }
+		for (int i = 0; i < 3; ++i) {
+			if (!(std::fabs(lod_origin[i]) < 16777216.f)) { set_error("bm_scene_cast_rays: lod_origin must be finite and below 2^24"); return BM_EINVAL; }
+			campos[i] = static_cast<int>(lod_origin[i] / 8.f); // as fill_frame_constants: ivec3(camera.position / 8.f)
+		}
+	}
+	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	BM_HIP(hipSetDevice(device_));
+	if (!d_query_tickets_) {
+		BM_HIP(hipMalloc(&d_query_tickets_, kQueryRing * 128));
+		for (hipEvent_t& e : ev_query_) BM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		query_blocks_per_cu_[0] = query_blocks_per_cu(false);
+		query_blocks_per_cu_[1] = query_blocks_per_cu(true);
+	}
+	const bool request = !(flags & BM_QUERY_NO_REQUESTS);
+	DeviceScene view;
+	if (int e = begin_frame(stream, &view, nullptr)) return e;
+	if (!(flags & BM_QUERY_LOD)) view.lod_distance_8x8x8 = view.lod_distance_2x2x2 = INT_MAX; // exact: every brick at voxel level
+	const int slot = static_cast<int>(queries_ % kQueryRing);
+	uint32_t* ticket = d_query_tickets_ + slot * 32;
+	if (queries_ >= static_cast<uint64_t>(kQueryRing)) BM_HIP(hipStreamWaitEvent(stream, ev_query_[slot], 0));
+	BM_HIP(hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream));
+	launch_query(view, campos, rays, hits, static_cast<uint32_t>(n), ticket, query_blocks_per_cu_[request ? 1 : 0] * compute_units_, request, stream);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_query_[slot], stream));
+	queries_++;
+	end_frame(stream);
 	return 0;
 }
 

@@ -61,6 +61,8 @@ public:
 	int device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
+	// ray queries (query.hip): issued like a frame (begin_frame / end_frame), asynchronous to the host
+	int cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream);
 	int render(const bm_camera* cam, const bm_frame_params* fp, float* accum, uint32_t* dbg, hipStream_t stream);
 	// `count` consecutive frames as one launch (the frame ring, trace.hip); dbgs may be null, and so may any of its entries
 	int render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream);
@@ -192,6 +194,12 @@ private:
 	bool edit_busy_ = false;
 	uint8_t* d_cf_tmp_ = nullptr;
 	size_t cf_tmp_cap_ = 0;
+	// ray queries: a ring of slot counters (one 128-byte line each); a query that reuses an entry waits for the one that used it last
+	static constexpr int kQueryRing = 64;
+	uint32_t* d_query_tickets_ = nullptr;
+	hipEvent_t ev_query_[kQueryRing] = {};
+	uint64_t queries_ = 0;
+	int query_blocks_per_cu_[2] = {0, 0};
 	int queue_cap_ = 1024;                       // variables.h:35
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27
 	DeviceScene view_{};

@@ -455,7 +455,9 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 }
 
 // voxel.cuh:200-247: the current cell holds a non-empty brick -- read its index word and resolve it.
-template <bool DBG>
+// INFO: fill `info` (level, brick id, sub id) -- the instrumented kernels with their tallies, the ray queries (query.hip) without.
+// REQUEST: a brick that is not resident is requested through the atomic protocol below (false: only reported, as level 3).
+template <bool DBG, bool INFO = DBG, bool REQUEST = true>
 __device__ __forceinline__ int process_candidate(const DeviceScene& sc, const int* campos, RayState& r, HitInfo& info, Tally& tally,
 													 unsigned long long* lds_brick, uint32_t* walk_trips = nullptr) {
 	int px, py, pz;
@@ -481,10 +483,10 @@ __device__ __forceinline__ int process_candidate(const DeviceScene& sc, const in
 	const int ddx = campos[0] - px, ddy = campos[1] - py, ddz = campos[2] - pz;
 	const int lod2 = __mul24(ddx, ddx) + __mul24(ddy, ddy) + __mul24(ddz, ddz); // |dd| < 2^11: exact
 	float sub_distance = 0.f;
-	if (DBG) info.brick_id = px + py * sc.cells + pz * sc.cells * sc.cells;
+	if (INFO) info.brick_id = px + py * sc.cells + pz * sc.cells * sc.cells;
 	if (lod2 > sc.lod_distance_8x8x8) {
 		r.distance = new_distance * 8.f + r.tminn;
-		if (DBG) { info.level = 0; info.sub_id = 0; }
+		if (INFO) { info.level = 0; info.sub_id = 0; }
 		r.hit = true;
 		return ST_NEED;
 	} else if (lod2 > sc.lod_distance_2x2x2) {
@@ -493,7 +495,7 @@ __device__ __forceinline__ int process_candidate(const DeviceScene& sc, const in
 		const f3 o2 = (r.o + r.d * new_distance) * 2.f - r.n * 0.2f * kEpsilon;
 		if (intersect_grid<2, DBG>(o2, r.d, sx, sy, sz, r.dx, r.dy, r.dz, r.n, sub_distance, brick, (index & kLodBits) >> 12, sub, tally)) {
 			r.distance = new_distance * 8.f + sub_distance * 4.f + r.tminn;
-			if (DBG) { info.level = 1; info.sub_id = sub; }
+			if (INFO) { info.level = 1; info.sub_id = sub; }
 			r.hit = true;
 			return ST_NEED;
 		}
@@ -505,13 +507,13 @@ __device__ __forceinline__ int process_candidate(const DeviceScene& sc, const in
 		if (!BM_LDS_DMA) { brick.q0 = bq[0]; brick.q1 = bq[1]; brick.q2 = bq[2]; brick.q3 = bq[3]; }
 		if (intersect_grid<8, DBG>(o8, r.d, sx, sy, sz, r.dx, r.dy, r.dz, r.n, sub_distance, brick, 0u, sub, tally, lds_brick, walk_trips, reinterpret_cast<const uint32_t*>(bq))) {
 			r.distance = new_distance * 8.f + sub_distance + r.tminn;
-			if (DBG) { info.level = 2; info.sub_id = sub; }
+			if (INFO) { info.level = 2; info.sub_id = sub; }
 			r.hit = true;
 			return ST_NEED;
 		}
 	} else if (index & kUnloadedBit) {
 		// brick-request protocol (voxel.cuh:228-245): 32-bit atomics on the index word and the ring counter
-		const uint32_t old = atomicOr(&sc.index_grid[flat], kRequestedBit);
+		const uint32_t old = REQUEST ? atomicOr(&sc.index_grid[flat], kRequestedBit) : kRequestedBit;
 		if (!(old & kRequestedBit)) {
 			const uint32_t load_index = atomicAdd(sc.load_queue_count, 1u);
 			if (load_index < sc.queue_cap) {
@@ -523,7 +525,7 @@ __device__ __forceinline__ int process_candidate(const DeviceScene& sc, const in
 			}
 		}
 		r.distance = new_distance * 8.f + r.tminn;
-		if (DBG) { info.level = 3; info.sub_id = 0; }
+		if (INFO) { info.level = 3; info.sub_id = 0; }
 		r.hit = true;
 		return ST_NEED;
 	}

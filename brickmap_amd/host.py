@@ -13,7 +13,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, bm_camera, bm_counters, bm_edit, bm_frame_params, bm_scene_info, check
+from ._lib import (BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, BM_QUERY_LOD, BM_QUERY_NO_REQUESTS, bm_camera, bm_counters, bm_edit, bm_frame_params,
+                   bm_scene_info, check)
 
 
 # The reference's fly-through presets (performance_measure.h:4-25): camera position + (horizontal, vertical) angle.
@@ -203,6 +204,58 @@ def host_edit_supercell(grid_size, grid_height, sx, sy, sz, indices, bricks, edi
     return idx, buf[: n.value].copy()
 
 
+# ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmax", "<f4"), ("reserved", "<u4")])   # bm_ray
+RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("voxel", "<i4", 3), ("level", "<i4")])  # bm_ray_hit
+
+
+@dataclass
+class RayHits:
+    """Results of Scene.cast_rays, one row per ray, in the input's kind (torch CUDA tensors or numpy arrays): distance (+inf on a miss),
+    normal (entry face), voxel (int32 x 3, -1 on a miss), level (-1 miss, 0 brick LoD, 1 2^3 LoD, 2 voxel, 3 brick not resident).
+    `packed`: the bm_ray_hit records themselves (torch: float32 [n, 8] on the device; numpy: RAY_HIT_DTYPE)."""
+    distance: object
+    normal: object
+    voxel: object
+    level: object
+    packed: object = None
+
+    def __len__(self):
+        return len(self.distance)
+
+
+@dataclass
+class RayHit:
+    """One hit of Scene.pick: distance, normal (3 floats), voxel (3 ints), level."""
+    distance: float
+    normal: tuple
+    voxel: tuple
+    level: int
+
+
+def camera_pixel_rays(camera, width, height, px, py):
+    """bm_camera_pixel_rays (host only): rays of `camera` through continuous pixel positions (px[i], py[i]) of a width x height frame --
+    the frames' primary rays without jitter and lens; (x + 0.5, y + 0.5) is pixel (x, y)'s centre.  Returns a RAY_DTYPE array."""
+    px = np.ascontiguousarray(np.asarray(px, np.float32).reshape(-1))
+    py = np.ascontiguousarray(np.asarray(py, np.float32).reshape(-1))
+    assert px.shape == py.shape, "px and py: one value per ray"
+    out = np.zeros(len(px), RAY_DTYPE)
+    c = camera.to_c()
+    check(_lib.load().bm_camera_pixel_rays(C.byref(c), int(width), int(height), len(px), px.ctypes.data, py.ctypes.data, out.ctypes.data))
+    return out
+
+
+def pack_rays(origins, directions, tmax=None):
+    """numpy RAY_DTYPE records from N x 3 origins and directions (tmax: None = unbounded, a scalar, or one per ray)."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    assert len(o) == len(d), "one direction per origin"
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["origin"], rays["direction"] = o, d
+    rays["tmax"] = np.inf if tmax is None else np.asarray(tmax, np.float32)
+    return rays
+
+
 def probe_streams(count, device=0):
     """bm_probe_streams: `count` HIP streams (raw handles, ints) that demonstrably run side by side on `device` -- HIP maps streams
     onto a few hardware queues, and streams that share one do not overlap.  release_streams() gives them back."""
@@ -374,6 +427,74 @@ class Scene:
         a, b = C.c_float(0), C.c_float(0)
         check(self._L.bm_scene_last_edit_ms(self.gpuScene, C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
+
+    # ---- ray queries (bm_scene_cast_rays): issued like a frame -- after every edit and upload issued before, asynchronous to the host
+    def cast_rays_raw(self, n, rays_ptr, hits_ptr, flags=0, lod_origin=None, stream=None):
+        """bm_scene_cast_rays on device pointers (ints): n bm_ray records in, n bm_ray_hit records out."""
+        lo = None if lod_origin is None else (C.c_float * 3)(*[float(v) for v in lod_origin])
+        check(self._L.bm_scene_cast_rays(self.gpuScene, int(n), C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), int(flags), lo, self._stream(stream)))
+
+    def cast_rays(self, origins, directions=None, tmax=None, lod_origin=None, request=True, stream=None):
+        """First hit of each ray.  origins / directions: N x 3 torch CUDA tensors or numpy arrays; or, with directions=None, the packed
+        bm_ray records themselves -- a float32 [N, 8] CUDA tensor (used as it is, no copy) or a RAY_DTYPE array.  tmax: None (unbounded),
+        a scalar or one per ray.  lod_origin: None = exact (every brick at voxel level), else resolve with the frames' LoD rule around
+        this point.  request=False: bricks that are not resident are reported (level 3) but not requested.  stream: a raw HIP stream handle
+        (None = torch's current stream); the query runs there, behind the work already queued on the current stream.  Torch input: the
+        result is on the device, ready in stream order on `stream`, and the host does not wait; numpy input: the call waits and returns
+        numpy arrays."""
+        import torch
+        flags = (BM_QUERY_LOD if lod_origin is not None else 0) | (0 if request else BM_QUERY_NO_REQUESTS)
+        dev = origins.device if isinstance(origins, torch.Tensor) else torch.device("cuda", self.device)
+        # Everything the query touches is made on the stream it runs on: the packed rays and the hits come from that stream's pool, the
+        # stream first waits for the work queued so far on the current stream (which wrote the inputs), and an input tensor read there is
+        # marked as in use by it, so that the caching allocator does not hand its memory out again while the query still reads it.
+        current = torch.cuda.current_stream(dev)
+        target = current if stream is None else torch.cuda.ExternalStream(int(stream), device=dev)
+        other = target.cuda_stream != current.cuda_stream
+        if other:
+            target.wait_stream(current)
+        with torch.cuda.stream(target):
+            if isinstance(origins, torch.Tensor):
+                if directions is None:
+                    rays = origins
+                    assert rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8 and rays.is_contiguous(), "packed rays: float32 [N, 8]"
+                    inputs = [rays]
+                else:
+                    n = origins.shape[0]
+                    t = torch.full((n, 1), float("inf"), dtype=torch.float32, device=dev) if tmax is None else \
+                        torch.as_tensor(tmax, dtype=torch.float32, device=dev).reshape(-1, 1).expand(n, 1)
+                    inputs = [origins, directions] + ([t] if isinstance(tmax, torch.Tensor) else [])
+                    rays = torch.cat([origins.to(torch.float32).reshape(n, 3), directions.to(torch.float32).reshape(n, 3), t,
+                                      torch.zeros((n, 1), dtype=torch.float32, device=dev)], dim=1).contiguous()
+                assert rays.is_cuda, "torch rays must be on the GPU"
+                if other:
+                    for x in inputs:
+                        x.record_stream(target)
+                n = rays.shape[0]
+                hits = torch.empty((n, 8), dtype=torch.float32, device=dev)
+                self.cast_rays_raw(n, rays.data_ptr(), hits.data_ptr(), flags, lod_origin, target.cuda_stream)
+                return RayHits(hits[:, 0], hits[:, 1:4], hits[:, 4:7].view(torch.int32), hits[:, 7].view(torch.int32), hits)
+            rays = origins if directions is None else pack_rays(origins, directions, tmax)
+            rays = np.ascontiguousarray(rays)
+            assert rays.dtype == RAY_DTYPE, "packed rays: a RAY_DTYPE array"
+            n = len(rays)
+            out = np.zeros(n, RAY_HIT_DTYPE)
+            if n:
+                d_rays = torch.from_numpy(rays.view(np.float32).reshape(n, 8)).to(dev)
+                d_hits = torch.empty((n, 8), dtype=torch.float32, device=dev)
+                self.cast_rays_raw(n, d_rays.data_ptr(), d_hits.data_ptr(), flags, lod_origin, target.cuda_stream)
+                target.synchronize()
+                out = d_hits.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
+            return RayHits(out["distance"], out["normal"], out["voxel"], out["level"], out)
+
+    def pick(self, camera, x, y, width, height, lod_origin=None):
+        """The voxel under pixel (x, y) of a width x height frame of `camera`: one ray through the pixel's centre, one query, then the host
+        waits.  Returns a RayHit, or None on a miss.  (A level-3 hit means the brick is not resident yet: service the load queue and pick again.)"""
+        rays = camera_pixel_rays(camera, width, height, [x + 0.5], [y + 0.5])
+        h = self.cast_rays(rays, lod_origin=lod_origin).packed[0]
+        if int(h["level"]) < 0:
+            return None
+        return RayHit(float(h["distance"]), tuple(float(v) for v in h["normal"]), tuple(int(v) for v in h["voxel"]), int(h["level"]))
 
     def synchronize(self):
         check(self._L.bm_synchronize(self.gpuScene))

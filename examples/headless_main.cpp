@@ -1,8 +1,12 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--dig x,y,z,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--dig x,y,z,r] [--dig-at px,py,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
+// --dig-at picks the voxel under pixel (px, py) of the first frame's camera (Scene::pick) and carves a sphere of radius r there; the
+// world streams, so while the pick lands on a brick that is not resident yet (level 3) the load queue is serviced and the pick repeated
+// (at most 8 times).  Prints `picked voxel x,y,z level L`; after the carve, what the same pixel sees now.  A pick that stays
+// unresolved (level 3) digs nothing.
 // With `wavefront` the frames are rendered with the reference's own queue schedule (one segment per call); with `ring` the
 // world is made resident first and all frames are ONE launch of the persistent kernel (launch_frames, the frame ring).
 #include <cstdint>
@@ -19,7 +23,15 @@ using namespace brickmap;
 int main(int argc_in, char** argv_in) {
 	std::vector<char*> args;
 	int dig[4] = {0, 0, 0, -1};
+	int dig_at[3] = {0, 0, -1};
 	for (int i = 0; i < argc_in; ++i) {
+		if (std::string(argv_in[i]) == "--dig-at" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d,%d", &dig_at[0], &dig_at[1], &dig_at[2]) != 3 || dig_at[2] < 0) {
+				std::cerr << "--dig-at wants px,py,r (r >= 0)\n";
+				return 2;
+			}
+			continue;
+		}
 		if (std::string(argv_in[i]) == "--dig" && i + 1 < argc_in) {
 			if (std::sscanf(argv_in[++i], "%d,%d,%d,%d", &dig[0], &dig[1], &dig[2], &dig[3]) != 4 || dig[3] < 0) {
 				std::cerr << "--dig wants x,y,z,r (r >= 0)\n";
@@ -45,6 +57,28 @@ int main(int argc_in, char** argv_in) {
 	camera.horizontal_angle = 0.8;
 	camera.vertical_angle = -0.5;
 	camera.update();                            // main.cpp:140
+	if (dig_at[2] >= 0) {
+		if (dig_at[0] < 0 || dig_at[1] < 0 || dig_at[0] >= static_cast<int>(width) || dig_at[1] >= static_cast<int>(height)) {
+			std::cerr << "--dig-at: pixel outside the frame\n";
+			return 2;
+		}
+		auto pick = [&]() {
+			bm_ray_hit hit = scene.pick(camera, static_cast<int>(width), static_cast<int>(height), dig_at[0], dig_at[1]);
+			for (int k = 0; k < 8 && hit.level == 3; ++k) { // the brick was requested by the pick: make it resident, ask again
+				scene.process_load_queue();
+				hit = scene.pick(camera, static_cast<int>(width), static_cast<int>(height), dig_at[0], dig_at[1]);
+			}
+			return hit;
+		};
+		const bm_ray_hit hit = pick();
+		std::printf("picked voxel %d,%d,%d level %d\n", hit.voxel[0], hit.voxel[1], hit.voxel[2], hit.level);
+		if (hit.level >= 0 && hit.level <= 2) { // a resolved hit (level 3 after 8 rounds: the brick never arrived, nothing to dig at)
+			scene.carve_sphere(hit.voxel, dig_at[2]);
+			const bm_ray_hit now = pick();
+			std::printf("carved radius %d at %d,%d,%d; the pixel now sees voxel %d,%d,%d level %d\n", dig_at[2], hit.voxel[0], hit.voxel[1],
+						hit.voxel[2], now.voxel[0], now.voxel[1], now.voxel[2], now.level);
+		}
+	}
 
 	if (wavefront) {
 		Wavefront queues(scene.gpuScene); // state.h:19-21: ray_buffer_work / ray_buffer_next / shadow_queue_buffer

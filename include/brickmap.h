@@ -219,6 +219,45 @@ BM_API int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capaci
  * and the cube-field update (0 when no cell's occupancy changed); waits for that batch */
 BM_API int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms);
 
+/* ---- ray queries against the live scene (no reference counterpart: the reference only traces inside its frame kernels).
+ * What does a ray hit -- the voxel under the cursor, the ground under a walking camera, line of sight, collision probes.
+ * A query walks exactly as the frames' extend kernel does (csrc/traverse.h), so a hit equals the reference's intersect_voxel bit
+ * for bit: distance, entry normal, level and cell. */
+typedef struct bm_ray {         /* 32 bytes */
+	float origin[3];
+	float direction[3];         /* need not be unit length; the hit point is origin + distance * direction */
+	float tmax;                 /* hits with distance > tmax are reported as misses; +inf = unbounded */
+	uint32_t reserved;          /* 0 (a ray with another value is reported as a miss) */
+} bm_ray;
+typedef struct bm_ray_hit {     /* 32 bytes */
+	float distance;             /* +inf on a miss */
+	float normal[3];            /* entry face of the hit cell; (0,0,0) for a ray that starts inside a solid voxel, and on a miss */
+	int32_t voxel[3];           /* level 2: the voxel hit; level 1: first voxel of the 4^3 block; levels 0 and 3: first voxel of the brick; -1 on a miss */
+	int32_t level;              /* -1 miss, 0 brick-LoD hit, 1 2^3-LoD hit, 2 voxel hit, 3 unresolved: the brick is not resident */
+} bm_ray_hit;
+#define BM_QUERY_LOD         1u /* resolve with the frames' LoD rule around lod_origin (campos = int(lod_origin / 8), as in fill_frame_constants) */
+#define BM_QUERY_NO_REQUESTS 2u /* a non-resident brick is reported as level 3 but not requested, and no index word is written */
+/* The first hit of each of n rays (rays_dev, hits_dev: device memory, n records each; hit i belongs to ray i).
+ *  - Default (exact): every brick is walked at voxel level, whatever its distance; with BM_QUERY_LOD the frames' LoD rule applies
+ *    around lod_origin (voxel coordinates), with the scene's LoD distances (bm_scene_set_lod).
+ *  - A brick that is not resident gives level 3 at its entry distance and is requested through the frames' protocol (unless
+ *    BM_QUERY_NO_REQUESTS); the next bm_scene_process_load_queue services it, so a preloaded scene always answers exactly.
+ *  - tmax: the result equals the unbounded query's filtered by distance <= tmax.  The walk stops at the first brick cell whose
+ *    entry distance is beyond tmax and files no request for it.
+ *  - A zero or non-finite direction, or a non-finite origin, is a miss (checked before the walk); zero components are fine.
+ *  - Ordering: issued like a frame on hip_stream -- it sees every edit and upload issued before it, on any stream, and
+ *    bm_scene_process_load_queue orders itself behind it; asynchronous to the host.  It only reads the world (apart from request
+ *    atomics), so it may run beside frames.
+ *  - n == 0 is a no-op.  n < 0, n > 2^28, NULL buffers, unknown flags, or BM_QUERY_LOD with a NULL or non-finite lod_origin: BM_EINVAL;
+ *    a scene not on the device, or a failed one: BM_ESTATE.  Nothing is launched on error. */
+BM_API int bm_scene_cast_rays(bm_scene* scene, int64_t n, const bm_ray* rays_dev, bm_ray_hit* hits_dev, uint32_t flags,
+                              const float lod_origin[3], void* hip_stream);
+/* host only: pixel rays of a camera for a width x height frame -- the frames' primary_ray without jitter and lens: ray i starts at
+ * the camera position and passes through continuous pixel position (px[i], py[i]); (x + 0.5, y + 0.5) is pixel (x, y)'s centre.
+ * direction = normalize(dir + right * ni + up * nj) in the operation order of csrc/traverse.h primary_ray, with the camera basis of the
+ * frames; tmax = +inf. */
+BM_API int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t n, const float* px, const float* py, bm_ray* out);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

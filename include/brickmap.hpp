@@ -53,6 +53,21 @@ struct Camera { // camera.h:3-24
 		const float inv = 1.0f / std::sqrt((d.x * d.x + d.y * d.y) + d.z * d.z); // glm::normalize
 		direction = {d.x * inv, d.y * inv, d.z * inv};
 	}
+	bm_camera to_c() const {
+		bm_camera cam{};
+		cam.position[0] = position.x; cam.position[1] = position.y; cam.position[2] = position.z;
+		cam.direction[0] = direction.x; cam.direction[1] = direction.y; cam.direction[2] = direction.z;
+		cam.up[0] = up.x; cam.up[1] = up.y; cam.up[2] = up.z;
+		cam.focal_distance = focalDistance;
+		cam.lens_radius = lensRadius;
+		return cam;
+	}
+	// rays through continuous pixel positions (px[i], py[i]) of a width x height frame -- the frames' primary rays without jitter and
+	// lens; (x + 0.5, y + 0.5) is pixel (x, y)'s centre (bm_camera_pixel_rays, no counterpart in the reference)
+	void pixel_rays(int width, int height, int64_t n, const float* px, const float* py, bm_ray* out) const {
+		const bm_camera cam = to_c();
+		BM_CHECKED(bm_camera_pixel_rays(&cam, width, height, n, px, py, out));
+	}
 };
 inline Camera camera; // camera.h:24 `extern Camera camera;`
 
@@ -64,7 +79,9 @@ public:
 	GPUScene gpuScene;
 
 	// world dimensions are constexpr in the reference (variables.h:7-8: 4096 x 4096 x 512 voxels)
-	explicit Scene(int grid_size = 4096, int grid_height = 512, int device = 0) { BM_CHECKED(bm_scene_create(device, grid_size, grid_height, &gpuScene.handle)); }
+	explicit Scene(int grid_size = 4096, int grid_height = 512, int device = 0) : device_(device) {
+		BM_CHECKED(bm_scene_create(device, grid_size, grid_height, &gpuScene.handle));
+	}
 	~Scene() { bm_scene_destroy(gpuScene.handle); }
 	Scene(const Scene&) = delete;
 	Scene& operator=(const Scene&) = delete;
@@ -97,6 +114,33 @@ public:
 	void clear_box(const int lo[3], const int hi[3]) { edit({box(BM_EDIT_CLEAR, lo, hi)}); }
 	void fill_sphere(const int center[3], int radius) { edit({sphere(BM_EDIT_SET, center, radius)}); }
 	void carve_sphere(const int center[3], int radius) { edit({sphere(BM_EDIT_CLEAR, center, radius)}); }
+
+	// ray queries (no counterpart in the reference; bm_scene_cast_rays): the first hit of n rays, device buffers in and out, issued
+	// like a frame on hip_stream (after every edit and upload issued before it), asynchronous to the host
+	void cast_rays(int64_t n, const bm_ray* rays_dev, bm_ray_hit* hits_dev, uint32_t flags = 0, const float* lod_origin = nullptr,
+				   void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_cast_rays(gpuScene.handle, n, rays_dev, hits_dev, flags, lod_origin, hip_stream));
+	}
+	// the hit under pixel (x, y) of a width x height frame of `cam`: one ray through the pixel's centre, one query, then the host waits.
+	// level -1 = nothing there; level 3 = the brick is not resident yet (service the load queue, pick again)
+	bm_ray_hit pick(const Camera& cam, int width, int height, int x, int y) {
+		const float px = static_cast<float>(x) + 0.5f, py = static_cast<float>(y) + 0.5f;
+		bm_ray ray{};
+		cam.pixel_rays(width, height, 1, &px, &py, &ray);
+		void* buf = nullptr;
+		BM_CHECKED(bm_buffer_alloc(device_, sizeof(bm_ray) + sizeof(bm_ray_hit), &buf));
+		bm_ray* d_ray = static_cast<bm_ray*>(buf);
+		bm_ray_hit* d_hit = reinterpret_cast<bm_ray_hit*>(static_cast<char*>(buf) + sizeof(bm_ray));
+		BM_CHECKED(bm_buffer_write(device_, d_ray, &ray, sizeof ray));
+		cast_rays(1, d_ray, d_hit);
+		bm_ray_hit hit{};
+		BM_CHECKED(bm_buffer_read(device_, &hit, d_hit, sizeof hit)); // (waits for the device)
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return hit;
+	}
+
+private:
+	int device_;
 };
 
 // Which part of the frame this process renders (no counterpart in the reference, which is single-GPU: main.cpp:89 computes
@@ -137,15 +181,7 @@ private:
 };
 
 namespace detail {
-inline bm_camera camera_to_c() {
-	bm_camera cam{};
-	cam.position[0] = camera.position.x; cam.position[1] = camera.position.y; cam.position[2] = camera.position.z;
-	cam.direction[0] = camera.direction.x; cam.direction[1] = camera.direction.y; cam.direction[2] = camera.direction.z;
-	cam.up[0] = camera.up.x; cam.up[1] = camera.up.y; cam.up[2] = camera.up.z;
-	cam.focal_distance = camera.focalDistance;
-	cam.lens_radius = camera.lensRadius;
-	return cam;
-}
+inline bm_camera camera_to_c() { return camera.to_c(); }
 inline bm_frame_params frame_params(const State& state, int max_bounces) {
 	bm_frame_params fp{};
 	fp.width = static_cast<int32_t>(state.screen_width);
