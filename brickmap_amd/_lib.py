@@ -18,6 +18,8 @@ BM_FLAG_ORDERED = 16
 BM_FLAG_RAY_DIGEST = 32
 BM_QUERY_LOD = 1
 BM_QUERY_NO_REQUESTS = 2
+BM_VOXELS_HOST = 0
+BM_VOXELS_DEVICE = 1
 BRICK_INDEX_BITS = 0x00000FFF
 BRICK_LOD_BITS = 0x000FF000
 BRICK_REQUESTED_BIT = 0x20000000
@@ -123,11 +125,15 @@ SIGNATURES = {
     "bm_scene_device_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_scene_host_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_scene_last_edit_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "bm_scene_load_voxels": (_i, [_vp, _vp, C.c_size_t, _i, _vp]),
+    "bm_scene_host_voxels": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bm_scene_last_load_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bm_scene_cast_rays": (_i, [_vp, C.c_int64, _vp, _vp, C.c_uint32, _vp, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_host_column_heights": (_i, [_i, _i, _i, _i, _vp]),
     "bm_host_generate_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32]),
     "bm_host_edit_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32, _i, C.POINTER(bm_edit)]),
+    "bm_host_load_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _u32p]),
     "bm_host_cube_field": (_i, [_i, _i, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_buffer_alloc": (_i, [_i, C.c_size_t, C.POINTER(_vp)]),
     "bm_buffer_free": (_i, [_i, _vp]),

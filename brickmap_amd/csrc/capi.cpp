@@ -125,6 +125,13 @@ int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, s
 int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.host_cube_field(dst, capacity, bytes); }
 int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms) { BM_NEED(scene); return scene->impl.last_edit_ms(scatter_ms, field_ms); }
 
+int bm_scene_load_voxels(bm_scene* scene, const uint8_t* voxels, size_t bytes, int where, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.load_voxels(voxels, bytes, where, static_cast<hipStream_t>(hip_stream));
+}
+int bm_scene_host_voxels(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.host_voxels(dst, capacity, bytes); }
+int bm_scene_last_load_ms(bm_scene* scene, float* pack_ms, float* field_ms, float* mirror_ms) { BM_NEED(scene); return scene->impl.last_load_ms(pack_ms, field_ms, mirror_ms); }
+
 int bm_scene_cast_rays(bm_scene* scene, int64_t n, const bm_ray* rays_dev, bm_ray_hit* hits_dev, uint32_t flags, const float lod_origin[3], void* hip_stream) {
 	BM_NEED(scene);
 	return scene->impl.cast_rays(n, rays_dev, hits_dev, flags, lod_origin, static_cast<hipStream_t>(hip_stream));
@@ -225,6 +232,22 @@ int bm_host_edit_supercell(int grid_size, int grid_height, int sx, int sy, int s
 		if (!used[s]) c.free_slots.push_back(s);
 	bm::World::edit_supercell(w.dims, c, sx, sy, sz, edits, count, nullptr);
 	if (c.bricks.size() > brick_capacity) { set_error("brick buffer too small for the edited supercell"); return BM_EINVAL; }
+	std::memcpy(indices4096, c.indices.data(), bm::kCellsPerSupercell * sizeof(uint32_t));
+	if (!c.bricks.empty()) std::memcpy(bricks, c.bricks.data(), c.bricks.size() * sizeof(bm::Brick));
+	*brick_count = static_cast<uint32_t>(c.bricks.size());
+	return 0;
+}
+
+int bm_host_load_supercell(int grid_size, int grid_height, int sx, int sy, int sz, const uint8_t* voxels, uint32_t* indices4096, uint32_t* bricks,
+						   uint32_t* brick_count) {
+	bm::WorldDims dims;
+	if (!dims.set(grid_size, grid_height) || sx < 0 || sy < 0 || sz < 0 || sx >= dims.supergrid_xy || sy >= dims.supergrid_xy || sz >= dims.supergrid_z) {
+		set_error("bad world dimensions or supercell");
+		return BM_EINVAL;
+	}
+	if (!voxels || !indices4096 || !bricks || !brick_count) { set_error("null argument"); return BM_EINVAL; }
+	bm::HostSupercell c;
+	bm::World::load_supercell(dims, c, sx, sy, sz, voxels);
 	std::memcpy(indices4096, c.indices.data(), bm::kCellsPerSupercell * sizeof(uint32_t));
 	if (!c.bricks.empty()) std::memcpy(bricks, c.bricks.data(), c.bricks.size() * sizeof(bm::Brick));
 	*brick_count = static_cast<uint32_t>(c.bricks.size());

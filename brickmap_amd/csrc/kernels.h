@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip and wavefront.hip
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, query.hip and wavefront.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,6 +35,19 @@ size_t field_update_tmp_bytes(const FieldUpdate& u); // intermediate planes of t
 void launch_edit_scatter(const uint32_t* cells, const uint32_t* words, const uint32_t* slots, const uint32_t* bricks, uint32_t count,
 						 uint32_t* index_grid, uint32_t* arena, hipStream_t stream);
 void launch_field_update(const uint32_t* index_grid, uint8_t* field, uint8_t* tmp, const FieldUpdate& u, hipStream_t stream);
+
+// dense voxels -> scene (load.hip): the volume is V[z][y][x], one byte per voxel, in device memory.  classify leaves lod << 12 in every
+// cell's index word; number turns the words into slot | loaded | lod << 12 (slots in local cell order), fills counts[supercells] and
+// pool_base[supercells] (exclusive scan of the counts) and total[2] (the 64-bit brick total, low word first); pack writes the bricks
+// to arena[pool_base[sc] + slot] -- the arena must hold `total` bricks by then
+struct LoadDims {
+	uint32_t grid_size;      // voxels along x and y
+	uint32_t sg_xy, sg_xy2;  // supercells per axis, squared
+	uint32_t supercells;
+};
+void launch_load_classify(const uint8_t* voxels, uint32_t* index_grid, const LoadDims& d, hipStream_t stream);
+void launch_load_number(uint32_t* index_grid, uint32_t* counts, uint32_t* pool_base, uint32_t* total, const LoadDims& d, hipStream_t stream);
+void launch_load_pack(const uint8_t* voxels, const uint32_t* index_grid, const uint32_t* pool_base, uint32_t* arena, const LoadDims& d, hipStream_t stream);
 
 // ray queries (query.hip): n bm_ray records in, n bm_ray_hit records out; ticket = a zeroed word; campos = the LoD centre in brick cells
 int query_blocks_per_cu(bool request);

@@ -2,6 +2,7 @@
 #include "scene.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -10,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <thread>
 #include <unordered_map>
 
 #include "kernels.h"
@@ -229,6 +231,7 @@ Scene::~Scene() {
 	if (ev_edit_) hipEventDestroy(ev_edit_);
 	if (ev_edit_caller_) hipEventDestroy(ev_edit_caller_);
 	for (hipEvent_t e : ev_edit_time_) if (e) hipEventDestroy(e);
+	for (hipEvent_t e : ev_load_time_) if (e) hipEventDestroy(e);
 	if (d_counters_) hipFree(d_counters_);
 	if (d_work_counter_) hipFree(d_work_counter_);
 	if (d_query_tickets_) hipFree(d_query_tickets_);
@@ -580,6 +583,26 @@ int Scene::allocate_device() {
 	for (int i = 0; i < d.supercells; ++i) run += world.supercells[i].bricks.size();
 	if (run >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
 	total_bricks_ = run;
+	if (int e = alloc_index_grid()) return e;
+	if (int e = arena_open(4 * run + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
+	if (int e = alloc_cube_field()) return e;
+	{ // the host builds the field with tight rows (world.cpp) and every slice is copied row by row
+		std::vector<uint8_t> field;
+		world.build_cube_field(field, 8);
+		const int X = d.cells + 2, Z = d.cells_height + 2;
+		// 8 planes x Z slices, each X rows of X bytes -> rows of 2^shift bytes (the padding is never read)
+		for (int o = 0; o < 8; ++o)
+			BM_HIP(hipMemcpy2D(d_cube_field_ + static_cast<size_t>(o) * view_.cf_plane, static_cast<size_t>(1) << view_.cf_shift, field.data() + static_cast<size_t>(o) * X * X * Z, X, X,
+							   static_cast<size_t>(X) * Z, hipMemcpyHostToDevice));
+	}
+	set_view_dims();
+	on_device_ = true;
+	return reset_residency();
+}
+
+// the flat index grid and one pool-base word per supercell
+int Scene::alloc_index_grid() {
+	const WorldDims& d = world.dims;
 	const size_t index_bytes = static_cast<size_t>(d.supercells) * kCellsPerSupercell * sizeof(uint32_t);
 	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_index_grid_), index_bytes));
 	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_pool_base_), static_cast<size_t>(d.supercells) * sizeof(uint32_t)));
@@ -587,30 +610,33 @@ int Scene::allocate_device() {
 	view_.index_grid = d_index_grid_;
 	view_.pool_base = d_pool_base_;
 	view_.brick_arena = nullptr;
-	if (int e = arena_open(4 * run + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
-	{ // octant cube field: what the walk reads instead of index words while it crosses empty space.  Device layout: rows padded to a
-	  // power of two, so that a cell's entry offset -- which is what a ray carries as its position (traverse.h cell_offset) -- moves by
-	  // +-1 / +- 2^shift / +- slice pitch; the host builds the field with tight rows (world.cpp) and every slice is copied row by row.
-		std::vector<uint8_t> field;
-		world.build_cube_field(field, 8);
-		const int X = d.cells + 2, Z = d.cells_height + 2;
-		int shift = 2;
-		while ((1 << shift) < X) ++shift;
-		const uint64_t pxy = static_cast<uint64_t>(X) << shift, plane = pxy * static_cast<uint64_t>(Z);
-		if (pxy >= (1ull << 23) || plane * 8 >= (1ull << 32)) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
-		BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cube_field_), plane * 8));
-		BM_HIP(hipMemset(d_cube_field_, 255, plane * 8)); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
-		// 8 planes x Z slices, each X rows of X bytes -> rows of 2^shift bytes (the padding is never read)
-		for (int o = 0; o < 8; ++o)
-			BM_HIP(hipMemcpy2D(d_cube_field_ + static_cast<size_t>(o) * plane, static_cast<size_t>(1) << shift, field.data() + static_cast<size_t>(o) * X * X * Z, X, X,
-							   static_cast<size_t>(X) * Z, hipMemcpyHostToDevice));
-		view_.cf_shift = shift;
-		view_.cf_pxy = static_cast<uint32_t>(pxy);
-		view_.cf_plane = static_cast<uint32_t>(plane);
-		division_magic(view_.cf_pxy, &view_.cf_magic, &view_.cf_magic_shift);
-		view_.cube_field = d_cube_field_;
-		cube_field_bytes_ = plane * 8;
-	}
+	return 0;
+}
+
+// octant cube field: what the walk reads instead of index words while it crosses empty space.  Device layout: rows padded to a
+// power of two, so that a cell's entry offset -- which is what a ray carries as its position (traverse.h cell_offset) -- moves by
+// +-1 / +- 2^shift / +- slice pitch.  Allocated and set to 255 everywhere; the interior is the caller's (a host build copied up, or
+// the GPU passes of edit.hip).
+int Scene::alloc_cube_field() {
+	const WorldDims& d = world.dims;
+	const int X = d.cells + 2, Z = d.cells_height + 2;
+	int shift = 2;
+	while ((1 << shift) < X) ++shift;
+	const uint64_t pxy = static_cast<uint64_t>(X) << shift, plane = pxy * static_cast<uint64_t>(Z);
+	if (pxy >= (1ull << 23) || plane * 8 >= (1ull << 32)) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
+	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cube_field_), plane * 8));
+	BM_HIP(hipMemset(d_cube_field_, 255, plane * 8)); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
+	view_.cf_shift = shift;
+	view_.cf_pxy = static_cast<uint32_t>(pxy);
+	view_.cf_plane = static_cast<uint32_t>(plane);
+	division_magic(view_.cf_pxy, &view_.cf_magic, &view_.cf_magic_shift);
+	view_.cube_field = d_cube_field_;
+	cube_field_bytes_ = plane * 8;
+	return 0;
+}
+
+void Scene::set_view_dims() {
+	const WorldDims& d = world.dims;
 	view_.cells = d.cells;
 	view_.cells_height = d.cells_height;
 	view_.sg_xy = d.supergrid_xy;
@@ -619,8 +645,6 @@ int Scene::allocate_device() {
 	view_.grid_height_f = static_cast<float>(d.grid_height);
 	view_.lod_distance_8x8x8 = lod8_;
 	view_.lod_distance_2x2x2 = lod2_;
-	on_device_ = true;
-	return reset_residency();
 }
 
 int Scene::generate(int threads) {
@@ -732,6 +756,180 @@ int Scene::preload_all() {
 	stream_batches_ = stream_host_ns_ = 0;
 	upload_seq_ = 0;
 	for (FrameStream& f : frame_streams_) f.upload_seen = 0;
+	return 0;
+}
+
+// ---------------------------------------------------------------- dense voxels -> scene (bm_scene_load_voxels)
+// The canonical build of a dense volume (world.h load_voxels), on the device in the preloaded state.  Host memory: World::load_voxels
+// on CPU threads, then the generate route's allocate_device + preload_all.  Device memory: load.hip packs the volume where it lies --
+// classify and number fill the index grid and the pool bases, the brick total comes back to size the arena exactly, pack writes the
+// bricks, the cube-field passes of edit.hip run over the whole grid, and words and bricks are copied back into the host world, which
+// ends up the object the host route builds.  Everything runs on the load stream behind the work queued on the caller's stream.
+int Scene::load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream_t stream) {
+	const WorldDims& d = world.dims;
+	const size_t need = static_cast<size_t>(d.grid_size) * d.grid_size * d.grid_height;
+	if (!voxels) { set_error("bm_scene_load_voxels: null volume"); return BM_EINVAL; }
+	if (bytes != need) { set_error("bm_scene_load_voxels: the volume must hold grid_size^2 * grid_height bytes (" + std::to_string(need) + ")"); return BM_EINVAL; }
+	if (where != BM_VOXELS_HOST && where != BM_VOXELS_DEVICE) { set_error("bm_scene_load_voxels: `where` is BM_VOXELS_HOST or BM_VOXELS_DEVICE"); return BM_EINVAL; }
+	if (static_cast<uint64_t>(d.supercells) * kCellsPerSupercell >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	if (where == BM_VOXELS_DEVICE) { // the kernels read [voxels, voxels + bytes): it has to be memory of this device, all of it
+		hipPointerAttribute_t attr{};
+		void* base = nullptr;
+		size_t size = 0;
+		if (hipPointerGetAttributes(&attr, voxels) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device_ ||
+			hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, const_cast<uint8_t*>(voxels)) != hipSuccess ||
+			static_cast<const uint8_t*>(base) + size < voxels + bytes) {
+			(void)hipGetLastError();
+			set_error("bm_scene_load_voxels: BM_VOXELS_DEVICE needs `bytes` bytes of memory of the scene's device");
+			return BM_EINVAL;
+		}
+	}
+	BM_HIP(hipDeviceSynchronize()); // no frame, edit or upload in flight from here on: the old world (if any) can go
+	load_timed_ = false;
+	if (where == BM_VOXELS_HOST) {
+		world.load_voxels(voxels, 16);
+		if (int e = allocate_device()) return e;
+		return preload_all();
+	}
+	const int e = load_voxels_device(voxels, stream);
+	if (e) { // no half-built world: the scene is back to "created"
+		(void)hipDeviceSynchronize();
+		free_device();
+		world.supercells.clear();
+		world.generated = false;
+	}
+	return e;
+}
+
+int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
+	const WorldDims& d = world.dims;
+	free_device();
+	world.generated = false;
+	for (hipEvent_t& ev : ev_load_time_) if (!ev) BM_HIP(hipEventCreate(&ev));
+	if (int e = alloc_index_grid()) return e;
+	if (int e = alloc_cube_field()) return e;
+	set_view_dims();
+	LoadDims ld{static_cast<uint32_t>(d.grid_size), static_cast<uint32_t>(d.supergrid_xy), static_cast<uint32_t>(d.supergrid_xy * d.supergrid_xy),
+				static_cast<uint32_t>(d.supercells)};
+	// temporaries: one count per supercell + the 64-bit total; the intermediate planes of the field passes
+	struct Temp {
+		uint32_t* p = nullptr;
+		~Temp() { if (p) (void)hipFree(p); }
+	} counts;
+	BM_HIP(hipMalloc(reinterpret_cast<void**>(&counts.p), (static_cast<size_t>(d.supercells) + 2) * sizeof(uint32_t)));
+	uint32_t* d_total = counts.p + d.supercells;
+	// the field comes from the update of edit.hip with the box = every cell, into the field alloc_cube_field set to 255
+	FieldUpdate fu{};
+	fu.rx0 = fu.ry0 = fu.rz0 = fu.ay0 = fu.bz0 = 1;
+	fu.rx1 = fu.ry1 = fu.ay1 = d.cells + 1;
+	fu.rz1 = fu.bz1 = d.cells_height + 1;
+	fu.cells = d.cells; fu.cells_height = d.cells_height;
+	fu.sg_xy = d.supergrid_xy; fu.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
+	fu.cf_shift = view_.cf_shift; fu.cf_pxy = view_.cf_pxy; fu.cf_plane = view_.cf_plane;
+	if (field_update_tmp_bytes(fu) > cf_tmp_cap_) {
+		if (d_cf_tmp_) { BM_HIP(hipFree(d_cf_tmp_)); d_cf_tmp_ = nullptr; }
+		cf_tmp_cap_ = 0;
+		BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cf_tmp_), field_update_tmp_bytes(fu)));
+		cf_tmp_cap_ = field_update_tmp_bytes(fu);
+	}
+	BM_HIP(hipEventRecord(ev_edit_caller_, stream)); // the volume is whatever the caller's stream has written by now
+	BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
+	// ---- classify + number
+	BM_HIP(hipEventRecord(ev_load_time_[0], load_stream_));
+	launch_load_classify(voxels, d_index_grid_, ld, load_stream_);
+	BM_HIP(hipGetLastError());
+	launch_load_number(d_index_grid_, counts.p, d_pool_base_, d_total, ld, load_stream_);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_load_time_[1], load_stream_));
+	uint32_t total_words[2] = {0, 0};
+	BM_HIP(hipMemcpyAsync(total_words, d_total, sizeof total_words, hipMemcpyDeviceToHost, load_stream_));
+	BM_HIP(hipStreamSynchronize(load_stream_)); // the one host round trip: the arena is sized by what the volume holds
+	const uint64_t total = total_words[0] | (static_cast<uint64_t>(total_words[1]) << 32);
+	if (total >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
+	total_bricks_ = total;
+	if (int e = arena_open(4 * total + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
+	arena_reset();
+	if (int e = arena_reserve(std::max<uint64_t>(total, 1), true)) return e;
+	// ---- pack
+	BM_HIP(hipEventRecord(ev_load_time_[2], load_stream_));
+	launch_load_pack(voxels, d_index_grid_, d_pool_base_, d_arena_, ld, load_stream_);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_load_time_[3], load_stream_));
+	// ---- field
+	launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_load_time_[4], load_stream_));
+	// ---- mirror: the host world becomes what World::load_voxels builds, in the state preload_all leaves it in
+	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell), bases(d.supercells);
+	std::vector<Brick> bricks(total);
+	BM_HIP(hipMemcpyAsync(words.data(), d_index_grid_, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
+	BM_HIP(hipMemcpyAsync(bases.data(), d_pool_base_, bases.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
+	if (total) BM_HIP(hipMemcpyAsync(bricks.data(), d_arena_, total * sizeof(Brick), hipMemcpyDeviceToHost, load_stream_));
+	for (int r = 0; r < 2; ++r) BM_HIP(hipMemsetAsync(d_load_count_[r], 0, sizeof(uint32_t), load_stream_));
+	BM_HIP(hipEventRecord(ev_load_time_[5], load_stream_));
+	BM_HIP(hipStreamSynchronize(load_stream_));
+	world.supercells.clear();
+	world.supercells.resize(d.supercells);
+	std::atomic<int> next{0};
+	auto fill = [&]() {
+		for (int i = next.fetch_add(1); i < d.supercells; i = next.fetch_add(1)) {
+			HostSupercell& c = world.supercells[i];
+			const uint32_t* w = &words[static_cast<size_t>(i) * kCellsPerSupercell];
+			const uint64_t end = i + 1 < d.supercells ? bases[i + 1] : total;
+			c.indices.assign(w, w + kCellsPerSupercell);
+			c.bricks.assign(bricks.begin() + bases[i], bricks.begin() + static_cast<ptrdiff_t>(end));
+			c.pool_base = bases[i];
+			c.pool_capacity = c.resident = static_cast<uint32_t>(c.bricks.size());
+			c.dev_slot.resize(c.bricks.size());
+			for (size_t s = 0; s < c.bricks.size(); ++s) c.dev_slot[s] = static_cast<uint16_t>(s);
+		}
+	};
+	{
+		std::vector<std::thread> pool;
+		for (int t = 1; t < std::min(16, d.supercells); ++t) pool.emplace_back(fill);
+		fill();
+		for (auto& t : pool) t.join();
+	}
+	world.generated = true;
+	arena_top_ = pool_bricks_ = total;
+	resident_bricks_ = total;
+	on_device_ = true;
+	ring_cur_ = 0;
+	snapshot_pending_ = false;
+	view_.load_queue = d_load_queue_[0];
+	view_.load_queue_count = d_load_count_[0];
+	preloaded_ = true;
+	staging_busy_ = false;
+	failed_ = false;
+	stream_batches_ = stream_host_ns_ = 0;
+	upload_seq_ = 0;
+	for (FrameStream& f : frame_streams_) f.upload_seen = 0;
+	load_timed_ = true;
+	return 0;
+}
+
+int Scene::last_load_ms(float* pack_ms, float* field_ms, float* mirror_ms) {
+	if (!pack_ms || !field_ms || !mirror_ms) { set_error("null argument"); return BM_EINVAL; }
+	if (!load_timed_) { set_error("no volume has been loaded from device memory yet"); return BM_ESTATE; }
+	BM_HIP(hipSetDevice(device_));
+	float classify = 0.f, pack = 0.f;
+	BM_HIP(hipEventElapsedTime(&classify, ev_load_time_[0], ev_load_time_[1]));
+	BM_HIP(hipEventElapsedTime(&pack, ev_load_time_[2], ev_load_time_[3]));
+	*pack_ms = classify + pack; // without the host's round trip between them (the arena is mapped there)
+	BM_HIP(hipEventElapsedTime(field_ms, ev_load_time_[3], ev_load_time_[4]));
+	BM_HIP(hipEventElapsedTime(mirror_ms, ev_load_time_[4], ev_load_time_[5]));
+	return 0;
+}
+
+int Scene::host_voxels(uint8_t* dst, size_t capacity, size_t* bytes) {
+	const WorldDims& d = world.dims;
+	const size_t need = static_cast<size_t>(d.grid_size) * d.grid_size * d.grid_height;
+	if (bytes) *bytes = need;
+	if (!dst) return 0;
+	if (!world.generated) { set_error("world not generated"); return BM_ESTATE; }
+	if (capacity < need) { set_error("voxel buffer too small"); return BM_EINVAL; }
+	world.store_voxels(dst, 16);
 	return 0;
 }
 

@@ -61,6 +61,10 @@ public:
 	int device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
+	// dense voxels -> scene (load.hip / scene.cpp "dense voxels -> scene"): replaces whatever world the scene holds; preloaded afterwards
+	int load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream_t stream);
+	int host_voxels(uint8_t* dst, size_t capacity, size_t* bytes);
+	int last_load_ms(float* pack_ms, float* field_ms, float* mirror_ms); // device time of the last load from device memory
 	// ray queries (query.hip): issued like a frame (begin_frame / end_frame), asynchronous to the host
 	int cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream);
 	int render(const bm_camera* cam, const bm_frame_params* fp, float* accum, uint32_t* dbg, hipStream_t stream);
@@ -89,6 +93,10 @@ public:
 
 private:
 	int allocate_device();
+	int alloc_index_grid();   // the pieces of allocate_device that the device route of load_voxels shares with it
+	int alloc_cube_field();
+	void set_view_dims();
+	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
 	void free_device();
 	int alloc_queue();
 	int service_ring(int ring, uint32_t count, uint32_t* serviced);
@@ -194,6 +202,9 @@ private:
 	bool edit_busy_ = false;
 	uint8_t* d_cf_tmp_ = nullptr;
 	size_t cf_tmp_cap_ = 0;
+	// loads from device memory: events around classify + number, pack, field and mirror (created by the first such load)
+	hipEvent_t ev_load_time_[6] = {};
+	bool load_timed_ = false;
 	// ray queries: a ring of slot counters (one 128-byte line each); a query that reuses an entry waits for the one that used it last
 	static constexpr int kQueryRing = 64;
 	uint32_t* d_query_tickets_ = nullptr;

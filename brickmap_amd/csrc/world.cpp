@@ -6,6 +6,7 @@
 // reused for every z layer, and bricks that lie wholly below / above the terrain are
 // emitted without touching their 512 voxels.
 #include "world.h"
+#include "voxel_bits.h"
 
 #include <algorithm>
 #include <atomic>
@@ -200,6 +201,79 @@ uint64_t World::total_bricks() const {
 	uint64_t n = 0;
 	for (const auto& c : supercells) n += c.bricks.size() - c.free_slots.size();
 	return n;
+}
+
+// ---------------------------------------------------------------- dense voxels -> bricks
+namespace {
+// run work(i) for i in [0, n) on up to `threads` threads
+template <class F> void parallel_for(int n, int threads, F work) {
+	threads = std::max(1, std::min(threads, n));
+	std::atomic<int> next{0};
+	auto loop = [&]() {
+		for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) work(i);
+	};
+	std::vector<std::thread> pool;
+	for (int i = 1; i < threads; ++i) pool.emplace_back(loop);
+	loop();
+	for (auto& t : pool) t.join();
+}
+} // namespace
+
+void World::load_supercell(const WorldDims& dims, HostSupercell& cell, int sx, int sy, int sz, const uint8_t* voxels) {
+	cell = HostSupercell{};
+	cell.indices.assign(kCellsPerSupercell, 0u);
+	const size_t g = static_cast<size_t>(dims.grid_size);
+	for (int bz = 0; bz < kSupercell; ++bz)
+		for (int by = 0; by < kSupercell; ++by)
+			for (int bx = 0; bx < kSupercell; ++bx) { // ascending local cell index: the generator's loop order
+				const uint8_t* origin = voxels + (static_cast<size_t>(sz * kColumnSpan + bz * kBrickSize) * g + (sy * kColumnSpan + by * kBrickSize)) * g +
+										sx * kColumnSpan + bx * kBrickSize;
+				Brick brick;
+				uint32_t any = 0;
+				for (int w = 0; w < kBrickWords; ++w) { // word w = the x-rows (y = 4 (w & 1) ... + 3, z = w >> 1): byte (y + 8 z) of the brick
+					uint32_t word = 0;
+					for (int k = 0; k < 4; ++k) {
+						uint32_t lo, hi;
+						const uint8_t* row = origin + (static_cast<size_t>(w >> 1) * g + (4 * (w & 1) + k)) * g;
+						std::memcpy(&lo, row, 4);
+						std::memcpy(&hi, row + 4, 4);
+						word |= brick_row_bits(lo, hi) << (8 * k);
+					}
+					brick.data[w] = word;
+					any |= word;
+				}
+				if (!any) continue;
+				cell.bricks.push_back(brick);
+				cell.indices[bx + by * kSupercell + bz * kSupercell * kSupercell] =
+					static_cast<uint32_t>(cell.bricks.size() - 1) | BM_BRICK_LOADED_BIT | (brick_lod(brick) << 12); // Scene.cpp:104
+			}
+}
+
+void World::load_voxels(const uint8_t* voxels, int threads) {
+	supercells.clear();
+	supercells.resize(dims.supercells);
+	parallel_for(dims.supercells, threads, [&](int sc) {
+		load_supercell(dims, supercells[sc], sc % dims.supergrid_xy, (sc / dims.supergrid_xy) % dims.supergrid_xy, sc / (dims.supergrid_xy * dims.supergrid_xy), voxels);
+	});
+	generated = true;
+}
+
+void World::store_voxels(uint8_t* voxels, int threads) const {
+	const size_t g = static_cast<size_t>(dims.grid_size);
+	parallel_for(dims.supercells, threads, [&](int sc) {
+		const HostSupercell& c = supercells[sc];
+		const int sx = sc % dims.supergrid_xy, sy = (sc / dims.supergrid_xy) % dims.supergrid_xy, sz = sc / (dims.supergrid_xy * dims.supergrid_xy);
+		for (int cell = 0; cell < kCellsPerSupercell; ++cell) {
+			const uint32_t word = c.indices.empty() ? 0u : c.indices[cell];
+			const uint8_t* bits = word ? reinterpret_cast<const uint8_t*>(c.bricks[word & BM_BRICK_INDEX_BITS].data) : nullptr;
+			uint8_t* origin = voxels + (static_cast<size_t>(sz * kColumnSpan + (cell >> 8) * kBrickSize) * g + (sy * kColumnSpan + ((cell >> 4) & 15) * kBrickSize)) * g +
+							  sx * kColumnSpan + (cell & 15) * kBrickSize;
+			for (int r = 0; r < 64; ++r) { // x-row (y = r & 7, z = r >> 3) is byte r of the brick
+				uint8_t* row = origin + (static_cast<size_t>(r >> 3) * g + (r & 7)) * g;
+				for (int x = 0; x < kBrickSize; ++x) row[x] = bits ? (bits[r] >> x) & 1 : 0;
+			}
+		}
+	});
 }
 
 // ---------------------------------------------------------------- voxel edits

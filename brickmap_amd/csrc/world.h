@@ -64,6 +64,13 @@ public:
 	// CPU half of Scene::generate (Scene.cpp:118-147)
 	void generate(int threads);
 	uint64_t total_bricks() const; // non-empty bricks (host slots minus freed ones)
+
+	// ---- dense voxels (bm_scene_load_voxels): V[z][y][x], x fastest, (grid_height, grid_size, grid_size), one byte per voxel, non-zero =
+	// solid.  The canonical build of V: what build_supercell would store if the terrain were V -- a brick per cell that holds a solid
+	// voxel, host slots 0, 1, 2 ... in ascending local cell index, word = slot | loaded | lod << 12, no free slots.
+	static void load_supercell(const WorldDims& dims, HostSupercell& c, int sx, int sy, int sz, const uint8_t* voxels);
+	void load_voxels(const uint8_t* voxels, int threads); // every supercell, one per work item; the world counts as generated afterwards
+	void store_voxels(uint8_t* voxels, int threads) const; // the inverse: the host world as a dense volume of 0 / 1
 	// Octant cube field for the GPU walk (device_types.h DeviceScene::cube_field): 8 planes of
 	// (cells + 2)^2 * (cells_height + 2) bytes.  Plane o, cell c: edge (capped at 254) of the largest cube of empty
 	// cells inside the grid that has c as its near corner and extends towards -x / -y / -z where bit 0 / 1 / 2 of o is

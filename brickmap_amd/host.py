@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, BM_QUERY_LOD, BM_QUERY_NO_REQUESTS, bm_camera, bm_counters, bm_edit, bm_frame_params,
+from ._lib import (BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, BM_QUERY_LOD, BM_QUERY_NO_REQUESTS, BM_VOXELS_DEVICE, BM_VOXELS_HOST, bm_camera, bm_counters, bm_edit, bm_frame_params,
                    bm_scene_info, check)
 
 
@@ -204,6 +204,43 @@ def host_edit_supercell(grid_size, grid_height, sx, sy, sz, indices, bricks, edi
     return idx, buf[: n.value].copy()
 
 
+# ---- dense voxels (bm_scene_load_voxels): a volume [z, y, x] of one byte per voxel, non-zero = solid
+def volume_dims(volume, grid_size=None, grid_height=None):
+    """(grid_size, grid_height) of a dense voxel volume, after checking it: a numpy array or torch tensor of shape
+    (grid_height, grid_size, grid_size) -- [z, y, x], x fastest --, dtype uint8 or bool, C-contiguous, both dimensions positive multiples
+    of 128; with grid_size / grid_height given the shape must be exactly that.  Raises ValueError otherwise (no library call is made)."""
+    shape = tuple(getattr(volume, "shape", ()))
+    if len(shape) != 3 or shape[1] != shape[2] or shape[0] <= 0 or shape[1] <= 0 or shape[0] % 128 or shape[1] % 128:
+        raise ValueError(f"volume: shape (grid_height, grid_size, grid_size) in positive multiples of 128 voxels expected, got {shape}")
+    if grid_size is not None and shape != (grid_height, grid_size, grid_size):
+        raise ValueError(f"volume: shape {(grid_height, grid_size, grid_size)} expected for this scene, got {shape}")
+    if hasattr(volume, "is_contiguous"):  # torch
+        import torch
+        if volume.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"volume: dtype uint8 or bool expected, got {volume.dtype}")
+        if not volume.is_contiguous():
+            raise ValueError("volume: a contiguous tensor expected (x fastest)")
+    else:
+        if not isinstance(volume, np.ndarray):
+            raise ValueError(f"volume: a numpy array or torch tensor expected, got {type(volume).__name__}")
+        if volume.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise ValueError(f"volume: dtype uint8 or bool expected, got {volume.dtype}")
+        if not volume.flags["C_CONTIGUOUS"]:
+            raise ValueError("volume: a C-contiguous array expected (x fastest)")
+    return int(shape[1]), int(shape[0])
+
+
+def host_load_supercell(volume, sx, sy, sz):
+    """bm_host_load_supercell: (indices[4096], bricks[n, 16]) of one supercell of the canonical build of `volume` (a numpy volume as
+    volume_dims describes it; no device needed)."""
+    gs, gh = volume_dims(volume)
+    idx = np.zeros(4096, np.uint32)
+    bricks = np.zeros((4096, 16), np.uint32)
+    n = C.c_uint32(0)
+    check(_lib.load().bm_host_load_supercell(gs, gh, sx, sy, sz, volume.ctypes.data, idx.ctypes.data, bricks.ctypes.data, C.byref(n)))
+    return idx, bricks[: n.value].copy()
+
+
 # ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmax", "<f4"), ("reserved", "<u4")])   # bm_ray
 RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("voxel", "<i4", 3), ("level", "<i4")])  # bm_ray_hit
@@ -367,6 +404,48 @@ class Scene:
         out = np.zeros((128, 128), np.float32)
         check(self._L.bm_scene_column_heights(self.gpuScene, sx, sy, out.ctypes.data))
         return out
+
+    # ---- a scene from the caller's voxels (bm_scene_load_voxels)
+    def load_voxels(self, volume, stream=None):
+        """Make `volume` the scene's world (replacing the one it holds, if any): a numpy array or a torch tensor, [z, y, x] of shape
+        (grid_height, grid_size, grid_size), uint8 or bool, contiguous.  Host memory is built on CPU threads and uploaded; a tensor on
+        the scene's GPU is packed on the GPU without leaving it, behind the work queued on `stream` (a raw HIP stream handle; None =
+        torch's current stream, which the given stream is made to wait for).  The scene is preloaded when the call returns.  A wrong
+        shape, dtype or layout raises ValueError before the library is called."""
+        volume_dims(volume, self.grid_size, self.grid_height)
+        if hasattr(volume, "is_contiguous"):
+            import torch
+            if volume.is_cuda:
+                if volume.device.index != self.device:
+                    raise ValueError(f"volume: a tensor on cuda:{self.device} (the scene's GPU) or on the CPU expected, got {volume.device}")
+                current = torch.cuda.current_stream(volume.device)
+                target = current if stream is None else torch.cuda.ExternalStream(int(stream), device=volume.device)
+                if target.cuda_stream != current.cuda_stream:
+                    target.wait_stream(current)
+                check(self._L.bm_scene_load_voxels(self.gpuScene, C.c_void_p(volume.data_ptr()), volume.numel(), BM_VOXELS_DEVICE, C.c_void_p(target.cuda_stream)))
+                return self
+            volume = volume.numpy()
+        check(self._L.bm_scene_load_voxels(self.gpuScene, C.c_void_p(volume.ctypes.data), volume.size, BM_VOXELS_HOST, None))
+        return self
+
+    @classmethod
+    def from_voxels(cls, volume, device=0):
+        """A scene whose world is `volume` (see load_voxels); the dimensions come from its shape (grid_height, grid_size, grid_size)."""
+        grid_size, grid_height = volume_dims(volume)
+        return cls(grid_size, grid_height, device=device).load_voxels(volume)
+
+    def voxels(self):
+        """bm_scene_host_voxels: the host world as a bool volume [z, y, x]."""
+        out = np.zeros((self.grid_height, self.grid_size, self.grid_size), np.uint8)
+        n = C.c_size_t(0)
+        check(self._L.bm_scene_host_voxels(self.gpuScene, out.ctypes.data, out.size, C.byref(n)))
+        return out.view(np.bool_)
+
+    def last_load_ms(self):
+        """(pack_ms, field_ms, mirror_ms) of the last load from a device tensor (hipEvents on the load stream)."""
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        check(self._L.bm_scene_last_load_ms(self.gpuScene, C.byref(a), C.byref(b), C.byref(c)))
+        return float(a.value), float(b.value), float(c.value)
 
     # ---- voxel edits (bm_scene_edit): ordered behind the frames in flight, seen by every frame issued after the call
     def _stream(self, stream):

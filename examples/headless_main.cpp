@@ -1,7 +1,9 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--dig x,y,z,r] [--dig-at px,py,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--voxels FILE] [--dig x,y,z,r] [--dig-at px,py,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+// --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
+// grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
 // --dig-at picks the voxel under pixel (px, py) of the first frame's camera (Scene::pick) and carves a sphere of radius r there; the
 // world streams, so while the pick lands on a brick that is not resident yet (level 3) the load queue is serviced and the pick repeated
@@ -24,7 +26,12 @@ int main(int argc_in, char** argv_in) {
 	std::vector<char*> args;
 	int dig[4] = {0, 0, 0, -1};
 	int dig_at[3] = {0, 0, -1};
+	const char* voxels_path = nullptr;
 	for (int i = 0; i < argc_in; ++i) {
+		if (std::string(argv_in[i]) == "--voxels" && i + 1 < argc_in) {
+			voxels_path = argv_in[++i];
+			continue;
+		}
 		if (std::string(argv_in[i]) == "--dig-at" && i + 1 < argc_in) {
 			if (std::sscanf(argv_in[++i], "%d,%d,%d", &dig_at[0], &dig_at[1], &dig_at[2]) != 3 || dig_at[2] < 0) {
 				std::cerr << "--dig-at wants px,py,r (r >= 0)\n";
@@ -51,7 +58,17 @@ int main(int argc_in, char** argv_in) {
 
 	State state(width, height);                 // main.cpp:102
 	Scene scene(grid_size, grid_height);        // main.cpp:104
-	scene.generate();                           // main.cpp:105 -- nothing resident yet: bricks stream in on demand
+	if (voxels_path) {
+		std::ifstream in(voxels_path, std::ios::binary);
+		std::vector<uint8_t> volume(static_cast<size_t>(grid_size) * grid_size * grid_height);
+		if (!in || !in.read(reinterpret_cast<char*>(volume.data()), static_cast<std::streamsize>(volume.size())) || in.peek() != EOF) {
+			std::cerr << "--voxels: " << voxels_path << " does not hold " << volume.size() << " bytes\n";
+			return 2;
+		}
+		scene.load_voxels(volume.data(), volume.size());
+	} else {
+		scene.generate();                       // main.cpp:105 -- nothing resident yet: bricks stream in on demand
+	}
 	if (dig[3] >= 0) scene.carve_sphere(dig, dig[3]);
 	camera.position = {grid_size / 2.f, grid_size / 8.f, 0.8f * grid_height};
 	camera.horizontal_angle = 0.8;

@@ -219,6 +219,31 @@ BM_API int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capaci
  * and the cube-field update (0 when no cell's occupancy changed); waits for that batch */
 BM_API int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms);
 
+/* ---- a scene from the caller's own voxels (no reference counterpart: the reference's only world is its terrain).
+ * voxels: a dense volume V[z][y][x], x fastest, (grid_height, grid_size, grid_size), one byte per voxel, non-zero = solid; `bytes`
+ * must be grid_size^2 * grid_height.  The scene becomes the CANONICAL BUILD of V -- what bm_scene_generate would store if the
+ * terrain were V: a brick for every cell that holds a solid voxel (bit x + 8 y + 64 z, Scene.cpp:91-93), host slots 0, 1, 2 ... in
+ * ascending local cell index, word = slot | loaded | lod << 12 (Scene.cpp:95,104), no free slots -- and is on the device in the
+ * state bm_scene_generate + bm_scene_preload_all leave it in, the octant cube field included; the host world is populated and
+ * authoritative, so resetting residency, edits, queries and frames work on it as on a generated scene.  Allowed right after
+ * bm_scene_create and on a scene that holds a world (which it replaces).  The call waits for the device first and returns when
+ * the scene is ready; the volume is only read during the call.
+ *  - BM_VOXELS_HOST: the volume is host memory; built on CPU threads and uploaded.
+ *  - BM_VOXELS_DEVICE: the volume is memory of the scene's device; packed there by the kernels of csrc/load.hip without crossing
+ *    to the host, behind the work queued on hip_stream so far (the stream that produced the volume).  The cube field is computed
+ *    on the GPU; words and bricks are copied back into the host world.
+ * A null volume, a wrong byte count, an unknown `where` or (BM_VOXELS_DEVICE) a pointer that is not `bytes` bytes of that device's
+ * memory: BM_EINVAL, and the scene keeps the world it held.  A world of 2^32 bricks or more is refused as by bm_scene_generate. */
+#define BM_VOXELS_HOST   0
+#define BM_VOXELS_DEVICE 1
+BM_API int bm_scene_load_voxels(bm_scene* scene, const uint8_t* voxels, size_t bytes, int where, void* hip_stream);
+/* the host world as a dense volume of 0 / 1 in the layout above (host only); *bytes = size needed (dst = NULL to query) */
+BM_API int bm_scene_host_voxels(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes);
+/* device time of the last BM_VOXELS_DEVICE load (hipEvents on the load stream): pack = classify + number + pack kernels (without the
+ * host's round trip that sizes the arena), the cube-field passes, and the copy back into the host world.  BM_ESTATE when the last load
+ * was not from device memory. */
+BM_API int bm_scene_last_load_ms(bm_scene* scene, float* pack_ms, float* field_ms, float* mirror_ms);
+
 /* ---- ray queries against the live scene (no reference counterpart: the reference only traces inside its frame kernels).
  * What does a ray hit -- the voxel under the cursor, the ground under a walking camera, line of sight, collision probes.
  * A query walks exactly as the frames' extend kernel does (csrc/traverse.h), so a hit equals the reference's intersect_voxel bit
@@ -267,6 +292,11 @@ BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, in
  * (up to brick_capacity, else BM_EINVAL); on any error the arrays are left unchanged. */
 BM_API int bm_host_edit_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,
                                   uint32_t* brick_count, uint32_t* bricks, uint32_t brick_capacity, int count, const bm_edit* edits);
+
+/* the host route of bm_scene_load_voxels on one supercell (no device needed): voxels is the whole volume of a grid_size x grid_size x
+ * grid_height world; indices4096 and bricks[4096][16] receive the supercell's canonical build, *brick_count its bricks */
+BM_API int bm_host_load_supercell(int grid_size, int grid_height, int sx, int sy, int sz, const uint8_t* voxels, uint32_t* indices4096,
+                                  uint32_t* bricks, uint32_t* brick_count);
 
 /* test door: the constants with which the walk divides a cube-field offset by the slice pitch (floor(n / divisor) ==
  * (uint64(n) * magic >> 32) >> shift for every n < 2^30; 3 <= divisor < 2^23) */

@@ -93,6 +93,21 @@ public:
 	// BASELINE configs 1-2: everything resident up front (no counterpart in the reference)
 	void preload_all() { BM_CHECKED(bm_scene_preload_all(gpuScene.handle)); }
 
+	// the caller's own voxels as the world (no counterpart in the reference; bm_scene_load_voxels): a dense volume [z][y][x] of one byte
+	// per voxel, non-zero = solid, in host memory (BM_VOXELS_HOST) or in memory of the scene's device (BM_VOXELS_DEVICE: packed on the
+	// GPU, behind the work queued on hip_stream).  Instead of generate(), or to replace the world; the scene is preloaded afterwards.
+	void load_voxels(const uint8_t* voxels, size_t bytes, int where = BM_VOXELS_HOST, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_load_voxels(gpuScene.handle, voxels, bytes, where, hip_stream));
+	}
+	// the host world as a dense volume of 0 / 1 in the same layout
+	std::vector<uint8_t> voxels() const {
+		size_t bytes = 0;
+		BM_CHECKED(bm_scene_host_voxels(gpuScene.handle, nullptr, 0, &bytes));
+		std::vector<uint8_t> out(bytes);
+		BM_CHECKED(bm_scene_host_voxels(gpuScene.handle, out.data(), out.size(), &bytes));
+		return out;
+	}
+
 	// voxel edits of the live world (no counterpart in the reference; bm_scene_edit): applied in order, behind the frames in flight,
 	// seen by every frame issued afterwards.  Integer voxel coordinates; boxes are half-open [lo, hi), spheres hold |v - c|^2 <= r^2.
 	void edit(const std::vector<bm_edit>& edits, void* hip_stream = nullptr) {
