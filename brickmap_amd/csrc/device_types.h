@@ -33,7 +33,7 @@ struct DeviceScene {
 	int cf_shift;        // log2 of the row pitch
 	uint32_t cf_pxy;     // slice pitch in bytes: (cells + 2) << cf_shift
 	uint32_t cf_plane;   // bytes per plane: (cells_height + 2) * cf_pxy
-	uint32_t cf_magic;   // floor(n / cf_pxy) == umulhi(n, cf_magic) >> cf_magic_shift for every n < 2^30 (scene.cpp division_magic)
+	uint32_t cf_magic;   // floor(n / cf_pxy) == umulhi(n, cf_magic) >> cf_magic_shift for every n < 2^30 (frame_plan.cpp division_magic)
 	int cf_magic_shift;
 	int* load_queue;             // 3 ints per entry
 	uint32_t* load_queue_count;
@@ -78,7 +78,7 @@ struct FrameConstants {
 	int tiles_x, tiles_y; // 16x16-pixel tiles covering this shard's rows
 	int xcd_handout;      // 1: XCD-aware hand-out (trace.hip refill: 256x256-pixel super-tiles dealt to the eight XCDs' counters); big frames only
 	int refill_min;       // a wave takes new work items once this many of its lanes are idle (frame_constants(): by the length of an item)
-	// the hand-out's divisions by per-frame constants as multiply-high + shift (scene.cpp division_magic; magic == 0: the divisor is 1):
+	// the hand-out's divisions by per-frame constants as multiply-high + shift (frame_plan.cpp division_magic; magic == 0: the divisor is 1):
 	// samples per (chunk, sample) ticket group, tiles per row, rows per band, super-tiles per row.  Exact for dividends < 2^30.
 	uint32_t div_samples_magic, div_tiles_x_magic, div_band_magic, div_st_x_magic;
 	int div_samples_shift, div_tiles_x_shift, div_band_shift, div_st_x_shift;

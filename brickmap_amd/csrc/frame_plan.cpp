@@ -1,0 +1,198 @@
+// frame_plan.cpp -- the pure-host plan of a frame: FrameConstants from a camera and frame parameters (view basis, sky constants, the
+// hand-out's geometry, refill and helper-lane rules), the tuning overrides of the environment and the multiply-high division constants.
+// Calls no HIP function.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "scene.h"
+
+namespace bm {
+
+// ---------------------------------------------------------------- small host vector helpers (GLM operation order)
+namespace {
+struct V3 {
+	float x, y, z;
+};
+inline V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+inline float dot3(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+inline V3 cross3(V3 x, V3 y) { return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y}; }
+inline V3 normalize3(V3 v) { return v * (1.0f / std::sqrt(dot3(v, v))); }
+constexpr float kPi = 3.1415926535897932f;
+
+// sunsky.cu:24-26 -- double literals make the tail of this expression double
+float sun_intensity(float zenith_cos) {
+	const float cutoff = kPi / 1.95f, steepness = 1.5f;
+	const double e = 1.0 - static_cast<double>(std::exp(-((cutoff - std::acos(zenith_cos)) / steepness)));
+	return static_cast<float>(1000.0 * (0.0 < e ? e : 0.0));
+}
+} // namespace
+
+// floor(n / d) for every n < 2^30 as umulhi(n, magic) >> shift (Granlund-Montgomery: with l = ceil(log2 d) and
+// magic = ceil(2^(30 + l) / d) one has 2^(30+l) <= magic * d < 2^(30+l) + 2^l, which makes the truncated product exact for 30-bit n;
+// magic < 2^31 + 1 fits 32 bits; tests/test_host_logic.py replays it against integer division)
+void division_magic(uint32_t d, uint32_t* magic, int* shift) {
+	int l = 0;
+	while ((1ull << l) < d) ++l;
+	if (l < 2) l = 2;
+	const unsigned __int128 one = static_cast<unsigned __int128>(1) << (30 + l);
+	*magic = static_cast<uint32_t>((one + d - 1) / d);
+	*shift = l - 2; // (30 + l) - 32
+}
+
+// Tuning overrides, read from the environment ONCE per process (A/B runs, tools/): BM_REFILL_MIN (1 ... 64), BM_XCD_HANDOUT (0 / 1),
+// BM_HELPERS (0 / 1), BM_TRACE_BLOCKS_PER_CU (> 0).  None set = the product's own rules.  bm_tuning_overrides() reports them, so that
+// a measurement can say what it ran under (bench.py echoes them into its line and refuses to go on under BM_BENCH_STRICT=1).
+const Tuning& tuning() {
+	static const Tuning t = [] {
+		Tuning v;
+		auto num = [](const char* name, int unset) { const char* e = std::getenv(name); return e && *e ? std::atoi(e) : unset; };
+		v.refill_min = num("BM_REFILL_MIN", 0);
+		v.xcd_handout = num("BM_XCD_HANDOUT", -1);
+		v.helpers = num("BM_HELPERS", -1);
+		v.blocks_per_cu = num("BM_TRACE_BLOCKS_PER_CU", 0);
+		return v;
+	}();
+	return t;
+}
+
+int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_in, FrameConstants* fc, bool hit_records) {
+	if (!fp_in) { set_error("null argument"); return BM_EINVAL; }
+	if (fp_in->flags & ~(BM_FLAG_PRIMARY_ONLY | BM_FLAG_COUNTERS | BM_FLAG_SAMPLE_ITEMS | BM_FLAG_ORDERED | BM_FLAG_RAY_DIGEST)) {
+		set_error("unknown frame flag (bit 8 was the retired K-slot schedule's)");
+		return BM_EINVAL;
+	}
+	// Which frames are ORDERED (every pixel's events accumulated in path order by one lane, one plain write-back: reproducible sums)?
+	// Those that ask for it, those that write hit records, primary-only frames.  Every other frame -- the production
+	// default -- may add in any order, like the reference's own atomicAdds (kernel.cu:319-322,341-343): it runs with helper lanes
+	// (trace.hip HELP) and, when a pixel has several samples, with (4x4 chunk, sample) work items: shorter items, a shorter tail,
+	// coherent neighbouring samples (1080p at 4 spp 4.0 -> 3.4 ms, config 3 -4 %).  BM_HELPERS=0 / 1 overrides helper lanes (A/B runs).
+	bm_frame_params promoted = *fp_in;
+	// (hit records are chains in path order -- an ordered frame -- unless the caller asked for the order-independent ray digest)
+	const bool ordered = (promoted.flags & (BM_FLAG_ORDERED | BM_FLAG_PRIMARY_ONLY)) != 0 || (hit_records && !(promoted.flags & BM_FLAG_RAY_DIGEST)) || promoted.spp < 1; // (spp = 0: nothing to trace)
+	const bm_frame_params* const fp = &promoted;
+	if (!cam || !fp || !fc) { set_error("null argument"); return BM_EINVAL; }
+	if (fp->width <= 0 || fp->height <= 0 || fp->spp < 0 || fp->max_bounces < 0 || fp->band_rows <= 0 || fp->shard_count <= 0 ||
+		fp->shard_rank < 0 || fp->shard_rank >= fp->shard_count) {
+		set_error("bad frame parameters");
+		return BM_EINVAL;
+	}
+	// the kernels pack a pixel as x | y << 16 and index the shard's packed buffers with 32-bit pixel numbers
+	if (fp->width > 65535 || fp->height > 65535 || static_cast<long long>(bm_local_rows(fp)) * fp->width >= (1ll << 32)) {
+		set_error("frame too large: width and height are limited to 65535 and a shard to 2^32 pixels");
+		return BM_EINVAL;
+	}
+	if ((fp->flags & BM_FLAG_RAY_DIGEST) && (fp->max_bounces >= 255 || static_cast<long long>(fp->spp) * (fp->max_bounces + 1) >= 65536)) {
+		set_error("BM_FLAG_RAY_DIGEST: the digest counts a pixel's rays in 16 bits and keys them with 8 bits of segment: spp x segments < 65536, max_bounces < 255");
+		return BM_EINVAL;
+	}
+	const int geo_tiles_x = (fp->width + 15) / 16, geo_tiles_y = (bm_local_rows(fp) + 15) / 16;
+	// XCD-aware hand-out: neighbouring rays behind ONE L2 instead of all eight.  Pays where the scene does not fit the caches and the
+	// frame has enough 256x256-pixel super-tiles for eight even shares (8K: 510, 4K: 135) -- config 5 115.0 -> 111.5 ms, config 3
+	// 24.05 -> 23.90; on a 1080p frame (40 super-tiles) the shares are too uneven: +8 % (profiles/r04_xcd_handout.txt)
+	int geo_xcd = (static_cast<long long>(geo_tiles_x) * geo_tiles_y >= 32000) ? 1 : 0;
+	if (tuning().xcd_handout == 0 || tuning().xcd_handout == 1) geo_xcd = tuning().xcd_handout;
+	// The hand-out counts tickets in 32 bits (trace.hip: `my_tickets`, `base + want`).  The busiest counter owns a 1/8 share of the
+	// units -- groups of four chunks, or 256x256-pixel super-tiles of 4096 chunks -- times 16 tickets per chunk and, with (chunk,
+	// sample) items, per sample; every wave may overshoot a used-up counter once by up to 64.
+	auto tickets_fit = [&](bool sample_items) {
+		const long long tiles = static_cast<long long>(geo_tiles_x) * geo_tiles_y;
+		const long long per_chunk = 16ll * (sample_items ? std::max(fp->spp, 1) : 1);
+		long long share;
+		if (geo_xcd) {
+			const long long st = static_cast<long long>((geo_tiles_x + 15) / 16) * ((geo_tiles_y + 15) / 16);
+			share = ((st + 7) / 8) * 4096ll * per_chunk;
+		} else {
+			share = ((tiles * 4 + 7) / 8) * 4ll * per_chunk;
+		}
+		return share < (1ll << 30) - (1ll << 24); // (2^30: the hand-out divides ticket numbers with 30-bit-exact multiply-high constants)
+	};
+	if (!tickets_fit((promoted.flags & BM_FLAG_SAMPLE_ITEMS) != 0)) { // what the caller asked for does not fit: refuse
+		set_error("frame too large for the 32-bit ticket counters: tiles x samples per launch (lower spp per call, or render row-band shards)");
+		return BM_EINVAL;
+	}
+	// (chunk, sample) items as the library's own choice -- only where their tickets fit; pixel items carry no spp factor and always
+	// do at this point (helper lanes work with either: atomic_acc = HELP)
+	if (!ordered && promoted.spp >= 2 && tickets_fit(true)) promoted.flags |= BM_FLAG_SAMPLE_ITEMS;
+	std::memset(fc, 0, sizeof *fc);
+	const V3 dir{cam->direction[0], cam->direction[1], cam->direction[2]};
+	const V3 upv{cam->up[0], cam->up[1], cam->up[2]};
+	const float aspect = static_cast<float>(fp->width) / static_cast<float>(fp->height);
+	const V3 right = (normalize3(cross3(dir, upv)) * 1.5f) * aspect;   // launch_kernels:384
+	const V3 up = normalize3(cross3(right, dir)) * 1.5f;               // launch_kernels:385
+	fc->right[0] = right.x; fc->right[1] = right.y; fc->right[2] = right.z;
+	fc->up[0] = up.x; fc->up[1] = up.y; fc->up[2] = up.z;
+	for (int i = 0; i < 3; ++i) {
+		fc->dir[i] = cam->direction[i];
+		fc->origin[i] = cam->position[i];
+		fc->campos[i] = static_cast<int>(cam->position[i] / 8.f); // kernel.cu:418
+	}
+	fc->focal3 = cam->focal_distance * 3; // kernel.cu:191-192 (int 3)
+	fc->lens_radius = cam->lens_radius;
+
+	// sky constants (kernel.cu:374,393; sunsky.cu:14-18,28-30,34-44,66-67)
+	fc->sun_angular_cos = std::cos(1.5f * kPi / 180.f);
+	fc->cone_extent = 1.0f - fc->sun_angular_cos;
+	const float px = (fp->sun_position[0] - 0.0f) * 6.28f, py = (fp->sun_position[1] - 0.5f) * 3.14f;
+	const V3 sun = normalize3(V3{std::cos(px) * std::sin(py), std::sin(px) * std::sin(py), std::cos(py)});
+	fc->sun_direction[0] = sun.x; fc->sun_direction[1] = sun.y; fc->sun_direction[2] = sun.z;
+	{ // getConeSample's frame around the sun direction (sunsky.cu:163-174), same fp32 operations as the reference
+		const V3 cd = normalize3(sun);
+		const V3 ortho = std::fabs(cd.x) > std::fabs(cd.z) ? V3{-cd.y, cd.x, 0.0f} : V3{0.0f, -cd.z, cd.y};
+		const V3 o1 = normalize3(ortho);
+		const V3 o2 = normalize3(cross3(cd, o1));
+		fc->cone_dir[0] = cd.x; fc->cone_dir[1] = cd.y; fc->cone_dir[2] = cd.z;
+		fc->cone_o1[0] = o1.x; fc->cone_o1[1] = o1.y; fc->cone_o1[2] = o1.z;
+		fc->cone_o2[0] = o2.x; fc->cone_o2[1] = o2.y; fc->cone_o2[2] = o2.z;
+	}
+	const V3 sky_up{0.0f, 0.0f, 1.0f};
+	fc->sunE = sun_intensity(dot3(sun, sky_up));
+	const float rayleigh[3] = {5.176821E-6f, 1.2785348E-5f, 2.8530756E-5f};
+	const float lambda[3] = {680E-9f, 550E-9f, 450E-9f};
+	const float K[3] = {0.686f, 0.678f, 0.666f};
+	const float c = static_cast<float>((0.2 * static_cast<double>(1.f)) * 10E-18); // turbidity 1
+	const float mie_scale = 0.434f * c * kPi;
+	const float expo = static_cast<float>(static_cast<double>(4.0f) - 2.0);
+	for (int i = 0; i < 3; ++i) {
+		const float total_mie = (std::pow((2.0f * kPi) / lambda[i], expo) * mie_scale) * K[i];
+		fc->rayleigh[i] = rayleigh[i];
+		fc->mie[i] = total_mie * 0.005f;
+		fc->inv_total[i] = 1.0f / (fc->rayleigh[i] + fc->mie[i]);
+	}
+	const float m = std::pow(1.0f - dot3(sky_up, sun), 5.0f);
+	fc->mixf = std::min(std::max(m, 0.0f), 1.0f);
+
+	fc->width = fp->width; fc->height = fp->height;
+	fc->spp = fp->spp; fc->sample_base = fp->sample_base; fc->max_bounces = fp->max_bounces;
+	fc->base_frame = fp->base_frame; fc->flags = fp->flags;
+	fc->band_rows = fp->band_rows; fc->shard_rank = fp->shard_rank; fc->shard_count = fp->shard_count;
+	fc->local_rows = bm_local_rows(fp);
+	fc->tiles_x = geo_tiles_x;
+	fc->tiles_y = geo_tiles_y;
+	// When does a wave stop to refill?  Every refill costs the whole wave an atomic's round trip and ~110 instructions, every idle
+	// lane costs its share of all passes until then.  An item is all samples of a pixel (or ONE with BM_FLAG_SAMPLE_ITEMS): the
+	// longer it is, the rarer the refills, the earlier they pay (measured per workload, profiles/r04_refill_sweep.txt).
+	const int refill_override = tuning().refill_min;
+	const int samples_per_item = (fp->flags & BM_FLAG_SAMPLE_ITEMS) ? 1 : fp->spp;
+	fc->refill_min = samples_per_item >= 4 ? 4 : (samples_per_item >= 2 ? 8 : 16);
+	fc->xcd_handout = geo_xcd;
+	if (refill_override >= 1 && refill_override <= 64) fc->refill_min = refill_override;
+	// shadow rays on helper lanes (trace.hip HELP): every frame that is not ordered (above)
+	fc->helpers = ordered ? 0 : 1;
+	const int help_override = tuning().helpers;
+	if (help_override == 0 || (help_override == 1 && !ordered)) fc->helpers = help_override;
+	// with helper lanes an idle lane is not wasted while it waits for the refill -- it takes shadow rays -- so the wave refills later:
+	// 24 idle lanes instead of 16 (config 2 -0.2 %, 1080p at 4 spp -1.1 %, config 3 -0.8 %; 32: worse again; profiles/r05_refill_sweep.txt)
+	if (fc->helpers && refill_override <= 0) fc->refill_min = 24;
+	{ // divisions of the hand-out by per-frame constants (trace.hip refill): multiply-high + shift
+		auto set = [](uint32_t d, uint32_t* magic, int* shift) { if (d <= 1u) { *magic = 0u; *shift = 0; } else division_magic(d, magic, shift); };
+		set((fp->flags & BM_FLAG_SAMPLE_ITEMS) ? static_cast<uint32_t>(std::max(fp->spp, 1)) : 1u, &fc->div_samples_magic, &fc->div_samples_shift);
+		set(static_cast<uint32_t>(fc->tiles_x), &fc->div_tiles_x_magic, &fc->div_tiles_x_shift);
+		set(static_cast<uint32_t>(fc->band_rows), &fc->div_band_magic, &fc->div_band_shift);
+		set(static_cast<uint32_t>((fc->tiles_x + 15) / 16), &fc->div_st_x_magic, &fc->div_st_x_shift);
+	}
+	return 0;
+}
+
+} // namespace bm

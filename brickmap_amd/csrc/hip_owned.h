@@ -1,0 +1,89 @@
+// hip_owned.h -- move-only owners of HIP resources: device memory, pinned host memory, an event, a stream.  Each frees what it holds
+// in its destructor (on whatever device is current: the owner's destructor body selects it) and allocates through a method that
+// returns the project's int error.  A default-constructed owner holds nothing, so an object whose init() failed halfway destructs cleanly.
+// None of them synchronises: a buffer that work in flight may still use is waited for by the caller before reserve() / alloc().
+#pragma once
+#include <cstddef>
+#include <utility>
+
+#include "error.h"
+
+namespace bm {
+
+// what DeviceBuffer and PinnedBuffer share; use those two
+template <typename T>
+class HipBuffer {
+public:
+	HipBuffer(HipBuffer&& o) noexcept : pinned_(o.pinned_) { swap(o); }
+	HipBuffer& operator=(HipBuffer&& o) noexcept { swap(o); return *this; } // (what this held goes with `o`)
+	~HipBuffer() { (void)release(); }
+	int release() {
+		T* const p = p_;
+		p_ = nullptr;
+		bytes_ = 0;
+		if (p) BM_HIP(pinned_ ? hipHostFree(p) : hipFree(p));
+		return 0;
+	}
+	int alloc(size_t bytes) { // contents undefined; whatever was held is freed first
+		if (int e = release()) return e;
+		void** const at = reinterpret_cast<void**>(&p_);
+		BM_HIP(pinned_ ? hipHostMalloc(at, bytes, hipHostMallocDefault) : hipMalloc(at, bytes));
+		bytes_ = bytes;
+		return 0;
+	}
+	int reserve(size_t bytes) { return bytes <= bytes_ ? 0 : alloc(bytes); } // grows without keeping the contents
+	T* get() const { return p_; }
+	operator T*() const { return p_; }
+	size_t bytes() const { return bytes_; }
+
+protected:
+	explicit HipBuffer(bool pinned) : pinned_(pinned) {}
+
+private:
+	void swap(HipBuffer& o) { std::swap(p_, o.p_); std::swap(bytes_, o.bytes_); }
+	const bool pinned_;
+	T* p_ = nullptr;
+	size_t bytes_ = 0;
+};
+template <typename T>
+struct DeviceBuffer : HipBuffer<T> {
+	DeviceBuffer() : HipBuffer<T>(false) {}
+};
+template <typename T>
+struct PinnedBuffer : HipBuffer<T> {
+	PinnedBuffer() : HipBuffer<T>(true) {}
+};
+
+class Event {
+public:
+	Event() = default;
+	Event(Event&& o) noexcept { std::swap(e_, o.e_); }
+	Event& operator=(Event&& o) noexcept { std::swap(e_, o.e_); return *this; }
+	~Event() { if (e_) (void)hipEventDestroy(e_); }
+	int create(unsigned flags = hipEventDefault) { // no-op when the event exists already (events made on first use)
+		if (!e_) BM_HIP(hipEventCreateWithFlags(&e_, flags));
+		return 0;
+	}
+	operator hipEvent_t() const { return e_; }
+
+private:
+	hipEvent_t e_ = nullptr;
+};
+
+class Stream {
+public:
+	Stream() = default;
+	Stream(const Stream&) = delete;
+	Stream& operator=(const Stream&) = delete;
+	~Stream() { if (s_) (void)hipStreamDestroy(s_); }
+	int create(unsigned flags) {
+		BM_HIP(hipStreamCreateWithFlags(&s_, flags));
+		return 0;
+	}
+	operator hipStream_t() const { return s_; }
+
+private:
+	hipStream_t s_ = nullptr;
+};
+
+} // namespace bm

@@ -31,220 +31,59 @@ int hip_fail(hipError_t e, const char* what, const char* file, int line) {
 	return static_cast<int>(e);
 }
 
-// ---------------------------------------------------------------- small host vector helpers (GLM operation order)
-namespace {
-struct V3 {
-	float x, y, z;
-};
-inline V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-inline float dot3(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-inline V3 cross3(V3 x, V3 y) { return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y}; }
-inline V3 normalize3(V3 v) { return v * (1.0f / std::sqrt(dot3(v, v))); }
-constexpr float kPi = 3.1415926535897932f;
+// ---------------------------------------------------------------- lifetime
+Scene::~Scene() {
+	hipSetDevice(device_); // the members free themselves on it (scene.h: the arena synchronises before it unmaps, the streams go last)
+}
 
-// sunsky.cu:24-26 -- double literals make the tail of this expression double
-float sun_intensity(float zenith_cos) {
-	const float cutoff = kPi / 1.95f, steepness = 1.5f;
-	const double e = 1.0 - static_cast<double>(std::exp(-((cutoff - std::acos(zenith_cos)) / steepness)));
-	return static_cast<float>(1000.0 * (0.0 < e ? e : 0.0));
+// octant cube field, device layout: rows padded to a power of two (1 << shift bytes), pxy = bytes of a slice, plane = bytes of one of the 8
+// planes.  The walk keeps a ray's cell as ONE 32-bit byte offset into the 8 planes and steps slices with 23-bit immediates (traverse.h cell_offset).
+namespace {
+struct CubeFieldLayout {
+	int shift;
+	uint64_t pxy, plane;
+	bool fits;
+};
+CubeFieldLayout cube_field_layout(const WorldDims& d) {
+	int shift = 2;
+	while ((1 << shift) < d.cells + 2) ++shift;
+	CubeFieldLayout l{};
+	l.shift = shift;
+	l.pxy = static_cast<uint64_t>(d.cells + 2) << shift;
+	l.plane = l.pxy * static_cast<uint64_t>(d.cells_height + 2);
+	l.fits = l.pxy < (1ull << 23) && l.plane * 8 < (1ull << 32);
+	return l;
+}
+
+// The box of the cube field that has to be recomputed when the occupancy of the cells in [lo, hi] (unbordered, inclusive) has changed:
+// an entry can change up to 254 cells away from a changed cell (kernels.h FieldUpdate)
+FieldUpdate field_update_box(const WorldDims& d, const int lo[3], const int hi[3]) {
+	FieldUpdate fu{};
+	const int lim[3] = {d.cells, d.cells, d.cells_height};
+	int r0[3], r1[3];
+	for (int k = 0; k < 3; ++k) { // bordered coordinates: interior cells are 1 ... lim
+		r0[k] = std::max(1, lo[k] + 1 - 254);
+		r1[k] = std::min(lim[k] + 1, hi[k] + 1 + 254 + 1);
+	}
+	fu.rx0 = r0[0]; fu.rx1 = r1[0]; fu.ry0 = r0[1]; fu.ry1 = r1[1]; fu.rz0 = r0[2]; fu.rz1 = r1[2];
+	fu.ay0 = std::max(1, fu.ry0 - 254); fu.ay1 = std::min(d.cells + 1, fu.ry1 + 254);
+	fu.bz0 = std::max(1, fu.rz0 - 254); fu.bz1 = std::min(d.cells_height + 1, fu.rz1 + 254);
+	fu.cells = d.cells; fu.cells_height = d.cells_height;
+	fu.sg_xy = d.supergrid_xy; fu.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
+	const CubeFieldLayout l = cube_field_layout(d);
+	fu.cf_shift = l.shift; fu.cf_pxy = static_cast<uint32_t>(l.pxy); fu.cf_plane = static_cast<uint32_t>(l.plane);
+	return fu;
 }
 } // namespace
 
-void division_magic(uint32_t d, uint32_t* magic, int* shift);
-
-// Tuning overrides, read from the environment ONCE per process (A/B runs, tools/): BM_REFILL_MIN (1 ... 64), BM_XCD_HANDOUT (0 / 1),
-// BM_HELPERS (0 / 1), BM_TRACE_BLOCKS_PER_CU (> 0).  None set = the product's own rules.  bm_tuning_overrides() reports them, so that
-// a measurement can say what it ran under (bench.py echoes them into its line and refuses to go on under BM_BENCH_STRICT=1).
-const Tuning& tuning() {
-	static const Tuning t = [] {
-		Tuning v;
-		auto num = [](const char* name, int unset) { const char* e = std::getenv(name); return e && *e ? std::atoi(e) : unset; };
-		v.refill_min = num("BM_REFILL_MIN", 0);
-		v.xcd_handout = num("BM_XCD_HANDOUT", -1);
-		v.helpers = num("BM_HELPERS", -1);
-		v.blocks_per_cu = num("BM_TRACE_BLOCKS_PER_CU", 0);
-		return v;
-	}();
-	return t;
-}
-
-int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_in, FrameConstants* fc, bool hit_records) {
-	if (!fp_in) { set_error("null argument"); return BM_EINVAL; }
-	if (fp_in->flags & ~(BM_FLAG_PRIMARY_ONLY | BM_FLAG_COUNTERS | BM_FLAG_SAMPLE_ITEMS | BM_FLAG_ORDERED | BM_FLAG_RAY_DIGEST)) {
-		set_error("unknown frame flag (bit 8 was the retired K-slot schedule's)");
-		return BM_EINVAL;
-	}
-	// Which frames are ORDERED (every pixel's events accumulated in path order by one lane, one plain write-back: reproducible sums)?
-	// Those that ask for it, those that write hit records, primary-only frames.  Every other frame -- the production
-	// default -- may add in any order, like the reference's own atomicAdds (kernel.cu:319-322,341-343): it runs with helper lanes
-	// (trace.hip HELP) and, when a pixel has several samples, with (4x4 chunk, sample) work items: shorter items, a shorter tail,
-	// coherent neighbouring samples (1080p at 4 spp 4.0 -> 3.4 ms, config 3 -4 %).  BM_HELPERS=0 / 1 overrides helper lanes (A/B runs).
-	bm_frame_params promoted = *fp_in;
-	// (hit records are chains in path order -- an ordered frame -- unless the caller asked for the order-independent ray digest)
-	const bool ordered = (promoted.flags & (BM_FLAG_ORDERED | BM_FLAG_PRIMARY_ONLY)) != 0 || (hit_records && !(promoted.flags & BM_FLAG_RAY_DIGEST)) || promoted.spp < 1; // (spp = 0: nothing to trace)
-	const bm_frame_params* const fp = &promoted;
-	if (!cam || !fp || !fc) { set_error("null argument"); return BM_EINVAL; }
-	if (fp->width <= 0 || fp->height <= 0 || fp->spp < 0 || fp->max_bounces < 0 || fp->band_rows <= 0 || fp->shard_count <= 0 ||
-		fp->shard_rank < 0 || fp->shard_rank >= fp->shard_count) {
-		set_error("bad frame parameters");
-		return BM_EINVAL;
-	}
-	// the kernels pack a pixel as x | y << 16 and index the shard's packed buffers with 32-bit pixel numbers
-	if (fp->width > 65535 || fp->height > 65535 || static_cast<long long>(bm_local_rows(fp)) * fp->width >= (1ll << 32)) {
-		set_error("frame too large: width and height are limited to 65535 and a shard to 2^32 pixels");
-		return BM_EINVAL;
-	}
-	if ((fp->flags & BM_FLAG_RAY_DIGEST) && (fp->max_bounces >= 255 || static_cast<long long>(fp->spp) * (fp->max_bounces + 1) >= 65536)) {
-		set_error("BM_FLAG_RAY_DIGEST: the digest counts a pixel's rays in 16 bits and keys them with 8 bits of segment: spp x segments < 65536, max_bounces < 255");
-		return BM_EINVAL;
-	}
-	const int geo_tiles_x = (fp->width + 15) / 16, geo_tiles_y = (bm_local_rows(fp) + 15) / 16;
-	// XCD-aware hand-out: neighbouring rays behind ONE L2 instead of all eight.  Pays where the scene does not fit the caches and the
-	// frame has enough 256x256-pixel super-tiles for eight even shares (8K: 510, 4K: 135) -- config 5 115.0 -> 111.5 ms, config 3
-	// 24.05 -> 23.90; on a 1080p frame (40 super-tiles) the shares are too uneven: +8 % (profiles/r04_xcd_handout.txt)
-	int geo_xcd = (static_cast<long long>(geo_tiles_x) * geo_tiles_y >= 32000) ? 1 : 0;
-	if (tuning().xcd_handout == 0 || tuning().xcd_handout == 1) geo_xcd = tuning().xcd_handout;
-	// The hand-out counts tickets in 32 bits (trace.hip: `my_tickets`, `base + want`).  The busiest counter owns a 1/8 share of the
-	// units -- groups of four chunks, or 256x256-pixel super-tiles of 4096 chunks -- times 16 tickets per chunk and, with (chunk,
-	// sample) items, per sample; every wave may overshoot a used-up counter once by up to 64.
-	auto tickets_fit = [&](bool sample_items) {
-		const long long tiles = static_cast<long long>(geo_tiles_x) * geo_tiles_y;
-		const long long per_chunk = 16ll * (sample_items ? std::max(fp->spp, 1) : 1);
-		long long share;
-		if (geo_xcd) {
-			const long long st = static_cast<long long>((geo_tiles_x + 15) / 16) * ((geo_tiles_y + 15) / 16);
-			share = ((st + 7) / 8) * 4096ll * per_chunk;
-		} else {
-			share = ((tiles * 4 + 7) / 8) * 4ll * per_chunk;
-		}
-		return share < (1ll << 30) - (1ll << 24); // (2^30: the hand-out divides ticket numbers with 30-bit-exact multiply-high constants)
-	};
-	if (!tickets_fit((promoted.flags & BM_FLAG_SAMPLE_ITEMS) != 0)) { // what the caller asked for does not fit: refuse
-		set_error("frame too large for the 32-bit ticket counters: tiles x samples per launch (lower spp per call, or render row-band shards)");
-		return BM_EINVAL;
-	}
-	// (chunk, sample) items as the library's own choice -- only where their tickets fit; pixel items carry no spp factor and always
-	// do at this point (helper lanes work with either: atomic_acc = HELP)
-	if (!ordered && promoted.spp >= 2 && tickets_fit(true)) promoted.flags |= BM_FLAG_SAMPLE_ITEMS;
-	std::memset(fc, 0, sizeof *fc);
-	const V3 dir{cam->direction[0], cam->direction[1], cam->direction[2]};
-	const V3 upv{cam->up[0], cam->up[1], cam->up[2]};
-	const float aspect = static_cast<float>(fp->width) / static_cast<float>(fp->height);
-	const V3 right = (normalize3(cross3(dir, upv)) * 1.5f) * aspect;   // launch_kernels:384
-	const V3 up = normalize3(cross3(right, dir)) * 1.5f;               // launch_kernels:385
-	fc->right[0] = right.x; fc->right[1] = right.y; fc->right[2] = right.z;
-	fc->up[0] = up.x; fc->up[1] = up.y; fc->up[2] = up.z;
-	for (int i = 0; i < 3; ++i) {
-		fc->dir[i] = cam->direction[i];
-		fc->origin[i] = cam->position[i];
-		fc->campos[i] = static_cast<int>(cam->position[i] / 8.f); // kernel.cu:418
-	}
-	fc->focal3 = cam->focal_distance * 3; // kernel.cu:191-192 (int 3)
-	fc->lens_radius = cam->lens_radius;
-
-	// sky constants (kernel.cu:374,393; sunsky.cu:14-18,28-30,34-44,66-67)
-	fc->sun_angular_cos = std::cos(1.5f * kPi / 180.f);
-	fc->cone_extent = 1.0f - fc->sun_angular_cos;
-	const float px = (fp->sun_position[0] - 0.0f) * 6.28f, py = (fp->sun_position[1] - 0.5f) * 3.14f;
-	const V3 sun = normalize3(V3{std::cos(px) * std::sin(py), std::sin(px) * std::sin(py), std::cos(py)});
-	fc->sun_direction[0] = sun.x; fc->sun_direction[1] = sun.y; fc->sun_direction[2] = sun.z;
-	{ // getConeSample's frame around the sun direction (sunsky.cu:163-174), same fp32 operations as the reference
-		const V3 cd = normalize3(sun);
-		const V3 ortho = std::fabs(cd.x) > std::fabs(cd.z) ? V3{-cd.y, cd.x, 0.0f} : V3{0.0f, -cd.z, cd.y};
-		const V3 o1 = normalize3(ortho);
-		const V3 o2 = normalize3(cross3(cd, o1));
-		fc->cone_dir[0] = cd.x; fc->cone_dir[1] = cd.y; fc->cone_dir[2] = cd.z;
-		fc->cone_o1[0] = o1.x; fc->cone_o1[1] = o1.y; fc->cone_o1[2] = o1.z;
-		fc->cone_o2[0] = o2.x; fc->cone_o2[1] = o2.y; fc->cone_o2[2] = o2.z;
-	}
-	const V3 sky_up{0.0f, 0.0f, 1.0f};
-	fc->sunE = sun_intensity(dot3(sun, sky_up));
-	const float rayleigh[3] = {5.176821E-6f, 1.2785348E-5f, 2.8530756E-5f};
-	const float lambda[3] = {680E-9f, 550E-9f, 450E-9f};
-	const float K[3] = {0.686f, 0.678f, 0.666f};
-	const float c = static_cast<float>((0.2 * static_cast<double>(1.f)) * 10E-18); // turbidity 1
-	const float mie_scale = 0.434f * c * kPi;
-	const float expo = static_cast<float>(static_cast<double>(4.0f) - 2.0);
-	for (int i = 0; i < 3; ++i) {
-		const float total_mie = (std::pow((2.0f * kPi) / lambda[i], expo) * mie_scale) * K[i];
-		fc->rayleigh[i] = rayleigh[i];
-		fc->mie[i] = total_mie * 0.005f;
-		fc->inv_total[i] = 1.0f / (fc->rayleigh[i] + fc->mie[i]);
-	}
-	const float m = std::pow(1.0f - dot3(sky_up, sun), 5.0f);
-	fc->mixf = std::min(std::max(m, 0.0f), 1.0f);
-
-	fc->width = fp->width; fc->height = fp->height;
-	fc->spp = fp->spp; fc->sample_base = fp->sample_base; fc->max_bounces = fp->max_bounces;
-	fc->base_frame = fp->base_frame; fc->flags = fp->flags;
-	fc->band_rows = fp->band_rows; fc->shard_rank = fp->shard_rank; fc->shard_count = fp->shard_count;
-	fc->local_rows = bm_local_rows(fp);
-	fc->tiles_x = geo_tiles_x;
-	fc->tiles_y = geo_tiles_y;
-	// When does a wave stop to refill?  Every refill costs the whole wave an atomic's round trip and ~110 instructions, every idle
-	// lane costs its share of all passes until then.  An item is all samples of a pixel (or ONE with BM_FLAG_SAMPLE_ITEMS): the
-	// longer it is, the rarer the refills, the earlier they pay (measured per workload, profiles/r04_refill_sweep.txt).
-	const int refill_override = tuning().refill_min;
-	const int samples_per_item = (fp->flags & BM_FLAG_SAMPLE_ITEMS) ? 1 : fp->spp;
-	fc->refill_min = samples_per_item >= 4 ? 4 : (samples_per_item >= 2 ? 8 : 16);
-	fc->xcd_handout = geo_xcd;
-	if (refill_override >= 1 && refill_override <= 64) fc->refill_min = refill_override;
-	// shadow rays on helper lanes (trace.hip HELP): every frame that is not ordered (above)
-	fc->helpers = ordered ? 0 : 1;
-	const int help_override = tuning().helpers;
-	if (help_override == 0 || (help_override == 1 && !ordered)) fc->helpers = help_override;
-	// with helper lanes an idle lane is not wasted while it waits for the refill -- it takes shadow rays -- so the wave refills later:
-	// 24 idle lanes instead of 16 (config 2 -0.2 %, 1080p at 4 spp -1.1 %, config 3 -0.8 %; 32: worse again; profiles/r05_refill_sweep.txt)
-	if (fc->helpers && refill_override <= 0) fc->refill_min = 24;
-	{ // divisions of the hand-out by per-frame constants (trace.hip refill): multiply-high + shift
-		auto set = [](uint32_t d, uint32_t* magic, int* shift) { if (d <= 1u) { *magic = 0u; *shift = 0; } else division_magic(d, magic, shift); };
-		set((fp->flags & BM_FLAG_SAMPLE_ITEMS) ? static_cast<uint32_t>(std::max(fp->spp, 1)) : 1u, &fc->div_samples_magic, &fc->div_samples_shift);
-		set(static_cast<uint32_t>(fc->tiles_x), &fc->div_tiles_x_magic, &fc->div_tiles_x_shift);
-		set(static_cast<uint32_t>(fc->band_rows), &fc->div_band_magic, &fc->div_band_shift);
-		set(static_cast<uint32_t>((fc->tiles_x + 15) / 16), &fc->div_st_x_magic, &fc->div_st_x_shift);
-	}
+int Scene::require_on_device() const {
+	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
 	return 0;
 }
 
-// ---------------------------------------------------------------- lifetime
-Scene::~Scene() {
-	hipSetDevice(device_);
-	free_device();
-	for (int r = 0; r < 2; ++r) {
-		if (h_positions_[r]) hipHostFree(h_positions_[r]);
-		if (h_count_[r]) hipHostFree(h_count_[r]);
-		if (d_load_queue_[r]) hipFree(d_load_queue_[r]);
-		if (d_load_count_[r]) hipFree(d_load_count_[r]);
-	}
-	if (ev_snapshot_) hipEventDestroy(ev_snapshot_);
-	drop_frame_streams();
-	if (h_bricks_) hipHostFree(h_bricks_);
-	if (h_indices_) hipHostFree(h_indices_);
-	if (h_moves_) hipHostFree(h_moves_);
-	if (d_moves_) hipFree(d_moves_);
-	if (d_bricks_queue_) hipFree(d_bricks_queue_);
-	if (d_indices_queue_) hipFree(d_indices_queue_);
-	if (d_positions_) hipFree(d_positions_);
-	if (h_edit_) hipHostFree(h_edit_);
-	if (d_edit_) hipFree(d_edit_);
-	if (d_cf_tmp_) hipFree(d_cf_tmp_);
-	if (ev_edit_) hipEventDestroy(ev_edit_);
-	if (ev_edit_caller_) hipEventDestroy(ev_edit_caller_);
-	for (hipEvent_t e : ev_edit_time_) if (e) hipEventDestroy(e);
-	for (hipEvent_t e : ev_load_time_) if (e) hipEventDestroy(e);
-	if (d_counters_) hipFree(d_counters_);
-	if (d_work_counter_) hipFree(d_work_counter_);
-	if (d_query_tickets_) hipFree(d_query_tickets_);
-	for (hipEvent_t e : ev_query_) if (e) hipEventDestroy(e);
-	if (d_frame_constants_) hipFree(d_frame_constants_);
-	if (h_frame_constants_) hipHostFree(h_frame_constants_);
-	for (int i = 0; i < kTimingRing; ++i) {
-		if (ev_start_[i]) hipEventDestroy(ev_start_[i]);
-		if (ev_stop_[i]) hipEventDestroy(ev_stop_[i]);
-	}
-	if (ev_upload_) hipEventDestroy(ev_upload_);
-	if (load_stream_) hipStreamDestroy(load_stream_);
-	if (kernel_stream_) hipStreamDestroy(kernel_stream_);
+int Scene::require_not_failed() const {
+	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	return 0;
 }
 
 int Scene::init(int grid_size, int grid_height) {
@@ -258,37 +97,29 @@ int Scene::init(int grid_size, int grid_height) {
 	}
 	// the walk keeps a ray's cell as ONE 32-bit byte offset into the 8 planes of the octant cube field, whose rows are padded to a
 	// power of two (traverse.h cell_offset; allocate_device lays it out): 8 x (cells_h + 2) x (cells + 2) x 2^shift bytes < 4 GiB
-	{
-		int shift = 2;
-		while ((1 << shift) < world.dims.cells + 2) ++shift;
-		const uint64_t plane = (static_cast<uint64_t>(world.dims.cells + 2) << shift) * static_cast<uint64_t>(world.dims.cells_height + 2);
-		if (plane * 8 >= (1ull << 32)) {
-			set_error("world too large: the octant cube field (8 planes of (cells_h + 2) x (cells + 2) rows padded to a power of two) must stay below 4 GiB -- cubic worlds up to 5760 voxels a side");
-			return BM_EINVAL;
-		}
+	if (!cube_field_layout(world.dims).fits) { // (the slice-pitch limit cannot be what fails here: cells <= 1024 above)
+		set_error("world too large: the octant cube field (8 planes of (cells_h + 2) x (cells + 2) rows padded to a power of two) must stay below 4 GiB -- cubic worlds up to 5760 voxels a side");
+		return BM_EINVAL;
 	}
 	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipStreamCreateWithFlags(&load_stream_, hipStreamNonBlocking));
-	BM_HIP(hipStreamCreateWithFlags(&kernel_stream_, hipStreamNonBlocking));
+	if (int e = load_stream_.create(hipStreamNonBlocking)) return e;
+	if (int e = kernel_stream_.create(hipStreamNonBlocking)) return e;
 	for (int i = 0; i < kTimingRing; ++i) {
-		BM_HIP(hipEventCreate(&ev_start_[i]));
-		BM_HIP(hipEventCreate(&ev_stop_[i]));
+		if (int e = ev_start_[i].create()) return e;
+		if (int e = ev_stop_[i].create()) return e;
 	}
-	BM_HIP(hipEventCreateWithFlags(&ev_upload_, hipEventDisableTiming));
-	BM_HIP(hipEventCreateWithFlags(&ev_snapshot_, hipEventDisableTiming));
-	BM_HIP(hipEventCreateWithFlags(&ev_edit_, hipEventDisableTiming));
-	BM_HIP(hipEventCreateWithFlags(&ev_edit_caller_, hipEventDisableTiming));
-	for (int i = 0; i < 3; ++i) BM_HIP(hipEventCreate(&ev_edit_time_[i]));
+	for (Event* ev : {&ev_upload_, &ev_snapshot_, &ev_edit_, &ev_edit_caller_}) if (int e = ev->create(hipEventDisableTiming)) return e;
+	for (Event& ev : ev_edit_time_) if (int e = ev.create()) return e;
 	for (int r = 0; r < 2; ++r) {
-		BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_count_[r]), sizeof(uint32_t), hipHostMallocDefault));
-		BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_load_count_[r]), sizeof(uint32_t)));
+		if (int e = h_count_[r].alloc(sizeof(uint32_t))) return e;
+		if (int e = d_load_count_[r].alloc(sizeof(uint32_t))) return e;
 		BM_HIP(hipMemset(d_load_count_[r], 0, sizeof(uint32_t)));
 	}
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_counters_), sizeof(DeviceCounters)));
+	if (int e = d_counters_.alloc(sizeof(DeviceCounters))) return e;
 	BM_HIP(hipMemset(d_counters_, 0, sizeof(DeviceCounters)));
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_work_counter_), kWorkCounterBytes * kFrameRing)); // one block of counters per frame in flight
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_frame_constants_), kFrameRing * sizeof(FrameConstants)));
-	BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_frame_constants_), kFrameRing * sizeof(FrameConstants), hipHostMallocDefault));
+	if (int e = d_work_counter_.alloc(kWorkCounterBytes * kFrameRing)) return e; // one block of counters per frame in flight
+	if (int e = d_frame_constants_.alloc(kFrameRing * sizeof(FrameConstants))) return e;
+	if (int e = h_frame_constants_.alloc(kFrameRing * sizeof(FrameConstants))) return e;
 	std::fill(ring_owner_, ring_owner_ + kFrameRing, -1ll);
 	hipDeviceProp_t prop;
 	BM_HIP(hipGetDeviceProperties(&prop, device_));
@@ -301,37 +132,42 @@ int Scene::init(int grid_size, int grid_height) {
 
 int Scene::alloc_queue() {
 	BM_HIP(hipSetDevice(device_));
-	if (h_bricks_) { hipHostFree(h_bricks_); h_bricks_ = nullptr; }
-	if (h_indices_) { hipHostFree(h_indices_); h_indices_ = nullptr; }
-	if (d_bricks_queue_) { hipFree(d_bricks_queue_); d_bricks_queue_ = nullptr; }
-	if (d_indices_queue_) { hipFree(d_indices_queue_); d_indices_queue_ = nullptr; }
-	if (d_positions_) { hipFree(d_positions_); d_positions_ = nullptr; }
 	const size_t n = static_cast<size_t>(queue_cap_);
 	for (int r = 0; r < 2; ++r) {
-		if (h_positions_[r]) { hipHostFree(h_positions_[r]); h_positions_[r] = nullptr; }
-		if (d_load_queue_[r]) { hipFree(d_load_queue_[r]); d_load_queue_[r] = nullptr; }
-		BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_positions_[r]), n * 3 * sizeof(int), hipHostMallocDefault)); // Scene.cpp:30
-		BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_load_queue_[r]), n * 3 * sizeof(int)));                          // Scene.cpp:186
+		if (int e = h_positions_[r].alloc(n * 3 * sizeof(int))) return e; // Scene.cpp:30
+		if (int e = d_load_queue_[r].alloc(n * 3 * sizeof(int))) return e; // Scene.cpp:186
 		BM_HIP(hipMemset(d_load_queue_[r], 0, n * 3 * sizeof(int)));
 		BM_HIP(hipMemset(d_load_count_[r], 0, sizeof(uint32_t)));
 	}
-	BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_bricks_), n * sizeof(Brick), hipHostMallocDefault));      // Scene.cpp:31
-	BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_indices_), n * sizeof(uint32_t), hipHostMallocDefault));  // Scene.cpp:32
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_bricks_queue_), n * sizeof(Brick)));                          // Scene.cpp:189
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_indices_queue_), n * sizeof(uint32_t)));                      // Scene.cpp:190
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_positions_), n * 3 * sizeof(int)));
+	if (int e = h_bricks_.alloc(n * sizeof(Brick))) return e;             // Scene.cpp:31
+	if (int e = h_indices_.alloc(n * sizeof(uint32_t))) return e;         // Scene.cpp:32
+	if (int e = d_bricks_queue_.alloc(n * sizeof(Brick))) return e;       // Scene.cpp:189
+	if (int e = d_indices_queue_.alloc(n * sizeof(uint32_t))) return e;   // Scene.cpp:190
+	if (int e = d_positions_.alloc(n * 3 * sizeof(int))) return e;
 	// a batch of n requests can make at most n pools grow
-	if (h_moves_) { hipHostFree(h_moves_); h_moves_ = nullptr; }
-	if (d_moves_) { hipFree(d_moves_); d_moves_ = nullptr; }
-	BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_moves_), n * sizeof(PoolMove), hipHostMallocDefault));
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_moves_), n * sizeof(PoolMove)));
-	moves_cap_ = static_cast<uint32_t>(n);
-	ring_cur_ = 0;
+	if (int e = h_moves_.alloc(n * sizeof(PoolMove))) return e;
+	if (int e = d_moves_.alloc(n * sizeof(PoolMove))) return e;
+	use_ring(0);
 	snapshot_pending_ = false;
-	view_.load_queue = d_load_queue_[0];
-	view_.load_queue_count = d_load_count_[0];
 	view_.queue_cap = static_cast<uint32_t>(queue_cap_);
 	return 0;
+}
+
+void Scene::use_ring(int ring) {
+	ring_cur_ = ring;
+	view_.load_queue = d_load_queue_[ring];
+	view_.load_queue_count = d_load_count_[ring];
+}
+
+void Scene::residency_rebuilt(bool preloaded) {
+	use_ring(0);
+	snapshot_pending_ = false;
+	preloaded_ = preloaded;
+	staging_busy_ = false;
+	failed_ = false;
+	stream_batches_ = stream_host_ns_ = 0;
+	upload_seq_ = 0;
+	for (FrameStream& f : frame_streams_) f.upload_seen = 0;
 }
 
 int Scene::set_streaming_mode(int overlapped) {
@@ -350,9 +186,7 @@ int Scene::set_streaming_mode(int overlapped) {
 		BM_HIP(hipMemcpy(d_load_queue_[0], d_load_queue_[1], static_cast<size_t>(queue_cap_) * 3 * sizeof(int), hipMemcpyDeviceToDevice));
 		BM_HIP(hipMemcpy(d_load_count_[0], d_load_count_[1], sizeof(uint32_t), hipMemcpyDeviceToDevice));
 		BM_HIP(hipMemset(d_load_count_[1], 0, sizeof(uint32_t)));
-		ring_cur_ = 0;
-		view_.load_queue = d_load_queue_[0];
-		view_.load_queue_count = d_load_count_[0];
+		use_ring(0);
 	}
 	overlapped_ = overlapped != 0;
 	return 0;
@@ -378,199 +212,28 @@ int Scene::set_queue_capacity(int cap) {
 }
 
 void Scene::free_device() {
-	if (d_index_grid_) hipFree(d_index_grid_);
-	if (d_pool_base_) hipFree(d_pool_base_);
-	arena_close();
-	if (d_cube_field_) hipFree(d_cube_field_);
-	d_cube_field_ = nullptr;
-	d_index_grid_ = d_arena_ = d_pool_base_ = nullptr;
-	arena_capacity_ = arena_top_ = pool_bricks_ = 0;
+	(void)d_index_grid_.release();
+	(void)d_pool_base_.release();
+	arena_.close();
+	(void)d_cube_field_.release();
 	on_device_ = false;
 }
 
-// ---------------------------------------------------------------- brick arena
-void Scene::arena_reset() {
-	arena_top_ = 0;
-	pool_bricks_ = 0;
-	for (auto& f : free_regions_) f.clear();
-	freed_this_batch_.clear();
+// ---------------------------------------------------------------- brick arena (arena.h): the device view follows its base
+int Scene::arena_fit(uint64_t bricks) {
+	arena_.reset();
+	bool left_unmapped = false;
+	const int e = arena_.reserve(std::max<uint64_t>(bricks, 1), true, &left_unmapped);
+	// (frames are refused until bm_scene_reset_residency / bm_scene_preload_all succeeds: view_.brick_arena points at an unmapped range)
+	if (left_unmapped) failed_ = true;
+	view_.brick_arena = arena_.base();
+	return e;
 }
 
-// ---- the arena's address range.  Reserved once per world for the worst case -- every pool is a power of two >= its
-// supercell's brick count, and a pool that doubles its way up leaves regions of every smaller size behind (reused only by
-// pools of that size) -- i.e. below 4 x the world's bricks + 32 per supercell; address space costs nothing.
-int Scene::arena_open(uint64_t max_bricks) {
-	arena_close();
-	int vmm = 0;
-	if (hipDeviceGetAttribute(&vmm, hipDeviceAttributeVirtualMemoryManagementSupported, device_) != hipSuccess) vmm = 0;
-	if (const char* e = std::getenv("BM_ARENA_VMM")) vmm = vmm && std::atoi(e) != 0; // experiment knob: 0 = reallocate + copy
-	if (!vmm) { (void)hipGetLastError(); arena_virtual_ = false; return 0; }
-	hipMemAllocationProp prop{};
-	prop.type = hipMemAllocationTypePinned;
-	prop.location.type = hipMemLocationTypeDevice;
-	prop.location.id = device_;
-	size_t gran = 0;
-	BM_HIP(hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended));
-	if (gran == 0) gran = 2u << 20;
-	arena_granularity_ = gran;
-	uint64_t bytes = std::min<uint64_t>(max_bricks, (1ull << 32) - 1) * sizeof(Brick);
-	bytes = (std::max<uint64_t>(bytes, 1ull << 22) + gran - 1) / gran * gran;
-	void* va = nullptr;
-	BM_HIP(hipMemAddressReserve(&va, bytes, 0, nullptr, 0));
-	d_arena_ = static_cast<uint32_t*>(va);
-	arena_va_bytes_ = bytes;
-	arena_virtual_ = true;
-	arena_capacity_ = 0;
-	view_.brick_arena = d_arena_;
-	return 0;
-}
-
-int Scene::arena_unmap_all() {
-	// every chunk is taken off the list as it is processed (a chunk that failed to unmap must not be unmapped and released a
-	// second time by a later call); the first error is reported after all of them have been tried
-	hipError_t first = hipSuccess;
-	const char* what = "";
-	while (!arena_chunks_.empty()) {
-		const ArenaChunk c = arena_chunks_.back();
-		arena_chunks_.pop_back();
-		if (hipError_t e = hipMemUnmap(reinterpret_cast<char*>(d_arena_) + c.offset, c.bytes); e != hipSuccess && first == hipSuccess) { first = e; what = "hipMemUnmap"; }
-		if (hipError_t e = hipMemRelease(c.handle); e != hipSuccess && first == hipSuccess) { first = e; what = "hipMemRelease"; }
-	}
-	arena_capacity_ = 0;
-	if (first != hipSuccess) return hip_fail(first, what, __FILE__, __LINE__);
-	return 0;
-}
-
-void Scene::arena_close() {
-	if (arena_virtual_) {
-		// unlike hipFree, unmapping does not wait for work that still uses the range
-		if (!arena_chunks_.empty()) (void)hipDeviceSynchronize();
-		const int unmap_error = arena_unmap_all();
-		// (a range that may still hold a mapping is not handed back: leaking address space is harmless, freeing a mapped range is not)
-		if (d_arena_ && unmap_error == 0) (void)hipMemAddressFree(d_arena_, arena_va_bytes_);
-	} else if (d_arena_) {
-		(void)hipFree(d_arena_);
-	}
-	d_arena_ = nullptr;
-	arena_virtual_ = false;
-	arena_va_bytes_ = 0;
-	arena_capacity_ = 0;
-	arena_chunks_.clear();
-}
-
-// Make the arena at least `bricks` large, keeping what it holds.  Virtual arena: map one more physical chunk behind the
-// mapped part (the mapped size doubles) -- no copy, no synchronisation, nothing moves, so frames in flight and upload
-// batches already queued are not disturbed (the reference grows one pool at a time with a blocking cudaMemcpy,
-// Scene.cpp:242-247).  exact: (re)size an EMPTY arena to fit a known residency (callers have synchronised the device).
-int Scene::arena_reserve(uint64_t bricks, bool exact) {
-	if (bricks <= arena_capacity_ && !(exact && arena_top_ == 0 && arena_capacity_ > 2 * std::max<uint64_t>(bricks, 1ull << 16))) return 0;
-	if (bricks >= (1ull << 32)) { set_error("brick arena would exceed 2^32 bricks"); return BM_EINVAL; }
-	if (arena_virtual_) {
-		const size_t gran = arena_granularity_;
-		auto round_up = [gran](uint64_t b) { return (b + gran - 1) / gran * gran; };
-		uint64_t want_bytes;
-		bool remapping_empty_arena = false;
-		// (when the arena was unmapped for an exact re-size, any failure below marks the scene failed: frames are refused until
-		// bm_scene_reset_residency / bm_scene_preload_all succeeds -- the device index words may still carry loaded bits)
-		auto fail = [&](int code) { if (remapping_empty_arena) failed_ = true; return code; };
-		if (exact && arena_top_ == 0) {
-			if (!arena_chunks_.empty()) BM_HIP(hipDeviceSynchronize()); // (callers have synchronised already; unmapping itself does not wait)
-			if (int e = arena_unmap_all()) { failed_ = true; return e; }
-			remapping_empty_arena = true; // from here on a failure leaves view_.brick_arena pointing at an unmapped range
-			want_bytes = round_up(std::max<uint64_t>(bricks, 1ull << 16) * sizeof(Brick));
-		} else {
-			want_bytes = round_up(std::max<uint64_t>(arena_capacity_, 1ull << 16) * sizeof(Brick)); // 4 MiB to start with
-			while (want_bytes < bricks * sizeof(Brick)) want_bytes *= 2;
-		}
-		if (want_bytes > arena_va_bytes_) want_bytes = arena_va_bytes_;
-		if (want_bytes < bricks * sizeof(Brick)) { set_error("brick arena: reserved address range exhausted"); return fail(BM_ESTATE); }
-		const size_t have = static_cast<size_t>(arena_capacity_) * sizeof(Brick);
-		if (want_bytes > have) {
-			hipMemAllocationProp prop{};
-			prop.type = hipMemAllocationTypePinned;
-			prop.location.type = hipMemLocationTypeDevice;
-			prop.location.id = device_;
-			ArenaChunk c{};
-			c.offset = have;
-			c.bytes = want_bytes - have;
-			if (hipError_t e = hipMemCreate(&c.handle, c.bytes, &prop, 0); e != hipSuccess) return fail(hip_fail(e, "hipMemCreate", __FILE__, __LINE__));
-			char* at = reinterpret_cast<char*>(d_arena_) + c.offset;
-			if (hipError_t e = hipMemMap(at, c.bytes, 0, c.handle, 0); e != hipSuccess) { (void)hipMemRelease(c.handle); return fail(hip_fail(e, "hipMemMap", __FILE__, __LINE__)); }
-			hipMemAccessDesc access{};
-			access.location = prop.location;
-			access.flags = hipMemAccessFlagsProtReadWrite;
-			// access is (re)declared for the WHOLE mapped range, from the base: on this runtime (ROCm 7.2) hipMemSetAccess on a
-			// chunk at an offset fails sporadically with "invalid argument" when the chunks differ in size
-			// (tools/ubench/vmm_probe2.hip: 33 of 144 growths; 0 of 144 this way, with kernels in flight over the range)
-			if (hipError_t e = hipMemSetAccess(d_arena_, want_bytes, &access, 1); e != hipSuccess) {
-				(void)hipMemUnmap(at, c.bytes); (void)hipMemRelease(c.handle);
-				return fail(hip_fail(e, "hipMemSetAccess", __FILE__, __LINE__));
-			}
-			arena_chunks_.push_back(c);
-			if (arena_capacity_ > 0) arena_growths_++;
-			arena_capacity_ = want_bytes / sizeof(Brick);
-		}
-		return 0;
-	}
-	// ---- no virtual memory management on this device: reallocate + copy.  Synchronises the device: frames in flight may
-	// still read the old allocation, and the copy must see every upload.
-	uint64_t cap = bricks;
-	if (!exact) { // growth by residency: double
-		cap = std::max<uint64_t>(arena_capacity_, 1ull << 16); // 4 MiB to start with
-		while (cap < bricks) cap *= 2;
-	} else if (arena_top_ == 0) {
-		cap = std::max<uint64_t>(bricks, 1ull << 16); // (re)sized for a known residency: exact fit, shrinking an oversized arena
-	}
-	if (cap >= (1ull << 32)) { set_error("brick arena would exceed 2^32 bricks"); return BM_EINVAL; }
-	BM_HIP(hipDeviceSynchronize());
-	uint32_t* fresh = nullptr;
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), cap * sizeof(Brick)));
-	if (d_arena_ && arena_top_ > 0) {
-		BM_HIP(hipMemcpy(fresh, d_arena_, arena_top_ * sizeof(Brick), hipMemcpyDeviceToDevice));
-		arena_growths_++; arena_copy_growths_++;
-	}
-	if (d_arena_) BM_HIP(hipFree(d_arena_));
-	d_arena_ = fresh;
-	arena_capacity_ = cap;
-	view_.brick_arena = d_arena_;
-	return 0;
-}
-
-// A region of `bricks` (a power of two >= kStartingPool) for one pool: from the free list of that size, else from the top.
-int Scene::region_alloc(uint32_t bricks, uint32_t* offset) {
-	int cls = 0;
-	while ((1u << cls) < bricks) ++cls;
-	if (!free_regions_[cls].empty()) {
-		*offset = free_regions_[cls].back();
-		free_regions_[cls].pop_back();
-	} else {
-		if (int e = arena_reserve(arena_top_ + bricks)) return e;
-		*offset = static_cast<uint32_t>(arena_top_);
-		arena_top_ += bricks;
-	}
-	pool_bricks_ += bricks;
-	return 0;
-}
-
-// A vacated region becomes reusable once the batch that vacates it has been queued: its move kernel still reads it, and
-// a pool growing in the SAME batch must not be given it (later batches are ordered behind this one on the load stream).
-void Scene::region_free_deferred(uint32_t bricks, uint32_t offset) {
-	int cls = 0;
-	while ((1u << cls) < bricks) ++cls;
-	freed_this_batch_.emplace_back(cls, offset);
-	pool_bricks_ -= bricks;
-}
-
-// floor(n / d) for every n < 2^30 as umulhi(n, magic) >> shift (Granlund-Montgomery: with l = ceil(log2 d) and
-// magic = ceil(2^(30 + l) / d) one has 2^(30+l) <= magic * d < 2^(30+l) + 2^l, which makes the truncated product exact for 30-bit n;
-// magic < 2^31 + 1 fits 32 bits; tests/test_host_logic.py replays it against integer division)
-void division_magic(uint32_t d, uint32_t* magic, int* shift) {
-	int l = 0;
-	while ((1ull << l) < d) ++l;
-	if (l < 2) l = 2;
-	const unsigned __int128 one = static_cast<unsigned __int128>(1) << (30 + l);
-	*magic = static_cast<uint32_t>((one + d - 1) / d);
-	*shift = l - 2; // (30 + l) - 32
+int Scene::pool_region(uint32_t bricks, uint32_t* offset) {
+	const int e = arena_.region_alloc(bricks, offset);
+	view_.brick_arena = arena_.base();
+	return e;
 }
 
 // device half of Scene::generate (Scene.cpp:152-190): one flat index grid, one pool-base word per supercell and one
@@ -582,9 +245,9 @@ int Scene::allocate_device() {
 	uint64_t run = 0;
 	for (int i = 0; i < d.supercells; ++i) run += world.supercells[i].bricks.size();
 	if (run >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
-	total_bricks_ = run;
 	if (int e = alloc_index_grid()) return e;
-	if (int e = arena_open(4 * run + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
+	if (int e = arena_.open(device_, 4 * run + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
+	view_.brick_arena = arena_.base();
 	if (int e = alloc_cube_field()) return e;
 	{ // the host builds the field with tight rows (world.cpp) and every slice is copied row by row
 		std::vector<uint8_t> field;
@@ -604,8 +267,8 @@ int Scene::allocate_device() {
 int Scene::alloc_index_grid() {
 	const WorldDims& d = world.dims;
 	const size_t index_bytes = static_cast<size_t>(d.supercells) * kCellsPerSupercell * sizeof(uint32_t);
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_index_grid_), index_bytes));
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_pool_base_), static_cast<size_t>(d.supercells) * sizeof(uint32_t)));
+	if (int e = d_index_grid_.alloc(index_bytes)) return e;
+	if (int e = d_pool_base_.alloc(static_cast<size_t>(d.supercells) * sizeof(uint32_t))) return e;
 	BM_HIP(hipMemset(d_pool_base_, 0, static_cast<size_t>(d.supercells) * sizeof(uint32_t)));
 	view_.index_grid = d_index_grid_;
 	view_.pool_base = d_pool_base_;
@@ -618,20 +281,15 @@ int Scene::alloc_index_grid() {
 // +-1 / +- 2^shift / +- slice pitch.  Allocated and set to 255 everywhere; the interior is the caller's (a host build copied up, or
 // the GPU passes of edit.hip).
 int Scene::alloc_cube_field() {
-	const WorldDims& d = world.dims;
-	const int X = d.cells + 2, Z = d.cells_height + 2;
-	int shift = 2;
-	while ((1 << shift) < X) ++shift;
-	const uint64_t pxy = static_cast<uint64_t>(X) << shift, plane = pxy * static_cast<uint64_t>(Z);
-	if (pxy >= (1ull << 23) || plane * 8 >= (1ull << 32)) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cube_field_), plane * 8));
-	BM_HIP(hipMemset(d_cube_field_, 255, plane * 8)); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
-	view_.cf_shift = shift;
-	view_.cf_pxy = static_cast<uint32_t>(pxy);
-	view_.cf_plane = static_cast<uint32_t>(plane);
+	const CubeFieldLayout l = cube_field_layout(world.dims);
+	if (!l.fits) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
+	if (int e = d_cube_field_.alloc(l.plane * 8)) return e;
+	BM_HIP(hipMemset(d_cube_field_, 255, l.plane * 8)); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
+	view_.cf_shift = l.shift;
+	view_.cf_pxy = static_cast<uint32_t>(l.pxy);
+	view_.cf_plane = static_cast<uint32_t>(l.plane);
 	division_magic(view_.cf_pxy, &view_.cf_magic, &view_.cf_magic_shift);
 	view_.cube_field = d_cube_field_;
-	cube_field_bytes_ = plane * 8;
 	return 0;
 }
 
@@ -668,17 +326,16 @@ int Scene::generate_supercell(int sx, int sy, int sz) {
 
 // reference initial state: every non-empty brick is "unloaded | lod", nothing resident (Scene.cpp:157-175)
 int Scene::reset_residency() {
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
 	const WorldDims& d = world.dims;
 	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell);
 	std::vector<uint32_t> bases(d.supercells, 0u);
 	// every supercell that holds bricks starts with a pool of kStartingPool bricks (Scene.cpp:157-175, variables.h:15)
-	arena_reset();
 	uint64_t initial = 0;
 	for (int i = 0; i < d.supercells; ++i) initial += world.supercells[i].bricks.empty() ? 0u : kStartingPool;
-	if (int e = arena_reserve(std::max<uint64_t>(initial, 1), true)) return e;
+	if (int e = arena_fit(initial)) return e;
 	for (int i = 0; i < d.supercells; ++i) {
 		HostSupercell& c = world.supercells[i];
 		c.resident = 0;
@@ -687,7 +344,7 @@ int Scene::reset_residency() {
 		c.dev_slot.assign(c.bricks.size(), kNoDeviceSlot);
 		c.pool_free.clear();
 		if (!c.bricks.empty()) {
-			if (int e = region_alloc(kStartingPool, &c.pool_base)) return e;
+			if (int e = pool_region(kStartingPool, &c.pool_base)) return e;
 			c.pool_capacity = kStartingPool;
 		}
 		bases[i] = c.pool_base;
@@ -698,22 +355,13 @@ int Scene::reset_residency() {
 	BM_HIP(hipMemcpy(d_index_grid_, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 	BM_HIP(hipMemcpy(d_pool_base_, bases.data(), bases.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 	for (int r = 0; r < 2; ++r) BM_HIP(hipMemset(d_load_count_[r], 0, sizeof(uint32_t)));
-	ring_cur_ = 0;
-	snapshot_pending_ = false;
-	view_.load_queue = d_load_queue_[0];
-	view_.load_queue_count = d_load_count_[0];
 	resident_bricks_ = 0;
-	preloaded_ = false;
-	staging_busy_ = false;
-	failed_ = false;
-	stream_batches_ = stream_host_ns_ = 0;
-	upload_seq_ = 0;
-	for (FrameStream& f : frame_streams_) f.upload_seen = 0;
+	residency_rebuilt(false);
 	return 0;
 }
 
 int Scene::preload_all() {
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
 	const WorldDims& d = world.dims;
@@ -722,15 +370,13 @@ int Scene::preload_all() {
 	// "all bricks pre-loaded" (BASELINE configs 1-2): every pool is its supercell's full host brick vector, exact fit, and
 	// the device words are the host words (slot | loaded | lod, Scene.cpp:104).  Host slots that edits freed keep their place in the
 	// pool and are the pool's free slots.
-	total_bricks_ = 0;
-	for (int i = 0; i < d.supercells; ++i) total_bricks_ += world.supercells[i].bricks.size();
-	arena_reset();
-	if (int e = arena_reserve(std::max<uint64_t>(total_bricks_, 1), true)) return e;
+	uint64_t total_bricks = 0;
+	for (int i = 0; i < d.supercells; ++i) total_bricks += world.supercells[i].bricks.size();
+	if (int e = arena_fit(total_bricks)) return e;
 	for (int i = 0; i < d.supercells; ++i) {
 		HostSupercell& c = world.supercells[i];
-		c.pool_base = static_cast<uint32_t>(arena_top_);
+		c.pool_base = arena_.claim_top(c.bricks.size());
 		c.pool_capacity = static_cast<uint32_t>(c.bricks.size());
-		arena_top_ += c.bricks.size();
 		bases[i] = c.pool_base;
 		std::memcpy(&words[static_cast<size_t>(i) * kCellsPerSupercell], c.indices.data(), kCellsPerSupercell * sizeof(uint32_t));
 		c.resident = static_cast<uint32_t>(c.bricks.size());
@@ -738,24 +384,14 @@ int Scene::preload_all() {
 		for (size_t s = 0; s < c.bricks.size(); ++s) c.dev_slot[s] = static_cast<uint16_t>(s);
 		c.pool_free = c.free_slots;
 		if (!c.bricks.empty())
-			BM_HIP(hipMemcpy(d_arena_ + static_cast<size_t>(c.pool_base) * kBrickWords, c.bricks.data(), c.bricks.size() * sizeof(Brick), hipMemcpyHostToDevice));
+			BM_HIP(hipMemcpy(arena_.base() + static_cast<size_t>(c.pool_base) * kBrickWords, c.bricks.data(), c.bricks.size() * sizeof(Brick), hipMemcpyHostToDevice));
 	}
-	pool_bricks_ = total_bricks_;
 	BM_HIP(hipMemcpy(d_pool_base_, bases.data(), bases.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 	BM_HIP(hipMemcpyAsync(d_index_grid_, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, load_stream_));
 	for (int r = 0; r < 2; ++r) BM_HIP(hipMemsetAsync(d_load_count_[r], 0, sizeof(uint32_t), load_stream_));
 	BM_HIP(hipStreamSynchronize(load_stream_));
-	ring_cur_ = 0;
-	snapshot_pending_ = false;
-	view_.load_queue = d_load_queue_[0];
-	view_.load_queue_count = d_load_count_[0];
 	resident_bricks_ = world.total_bricks();
-	preloaded_ = true;
-	staging_busy_ = false;
-	failed_ = false;
-	stream_batches_ = stream_host_ns_ = 0;
-	upload_seq_ = 0;
-	for (FrameStream& f : frame_streams_) f.upload_seen = 0;
+	residency_rebuilt(true);
 	return 0;
 }
 
@@ -806,40 +442,27 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	const WorldDims& d = world.dims;
 	free_device();
 	world.generated = false;
-	for (hipEvent_t& ev : ev_load_time_) if (!ev) BM_HIP(hipEventCreate(&ev));
+	for (Event& ev : ev_load_time_) if (int e = ev.create()) return e;
 	if (int e = alloc_index_grid()) return e;
 	if (int e = alloc_cube_field()) return e;
 	set_view_dims();
 	LoadDims ld{static_cast<uint32_t>(d.grid_size), static_cast<uint32_t>(d.supergrid_xy), static_cast<uint32_t>(d.supergrid_xy * d.supergrid_xy),
 				static_cast<uint32_t>(d.supercells)};
 	// temporaries: one count per supercell + the 64-bit total; the intermediate planes of the field passes
-	struct Temp {
-		uint32_t* p = nullptr;
-		~Temp() { if (p) (void)hipFree(p); }
-	} counts;
-	BM_HIP(hipMalloc(reinterpret_cast<void**>(&counts.p), (static_cast<size_t>(d.supercells) + 2) * sizeof(uint32_t)));
-	uint32_t* d_total = counts.p + d.supercells;
+	DeviceBuffer<uint32_t> counts;
+	if (int e = counts.alloc((static_cast<size_t>(d.supercells) + 2) * sizeof(uint32_t))) return e;
+	uint32_t* d_total = counts + d.supercells;
 	// the field comes from the update of edit.hip with the box = every cell, into the field alloc_cube_field set to 255
-	FieldUpdate fu{};
-	fu.rx0 = fu.ry0 = fu.rz0 = fu.ay0 = fu.bz0 = 1;
-	fu.rx1 = fu.ry1 = fu.ay1 = d.cells + 1;
-	fu.rz1 = fu.bz1 = d.cells_height + 1;
-	fu.cells = d.cells; fu.cells_height = d.cells_height;
-	fu.sg_xy = d.supergrid_xy; fu.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
-	fu.cf_shift = view_.cf_shift; fu.cf_pxy = view_.cf_pxy; fu.cf_plane = view_.cf_plane;
-	if (field_update_tmp_bytes(fu) > cf_tmp_cap_) {
-		if (d_cf_tmp_) { BM_HIP(hipFree(d_cf_tmp_)); d_cf_tmp_ = nullptr; }
-		cf_tmp_cap_ = 0;
-		BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cf_tmp_), field_update_tmp_bytes(fu)));
-		cf_tmp_cap_ = field_update_tmp_bytes(fu);
-	}
+	const int box_lo[3] = {0, 0, 0}, box_hi[3] = {d.cells - 1, d.cells - 1, d.cells_height - 1};
+	const FieldUpdate fu = field_update_box(d, box_lo, box_hi);
+	if (int e = d_cf_tmp_.reserve(field_update_tmp_bytes(fu))) return e; // (load_voxels has synchronised the device)
 	BM_HIP(hipEventRecord(ev_edit_caller_, stream)); // the volume is whatever the caller's stream has written by now
 	BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
 	// ---- classify + number
 	BM_HIP(hipEventRecord(ev_load_time_[0], load_stream_));
 	launch_load_classify(voxels, d_index_grid_, ld, load_stream_);
 	BM_HIP(hipGetLastError());
-	launch_load_number(d_index_grid_, counts.p, d_pool_base_, d_total, ld, load_stream_);
+	launch_load_number(d_index_grid_, counts, d_pool_base_, d_total, ld, load_stream_);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(ev_load_time_[1], load_stream_));
 	uint32_t total_words[2] = {0, 0};
@@ -847,13 +470,11 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	BM_HIP(hipStreamSynchronize(load_stream_)); // the one host round trip: the arena is sized by what the volume holds
 	const uint64_t total = total_words[0] | (static_cast<uint64_t>(total_words[1]) << 32);
 	if (total >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
-	total_bricks_ = total;
-	if (int e = arena_open(4 * total + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
-	arena_reset();
-	if (int e = arena_reserve(std::max<uint64_t>(total, 1), true)) return e;
+	if (int e = arena_.open(device_, 4 * total + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
+	if (int e = arena_fit(total)) return e;
 	// ---- pack
 	BM_HIP(hipEventRecord(ev_load_time_[2], load_stream_));
-	launch_load_pack(voxels, d_index_grid_, d_pool_base_, d_arena_, ld, load_stream_);
+	launch_load_pack(voxels, d_index_grid_, d_pool_base_, arena_.base(), ld, load_stream_);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(ev_load_time_[3], load_stream_));
 	// ---- field
@@ -865,7 +486,7 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	std::vector<Brick> bricks(total);
 	BM_HIP(hipMemcpyAsync(words.data(), d_index_grid_, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
 	BM_HIP(hipMemcpyAsync(bases.data(), d_pool_base_, bases.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
-	if (total) BM_HIP(hipMemcpyAsync(bricks.data(), d_arena_, total * sizeof(Brick), hipMemcpyDeviceToHost, load_stream_));
+	if (total) BM_HIP(hipMemcpyAsync(bricks.data(), arena_.base(), total * sizeof(Brick), hipMemcpyDeviceToHost, load_stream_));
 	for (int r = 0; r < 2; ++r) BM_HIP(hipMemsetAsync(d_load_count_[r], 0, sizeof(uint32_t), load_stream_));
 	BM_HIP(hipEventRecord(ev_load_time_[5], load_stream_));
 	BM_HIP(hipStreamSynchronize(load_stream_));
@@ -892,19 +513,10 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 		for (auto& t : pool) t.join();
 	}
 	world.generated = true;
-	arena_top_ = pool_bricks_ = total;
+	arena_.claim_top(total);
 	resident_bricks_ = total;
 	on_device_ = true;
-	ring_cur_ = 0;
-	snapshot_pending_ = false;
-	view_.load_queue = d_load_queue_[0];
-	view_.load_queue_count = d_load_count_[0];
-	preloaded_ = true;
-	staging_busy_ = false;
-	failed_ = false;
-	stream_batches_ = stream_host_ns_ = 0;
-	upload_seq_ = 0;
-	for (FrameStream& f : frame_streams_) f.upload_seen = 0;
+	residency_rebuilt(true);
 	load_timed_ = true;
 	return 0;
 }
@@ -937,7 +549,7 @@ int Scene::host_voxels(uint8_t* dst, size_t capacity, size_t* bytes) {
 // A frame on `stream` must see every brick batch queued so far: wait for the latest upload event unless this stream
 // already has.  (Per stream, not per scene: with frames on several streams each of them has to be ordered.)
 int Scene::frame_begin(hipStream_t stream) {
-	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	if (int e = require_not_failed()) return e;
 	FrameStream* fs = nullptr;
 	bool created = false;
 	for (FrameStream& f : frame_streams_) if (f.stream == stream) { fs = &f; break; }
@@ -949,13 +561,12 @@ int Scene::frame_begin(hipStream_t stream) {
 			size_t lru = 0;
 			for (size_t i = 1; i < frame_streams_.size(); ++i) if (frame_streams_[i].last_use < frame_streams_[lru].last_use) lru = i;
 			BM_HIP(hipEventSynchronize(frame_streams_[lru].done));
-			BM_HIP(hipEventDestroy(frame_streams_[lru].done));
 			frame_streams_.erase(frame_streams_.begin() + static_cast<long>(lru));
 		}
 		FrameStream f;
 		f.stream = stream;
-		BM_HIP(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
-		frame_streams_.push_back(f);
+		if (int e = f.done.create(hipEventDisableTiming)) return e;
+		frame_streams_.push_back(std::move(f));
 		fs = &frame_streams_.back();
 	}
 	// (a stream handle can be recycled by the runtime after its owner destroyed it: an entry that claims to have seen the
@@ -993,12 +604,6 @@ int Scene::order_load_stream_behind_frames() {
 	return 0;
 }
 
-void Scene::drop_frame_streams() {
-	for (FrameStream& f : frame_streams_)
-		if (f.done) (void)hipEventDestroy(f.done);
-	frame_streams_.clear();
-}
-
 // ---------------------------------------------------------------- streaming
 // Stage the first `count` requests of a ring (positions already in its pinned mirror), copy them up and scatter
 // them into the arena / index grid on the load stream (Scene.cpp:215-229 + the upload kernel, kernel.cu:141-151,412-413).
@@ -1020,7 +625,7 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 			return BM_ESTATE;
 		}
 		const HostSupercell& c = world.supercells[d.supercell_id(px / kSupercell, py / kSupercell, pz / kSupercell)];
-		const uint32_t word = c.indices[static_cast<uint32_t>((px % kSupercell) + (py % kSupercell) * kSupercell + (pz % kSupercell) * kSupercell * kSupercell)];
+		const uint32_t word = c.indices[cell_local_index(px, py, pz)];
 		if (word != 0 && (!(word & BM_BRICK_LOADED_BIT) || (word & BM_BRICK_INDEX_BITS) >= c.bricks.size() || (word & BM_BRICK_INDEX_BITS) >= c.dev_slot.size())) {
 			set_error("brick request ring names a brick that does not exist");
 			failed_ = true;
@@ -1040,8 +645,7 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 		const int px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
 		const int sci = d.supercell_id(px / kSupercell, py / kSupercell, pz / kSupercell);
 		HostSupercell& c = world.supercells[sci];
-		const uint32_t local = static_cast<uint32_t>((px % kSupercell) + (py % kSupercell) * kSupercell + (pz % kSupercell) * kSupercell * kSupercell);
-		const uint32_t word = c.indices[local];
+		const uint32_t word = c.indices[cell_local_index(px, py, pz)];
 		if (word == 0 || c.dev_slot[word & BM_BRICK_INDEX_BITS] != kNoDeviceSlot) continue; // stale (above)
 		const uint32_t i_out = kept++;
 		if (i_out != i) { pos[3 * i_out] = px; pos[3 * i_out + 1] = py; pos[3 * i_out + 2] = pz; }
@@ -1059,7 +663,7 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 		if (c.resident >= c.pool_capacity) {
 			const uint32_t grown = std::max<uint32_t>(kStartingPool, c.pool_capacity * 2u);
 			uint32_t fresh = 0;
-			if (int e = region_alloc(grown, &fresh)) { failed_ = true; return e; }
+			if (int e = pool_region(grown, &fresh)) { failed_ = true; return e; }
 			// Only the bricks that were resident BEFORE this batch have to be copied (the batch's own bricks are scattered to
 			// base + slot after the bases are published), and only once: a pool that grows twice in one batch moves from
 			// the region it had when the batch began straight to the last one.
@@ -1070,7 +674,7 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 			} else {
 				h_moves_[mv->second].dst = fresh;
 			}
-			if (c.pool_capacity > 0) region_free_deferred(c.pool_capacity, c.pool_base);
+			if (c.pool_capacity > 0) arena_.region_free_deferred(c.pool_capacity, c.pool_base);
 			c.pool_base = fresh;
 			c.pool_capacity = grown;
 		}
@@ -1089,22 +693,21 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 		// frame in flight, whatever stream it is on; the copies above already overlap them.
 		if (overlapped_) { if (int e = order_load_stream_behind_frames()) return e; }
 		DeviceScene ring_view = view_;
-		ring_view.load_queue = compacted ? d_positions_ : d_load_queue_[ring];
+		ring_view.load_queue = compacted ? d_positions_.get() : d_load_queue_[ring].get();
 		ring_view.load_queue_count = d_load_count_[ring];
 		if (n_moves > 0) { // grown pools: copy their bricks to the new regions and publish the new bases, ahead of the scatter
 			BM_HIP(hipMemcpyAsync(d_moves_, h_moves_, static_cast<size_t>(n_moves) * sizeof(PoolMove), hipMemcpyHostToDevice, load_stream_));
-			launch_pool_moves(d_moves_, n_moves, d_arena_, d_pool_base_, load_stream_);
+			launch_pool_moves(d_moves_, n_moves, arena_.base(), d_pool_base_, load_stream_);
 			BM_HIP(hipGetLastError());
 		}
-		launch_upload(ring_view, d_bricks_queue_, d_indices_queue_, d_arena_, kept, load_stream_); // kernel.cu:412
+		launch_upload(ring_view, d_bricks_queue_, d_indices_queue_, arena_.base(), kept, load_stream_); // kernel.cu:412
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipMemsetAsync(d_load_count_[ring], 0, sizeof(uint32_t), load_stream_));             // kernel.cu:413
 		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
 		return 0;
 	};
 	if (int e = queue()) { failed_ = true; return e; } // the host bookkeeping is ahead of the device: refuse to go on
-	for (const auto& f : freed_this_batch_) free_regions_[f.first].push_back(f.second); // reusable by the NEXT batch
-	freed_this_batch_.clear();
+	arena_.commit_freed_regions();
 	staging_busy_ = true;
 	upload_seq_++;
 	resident_bricks_ += kept;
@@ -1116,8 +719,8 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 
 int Scene::process_load_queue(uint32_t* serviced) {
 	if (serviced) *serviced = 0;
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
-	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
+	if (int e = require_not_failed()) return e;
 	BM_HIP(hipSetDevice(device_));
 	if (!overlapped_) {
 		// ---- reference order (main.cpp:142-144): the frames that raised the requests have finished (kernel.cu:431), the host
@@ -1157,9 +760,7 @@ int Scene::process_load_queue(uint32_t* serviced) {
 	BM_HIP(hipEventRecord(ev_snapshot_, load_stream_));
 	snapshot_pending_ = true;
 	ring_snapshot_ = ring;
-	ring_cur_ = ring ^ 1;
-	view_.load_queue = d_load_queue_[ring_cur_];
-	view_.load_queue_count = d_load_count_[ring_cur_];
+	use_ring(ring ^ 1);
 	return 0;
 }
 
@@ -1183,12 +784,12 @@ int Scene::info(bm_scene_info* out) {
 	out->total_bricks = world.generated ? world.total_bricks() : 0;
 	out->resident_bricks = resident_bricks_;
 	out->index_bytes = on_device_ ? static_cast<uint64_t>(d.supercells) * kCellsPerSupercell * 4 : 0;
-	out->brick_bytes = on_device_ ? arena_capacity_ * 64 : 0;
-	out->pool_bytes = on_device_ ? pool_bricks_ * 64 : 0;
-	out->cube_field_bytes = on_device_ ? cube_field_bytes_ : 0;
-	out->arena_growths = arena_growths_;
-	out->arena_copy_growths = arena_copy_growths_;
-	out->arena_virtual = arena_virtual_ ? 1 : 0;
+	out->brick_bytes = on_device_ ? arena_.capacity() * 64 : 0;
+	out->pool_bytes = on_device_ ? arena_.pool_bricks() * 64 : 0;
+	out->cube_field_bytes = on_device_ ? d_cube_field_.bytes() : 0;
+	out->arena_growths = arena_.growths();
+	out->arena_copy_growths = arena_.copy_growths();
+	out->arena_virtual = arena_.is_virtual() ? 1 : 0;
 	out->failed = failed_ ? 1 : 0;
 	out->stream_batches = stream_batches_;
 	out->stream_host_ns = stream_host_ns_;
@@ -1196,7 +797,7 @@ int Scene::info(bm_scene_info* out) {
 }
 
 int Scene::device_indices(int supercell, uint32_t* out4096) {
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
 	if (supercell < 0 || supercell >= world.dims.supercells || !out4096) { set_error("bad supercell"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
@@ -1205,14 +806,14 @@ int Scene::device_indices(int supercell, uint32_t* out4096) {
 }
 
 int Scene::device_brick(int supercell, uint32_t device_slot, uint32_t* out16) {
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
 	if (supercell < 0 || supercell >= world.dims.supercells || !out16 || device_slot >= world.supercells[supercell].resident) {
 		set_error("bad supercell or slot");
 		return BM_EINVAL;
 	}
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
-	BM_HIP(hipMemcpy(out16, d_arena_ + (static_cast<size_t>(world.supercells[supercell].pool_base) + device_slot) * kBrickWords, sizeof(Brick), hipMemcpyDeviceToHost));
+	BM_HIP(hipMemcpy(out16, arena_.base() + (static_cast<size_t>(world.supercells[supercell].pool_base) + device_slot) * kBrickWords, sizeof(Brick), hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -1228,7 +829,7 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 	std::string why;
 	if (!World::validate_edits(edits, count, &why)) { set_error("bm_scene_edit: " + why); return BM_EINVAL; }
 	if (!on_device_) { set_error("bm_scene_edit: scene not generated"); return BM_ESTATE; }
-	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	if (int e = require_not_failed()) return e;
 	const WorldDims& d = world.dims;
 	std::vector<int> reached;
 	{
@@ -1292,14 +893,9 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 				uint32_t grown = kStartingPool;
 				while (grown < c.resident + appends || grown < 2 * c.pool_capacity) grown *= 2;
 				uint32_t fresh = 0;
-				if (int e = region_alloc(grown, &fresh)) { failed_ = true; return e; }
+				if (int e = pool_region(grown, &fresh)) { failed_ = true; return e; }
 				moves.push_back(PoolMove{c.pool_capacity ? c.pool_base : fresh, fresh, c.pool_capacity ? c.resident : 0u, static_cast<uint32_t>(sci)});
-				if (c.pool_capacity > 0) { // (a preloaded pool is an exact fit: only its largest power of two is handed out again)
-					int cls = 0;
-					while ((2u << cls) <= c.pool_capacity) ++cls;
-					freed_this_batch_.emplace_back(cls, c.pool_base);
-					pool_bricks_ -= c.pool_capacity;
-				}
+				if (c.pool_capacity > 0) arena_.region_free_deferred(c.pool_capacity, c.pool_base); // (a preloaded pool is an exact fit: only its largest power of two is handed out again)
 				c.pool_base = fresh;
 				c.pool_capacity = grown;
 			}
@@ -1326,8 +922,7 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 	}
 	const uint32_t n = static_cast<uint32_t>(cells.size());
 	if (n == 0) { // nothing inside the world changed a brick (e.g. clearing empty space)
-		for (const auto& f : freed_this_batch_) free_regions_[f.first].push_back(f.second);
-		freed_this_batch_.clear();
+		arena_.commit_freed_regions();
 		return 0;
 	}
 
@@ -1336,38 +931,17 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 	const size_t o_cells = up(moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
 				 o_bricks = o_slots + up(n * 4ull), bytes = o_bricks + n * sizeof(Brick);
 	const bool field = box_hi[0] >= 0;
-	FieldUpdate fu{};
-	if (field) {
-		const int lim[3] = {d.cells, d.cells, d.cells_height};
-		int r0[3], r1[3];
-		for (int k = 0; k < 3; ++k) { // bordered coordinates: interior cells are 1 ... lim
-			r0[k] = std::max(1, box_lo[k] + 1 - 254);
-			r1[k] = std::min(lim[k] + 1, box_hi[k] + 1 + 254 + 1);
-		}
-		fu.rx0 = r0[0]; fu.rx1 = r1[0]; fu.ry0 = r0[1]; fu.ry1 = r1[1]; fu.rz0 = r0[2]; fu.rz1 = r1[2];
-		fu.ay0 = std::max(1, fu.ry0 - 254); fu.ay1 = std::min(d.cells + 1, fu.ry1 + 254);
-		fu.bz0 = std::max(1, fu.rz0 - 254); fu.bz1 = std::min(d.cells_height + 1, fu.rz1 + 254);
-		fu.cells = d.cells; fu.cells_height = d.cells_height;
-		fu.sg_xy = d.supergrid_xy; fu.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
-		fu.cf_shift = view_.cf_shift; fu.cf_pxy = view_.cf_pxy; fu.cf_plane = view_.cf_plane;
-	}
+	const FieldUpdate fu = field ? field_update_box(d, box_lo, box_hi) : FieldUpdate{};
 	auto queue = [&]() -> int {
-		if (bytes > edit_cap_) {
+		if (bytes > d_edit_.bytes()) { // (the two grow together: h_edit_ is as large as d_edit_)
 			BM_HIP(hipStreamSynchronize(load_stream_)); // the previous batch's kernels may still read the device staging
-			if (h_edit_) { BM_HIP(hipHostFree(h_edit_)); h_edit_ = nullptr; }
-			if (d_edit_) { BM_HIP(hipFree(d_edit_)); d_edit_ = nullptr; }
-			edit_cap_ = 0;
 			const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-			BM_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_edit_), cap, hipHostMallocDefault));
-			BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_edit_), cap));
-			edit_cap_ = cap;
+			if (int e = h_edit_.reserve(cap)) return e;
+			if (int e = d_edit_.reserve(cap)) return e;
 		}
-		if (field && field_update_tmp_bytes(fu) > cf_tmp_cap_) {
+		if (field && field_update_tmp_bytes(fu) > d_cf_tmp_.bytes()) {
 			BM_HIP(hipStreamSynchronize(load_stream_));
-			if (d_cf_tmp_) { BM_HIP(hipFree(d_cf_tmp_)); d_cf_tmp_ = nullptr; }
-			cf_tmp_cap_ = 0;
-			BM_HIP(hipMalloc(reinterpret_cast<void**>(&d_cf_tmp_), field_update_tmp_bytes(fu)));
-			cf_tmp_cap_ = field_update_tmp_bytes(fu);
+			if (int e = d_cf_tmp_.reserve(field_update_tmp_bytes(fu))) return e;
 		}
 		if (!moves.empty()) std::memcpy(h_edit_, moves.data(), moves.size() * sizeof(PoolMove));
 		std::memcpy(h_edit_ + o_cells, cells.data(), n * 4ull);
@@ -1382,11 +956,11 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 		BM_HIP(hipEventRecord(ev_edit_, load_stream_)); // the pinned staging is free again from here on
 		BM_HIP(hipEventRecord(ev_edit_time_[0], load_stream_));
 		if (!moves.empty()) {
-			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_), static_cast<uint32_t>(moves.size()), d_arena_, d_pool_base_, load_stream_);
+			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_.get()), static_cast<uint32_t>(moves.size()), arena_.base(), d_pool_base_, load_stream_);
 			BM_HIP(hipGetLastError());
 		}
 		launch_edit_scatter(reinterpret_cast<const uint32_t*>(d_edit_ + o_cells), reinterpret_cast<const uint32_t*>(d_edit_ + o_words),
-							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, d_index_grid_, d_arena_,
+							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, d_index_grid_, arena_.base(),
 							load_stream_);
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipEventRecord(ev_edit_time_[1], load_stream_));
@@ -1399,8 +973,7 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 		return 0;
 	};
 	if (int e = queue()) { failed_ = true; return e; } // the host world is ahead of the device: refuse to go on
-	for (const auto& f : freed_this_batch_) free_regions_[f.first].push_back(f.second); // reusable by the NEXT batch
-	freed_this_batch_.clear();
+	arena_.commit_freed_regions();
 	edit_busy_ = true;
 	edit_timed_ = true;
 	edit_field_timed_ = field;
@@ -1420,7 +993,7 @@ int Scene::last_edit_ms(float* scatter_ms, float* field_ms) {
 }
 
 int Scene::device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
 	const WorldDims& d = world.dims;
 	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = 8 * X * X * Z;
 	if (bytes) *bytes = need;
@@ -1455,7 +1028,7 @@ int Scene::render(const bm_camera* cam, const bm_frame_params* fp, float* accum,
 // of the persistent kernel (trace.hip "FRAME RING"): frame i's constants, ticket counters and buffers are entry first + i of the
 // scene's rings, and every wave walks from frame to frame by itself.
 int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream) {
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
 	if (count < 1 || count > kMaxFramesPerLaunch) { set_error("bm_render_frames: 1 ... 256 frames per launch"); return BM_EINVAL; }
 	if (!cams || !fps || !accums) { set_error("null argument"); return BM_EINVAL; }
 	bool hit_records = false;
@@ -1586,7 +1159,7 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 #ifdef BM_PHASE_TIMING
 	DeviceCounters* const counters_arg = d_counters_; // profiling build: the plain kernel reports its phase timers too
 #else
-	DeviceCounters* const counters_arg = (fc.flags & BM_FLAG_COUNTERS) ? d_counters_ : nullptr;
+	DeviceCounters* const counters_arg = (fc.flags & BM_FLAG_COUNTERS) ? d_counters_.get() : nullptr;
 #endif
 	launch_trace(view_, fc, d_frame_constants_ + first, counters_arg, work_counter, instrumented,
 				 compute_units_, blocks_per_cu_[instrumented ? 1 : 0], stream);
@@ -1615,12 +1188,12 @@ int Scene::cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t f
 			campos[i] = static_cast<int>(lod_origin[i] / 8.f); // as fill_frame_constants: ivec3(camera.position / 8.f)
 		}
 	}
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
-	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
+	if (int e = require_not_failed()) return e;
 	BM_HIP(hipSetDevice(device_));
 	if (!d_query_tickets_) {
-		BM_HIP(hipMalloc(&d_query_tickets_, kQueryRing * 128));
-		for (hipEvent_t& e : ev_query_) BM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		if (int e = d_query_tickets_.alloc(kQueryRing * 128)) return e;
+		for (Event& ev : ev_query_) if (int e = ev.create(hipEventDisableTiming)) return e;
 		query_blocks_per_cu_[0] = query_blocks_per_cu(false);
 		query_blocks_per_cu_[1] = query_blocks_per_cu(true);
 	}
@@ -1641,7 +1214,7 @@ int Scene::cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t f
 }
 
 int Scene::begin_frame(hipStream_t stream, DeviceScene* view, DeviceCounters** counters) {
-	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
+	if (int e = require_on_device()) return e;
 	BM_HIP(hipSetDevice(device_));
 	if (int e = frame_begin(stream)) return e; // bricks uploaded on the load stream must be visible to this frame
 	if (view) *view = view_;
@@ -1706,7 +1279,7 @@ int Scene::sched_stats_read(bm_sched_stats* out) {
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
 	static_assert(sizeof(bm_sched_stats) == sizeof(DeviceCounters::sched) + sizeof(DeviceCounters::cycles), "scheduler stat blocks must match");
-	BM_HIP(hipMemcpy(out, reinterpret_cast<const char*>(d_counters_) + offsetof(DeviceCounters, sched), sizeof(bm_sched_stats), hipMemcpyDeviceToHost));
+	BM_HIP(hipMemcpy(out, reinterpret_cast<const char*>(d_counters_.get()) + offsetof(DeviceCounters, sched), sizeof(bm_sched_stats), hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -1714,7 +1287,7 @@ int Scene::sched_detail_read(uint64_t* out8) {
 	if (!out8) { set_error("null argument"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
-	BM_HIP(hipMemcpy(out8, reinterpret_cast<const char*>(d_counters_) + offsetof(DeviceCounters, detail), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	BM_HIP(hipMemcpy(out8, reinterpret_cast<const char*>(d_counters_.get()) + offsetof(DeviceCounters, detail), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
 	return 0;
 }
 

@@ -245,7 +245,7 @@ __device__ __forceinline__ uint32_t cell_offset(const DeviceScene& sc, uint32_t 
 }
 __device__ __forceinline__ void cell_coords(const DeviceScene& sc, const RayState& r, int& x, int& y, int& z) {
 	const uint32_t rel = r.p - r.field_off;                               // < cf_plane < 2^30
-	const uint32_t fz = __umulhi(rel, sc.cf_magic) >> sc.cf_magic_shift;  // floor(rel / cf_pxy), exact (scene.cpp division_magic)
+	const uint32_t fz = __umulhi(rel, sc.cf_magic) >> sc.cf_magic_shift;  // floor(rel / cf_pxy), exact (frame_plan.cpp division_magic)
 	const uint32_t low = rel - __umul24(fz, sc.cf_pxy);
 	x = static_cast<int>(low & ((1u << sc.cf_shift) - 1u)) - 1;
 	y = static_cast<int>(low >> sc.cf_shift) - 1;

@@ -8,35 +8,29 @@
 
 namespace bm {
 
-Wavefront::~Wavefront() {
-	if (hipSetDevice(device_) != hipSuccess) return;
-	(void)hipDeviceSynchronize();
-	(void)hipFree(d_work_); (void)hipFree(d_next_); (void)hipFree(d_shadow_); (void)hipFree(d_state_); (void)hipFree(d_block_counts_); (void)hipFree(d_cold_); (void)hipFree(d_counters_);
-	(void)hipFree(d_frame_constants_);
-	if (h_frame_constants_) (void)hipHostFree(h_frame_constants_);
-	for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-	for (auto& e : ev_slot_) if (e) (void)hipEventDestroy(e);
+Wavefront::~Wavefront() { // the members free themselves, once nothing in flight uses them
+	if (hipSetDevice(device_) == hipSuccess) (void)hipDeviceSynchronize();
 }
 
 int Wavefront::init() {
 	if (queue_size_ == 0 || queue_size_ > (1u << 30)) { set_error("bad queue size"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipMalloc(&d_work_, static_cast<size_t>(queue_size_) * sizeof(WfRay)));
-	BM_HIP(hipMalloc(&d_next_, static_cast<size_t>(queue_size_) * sizeof(WfRay)));
-	BM_HIP(hipMalloc(&d_shadow_, static_cast<size_t>(queue_size_) * sizeof(WfShadow)));
-	BM_HIP(hipMalloc(&d_state_, sizeof(WfState)));
-	BM_HIP(hipMalloc(&d_block_counts_, (static_cast<size_t>(queue_size_) / 256 + 1) * 8));
-	BM_HIP(hipMalloc(&d_cold_, static_cast<size_t>(queue_size_) * 16));
-	BM_HIP(hipMalloc(&d_frame_constants_, kConstantsRing * sizeof(FrameConstants)));
-	BM_HIP(hipHostMalloc(&h_frame_constants_, kConstantsRing * sizeof(FrameConstants), hipHostMallocDefault));
+	if (int e = d_work_.alloc(static_cast<size_t>(queue_size_) * sizeof(WfRay))) return e;
+	if (int e = d_next_.alloc(static_cast<size_t>(queue_size_) * sizeof(WfRay))) return e;
+	if (int e = d_shadow_.alloc(static_cast<size_t>(queue_size_) * sizeof(WfShadow))) return e;
+	if (int e = d_state_.alloc(sizeof(WfState))) return e;
+	if (int e = d_block_counts_.alloc((static_cast<size_t>(queue_size_) / 256 + 1) * 8)) return e;
+	if (int e = d_cold_.alloc(static_cast<size_t>(queue_size_) * 16)) return e;
+	if (int e = d_frame_constants_.alloc(kConstantsRing * sizeof(FrameConstants))) return e;
+	if (int e = h_frame_constants_.alloc(kConstantsRing * sizeof(FrameConstants))) return e;
 	BM_HIP(hipMemset(d_work_, 0, static_cast<size_t>(queue_size_) * sizeof(WfRay)));
 	BM_HIP(hipMemset(d_next_, 0, static_cast<size_t>(queue_size_) * sizeof(WfRay)));
 	BM_HIP(hipMemset(d_shadow_, 0, static_cast<size_t>(queue_size_) * sizeof(WfShadow)));
 	BM_HIP(hipMemset(d_state_, 0, sizeof(WfState)));
-	BM_HIP(hipMalloc(&d_counters_, 2 * sizeof(DeviceCounters)));
+	if (int e = d_counters_.alloc(2 * sizeof(DeviceCounters))) return e;
 	BM_HIP(hipMemset(d_counters_, 0, 2 * sizeof(DeviceCounters)));
-	for (auto& e : ev_) BM_HIP(hipEventCreate(&e));
-	for (auto& e : ev_slot_) BM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+	for (Event& ev : ev_) if (int e = ev.create()) return e;
+	for (Event& ev : ev_slot_) if (int e = ev.create(hipEventDisableTiming)) return e;
 	for (int c = 0; c < 2; ++c)
 		for (int i = 0; i < 2; ++i) blocks_per_cu_[c][i] = std::min(wavefront_blocks_per_cu(c != 0, i != 0), kMaxBlocksPerCu);
 	if (const char* cap = std::getenv("BM_WF_BLOCKS_PER_CU")) { // experiment knob: fewer resident waves per SIMD
@@ -67,7 +61,7 @@ int Wavefront::frame(const bm_camera* cam, const bm_frame_params* fp, float* acc
 	DeviceScene view;
 	if (int e = scene_->begin_frame(stream, &view, nullptr)) return e;
 	const bool instrumented = (fp->flags & BM_FLAG_COUNTERS) != 0;
-	DeviceCounters* const counters_extend = instrumented ? d_counters_ : nullptr;
+	DeviceCounters* const counters_extend = instrumented ? d_counters_.get() : nullptr;
 	DeviceCounters* const counters_connect = instrumented ? d_counters_ + 1 : nullptr;
 	const int slot = static_cast<int>(frame_ % kConstantsRing);
 	// the pinned slot is reused every kConstantsRing frames: wait until the copy that read it last has run (see Scene::render)
@@ -76,7 +70,7 @@ int Wavefront::frame(const bm_camera* cam, const bm_frame_params* fp, float* acc
 	const FrameConstants* fc_dev = d_frame_constants_ + slot;
 	BM_HIP(hipMemcpyAsync(d_frame_constants_ + slot, h_frame_constants_ + slot, sizeof(FrameConstants), hipMemcpyHostToDevice, stream));
 	if (reset_pending_) {
-		BM_HIP(hipMemsetAsync(&d_state_->primary_ray_cnt, 0, sizeof(uint32_t), stream));
+		BM_HIP(hipMemsetAsync(&d_state_.get()->primary_ray_cnt, 0, sizeof(uint32_t), stream));
 		reset_pending_ = false;
 	}
 	const int cus = scene_->compute_units();

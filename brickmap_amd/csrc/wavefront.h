@@ -29,18 +29,17 @@ private:
 	uint32_t queue_size_;
 	uint32_t frame_ = 1; // kernel.cu:369
 	bool reset_pending_ = false;
-	WfRay* d_work_ = nullptr;   // ray_buffer_work / ray_buffer_next (state.h:19-20), swapped after every frame (main.cpp:146)
-	WfRay* d_next_ = nullptr;
-	WfShadow* d_shadow_ = nullptr;
-	WfState* d_state_ = nullptr;
-	void* d_block_counts_ = nullptr;
-	void* d_cold_ = nullptr; // 16 bytes per queue slot: ray state that only candidate resolution reads (wavefront.hip)
-	DeviceCounters* d_counters_ = nullptr; // [0] extend, [1] connect (BM_FLAG_COUNTERS frames)
+	DeviceBuffer<WfRay> d_work_, d_next_; // ray_buffer_work / ray_buffer_next (state.h:19-20), swapped after every frame (main.cpp:146)
+	DeviceBuffer<WfShadow> d_shadow_;
+	DeviceBuffer<WfState> d_state_;
+	DeviceBuffer<void> d_block_counts_;
+	DeviceBuffer<void> d_cold_; // 16 bytes per queue slot: ray state that only candidate resolution reads (wavefront.hip)
+	DeviceBuffer<DeviceCounters> d_counters_; // [0] extend, [1] connect (BM_FLAG_COUNTERS frames)
 	static constexpr int kConstantsRing = 64;
-	FrameConstants* d_frame_constants_ = nullptr;
-	FrameConstants* h_frame_constants_ = nullptr;
-	hipEvent_t ev_[5] = {};
-	hipEvent_t ev_slot_[kConstantsRing] = {}; // "the frame that used this constants slot has finished"
+	DeviceBuffer<FrameConstants> d_frame_constants_;
+	PinnedBuffer<FrameConstants> h_frame_constants_;
+	Event ev_[5];
+	Event ev_slot_[kConstantsRing]; // "the frame that used this constants slot has finished"
 	bool slot_used_[kConstantsRing] = {};
 	bool timed_ = false;
 	// resident workgroups per CU of the persistent kernels: the walk is instruction-bound, throughput saturates at 5 waves

@@ -7,7 +7,7 @@ from _load_model import canonical_supercell
 
 LOADED, UNLOADED, REQUESTED = 0x80000000, 0x40000000, 0x20000000
 FIELD_CAP = 254   # largest cube edge the field stores; 255 marks the border shell
-FIELD_REACH = 254  # cells by which Scene::edit grows the changed cells' bounding box (scene.cpp, the FieldUpdate block)
+FIELD_REACH = 254  # cells by which Scene::edit grows the changed cells' bounding box (scene.cpp field_update_box)
 
 
 # ---------------------------------------------------------------- the cube field, from its definition
@@ -76,7 +76,7 @@ def occupancy(volume):
 def update_box(changed_cells, cells, cells_height):
     """The box of the field that Scene::edit recomputes when the occupancy of `changed_cells` (N x 3: x, y, z) changes, in the field's
     bordered coordinates (interior cells are 1 ... cells): dict rx0, rx1, ry0, ry1, rz0, rz1 (the box, upper bounds exclusive) and
-    ay0, ay1, bz0, bz1 (the rows and slices that the x and y passes cover for it).  The formula of scene.cpp's FieldUpdate block."""
+    ay0, ay1, bz0, bz1 (the rows and slices that the x and y passes cover for it).  The formula of scene.cpp's field_update_box."""
     c = np.asarray(changed_cells, np.int64).reshape(-1, 3)
     assert len(c) > 0
     lim = (cells, cells, cells_height)

@@ -97,7 +97,7 @@ def test_the_cap_at_254_and_the_border_value():
 
 
 def test_update_box_formula():
-    """the box of scene.cpp's FieldUpdate block, in bordered coordinates, for cases worked out by hand"""
+    """the box of scene.cpp's field_update_box, in bordered coordinates, for cases worked out by hand"""
     b = update_box([[256, 256, 8]], 512, 16)
     assert (b["rx0"], b["rx1"], b["ry0"], b["ry1"], b["rz0"], b["rz1"]) == (3, 512, 3, 512, 1, 17)
     assert (b["ay0"], b["ay1"], b["bz0"], b["bz1"]) == (1, 513, 1, 17)
