@@ -59,6 +59,13 @@ class bm_edit(C.Structure):
                 ("radius", C.c_int32)]
 
 
+BM_REGION_REPLACE = 0
+
+
+class bm_region(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("row_pitch", C.c_int64), ("slice_pitch", C.c_int64)]
+
+
 class bm_ray(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("tmax", C.c_float), ("reserved", C.c_uint32)]
 
@@ -128,11 +135,15 @@ SIGNATURES = {
     "bm_scene_load_voxels": (_i, [_vp, _vp, C.c_size_t, _i, _vp]),
     "bm_scene_host_voxels": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_scene_last_load_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "bm_scene_write_region": (_i, [_vp, C.POINTER(bm_region), _i, _vp, _i, _vp]),
+    "bm_scene_read_region": (_i, [_vp, C.POINTER(bm_region), _vp, _i, _vp]),
+    "bm_scene_last_region_ms": (_i, [_vp] + [C.POINTER(C.c_float)] * 4),
     "bm_scene_cast_rays": (_i, [_vp, C.c_int64, _vp, _vp, C.c_uint32, _vp, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_host_column_heights": (_i, [_i, _i, _i, _i, _vp]),
     "bm_host_generate_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32]),
     "bm_host_edit_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32, _i, C.POINTER(bm_edit)]),
+    "bm_host_write_region_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32, C.POINTER(bm_region), _i, _vp]),
     "bm_host_load_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _u32p]),
     "bm_host_cube_field": (_i, [_i, _i, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_buffer_alloc": (_i, [_i, C.c_size_t, C.POINTER(_vp)]),

@@ -132,6 +132,19 @@ int bm_scene_load_voxels(bm_scene* scene, const uint8_t* voxels, size_t bytes, i
 int bm_scene_host_voxels(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.host_voxels(dst, capacity, bytes); }
 int bm_scene_last_load_ms(bm_scene* scene, float* pack_ms, float* field_ms, float* mirror_ms) { BM_NEED(scene); return scene->impl.last_load_ms(pack_ms, field_ms, mirror_ms); }
 
+int bm_scene_write_region(bm_scene* scene, const bm_region* region, int op, const uint8_t* voxels, int where, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.write_region(region, op, voxels, where, static_cast<hipStream_t>(hip_stream));
+}
+int bm_scene_read_region(bm_scene* scene, const bm_region* region, uint8_t* voxels, int where, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.read_region(region, voxels, where, static_cast<hipStream_t>(hip_stream));
+}
+int bm_scene_last_region_ms(bm_scene* scene, float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms) {
+	BM_NEED(scene);
+	return scene->impl.last_region_ms(pack_ms, copy_ms, scatter_ms, field_ms);
+}
+
 int bm_scene_cast_rays(bm_scene* scene, int64_t n, const bm_ray* rays_dev, bm_ray_hit* hits_dev, uint32_t flags, const float lod_origin[3], void* hip_stream) {
 	BM_NEED(scene);
 	return scene->impl.cast_rays(n, rays_dev, hits_dev, flags, lod_origin, static_cast<hipStream_t>(hip_stream));
@@ -204,38 +217,77 @@ int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, i
 	return 0;
 }
 
-int bm_host_edit_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096, uint32_t* brick_count,
-						   uint32_t* bricks, uint32_t brick_capacity, int count, const bm_edit* edits) {
-	bm::World w;
-	if (!w.dims.set(grid_size, grid_height) || sx < 0 || sy < 0 || sz < 0 || sx >= w.dims.supergrid_xy || sy >= w.dims.supergrid_xy ||
-		sz >= w.dims.supergrid_z) {
-		set_error("bad world dimensions or supercell");
-		return BM_EINVAL;
-	}
+} // extern "C"
+
+namespace {
+// the supercell arrays of the host doors below -> a HostSupercell (slots no word names are free; the lowest is reused first), and back
+int import_supercell(const uint32_t* indices4096, const uint32_t* brick_count, const uint32_t* bricks, uint32_t brick_capacity, bm::HostSupercell* c) {
 	if (!indices4096 || !brick_count || (!bricks && *brick_count > 0) || *brick_count > 4096u || *brick_count > brick_capacity) {
 		set_error("bad supercell arrays");
 		return BM_EINVAL;
 	}
-	std::string why;
-	if (!bm::World::validate_edits(edits, count, &why)) { set_error("bm_host_edit_supercell: " + why); return BM_EINVAL; }
-	bm::HostSupercell c;
-	c.indices.assign(indices4096, indices4096 + bm::kCellsPerSupercell);
-	c.bricks.resize(*brick_count);
-	if (*brick_count) std::memcpy(c.bricks.data(), bricks, *brick_count * sizeof(bm::Brick));
+	c->indices.assign(indices4096, indices4096 + bm::kCellsPerSupercell);
+	c->bricks.resize(*brick_count);
+	if (*brick_count) std::memcpy(c->bricks.data(), bricks, *brick_count * sizeof(bm::Brick));
 	std::vector<uint8_t> used(*brick_count, 0);
-	for (uint32_t word : c.indices) {
+	for (uint32_t word : c->indices) {
 		if (!word) continue;
 		if (!(word & BM_BRICK_LOADED_BIT) || (word & BM_BRICK_INDEX_BITS) >= *brick_count) { set_error("an index word names no brick"); return BM_EINVAL; }
 		used[word & BM_BRICK_INDEX_BITS] = 1;
 	}
-	for (uint32_t s = *brick_count; s-- > 0;) // slots no word names are free; the lowest is reused first
-		if (!used[s]) c.free_slots.push_back(s);
-	bm::World::edit_supercell(w.dims, c, sx, sy, sz, edits, count, nullptr);
+	for (uint32_t s = *brick_count; s-- > 0;)
+		if (!used[s]) c->free_slots.push_back(s);
+	return 0;
+}
+int export_supercell(const bm::HostSupercell& c, uint32_t* indices4096, uint32_t* brick_count, uint32_t* bricks, uint32_t brick_capacity) {
 	if (c.bricks.size() > brick_capacity) { set_error("brick buffer too small for the edited supercell"); return BM_EINVAL; }
 	std::memcpy(indices4096, c.indices.data(), bm::kCellsPerSupercell * sizeof(uint32_t));
 	if (!c.bricks.empty()) std::memcpy(bricks, c.bricks.data(), c.bricks.size() * sizeof(bm::Brick));
 	*brick_count = static_cast<uint32_t>(c.bricks.size());
 	return 0;
+}
+bool supercell_in_world(bm::WorldDims* dims, int grid_size, int grid_height, int sx, int sy, int sz) {
+	if (dims->set(grid_size, grid_height) && sx >= 0 && sy >= 0 && sz >= 0 && sx < dims->supergrid_xy && sy < dims->supergrid_xy && sz < dims->supergrid_z) return true;
+	set_error("bad world dimensions or supercell");
+	return false;
+}
+} // namespace
+
+extern "C" {
+
+int bm_host_edit_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096, uint32_t* brick_count,
+						   uint32_t* bricks, uint32_t brick_capacity, int count, const bm_edit* edits) {
+	bm::WorldDims dims;
+	if (!supercell_in_world(&dims, grid_size, grid_height, sx, sy, sz)) return BM_EINVAL;
+	bm::HostSupercell c;
+	if (int e = import_supercell(indices4096, brick_count, bricks, brick_capacity, &c)) return e;
+	std::string why;
+	if (!bm::World::validate_edits(edits, count, &why)) { set_error("bm_host_edit_supercell: " + why); return BM_EINVAL; }
+	bm::World::edit_supercell(dims, c, sx, sy, sz, edits, count, nullptr);
+	return export_supercell(c, indices4096, brick_count, bricks, brick_capacity);
+}
+
+int bm_host_write_region_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096, uint32_t* brick_count,
+								   uint32_t* bricks, uint32_t brick_capacity, const bm_region* region, int op, const uint8_t* voxels) {
+	bm::WorldDims dims;
+	if (!supercell_in_world(&dims, grid_size, grid_height, sx, sy, sz)) return BM_EINVAL;
+	bm::HostSupercell c;
+	if (int e = import_supercell(indices4096, brick_count, bricks, brick_capacity, &c)) return e;
+	if (!region || !voxels) { set_error("bm_host_write_region_supercell: null region or volume"); return BM_EINVAL; }
+	if (op != BM_REGION_REPLACE && op != BM_EDIT_SET && op != BM_EDIT_CLEAR) { set_error("bm_host_write_region_supercell: unknown op"); return BM_EINVAL; }
+	bm_region r = *region;
+	std::string why;
+	uint64_t span = 0;
+	if (!bm::World::validate_region(&r, &why, &span)) { set_error("bm_host_write_region_supercell: " + why); return BM_EINVAL; }
+	int lo[3], hi[3];
+	if (!bm::World::region_bounds(dims, r, lo, hi)) return 0;
+	bm::World::RegionSource src;
+	src.voxels = voxels;
+	src.row_pitch = r.row_pitch;
+	src.slice_pitch = r.slice_pitch;
+	for (int k = 0; k < 3; ++k) src.origin[k] = r.lo[k];
+	bm::World::write_region_supercell(dims, c, sx, sy, sz, lo, hi, op, src, nullptr);
+	return export_supercell(c, indices4096, brick_count, bricks, brick_capacity);
 }
 
 int bm_host_load_supercell(int grid_size, int grid_height, int sx, int sy, int sz, const uint8_t* voxels, uint32_t* indices4096, uint32_t* bricks,

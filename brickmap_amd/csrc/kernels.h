@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, query.hip and wavefront.hip
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, region.hip, query.hip and wavefront.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,6 +48,24 @@ struct LoadDims {
 void launch_load_classify(const uint8_t* voxels, uint32_t* index_grid, const LoadDims& d, hipStream_t stream);
 void launch_load_number(uint32_t* index_grid, uint32_t* counts, uint32_t* pool_base, uint32_t* total, const LoadDims& d, hipStream_t stream);
 void launch_load_pack(const uint8_t* voxels, const uint32_t* index_grid, const uint32_t* pool_base, uint32_t* arena, const LoadDims& d, hipStream_t stream);
+
+// dense regions (region.hip): a box of voxels as a volume V[z][y][x] in device memory, x contiguous.  [lo, hi) = the box clipped to the
+// world (world voxels, not empty); org = the world voxel of V[0][0][0] (the unclipped lo); c0 / nc = the brick cells the clipped box
+// overlaps (first cell, count per axis); g0 = c0[0] >> 4, the first run of 16 cells along x
+struct RegionDims {
+	int lo[3], hi[3], org[3];
+	int c0[3], nc[3], g0;
+	uint32_t sg_xy, sg_xy2;
+	int64_t row_pitch, slice_pitch;
+};
+// bricks[16 i ...] = the box's part of its cell i (cells in x-fastest order over c0 ... c0 + nc), bits outside the box 0
+void launch_region_pack(const uint8_t* voxels, uint32_t* bricks, const RegionDims& d, hipStream_t stream);
+// the box's voxels as bytes 0 / 1 from the device world: 0 where a cell is empty or its brick is not resident
+void launch_region_unpack(uint8_t* voxels, const uint32_t* index_grid, const uint32_t* pool_base, const uint32_t* arena, const RegionDims& d, hipStream_t stream);
+// the box's part of `count` (> 0) listed cells: cells[3 i ...] = brick cell (x, y, z), bricks[16 i ...] = its bits
+void launch_region_patch(uint8_t* voxels, const int* cells, const uint32_t* bricks, uint32_t count, const RegionDims& d, hipStream_t stream);
+// nz slices of ny rows of nx bytes from `voxels` on, set to 0 (all > 0)
+void launch_region_zero(uint8_t* voxels, int64_t row_pitch, int64_t slice_pitch, int64_t nx, int64_t ny, int64_t nz, hipStream_t stream);
 
 // ray queries (query.hip): n bm_ray records in, n bm_ray_hit records out; ticket = a zeroed word; campos = the LoD centre in brick cells
 int query_blocks_per_cu(bool request);

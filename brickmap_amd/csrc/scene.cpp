@@ -410,13 +410,7 @@ int Scene::load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream
 	if (static_cast<uint64_t>(d.supercells) * kCellsPerSupercell >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
 	if (where == BM_VOXELS_DEVICE) { // the kernels read [voxels, voxels + bytes): it has to be memory of this device, all of it
-		hipPointerAttribute_t attr{};
-		void* base = nullptr;
-		size_t size = 0;
-		if (hipPointerGetAttributes(&attr, voxels) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device_ ||
-			hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, const_cast<uint8_t*>(voxels)) != hipSuccess ||
-			static_cast<const uint8_t*>(base) + size < voxels + bytes) {
-			(void)hipGetLastError();
+		if (!device_span_ok(voxels, bytes)) {
 			set_error("bm_scene_load_voxels: BM_VOXELS_DEVICE needs `bytes` bytes of memory of the scene's device");
 			return BM_EINVAL;
 		}
@@ -436,6 +430,20 @@ int Scene::load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream
 		world.generated = false;
 	}
 	return e;
+}
+
+// [p, p + bytes) lies inside one allocation of this scene's device
+bool Scene::device_span_ok(const uint8_t* p, size_t bytes) const {
+	hipPointerAttribute_t attr{};
+	void* base = nullptr;
+	size_t size = 0;
+	if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device_ ||
+		hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, const_cast<uint8_t*>(p)) != hipSuccess ||
+		static_cast<const uint8_t*>(base) + size < p + bytes) {
+		(void)hipGetLastError();
+		return false;
+	}
+	return true;
 }
 
 int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
@@ -848,90 +856,114 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 	if (reached.empty()) return 0;
 	std::sort(reached.begin(), reached.end());
 	BM_HIP(hipSetDevice(device_));
-	if (edit_busy_) { BM_HIP(hipEventSynchronize(ev_edit_)); edit_busy_ = false; } // the staging of the previous batch has been copied
+	if (int e = wait_edit_staging()) return e;
 
 	// ---- host world, supercell by supercell (voxels of different supercells are independent: batch order is kept within each)
-	std::vector<uint32_t> cells, words, slots;
-	std::vector<Brick> bricks;
-	std::vector<PoolMove> moves;
-	int box_lo[3] = {1 << 30, 1 << 30, 1 << 30}, box_hi[3] = {-1, -1, -1}; // cells whose occupancy changed (unbordered, inclusive)
+	DeviceBatch batch;
 	std::vector<uint32_t> old_words;
-	std::vector<uint16_t> old_dev;
 	std::vector<uint8_t> touched;
-	std::vector<int> fresh_cells;
 	for (const int sci : reached) {
 		HostSupercell& c = world.supercells[sci];
 		const int sx = sci % d.supergrid_xy, sy = (sci / d.supergrid_xy) % d.supergrid_xy, sz = sci / (d.supergrid_xy * d.supergrid_xy);
 		old_words = c.indices;
-		old_dev = c.dev_slot;
 		touched.assign(kCellsPerSupercell, 0);
 		World::edit_supercell(d, c, sx, sy, sz, edits, count, touched.data());
-		// device slots of the host slots after the batch: untouched cells keep theirs (their host slots did not move)
-		std::vector<uint16_t> dev(c.bricks.size(), kNoDeviceSlot);
-		for (int j = 0; j < kCellsPerSupercell; ++j)
-			if (c.indices[j] && !touched[j]) dev[c.indices[j] & BM_BRICK_INDEX_BITS] = old_dev[c.indices[j] & BM_BRICK_INDEX_BITS];
-		fresh_cells.clear();
-		for (int j = 0; j < kCellsPerSupercell; ++j) {
-			if (!touched[j]) continue;
-			const uint32_t ow = old_words[j], nw = c.indices[j];
-			const uint16_t ods = ow ? old_dev[ow & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
-			if (ods != kNoDeviceSlot) {
-				if (nw) dev[nw & BM_BRICK_INDEX_BITS] = ods; // resident stays resident, rewritten in place
-				else { c.pool_free.push_back(ods); resident_bricks_--; }
-			} else if (nw && preloaded_) {
-				fresh_cells.push_back(j);
-			}
-			if ((ow != 0) != (nw != 0)) {
-				const int g[3] = {sx * kSupercell + (j & 15), sy * kSupercell + ((j >> 4) & 15), sz * kSupercell + (j >> 8)};
-				for (int k = 0; k < 3; ++k) { box_lo[k] = std::min(box_lo[k], g[k]); box_hi[k] = std::max(box_hi[k], g[k]); }
-			}
+		if (int e = stage_touched(sci, old_words, touched.data(), batch)) return e;
+	}
+	bool scattered = false, field = false;
+	if (int e = submit_batch(batch, stream, ev_edit_time_, &scattered, &field)) return e;
+	if (scattered) {
+		edit_timed_ = true;
+		edit_field_timed_ = field;
+	}
+	return 0;
+}
+
+int Scene::wait_edit_staging() {
+	if (edit_busy_) { BM_HIP(hipEventSynchronize(ev_edit_)); edit_busy_ = false; } // the staging of the previous batch has been copied
+	return 0;
+}
+
+// The device half of a change of the host world, shared by edits and region writes.  stage_touched: the touched cells of one supercell
+// whose host world has just changed (old_words = its index words before) get their device slots by the residency rule above and join the batch.
+int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b) {
+	const WorldDims& d = world.dims;
+	HostSupercell& c = world.supercells[sci];
+	const int sx = sci % d.supergrid_xy, sy = (sci / d.supergrid_xy) % d.supergrid_xy, sz = sci / (d.supergrid_xy * d.supergrid_xy);
+	const std::vector<uint16_t>& old_dev = c.dev_slot; // (the host half does not know about device slots)
+	// device slots of the host slots after the batch: untouched cells keep theirs (their host slots did not move)
+	std::vector<uint16_t> dev(c.bricks.size(), kNoDeviceSlot);
+	for (int j = 0; j < kCellsPerSupercell; ++j)
+		if (c.indices[j] && !touched[j]) dev[c.indices[j] & BM_BRICK_INDEX_BITS] = old_dev[c.indices[j] & BM_BRICK_INDEX_BITS];
+	std::vector<int> fresh_cells;
+	for (int j = 0; j < kCellsPerSupercell; ++j) {
+		if (!touched[j]) continue;
+		const uint32_t ow = old_words[j], nw = c.indices[j];
+		const uint16_t ods = ow ? old_dev[ow & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
+		if (ods != kNoDeviceSlot) {
+			if (nw) dev[nw & BM_BRICK_INDEX_BITS] = ods; // resident stays resident, rewritten in place
+			else { c.pool_free.push_back(ods); resident_bricks_--; }
+		} else if (nw && preloaded_) {
+			fresh_cells.push_back(j);
 		}
-		if (!fresh_cells.empty()) { // preloaded scene: new bricks get pool slots now, freed ones first
-			const uint32_t reuse = static_cast<uint32_t>(std::min(fresh_cells.size(), c.pool_free.size()));
-			const uint32_t appends = static_cast<uint32_t>(fresh_cells.size()) - reuse;
-			if (c.resident + appends > c.pool_capacity) {
-				uint32_t grown = kStartingPool;
-				while (grown < c.resident + appends || grown < 2 * c.pool_capacity) grown *= 2;
-				uint32_t fresh = 0;
-				if (int e = pool_region(grown, &fresh)) { failed_ = true; return e; }
-				moves.push_back(PoolMove{c.pool_capacity ? c.pool_base : fresh, fresh, c.pool_capacity ? c.resident : 0u, static_cast<uint32_t>(sci)});
-				if (c.pool_capacity > 0) arena_.region_free_deferred(c.pool_capacity, c.pool_base); // (a preloaded pool is an exact fit: only its largest power of two is handed out again)
-				c.pool_base = fresh;
-				c.pool_capacity = grown;
-			}
-			for (const int j : fresh_cells) {
-				uint32_t ds;
-				if (!c.pool_free.empty()) { ds = c.pool_free.back(); c.pool_free.pop_back(); }
-				else ds = c.resident++;
-				dev[c.indices[j] & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(ds);
-				resident_bricks_++;
-			}
-		}
-		c.dev_slot.swap(dev);
-		for (int j = 0; j < kCellsPerSupercell; ++j) {
-			if (!touched[j]) continue;
-			const uint32_t nw = c.indices[j];
-			const uint16_t ds = nw ? c.dev_slot[nw & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
-			cells.push_back(static_cast<uint32_t>(sci) * kCellsPerSupercell + static_cast<uint32_t>(j));
-			if (!nw) words.push_back(0u);
-			else if (ds == kNoDeviceSlot) words.push_back(BM_BRICK_UNLOADED_BIT | (nw & BM_BRICK_LOD_BITS));
-			else words.push_back(ds | BM_BRICK_LOADED_BIT | (nw & BM_BRICK_LOD_BITS));
-			slots.push_back(ds == kNoDeviceSlot ? 0xFFFFFFFFu : c.pool_base + ds);
-			bricks.push_back(nw ? c.bricks[nw & BM_BRICK_INDEX_BITS] : Brick{});
+		if ((ow != 0) != (nw != 0)) {
+			const int g[3] = {sx * kSupercell + (j & 15), sy * kSupercell + ((j >> 4) & 15), sz * kSupercell + (j >> 8)};
+			for (int k = 0; k < 3; ++k) { b.box_lo[k] = std::min(b.box_lo[k], g[k]); b.box_hi[k] = std::max(b.box_hi[k], g[k]); }
 		}
 	}
-	const uint32_t n = static_cast<uint32_t>(cells.size());
+	if (!fresh_cells.empty()) { // preloaded scene: new bricks get pool slots now, freed ones first
+		const uint32_t reuse = static_cast<uint32_t>(std::min(fresh_cells.size(), c.pool_free.size()));
+		const uint32_t appends = static_cast<uint32_t>(fresh_cells.size()) - reuse;
+		if (c.resident + appends > c.pool_capacity) {
+			uint32_t grown = kStartingPool;
+			while (grown < c.resident + appends || grown < 2 * c.pool_capacity) grown *= 2;
+			uint32_t fresh = 0;
+			if (int e = pool_region(grown, &fresh)) { failed_ = true; return e; }
+			b.moves.push_back(PoolMove{c.pool_capacity ? c.pool_base : fresh, fresh, c.pool_capacity ? c.resident : 0u, static_cast<uint32_t>(sci)});
+			if (c.pool_capacity > 0) arena_.region_free_deferred(c.pool_capacity, c.pool_base); // (a preloaded pool is an exact fit: only its largest power of two is handed out again)
+			c.pool_base = fresh;
+			c.pool_capacity = grown;
+		}
+		for (const int j : fresh_cells) {
+			uint32_t ds;
+			if (!c.pool_free.empty()) { ds = c.pool_free.back(); c.pool_free.pop_back(); }
+			else ds = c.resident++;
+			dev[c.indices[j] & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(ds);
+			resident_bricks_++;
+		}
+	}
+	c.dev_slot.swap(dev);
+	for (int j = 0; j < kCellsPerSupercell; ++j) {
+		if (!touched[j]) continue;
+		const uint32_t nw = c.indices[j];
+		const uint16_t ds = nw ? c.dev_slot[nw & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
+		b.cells.push_back(static_cast<uint32_t>(sci) * kCellsPerSupercell + static_cast<uint32_t>(j));
+		if (!nw) b.words.push_back(0u);
+		else if (ds == kNoDeviceSlot) b.words.push_back(BM_BRICK_UNLOADED_BIT | (nw & BM_BRICK_LOD_BITS));
+		else b.words.push_back(ds | BM_BRICK_LOADED_BIT | (nw & BM_BRICK_LOD_BITS));
+		b.slots.push_back(ds == kNoDeviceSlot ? 0xFFFFFFFFu : c.pool_base + ds);
+		b.bricks.push_back(nw ? c.bricks[nw & BM_BRICK_INDEX_BITS] : Brick{});
+	}
+	return 0;
+}
+
+// submit_batch: the staged cells go to the device on the load stream -- one copy, the pool moves, the scatter and, when some cell's
+// occupancy changed, the cube-field update -- as an upload batch.  times[0 ... 2] are recorded around the scatter and the field update.
+int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* scattered, bool* field_updated) {
+	const WorldDims& d = world.dims;
+	*scattered = *field_updated = false;
+	const uint32_t n = static_cast<uint32_t>(b.cells.size());
 	if (n == 0) { // nothing inside the world changed a brick (e.g. clearing empty space)
 		arena_.commit_freed_regions();
 		return 0;
 	}
 
 	// ---- staging: [pool moves][cells][words][slots][bricks], 64-byte aligned sections
-	auto up = [](size_t b) { return (b + 63) / 64 * 64; };
-	const size_t o_cells = up(moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
+	auto up = [](size_t v) { return (v + 63) / 64 * 64; };
+	const size_t o_cells = up(b.moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
 				 o_bricks = o_slots + up(n * 4ull), bytes = o_bricks + n * sizeof(Brick);
-	const bool field = box_hi[0] >= 0;
-	const FieldUpdate fu = field ? field_update_box(d, box_lo, box_hi) : FieldUpdate{};
+	const bool field = b.box_hi[0] >= 0;
+	const FieldUpdate fu = field ? field_update_box(d, b.box_lo, b.box_hi) : FieldUpdate{};
 	auto queue = [&]() -> int {
 		if (bytes > d_edit_.bytes()) { // (the two grow together: h_edit_ is as large as d_edit_)
 			BM_HIP(hipStreamSynchronize(load_stream_)); // the previous batch's kernels may still read the device staging
@@ -943,41 +975,41 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 			BM_HIP(hipStreamSynchronize(load_stream_));
 			if (int e = d_cf_tmp_.reserve(field_update_tmp_bytes(fu))) return e;
 		}
-		if (!moves.empty()) std::memcpy(h_edit_, moves.data(), moves.size() * sizeof(PoolMove));
-		std::memcpy(h_edit_ + o_cells, cells.data(), n * 4ull);
-		std::memcpy(h_edit_ + o_words, words.data(), n * 4ull);
-		std::memcpy(h_edit_ + o_slots, slots.data(), n * 4ull);
-		std::memcpy(h_edit_ + o_bricks, bricks.data(), n * sizeof(Brick));
+		if (!b.moves.empty()) std::memcpy(h_edit_, b.moves.data(), b.moves.size() * sizeof(PoolMove));
+		std::memcpy(h_edit_ + o_cells, b.cells.data(), n * 4ull);
+		std::memcpy(h_edit_ + o_words, b.words.data(), n * 4ull);
+		std::memcpy(h_edit_ + o_slots, b.slots.data(), n * 4ull);
+		std::memcpy(h_edit_ + o_bricks, b.bricks.data(), n * sizeof(Brick));
 		// behind every frame in flight (they read the words, pool bases, bricks and field this rewrites) and the caller's queued work
 		if (int e = order_load_stream_behind_frames()) return e;
 		BM_HIP(hipEventRecord(ev_edit_caller_, stream));
 		BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
 		BM_HIP(hipMemcpyAsync(d_edit_, h_edit_, bytes, hipMemcpyHostToDevice, load_stream_));
 		BM_HIP(hipEventRecord(ev_edit_, load_stream_)); // the pinned staging is free again from here on
-		BM_HIP(hipEventRecord(ev_edit_time_[0], load_stream_));
-		if (!moves.empty()) {
-			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_.get()), static_cast<uint32_t>(moves.size()), arena_.base(), d_pool_base_, load_stream_);
+		BM_HIP(hipEventRecord(times[0], load_stream_));
+		if (!b.moves.empty()) {
+			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_.get()), static_cast<uint32_t>(b.moves.size()), arena_.base(), d_pool_base_, load_stream_);
 			BM_HIP(hipGetLastError());
 		}
 		launch_edit_scatter(reinterpret_cast<const uint32_t*>(d_edit_ + o_cells), reinterpret_cast<const uint32_t*>(d_edit_ + o_words),
 							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, d_index_grid_, arena_.base(),
 							load_stream_);
 		BM_HIP(hipGetLastError());
-		BM_HIP(hipEventRecord(ev_edit_time_[1], load_stream_));
+		BM_HIP(hipEventRecord(times[1], load_stream_));
 		if (field) {
 			launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
 			BM_HIP(hipGetLastError());
 		}
-		BM_HIP(hipEventRecord(ev_edit_time_[2], load_stream_));
+		BM_HIP(hipEventRecord(times[2], load_stream_));
 		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
 		return 0;
 	};
 	if (int e = queue()) { failed_ = true; return e; } // the host world is ahead of the device: refuse to go on
 	arena_.commit_freed_regions();
 	edit_busy_ = true;
-	edit_timed_ = true;
-	edit_field_timed_ = field;
 	upload_seq_++;
+	*scattered = true;
+	*field_updated = field;
 	return 0;
 }
 
@@ -989,6 +1021,204 @@ int Scene::last_edit_ms(float* scatter_ms, float* field_ms) {
 	BM_HIP(hipEventElapsedTime(scatter_ms, ev_edit_time_[0], ev_edit_time_[1]));
 	BM_HIP(hipEventElapsedTime(field_ms, ev_edit_time_[1], ev_edit_time_[2]));
 	if (!edit_field_timed_) *field_ms = 0.0f;
+	return 0;
+}
+
+// ---------------------------------------------------------------- dense regions (bm_scene_write_region / bm_scene_read_region)
+namespace {
+// the parts of the box [blo, bhi) that lie outside its clipped part [lo, hi) (all of it when `inside` is false), as up to six boxes
+template <class F> void for_outside_slabs(const int32_t blo[3], const int32_t bhi[3], bool inside, const int lo[3], const int hi[3], F f) {
+	if (!inside) { f(blo[0], bhi[0], blo[1], bhi[1], blo[2], bhi[2]); return; }
+	if (blo[2] < lo[2]) f(blo[0], bhi[0], blo[1], bhi[1], blo[2], lo[2]);
+	if (hi[2] < bhi[2]) f(blo[0], bhi[0], blo[1], bhi[1], hi[2], bhi[2]);
+	if (blo[1] < lo[1]) f(blo[0], bhi[0], blo[1], lo[1], lo[2], hi[2]);
+	if (hi[1] < bhi[1]) f(blo[0], bhi[0], hi[1], bhi[1], lo[2], hi[2]);
+	if (blo[0] < lo[0]) f(blo[0], lo[0], lo[1], hi[1], lo[2], hi[2]);
+	if (hi[0] < bhi[0]) f(hi[0], bhi[0], lo[1], hi[1], lo[2], hi[2]);
+}
+int64_t region_offset(const bm_region& r, int64_t x, int64_t y, int64_t z) { return (z - r.lo[2]) * r.slice_pitch + (y - r.lo[1]) * r.row_pitch + (x - r.lo[0]); }
+} // namespace
+
+// what write_region and read_region refuse, before anything changes; *r gets its pitches filled in, *span the bytes of the volume
+int Scene::check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span) {
+	const std::string at = std::string(who) + ": ";
+	if (!region || !voxels) { set_error(at + "null region or volume"); return BM_EINVAL; }
+	*r = *region;
+	std::string why;
+	if (!World::validate_region(r, &why, span)) { set_error(at + why); return BM_EINVAL; }
+	if (where != BM_VOXELS_HOST && where != BM_VOXELS_DEVICE) { set_error(at + "`where` is BM_VOXELS_HOST or BM_VOXELS_DEVICE"); return BM_EINVAL; }
+	if (!on_device_) { set_error(at + "scene not generated"); return BM_ESTATE; }
+	if (int e = require_not_failed()) return e;
+	BM_HIP(hipSetDevice(device_));
+	if (where == BM_VOXELS_DEVICE && *span > 0 && !device_span_ok(static_cast<const uint8_t*>(voxels), *span)) {
+		set_error(at + "BM_VOXELS_DEVICE needs the volume's whole span inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	return 0;
+}
+
+RegionDims Scene::region_dims(const bm_region& r, const int lo[3], const int hi[3]) const {
+	RegionDims rd{};
+	for (int k = 0; k < 3; ++k) {
+		rd.lo[k] = lo[k]; rd.hi[k] = hi[k]; rd.org[k] = r.lo[k];
+		rd.c0[k] = lo[k] >> 3;
+		rd.nc[k] = ((hi[k] - 1) >> 3) - rd.c0[k] + 1;
+	}
+	rd.g0 = rd.c0[0] >> 4;
+	rd.sg_xy = static_cast<uint32_t>(world.dims.supergrid_xy);
+	rd.sg_xy2 = rd.sg_xy * rd.sg_xy;
+	rd.row_pitch = r.row_pitch;
+	rd.slice_pitch = r.slice_pitch;
+	return rd;
+}
+
+// The host world first, by World::write_region_supercell on every supercell the clipped box reaches (on CPU threads: supercells are
+// independent), then the touched cells go to the device as an edit's do (stage_touched / submit_batch).  A volume in device memory is
+// packed into one brick per covered cell on the load stream (region.hip), behind the work queued on the caller's stream, and those
+// bricks are copied to pinned memory: the call's one round trip -- the host world is authoritative and hands out the slots.
+int Scene::write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream) {
+	bm_region r;
+	uint64_t span = 0;
+	if (op != BM_REGION_REPLACE && op != BM_EDIT_SET && op != BM_EDIT_CLEAR) { set_error("bm_scene_write_region: unknown op"); return BM_EINVAL; }
+	if (int e = check_region("bm_scene_write_region", region, voxels, where, &r, &span)) return e;
+	const WorldDims& d = world.dims;
+	int lo[3], hi[3];
+	if (!World::region_bounds(d, r, lo, hi)) return 0;
+	if (int e = wait_edit_staging()) return e;
+	for (Event& ev : ev_region_time_) if (int e = ev.create()) return e;
+	const RegionDims rd = region_dims(r, lo, hi);
+	World::RegionSource src;
+	for (int k = 0; k < 3; ++k) { src.c0[k] = rd.c0[k]; src.nc[k] = rd.nc[k]; src.origin[k] = r.lo[k]; }
+	if (where == BM_VOXELS_DEVICE) {
+		const size_t bytes = static_cast<size_t>(rd.nc[0]) * rd.nc[1] * rd.nc[2] * sizeof(Brick);
+		if (bytes > d_region_.bytes()) { // (no earlier write still uses them: each waits for its copy)
+			if (int e = d_region_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
+			if (int e = h_region_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
+		}
+		BM_HIP(hipEventRecord(ev_edit_caller_, stream)); // the volume is whatever the caller's stream has written by now
+		BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
+		BM_HIP(hipEventRecord(ev_region_time_[0], load_stream_));
+		launch_region_pack(voxels, reinterpret_cast<uint32_t*>(d_region_.get()), rd, load_stream_);
+		BM_HIP(hipGetLastError());
+		BM_HIP(hipEventRecord(ev_region_time_[1], load_stream_));
+		BM_HIP(hipMemcpyAsync(h_region_, d_region_, bytes, hipMemcpyDeviceToHost, load_stream_));
+		BM_HIP(hipEventRecord(ev_region_time_[2], load_stream_));
+		BM_HIP(hipStreamSynchronize(load_stream_));
+		src.packed = h_region_;
+	} else {
+		src.voxels = voxels;
+		src.row_pitch = r.row_pitch;
+		src.slice_pitch = r.slice_pitch;
+	}
+	// ---- merge
+	std::vector<int> reached;
+	for (int sz = lo[2] / kColumnSpan; sz <= (hi[2] - 1) / kColumnSpan; ++sz)
+		for (int sy = lo[1] / kColumnSpan; sy <= (hi[1] - 1) / kColumnSpan; ++sy)
+			for (int sx = lo[0] / kColumnSpan; sx <= (hi[0] - 1) / kColumnSpan; ++sx) reached.push_back(d.supercell_id(sx, sy, sz));
+	std::vector<std::vector<uint32_t>> old_words(reached.size());
+	std::vector<std::vector<uint8_t>> touched(reached.size());
+	{
+		std::atomic<size_t> next{0};
+		auto merge = [&]() {
+			for (size_t i = next.fetch_add(1); i < reached.size(); i = next.fetch_add(1)) {
+				const int sci = reached[i];
+				HostSupercell& c = world.supercells[sci];
+				old_words[i] = c.indices;
+				touched[i].assign(kCellsPerSupercell, 0);
+				World::write_region_supercell(d, c, sci % d.supergrid_xy, (sci / d.supergrid_xy) % d.supergrid_xy, sci / (d.supergrid_xy * d.supergrid_xy), lo, hi, op, src,
+											  touched[i].data());
+			}
+		};
+		std::vector<std::thread> pool;
+		for (size_t t = 1; t < std::min<size_t>(16, reached.size()); ++t) pool.emplace_back(merge);
+		merge();
+		for (auto& t : pool) t.join();
+	}
+	DeviceBatch batch;
+	for (size_t i = 0; i < reached.size(); ++i)
+		if (int e = stage_touched(reached[i], old_words[i], touched[i].data(), batch)) return e;
+	region_timed_ = true;
+	region_packed_ = where == BM_VOXELS_DEVICE;
+	region_scattered_ = region_field_ = false;
+	return submit_batch(batch, stream, ev_region_time_ + 3, &region_scattered_, &region_field_);
+}
+
+int Scene::last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms) {
+	if (!pack_ms || !copy_ms || !scatter_ms || !field_ms) { set_error("null argument"); return BM_EINVAL; }
+	if (!region_timed_) { set_error("no region has been written yet"); return BM_ESTATE; }
+	BM_HIP(hipSetDevice(device_));
+	*pack_ms = *copy_ms = *scatter_ms = *field_ms = 0.0f;
+	if (region_packed_) {
+		BM_HIP(hipEventSynchronize(ev_region_time_[2]));
+		BM_HIP(hipEventElapsedTime(pack_ms, ev_region_time_[0], ev_region_time_[1]));
+		BM_HIP(hipEventElapsedTime(copy_ms, ev_region_time_[1], ev_region_time_[2]));
+	}
+	if (region_scattered_) {
+		BM_HIP(hipEventSynchronize(ev_region_time_[5]));
+		BM_HIP(hipEventElapsedTime(scatter_ms, ev_region_time_[3], ev_region_time_[4]));
+		if (region_field_) BM_HIP(hipEventElapsedTime(field_ms, ev_region_time_[4], ev_region_time_[5]));
+	}
+	return 0;
+}
+
+// The host world is authoritative, so a host read is World::store_region.  A device read is issued like a query: the unpack kernel reads
+// the device words and bricks; bricks that are not resident (a streaming scene) are staged from the host world and written by a second
+// small launch; what lies outside the world is zeroed.
+int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream) {
+	bm_region r;
+	uint64_t span = 0;
+	if (int e = check_region("bm_scene_read_region", region, voxels, where, &r, &span)) return e;
+	if (span == 0) return 0;
+	const WorldDims& d = world.dims;
+	int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+	const bool inside = World::region_bounds(d, r, lo, hi);
+	if (where == BM_VOXELS_HOST) {
+		for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
+			for (int64_t z = z0; z < z1; ++z)
+				for (int64_t y = y0; y < y1; ++y) std::memset(voxels + region_offset(r, x0, y, z), 0, static_cast<size_t>(x1 - x0));
+		});
+		if (inside) world.store_region(lo, hi, r.lo, voxels, r.row_pitch, r.slice_pitch, 16);
+		return 0;
+	}
+	// ---- the bricks of the box that the device does not hold, from the host world
+	std::vector<int> cells;
+	std::vector<Brick> bricks;
+	if (inside && !preloaded_)
+		for (int cz = lo[2] >> 3; cz <= (hi[2] - 1) >> 3; ++cz)
+			for (int cy = lo[1] >> 3; cy <= (hi[1] - 1) >> 3; ++cy)
+				for (int cx = lo[0] >> 3; cx <= (hi[0] - 1) >> 3; ++cx) {
+					const HostSupercell& c = world.supercells[d.supercell_id(cx / kSupercell, cy / kSupercell, cz / kSupercell)];
+					const uint32_t word = c.indices[cell_local_index(cx, cy, cz)];
+					if (word == 0 || c.dev_slot[word & BM_BRICK_INDEX_BITS] != kNoDeviceSlot) continue;
+					cells.insert(cells.end(), {cx, cy, cz});
+					bricks.push_back(c.bricks[word & BM_BRICK_INDEX_BITS]);
+				}
+	const size_t n = bricks.size(), o_bricks = (n * 3 * sizeof(int) + 63) / 64 * 64, bytes = o_bricks + n * sizeof(Brick);
+	if (n > 0) {
+		if (int e = ev_region_read_.create(hipEventDisableTiming)) return e;
+		if (region_read_busy_) { BM_HIP(hipEventSynchronize(ev_region_read_)); region_read_busy_ = false; } // the previous read's list has been used
+		if (int e = h_patch_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
+		if (int e = d_patch_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
+		std::memcpy(h_patch_, cells.data(), n * 3 * sizeof(int));
+		std::memcpy(h_patch_ + o_bricks, bricks.data(), n * sizeof(Brick));
+	}
+	DeviceScene view;
+	if (int e = begin_frame(stream, &view, nullptr)) return e;
+	for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
+		launch_region_zero(voxels + region_offset(r, x0, y0, z0), r.row_pitch, r.slice_pitch, x1 - x0, y1 - y0, z1 - z0, stream);
+	});
+	if (inside) {
+		const RegionDims rd = region_dims(r, lo, hi);
+		launch_region_unpack(voxels, view.index_grid, view.pool_base, view.brick_arena, rd, stream);
+		if (n > 0) {
+			BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));
+			launch_region_patch(voxels, reinterpret_cast<const int*>(d_patch_.get()), reinterpret_cast<const uint32_t*>(d_patch_ + o_bricks), static_cast<uint32_t>(n), rd, stream);
+			BM_HIP(hipEventRecord(ev_region_read_, stream));
+			region_read_busy_ = true;
+		}
+	}
+	BM_HIP(hipGetLastError());
+	end_frame(stream);
 	return 0;
 }
 

@@ -12,6 +12,7 @@
 #include "device_types.h"
 #include "error.h"
 #include "hip_owned.h"
+#include "kernels.h"
 #include "world.h"
 
 namespace bm {
@@ -53,6 +54,10 @@ public:
 	int device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
+	// dense regions (region.hip / scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
+	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
+	int read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream);
+	int last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms);
 	// dense voxels -> scene (load.hip / scene.cpp "dense voxels -> scene"): replaces whatever world the scene holds; preloaded afterwards
 	int load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream_t stream);
 	int host_voxels(uint8_t* dst, size_t capacity, size_t* bytes);
@@ -90,6 +95,19 @@ private:
 	int alloc_cube_field();
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
+	bool device_span_ok(const uint8_t* p, size_t bytes) const;
+	// the device half of a change of the host world (scene.cpp "voxel edits"): the touched cells of every changed supercell are staged, then submitted
+	struct DeviceBatch {
+		std::vector<uint32_t> cells, words, slots;
+		std::vector<Brick> bricks;
+		std::vector<PoolMove> moves;
+		int box_lo[3] = {1 << 30, 1 << 30, 1 << 30}, box_hi[3] = {-1, -1, -1}; // cells whose occupancy changed (unbordered, inclusive)
+	};
+	int wait_edit_staging();
+	int stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b);
+	int submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* scattered, bool* field_updated);
+	int check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span);
+	RegionDims region_dims(const bm_region& r, const int lo[3], const int hi[3]) const;
 	void free_device();
 	int alloc_queue();
 	int service_ring(int ring, uint32_t count, uint32_t* serviced);
@@ -172,6 +190,13 @@ private:
 	bool edit_timed_ = false, edit_field_timed_ = false;
 	bool edit_busy_ = false;
 	DeviceBuffer<uint8_t> d_cf_tmp_;
+	// region writes: the packed bricks of a device volume (64 bytes per covered cell, device + pinned, grown on demand) and the events
+	// around pack, copy, scatter and field; region reads: the list of non-resident bricks (pinned + device), free once ev_region_read_ has passed
+	DeviceBuffer<char> d_region_, d_patch_;
+	PinnedBuffer<Brick> h_region_;
+	PinnedBuffer<char> h_patch_;
+	Event ev_region_time_[6], ev_region_read_;
+	bool region_timed_ = false, region_packed_ = false, region_scattered_ = false, region_field_ = false, region_read_busy_ = false;
 	// loads from device memory: events around classify + number, pack, field and mirror (created by the first such load)
 	Event ev_load_time_[6];
 	bool load_timed_ = false;

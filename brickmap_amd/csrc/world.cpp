@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstring>
 #include <thread>
 
@@ -408,6 +409,134 @@ void World::edit_supercell(const WorldDims& dims, HostSupercell& c, int sx, int 
 					}
 				}
 	}
+}
+
+// ---------------------------------------------------------------- dense regions
+bool World::validate_region(bm_region* r, std::string* why, uint64_t* span) {
+	int64_t n[3];
+	for (int k = 0; k < 3; ++k) {
+		if (r->hi[k] < r->lo[k]) { *why = "region with hi < lo"; return false; }
+		n[k] = static_cast<int64_t>(r->hi[k]) - r->lo[k];
+	}
+	if (r->row_pitch == 0) r->row_pitch = n[0];
+	if (r->row_pitch < n[0]) { *why = "row_pitch is smaller than the row it spans (hi.x - lo.x bytes)"; return false; }
+	const __int128 slice = static_cast<__int128>(r->row_pitch) * n[1];
+	if (slice > INT64_MAX) { *why = "region too large"; return false; }
+	if (r->slice_pitch == 0) r->slice_pitch = static_cast<int64_t>(slice);
+	if (r->slice_pitch < static_cast<int64_t>(slice)) { *why = "slice_pitch is smaller than the slice it spans (row_pitch * (hi.y - lo.y) bytes)"; return false; }
+	*span = 0;
+	if (n[0] == 0 || n[1] == 0 || n[2] == 0) return true;
+	const __int128 bytes = static_cast<__int128>(n[2] - 1) * r->slice_pitch + static_cast<__int128>(n[1] - 1) * r->row_pitch + n[0];
+	if (bytes > INT64_MAX) { *why = "region too large"; return false; }
+	*span = static_cast<uint64_t>(bytes);
+	return true;
+}
+
+bool World::region_bounds(const WorldDims& dims, const bm_region& r, int lo[3], int hi[3]) {
+	bm_edit e{};
+	e.shape = BM_EDIT_BOX;
+	for (int k = 0; k < 3; ++k) { e.lo[k] = r.lo[k]; e.hi[k] = r.hi[k]; }
+	return edit_bounds(dims, e, lo, hi);
+}
+
+namespace {
+// (vol & cover) of the brick cell whose first voxel is world voxel cell0, for the box [lo, hi) (world voxels); cover = the box's voxels in the cell
+void region_cell_bits(const World::RegionSource& src, const int cell0[3], const int lo[3], const int hi[3], Brick* vol, Brick* cover) {
+	const int x0 = std::max(lo[0] - cell0[0], 0), x1 = std::min(hi[0] - cell0[0], kBrickSize);
+	const uint32_t xmask = ((1u << (x1 - x0)) - 1u) << x0;
+	uint8_t* vb = reinterpret_cast<uint8_t*>(vol->data);
+	uint8_t* cb = reinterpret_cast<uint8_t*>(cover->data);
+	const uint8_t* packed = nullptr;
+	if (src.packed) {
+		const size_t at = (static_cast<size_t>((cell0[2] >> 3) - src.c0[2]) * src.nc[1] + ((cell0[1] >> 3) - src.c0[1])) * src.nc[0] + ((cell0[0] >> 3) - src.c0[0]);
+		packed = reinterpret_cast<const uint8_t*>(src.packed[at].data);
+	}
+	for (int r = 0; r < 64; ++r) { // x-row (y = r & 7, z = r >> 3) is byte r of the brick
+		const int y = cell0[1] + (r & 7), z = cell0[2] + (r >> 3);
+		const bool in = y >= lo[1] && y < hi[1] && z >= lo[2] && z < hi[2];
+		cb[r] = in ? static_cast<uint8_t>(xmask) : 0;
+		if (!in) { vb[r] = 0; continue; }
+		if (packed) { vb[r] = packed[r] & static_cast<uint8_t>(xmask); continue; }
+		uint8_t row[8] = {};
+		const uint8_t* from = src.voxels + (static_cast<int64_t>(z) - src.origin[2]) * src.slice_pitch + (static_cast<int64_t>(y) - src.origin[1]) * src.row_pitch +
+							  (static_cast<int64_t>(cell0[0]) - src.origin[0]);
+		std::memcpy(row + x0, from + x0, static_cast<size_t>(x1 - x0));
+		uint32_t a, b;
+		std::memcpy(&a, row, 4);
+		std::memcpy(&b, row + 4, 4);
+		vb[r] = static_cast<uint8_t>(brick_row_bits(a, b));
+	}
+}
+} // namespace
+
+void World::write_region_supercell(const WorldDims&, HostSupercell& c, int sx, int sy, int sz, const int lo_w[3], const int hi_w[3], int op, const RegionSource& src,
+								   uint8_t* touched) {
+	const int org[3] = {sx * kColumnSpan, sy * kColumnSpan, sz * kColumnSpan};
+	int lo[3], hi[3]; // the box inside this supercell, world voxels
+	for (int k = 0; k < 3; ++k) {
+		lo[k] = std::max(lo_w[k], org[k]);
+		hi[k] = std::min(hi_w[k], org[k] + kColumnSpan);
+		if (lo[k] >= hi[k]) return;
+	}
+	for (int bz = (lo[2] - org[2]) >> 3; bz <= (hi[2] - 1 - org[2]) >> 3; ++bz)
+		for (int by = (lo[1] - org[1]) >> 3; by <= (hi[1] - 1 - org[1]) >> 3; ++by)
+			for (int bx = (lo[0] - org[0]) >> 3; bx <= (hi[0] - 1 - org[0]) >> 3; ++bx) { // ascending local cell index
+				const int local = bx + by * kSupercell + bz * kSupercell * kSupercell;
+				uint32_t& word = c.indices[local];
+				const int cell0[3] = {org[0] + bx * 8, org[1] + by * 8, org[2] + bz * 8};
+				Brick vol, cover, fresh;
+				region_cell_bits(src, cell0, lo, hi, &vol, &cover);
+				const Brick* old = word ? &c.bricks[word & BM_BRICK_INDEX_BITS] : nullptr;
+				uint32_t differs = 0, any = 0;
+				for (int w = 0; w < kBrickWords; ++w) {
+					const uint32_t o = old ? old->data[w] : 0u;
+					const uint32_t n = op == BM_REGION_REPLACE ? (o & ~cover.data[w]) | vol.data[w] : op == BM_EDIT_SET ? o | vol.data[w] : o & ~vol.data[w];
+					fresh.data[w] = n;
+					differs |= n ^ o;
+					any |= n;
+				}
+				if (!differs) continue; // not touched: word, brick, slot and device state stay as they are
+				if (touched) touched[local] = 1;
+				if (!any) { // the brick became empty: word 0, slot free
+					c.free_slots.push_back(word & BM_BRICK_INDEX_BITS);
+					word = 0;
+					continue;
+				}
+				uint32_t slot = word & BM_BRICK_INDEX_BITS;
+				if (word == 0) { // the cell gains a brick: a freed slot first, else a new one
+					if (!c.free_slots.empty()) {
+						slot = c.free_slots.back();
+						c.free_slots.pop_back();
+					} else {
+						slot = static_cast<uint32_t>(c.bricks.size());
+						c.bricks.emplace_back();
+					}
+				}
+				c.bricks[slot] = fresh;
+				word = slot | BM_BRICK_LOADED_BIT | (brick_lod(fresh) << 12); // Scene.cpp:104
+			}
+}
+
+void World::store_region(const int lo[3], const int hi[3], const int origin[3], uint8_t* voxels, int64_t row_pitch, int64_t slice_pitch, int threads) const {
+	const int nz = hi[2] - lo[2];
+	parallel_for(nz, threads, [&](int iz) {
+		const int z = lo[2] + iz;
+		for (int y = lo[1]; y < hi[1]; ++y) {
+			uint8_t* row = voxels + (static_cast<int64_t>(z) - origin[2]) * slice_pitch + (static_cast<int64_t>(y) - origin[1]) * row_pitch - origin[0]; // row[x] = world voxel x
+			for (int cx = lo[0] >> 3; cx <= (hi[0] - 1) >> 3; ++cx) {
+				const HostSupercell& c = supercells[dims.supercell_id(cx / kSupercell, (y >> 3) / kSupercell, (z >> 3) / kSupercell)];
+				const uint32_t word = c.indices.empty() ? 0u : c.indices[cell_local_index(cx, y >> 3, z >> 3)];
+				const uint32_t bits = word ? reinterpret_cast<const uint8_t*>(c.bricks[word & BM_BRICK_INDEX_BITS].data)[(y & 7) + 8 * (z & 7)] : 0u;
+				uint32_t a, b;
+				brick_row_bytes(bits, &a, &b);
+				uint8_t bytes[8];
+				std::memcpy(bytes, &a, 4);
+				std::memcpy(bytes + 4, &b, 4);
+				const int x0 = std::max(lo[0], cx * 8), x1 = std::min(hi[0], cx * 8 + 8);
+				std::memcpy(row + x0, bytes + (x0 - cx * 8), static_cast<size_t>(x1 - x0));
+			}
+		}
+	});
 }
 
 // Largest empty cube per cell and octant: the classic "maximal square" recurrence in 3-D.  A cube of edge n anchored at

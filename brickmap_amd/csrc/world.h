@@ -93,6 +93,31 @@ public:
 	// touched (4096 entries, may be null) is set to 1 for every cell whose word or brick the batch may have changed.
 	static void edit_supercell(const WorldDims& dims, HostSupercell& c, int sx, int sy, int sz, const bm_edit* edits, int count, uint8_t* touched);
 
+	// ---- dense regions (bm_scene_write_region / bm_scene_read_region): a box of voxels as a volume V[z][y][x] with pitches
+	// Check a region, an op and the pointers' presence before anything changes: hi >= lo, pitches that cover their extents (0 = tight,
+	// filled in), a span that fits 64 bits.  *span = bytes from the first to behind the last voxel of the volume (0 for an empty box).
+	static bool validate_region(bm_region* r, std::string* why, uint64_t* span);
+	// The region's box clipped to the world; false = nothing of it inside (or the box is empty).
+	static bool region_bounds(const WorldDims& dims, const bm_region& r, int lo[3], int hi[3]);
+	// Where the merge below takes the volume's bits of a brick cell from: the volume itself (host memory; origin = the world voxel of
+	// V[0][0][0]) or the bricks region.hip packed from it (one per cell of the clipped box's cells c0 ... c0 + nc, x fastest).
+	struct RegionSource {
+		const uint8_t* voxels = nullptr;
+		int64_t row_pitch = 0, slice_pitch = 0;
+		int origin[3] = {0, 0, 0};
+		const Brick* packed = nullptr;
+		int c0[3] = {0, 0, 0}, nc[3] = {0, 0, 0};
+	};
+	// THE RULE of a region write, per brick cell of one supercell, in ascending local cell index: cover = the box's voxels in the cell,
+	// new = (old & ~cover) | (vol & cover) for BM_REGION_REPLACE, old | (vol & cover) for BM_EDIT_SET, old & ~(vol & cover) for
+	// BM_EDIT_CLEAR.  new == old: the cell is not touched at all.  An empty cell that gains voxels takes a freed slot (last freed first),
+	// else a new one; a brick that becomes empty gets word 0 and its slot goes on free_slots; otherwise the cell keeps its slot and its
+	// bits and LoD mask are rewritten.  [lo, hi): the clipped box in world voxels.  touched as for edit_supercell, but only cells that changed.
+	static void write_region_supercell(const WorldDims& dims, HostSupercell& c, int sx, int sy, int sz, const int lo[3], const int hi[3], int op,
+									   const RegionSource& src, uint8_t* touched);
+	// The box [lo, hi) (world voxels, inside the world) of the host world as bytes 0 / 1 into V, whose V[0][0][0] is world voxel `origin`.
+	void store_region(const int lo[3], const int hi[3], const int origin[3], uint8_t* voxels, int64_t row_pitch, int64_t slice_pitch, int threads) const;
+
 private:
 	void build_supercell(int sx, int sy, int sz, const float* heights);
 };

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, BM_QUERY_LOD, BM_QUERY_NO_REQUESTS, BM_VOXELS_DEVICE, BM_VOXELS_HOST, bm_camera, bm_counters, bm_edit, bm_frame_params,
+from ._lib import (BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, BM_REGION_REPLACE, bm_region, BM_QUERY_LOD, BM_QUERY_NO_REQUESTS, BM_VOXELS_DEVICE, BM_VOXELS_HOST, bm_camera, bm_counters, bm_edit, bm_frame_params,
                    bm_scene_info, check)
 
 
@@ -239,6 +239,59 @@ def host_load_supercell(volume, sx, sy, sz):
     n = C.c_uint32(0)
     check(_lib.load().bm_host_load_supercell(gs, gh, sx, sy, sz, volume.ctypes.data, idx.ctypes.data, bricks.ctypes.data, C.byref(n)))
     return idx, bricks[: n.value].copy()
+
+
+# ---- dense regions (bm_scene_write_region / bm_scene_read_region): a box of voxels as a volume [z, y, x] with strides
+def _region_op(op):
+    return {"replace": BM_REGION_REPLACE, "set": BM_EDIT_SET, "clear": BM_EDIT_CLEAR}.get(op, op) if isinstance(op, str) else int(op)
+
+
+def region_of(lo, volume, name="volume"):
+    """(bm_region, data pointer, is_cuda) of `volume` placed with its voxel [0, 0, 0] at world voxel lo = (x, y, z): a numpy array or a
+    torch tensor [z, y, x], uint8 or bool, x contiguous (stride 1) and non-negative strides along y and z -- a slice of a larger array
+    works.  Raises ValueError otherwise (no library call is made)."""
+    shape = tuple(getattr(volume, "shape", ()))
+    if len(shape) != 3:
+        raise ValueError(f"{name}: three dimensions [z, y, x] expected, got shape {shape}")
+    if hasattr(volume, "is_contiguous"):  # torch
+        import torch
+        if volume.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"{name}: dtype uint8 or bool expected, got {volume.dtype}")
+        strides, ptr, cuda = tuple(volume.stride()), volume.data_ptr(), volume.is_cuda
+    elif isinstance(volume, np.ndarray):
+        if volume.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise ValueError(f"{name}: dtype uint8 or bool expected, got {volume.dtype}")
+        strides, ptr, cuda = volume.strides, volume.ctypes.data, False
+    else:
+        raise ValueError(f"{name}: a numpy array or torch tensor expected, got {type(volume).__name__}")
+    nz, ny, nx = shape
+    if min(shape) == 0:  # an empty box: no voxel, no layout
+        strides = (ny * nx, nx, 1)
+    if nx > 1 and strides[2] != 1:
+        raise ValueError(f"{name}: x must be contiguous (stride 1), got strides {strides}")
+    row = strides[1] if ny > 1 else nx
+    sl = strides[0] if nz > 1 else row * ny
+    if row < nx or sl < row * ny:
+        raise ValueError(f"{name}: rows and slices must not overlap or run backwards, got strides {strides} for shape {shape}")
+    r = bm_region()
+    r.lo[:] = [int(v) for v in lo]
+    r.hi[:] = [int(lo[0]) + nx, int(lo[1]) + ny, int(lo[2]) + nz]
+    r.row_pitch, r.slice_pitch = int(row), int(sl)
+    return r, ptr, cuda
+
+
+def host_write_region_supercell(grid_size, grid_height, sx, sy, sz, indices, bricks, lo, volume, op="replace"):
+    """bm_host_write_region_supercell: the host half of Scene.write_region on one supercell's arrays (no device needed; the arrays as
+    for host_edit_supercell).  Returns the new (indices, bricks)."""
+    r, ptr, cuda = region_of(lo, volume)
+    assert not cuda
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).copy()
+    n = C.c_uint32(len(bricks))
+    buf = np.zeros((4096, 16), np.uint32)
+    buf[: len(bricks)] = np.asarray(bricks, np.uint32).reshape(-1, 16)
+    check(_lib.load().bm_host_write_region_supercell(grid_size, grid_height, sx, sy, sz, idx.ctypes.data, C.byref(n), buf.ctypes.data, 4096, C.byref(r), _region_op(op),
+                                                     C.c_void_p(ptr)))
+    return idx, buf[: n.value].copy()
 
 
 # ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
@@ -506,6 +559,70 @@ class Scene:
         a, b = C.c_float(0), C.c_float(0)
         check(self._L.bm_scene_last_edit_ms(self.gpuScene, C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
+
+    # ---- dense regions (bm_scene_write_region / bm_scene_read_region)
+    def _volume_stream(self, tensor, stream):
+        """(current, target) torch streams for a CUDA tensor of the scene's GPU: the call is issued on `target` (the given raw handle, or
+        torch's current stream), which is made to wait for the current stream"""
+        import torch
+        if tensor.device.index != self.device:
+            raise ValueError(f"a tensor on cuda:{self.device} (the scene's GPU) or on the CPU expected, got {tensor.device}")
+        current = torch.cuda.current_stream(tensor.device)
+        target = current if stream is None else torch.cuda.ExternalStream(int(stream), device=tensor.device)
+        if target.cuda_stream != current.cuda_stream:
+            target.wait_stream(current)
+        return current, target
+
+    def write_region(self, lo, volume, op="replace", stream=None):
+        """Write a dense box of voxels into the live scene: `volume` ([z, y, x], uint8 or bool, numpy array or torch tensor; a slice of a
+        larger one works as long as x is contiguous) lands with its first voxel at world voxel lo = (x, y, z).  op: "replace" (the box's
+        voxels become the volume's), "set" (solid where the volume is non-zero) or "clear" (empty where it is non-zero).  Clipped to the
+        world.  A tensor on the scene's GPU is packed there, behind the work queued on `stream` (a raw HIP stream handle; None = torch's
+        current stream).  Ordered like an edit.  A wrong dtype, layout or device raises ValueError before the library is called."""
+        r, ptr, cuda = region_of(lo, volume)
+        if min(volume.shape) == 0:
+            return self
+        if cuda:
+            _, target = self._volume_stream(volume, stream)
+            check(self._L.bm_scene_write_region(self.gpuScene, C.byref(r), _region_op(op), C.c_void_p(ptr), BM_VOXELS_DEVICE, C.c_void_p(target.cuda_stream)))
+        else:
+            check(self._L.bm_scene_write_region(self.gpuScene, C.byref(r), _region_op(op), C.c_void_p(ptr), BM_VOXELS_HOST, self._stream(stream)))
+        return self
+
+    def read_region(self, lo, hi, out=None, device=False, stream=None):
+        """The voxels lo <= v < hi (x, y, z; clipped to the world, 0 outside it) as a volume [z, y, x]: a bool numpy array, or with
+        device=True a uint8 torch tensor on the scene's GPU, written there by a kernel issued like a query on `stream`.  With `out` (numpy
+        array or torch tensor of that shape, strides honoured as in write_region) the voxels are written into it and it is returned."""
+        shape = tuple(int(h) - int(l) for l, h in zip(lo, hi))[::-1]
+        if min(shape) < 0:
+            raise ValueError(f"read_region: hi < lo ({lo} ... {hi})")
+        result = out
+        if out is None:
+            if device:
+                import torch
+                out = result = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
+            else:
+                out = np.zeros(shape, np.uint8)
+                result = out.view(np.bool_)
+        elif tuple(out.shape) != shape:
+            raise ValueError(f"read_region: out of shape {shape} expected, got {tuple(out.shape)}")
+        r, ptr, cuda = region_of(lo, out, "out")
+        if min(shape) == 0:
+            return result
+        if cuda:
+            current, target = self._volume_stream(out, stream)
+            check(self._L.bm_scene_read_region(self.gpuScene, C.byref(r), C.c_void_p(ptr), BM_VOXELS_DEVICE, C.c_void_p(target.cuda_stream)))
+            if target.cuda_stream != current.cuda_stream:
+                current.wait_stream(target)
+        else:
+            check(self._L.bm_scene_read_region(self.gpuScene, C.byref(r), C.c_void_p(ptr), BM_VOXELS_HOST, None))
+        return result
+
+    def last_region_ms(self):
+        """(pack_ms, copy_ms, scatter_ms, field_ms) of the last write_region that reached the device (hipEvents on the load stream)."""
+        t = [C.c_float(0) for _ in range(4)]
+        check(self._L.bm_scene_last_region_ms(self.gpuScene, *[C.byref(v) for v in t]))
+        return tuple(float(v.value) for v in t)
 
     # ---- ray queries (bm_scene_cast_rays): issued like a frame -- after every edit and upload issued before, asynchronous to the host
     def cast_rays_raw(self, n, rays_ptr, hits_ptr, flags=0, lod_origin=None, stream=None):

@@ -1,9 +1,11 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--voxels FILE] [--dig x,y,z,r] [--dig-at px,py,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
+// --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
+// first voxel at (x, y, z) before the first frame, replacing what was there (Scene::write_region; clipped to the world).
 // --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
 // --dig-at picks the voxel under pixel (px, py) of the first frame's camera (Scene::pick) and carves a sphere of radius r there; the
 // world streams, so while the pick lands on a brick that is not resident yet (level 3) the load queue is serviced and the pick repeated
@@ -27,9 +29,22 @@ int main(int argc_in, char** argv_in) {
 	int dig[4] = {0, 0, 0, -1};
 	int dig_at[3] = {0, 0, -1};
 	const char* voxels_path = nullptr;
+	std::string paste_path;
+	int paste_size[3] = {0, 0, 0}, paste_at[3] = {0, 0, 0};
 	for (int i = 0; i < argc_in; ++i) {
 		if (std::string(argv_in[i]) == "--voxels" && i + 1 < argc_in) {
 			voxels_path = argv_in[++i];
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--paste" && i + 1 < argc_in) {
+			const std::string spec = argv_in[++i];
+			const size_t colon = spec.rfind(':');
+			if (colon == std::string::npos || std::sscanf(spec.c_str() + colon + 1, "%d,%d,%d@%d,%d,%d", &paste_size[0], &paste_size[1], &paste_size[2], &paste_at[0],
+														  &paste_at[1], &paste_at[2]) != 6 || paste_size[0] <= 0 || paste_size[1] <= 0 || paste_size[2] <= 0) {
+				std::cerr << "--paste wants FILE:nx,ny,nz@x,y,z (sizes > 0)\n";
+				return 2;
+			}
+			paste_path = spec.substr(0, colon);
 			continue;
 		}
 		if (std::string(argv_in[i]) == "--dig-at" && i + 1 < argc_in) {
@@ -68,6 +83,16 @@ int main(int argc_in, char** argv_in) {
 		scene.load_voxels(volume.data(), volume.size());
 	} else {
 		scene.generate();                       // main.cpp:105 -- nothing resident yet: bricks stream in on demand
+	}
+	if (!paste_path.empty()) {
+		std::ifstream in(paste_path, std::ios::binary);
+		std::vector<uint8_t> volume(static_cast<size_t>(paste_size[0]) * paste_size[1] * paste_size[2]);
+		if (!in || !in.read(reinterpret_cast<char*>(volume.data()), static_cast<std::streamsize>(volume.size())) || in.peek() != EOF) {
+			std::cerr << "--paste: " << paste_path << " does not hold " << volume.size() << " bytes\n";
+			return 2;
+		}
+		const int hi[3] = {paste_at[0] + paste_size[0], paste_at[1] + paste_size[1], paste_at[2] + paste_size[2]};
+		scene.write_region(Scene::Region(paste_at, hi), volume.data());
 	}
 	if (dig[3] >= 0) scene.carve_sphere(dig, dig[3]);
 	camera.position = {grid_size / 2.f, grid_size / 8.f, 0.8f * grid_height};

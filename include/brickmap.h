@@ -244,6 +244,45 @@ BM_API int bm_scene_host_voxels(bm_scene* scene, uint8_t* dst, size_t capacity, 
  * was not from device memory. */
 BM_API int bm_scene_last_load_ms(bm_scene* scene, float* pack_ms, float* field_ms, float* mirror_ms);
 
+/* ---- dense voxel regions of a live scene: write a box of arbitrary voxels into it, read one out (no reference counterpart).
+ * The volume is V[z][y][x], one byte per voxel, non-zero = solid; x is contiguous, rows and slices lie at the given pitches, so a
+ * sub-box of a larger array or tensor is passed without a copy.  `where` says where V lies: BM_VOXELS_HOST, or BM_VOXELS_DEVICE for
+ * memory of the scene's device (packed / unpacked there by the kernels of csrc/region.hip).
+ *  - Clipping: the box is clipped to the world like an edit's shape.  A write ignores the volume's voxels outside the world; a read
+ *    returns them as 0.  A box wholly outside the world is a no-op for a write and all zeros for a read; an empty box (hi == lo on some
+ *    axis) is a no-op.
+ *  - Refusals, BM_EINVAL with the scene as it was: hi < lo on an axis, an unknown op or `where`, a null pointer, a pitch smaller than
+ *    the extent it spans (row_pitch < hi.x - lo.x, slice_pitch < row_pitch * (hi.y - lo.y)), and for BM_VOXELS_DEVICE a pointer whose
+ *    span of (nz - 1) * slice_pitch + (ny - 1) * row_pitch + nx bytes does not lie inside one allocation of the scene's device.  A scene
+ *    that is not on the device, or a failed one: BM_ESTATE.  Everything is checked before anything changes.
+ *  - Result of a write, per brick cell, supercells independent, cells in ascending local index: with cover = the clipped box's voxels
+ *    in the cell, new = (old & ~cover) | (V & cover) for BM_REGION_REPLACE, old | (V & cover) for BM_EDIT_SET, old & ~(V & cover) for
+ *    BM_EDIT_CLEAR.  A cell with new == old is NOT TOUCHED: word, brick, slot and device state stay, the requested flag included (so
+ *    writing the same region every step causes no churn; bm_scene_edit marks every cell its shapes reach).  An empty cell that gains
+ *    voxels takes a freed slot (last freed first), else a new one; a brick that becomes empty gets word 0 and frees its slot; else the
+ *    cell keeps its slot.  This is what bm_scene_edit gives for the batch that, cell by cell, sets the voxels of new & ~old and then
+ *    clears those of old & ~new.  The changed cells reach the device exactly as an edit's do (residency rule, pool growth, scatter,
+ *    cube-field update where occupancy changed).
+ *  - Ordering: a write is ordered like bm_scene_edit (frames and queries issued before it see the old world, those issued after it
+ *    the new one; the volume is read behind the work queued on hip_stream so far, and is no longer needed when the call returns).  A
+ *    read is issued like a query on hip_stream: it sees every edit, write and upload issued before it; later edits and
+ *    bm_scene_process_load_queue order themselves behind it; a device read is asynchronous to the host in a preloaded scene.
+ *  - A device write packs the box into one 64-byte brick per covered cell on the GPU, copies those to the host (the call's one
+ *    round trip: 1/8 of the volume's bytes; the host world is authoritative and hands out the slots) and merges there.  Temporary
+ *    memory: 64 bytes per covered cell on the device and in pinned memory, kept and grown on demand. */
+typedef struct bm_region {
+	int32_t lo[3], hi[3];   /* voxels v with lo <= v < hi on (x, y, z), half-open like BM_EDIT_BOX */
+	int64_t row_pitch;      /* bytes from one x-row to the next y; 0 = tight (hi.x - lo.x) */
+	int64_t slice_pitch;    /* bytes from one z-slice to the next; 0 = tight (row_pitch * (hi.y - lo.y)) */
+} bm_region;
+#define BM_REGION_REPLACE 0 /* the region's voxels become exactly the volume's; BM_EDIT_SET: solid where V is non-zero; BM_EDIT_CLEAR: empty where V is non-zero */
+BM_API int bm_scene_write_region(bm_scene* scene, const bm_region* region, int op, const uint8_t* voxels, int where, void* hip_stream);
+BM_API int bm_scene_read_region(bm_scene* scene, const bm_region* region, uint8_t* voxels, int where, void* hip_stream);
+/* times of the last bm_scene_write_region that reached the device, in ms (hipEvents on the load stream; waits for that write): the
+ * pack kernel and the copy of the packed bricks to the host (both 0 for BM_VOXELS_HOST), the scatter and the cube-field update (0 when
+ * no cell changed / no cell's occupancy changed).  BM_ESTATE before the first write. */
+BM_API int bm_scene_last_region_ms(bm_scene* scene, float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms);
+
 /* ---- ray queries against the live scene (no reference counterpart: the reference only traces inside its frame kernels).
  * What does a ray hit -- the voxel under the cursor, the ground under a walking camera, line of sight, collision probes.
  * A query walks exactly as the frames' extend kernel does (csrc/traverse.h), so a hit equals the reference's intersect_voxel bit
@@ -292,6 +331,12 @@ BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, in
  * (up to brick_capacity, else BM_EINVAL); on any error the arrays are left unchanged. */
 BM_API int bm_host_edit_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,
                                   uint32_t* brick_count, uint32_t* bricks, uint32_t brick_capacity, int count, const bm_edit* edits);
+
+/* the host half of bm_scene_write_region on one supercell's arrays, in place (no device needed; the arrays as for
+ * bm_host_edit_supercell): `voxels` is the region's volume in host memory.  On any error the arrays are left unchanged. */
+BM_API int bm_host_write_region_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,
+                                          uint32_t* brick_count, uint32_t* bricks, uint32_t brick_capacity, const bm_region* region, int op,
+                                          const uint8_t* voxels);
 
 /* the host route of bm_scene_load_voxels on one supercell (no device needed): voxels is the whole volume of a grid_size x grid_size x
  * grid_height world; indices4096 and bricks[4096][16] receive the supercell's canonical build, *brick_count its bricks */

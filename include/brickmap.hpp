@@ -130,6 +130,25 @@ public:
 	void fill_sphere(const int center[3], int radius) { edit({sphere(BM_EDIT_SET, center, radius)}); }
 	void carve_sphere(const int center[3], int radius) { edit({sphere(BM_EDIT_CLEAR, center, radius)}); }
 
+	// dense regions of the live world (no counterpart in the reference; bm_scene_write_region / bm_scene_read_region): a box of voxels as a
+	// volume V[z][y][x] of one byte per voxel (non-zero = solid), x contiguous, rows and slices at the region's pitches, in host memory or
+	// in memory of the scene's device.  A write is ordered like an edit; a read is issued like a query on hip_stream.
+	struct Region : bm_region {
+		// voxels lo <= v < hi; pitches in bytes, 0 = tight
+		Region(const int lo_[3], const int hi_[3], int64_t row_pitch_ = 0, int64_t slice_pitch_ = 0) : bm_region{} {
+			for (int k = 0; k < 3; ++k) { lo[k] = lo_[k]; hi[k] = hi_[k]; }
+			row_pitch = row_pitch_;
+			slice_pitch = slice_pitch_;
+		}
+		size_t voxels() const { return static_cast<size_t>(hi[0] - lo[0]) * static_cast<size_t>(hi[1] - lo[1]) * static_cast<size_t>(hi[2] - lo[2]); }
+	};
+	void write_region(const Region& region, const uint8_t* voxels, int op = BM_REGION_REPLACE, int where = BM_VOXELS_HOST, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_write_region(gpuScene.handle, &region, op, voxels, where, hip_stream));
+	}
+	void read_region(const Region& region, uint8_t* voxels, int where = BM_VOXELS_HOST, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_read_region(gpuScene.handle, &region, voxels, where, hip_stream));
+	}
+
 	// ray queries (no counterpart in the reference; bm_scene_cast_rays): the first hit of n rays, device buffers in and out, issued
 	// like a frame on hip_stream (after every edit and upload issued before it), asynchronous to the host
 	void cast_rays(int64_t n, const bm_ray* rays_dev, bm_ray_hit* hits_dev, uint32_t flags = 0, const float* lod_origin = nullptr,
