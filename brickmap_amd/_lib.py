@@ -18,6 +18,7 @@ BM_FLAG_ORDERED = 16
 BM_FLAG_RAY_DIGEST = 32
 BM_QUERY_LOD = 1
 BM_QUERY_NO_REQUESTS = 2
+BM_VOLUME_ANY = 1
 BM_VOXELS_HOST = 0
 BM_VOXELS_DEVICE = 1
 BRICK_INDEX_BITS = 0x00000FFF
@@ -72,6 +73,14 @@ class bm_ray(C.Structure):
 
 class bm_ray_hit(C.Structure):
     _fields_ = [("distance", C.c_float), ("normal", C.c_float * 3), ("voxel", C.c_int32 * 3), ("level", C.c_int32)]
+
+
+class bm_volume(C.Structure):
+    _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class bm_volume_result(C.Structure):
+    _fields_ = [("solid", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("unresolved", C.c_uint32), ("status", C.c_uint32)]
 
 
 class bm_scene_info(C.Structure):
@@ -139,6 +148,7 @@ SIGNATURES = {
     "bm_scene_read_region": (_i, [_vp, C.POINTER(bm_region), _vp, _i, _vp]),
     "bm_scene_last_region_ms": (_i, [_vp] + [C.POINTER(C.c_float)] * 4),
     "bm_scene_cast_rays": (_i, [_vp, C.c_int64, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "bm_scene_query_volumes": (_i, [_vp, C.c_int64, _vp, _vp, C.c_uint32, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_host_column_heights": (_i, [_i, _i, _i, _i, _vp]),
     "bm_host_generate_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32]),

@@ -150,6 +150,11 @@ int bm_scene_cast_rays(bm_scene* scene, int64_t n, const bm_ray* rays_dev, bm_ra
 	return scene->impl.cast_rays(n, rays_dev, hits_dev, flags, lod_origin, static_cast<hipStream_t>(hip_stream));
 }
 
+int bm_scene_query_volumes(bm_scene* scene, int64_t n, const bm_volume* volumes_dev, bm_volume_result* results_dev, uint32_t flags, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.query_volumes(n, volumes_dev, results_dev, flags, static_cast<hipStream_t>(hip_stream));
+}
+
 int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t n, const float* px, const float* py, bm_ray* out) {
 	if (!camera || width <= 0 || height <= 0 || width > 65535 || height > 65535 || n < 0 || (n > 0 && (!px || !py || !out))) {
 		set_error("bm_camera_pixel_rays: bad argument");

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, region.hip, query.hip and wavefront.hip
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,6 +71,12 @@ void launch_region_zero(uint8_t* voxels, int64_t row_pitch, int64_t slice_pitch,
 int query_blocks_per_cu(bool request);
 void launch_query(const DeviceScene& sc, const int campos[3], const void* rays, void* hits, uint32_t n, uint32_t* ticket, int resident_blocks,
 				  bool request, hipStream_t stream);
+
+// volume queries (volume.hip): n bm_volume records in, n bm_volume_result records out (every byte written).  tmp: volume_tmp_bytes(n) bytes --
+// one 64-bit word per record and one per 256 records, plus one -- that no other launch uses until this one has finished
+int volume_blocks_per_cu(bool any);
+size_t volume_tmp_bytes(uint32_t n);
+void launch_volume_query(const DeviceScene& sc, const void* volumes, void* results, uint32_t n, bool any, uint64_t* tmp, int resident_blocks, hipStream_t stream);
 
 // wavefront mode (wavefront.hip)
 int wavefront_blocks_per_cu(bool connect, bool instrumented);

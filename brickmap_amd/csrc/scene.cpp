@@ -1443,6 +1443,42 @@ int Scene::cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t f
 	return 0;
 }
 
+// ---- volume queries (bm_scene_query_volumes).  Issued like a ray query; the kernels only read the world.  The item offsets are one
+// buffer, so a query is ordered behind the previous one (on whatever stream that ran), and the buffer grows only once that has finished.
+int Scene::query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* results, uint32_t flags, hipStream_t stream) {
+	if (flags & ~BM_VOLUME_ANY) { set_error("bm_scene_query_volumes: unknown flag"); return BM_EINVAL; }
+	if (n < 0 || n > (int64_t{1} << 24)) { set_error("bm_scene_query_volumes: n must be 0 ... 2^24"); return BM_EINVAL; }
+	if (n == 0) return 0;
+	if (!volumes || !results) { set_error("bm_scene_query_volumes: null volume or result buffer"); return BM_EINVAL; }
+	if (reinterpret_cast<uintptr_t>(volumes) % 4 != 0 || reinterpret_cast<uintptr_t>(results) % 8 != 0) {
+		set_error("bm_scene_query_volumes: volumes must be 4-byte aligned, results 8-byte aligned");
+		return BM_EINVAL;
+	}
+	if (int e = require_on_device()) return e;
+	if (int e = require_not_failed()) return e;
+	BM_HIP(hipSetDevice(device_));
+	if (!volume_blocks_per_cu_[0]) {
+		if (int e = ev_volume_.create(hipEventDisableTiming)) return e;
+		volume_blocks_per_cu_[0] = volume_blocks_per_cu(false);
+		volume_blocks_per_cu_[1] = volume_blocks_per_cu(true);
+	}
+	const size_t need = volume_tmp_bytes(static_cast<uint32_t>(n));
+	if (d_volume_tmp_.bytes() < need) {
+		if (volume_busy_) { BM_HIP(hipEventSynchronize(ev_volume_)); volume_busy_ = false; }
+		if (int e = d_volume_tmp_.reserve(std::max<size_t>(need, 1 << 16))) return e;
+	}
+	const bool any = (flags & BM_VOLUME_ANY) != 0;
+	DeviceScene view;
+	if (int e = begin_frame(stream, &view, nullptr)) return e;
+	if (volume_busy_) BM_HIP(hipStreamWaitEvent(stream, ev_volume_, 0));
+	launch_volume_query(view, volumes, results, static_cast<uint32_t>(n), any, d_volume_tmp_, volume_blocks_per_cu_[any ? 1 : 0] * compute_units_, stream);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_volume_, stream));
+	volume_busy_ = true;
+	end_frame(stream);
+	return 0;
+}
+
 int Scene::begin_frame(hipStream_t stream, DeviceScene* view, DeviceCounters** counters) {
 	if (int e = require_on_device()) return e;
 	BM_HIP(hipSetDevice(device_));

@@ -64,6 +64,8 @@ public:
 	int last_load_ms(float* pack_ms, float* field_ms, float* mirror_ms); // device time of the last load from device memory
 	// ray queries (query.hip): issued like a frame (begin_frame / end_frame), asynchronous to the host
 	int cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream);
+	// volume queries (volume.hip): issued like a ray query
+	int query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* results, uint32_t flags, hipStream_t stream);
 	int render(const bm_camera* cam, const bm_frame_params* fp, float* accum, uint32_t* dbg, hipStream_t stream);
 	// `count` consecutive frames as one launch (the frame ring, trace.hip); dbgs may be null, and so may any of its entries
 	int render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream);
@@ -206,6 +208,11 @@ private:
 	Event ev_query_[kQueryRing];
 	uint64_t queries_ = 0;
 	int query_blocks_per_cu_[2] = {0, 0};
+	// volume queries: the item offsets of one launch (volume_tmp_bytes, grown on demand); a query waits for the one before it, which used them
+	DeviceBuffer<uint64_t> d_volume_tmp_;
+	Event ev_volume_;
+	bool volume_busy_ = false;
+	int volume_blocks_per_cu_[2] = {0, 0};
 	int queue_cap_ = 1024;                       // variables.h:35
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27
 	DeviceScene view_{};

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import (BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, BM_REGION_REPLACE, bm_region, BM_QUERY_LOD, BM_QUERY_NO_REQUESTS, BM_VOXELS_DEVICE, BM_VOXELS_HOST, bm_camera, bm_counters, bm_edit, bm_frame_params,
+from ._lib import (BM_EDIT_BOX, BM_EDIT_CLEAR, BM_EDIT_SET, BM_EDIT_SPHERE, BM_REGION_REPLACE, bm_region, BM_QUERY_LOD, BM_QUERY_NO_REQUESTS, BM_VOLUME_ANY, BM_VOXELS_DEVICE, BM_VOXELS_HOST, bm_camera, bm_counters, bm_edit, bm_frame_params,
                    bm_scene_info, check)
 
 
@@ -344,6 +344,45 @@ def pack_rays(origins, directions, tmax=None):
     rays["origin"], rays["direction"] = o, d
     rays["tmax"] = np.inf if tmax is None else np.asarray(tmax, np.float32)
     return rays
+
+
+# ---- volume queries (bm_scene_query_volumes): packed records, 48 bytes in, 40 bytes out
+VOLUME_DTYPE = np.dtype([("shape", "<i4"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("center", "<i4", 3), ("radius", "<i4"), ("reserved", "<u4")])  # bm_volume
+VOLUME_RESULT_DTYPE = np.dtype([("solid", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3), ("unresolved", "<u4"), ("status", "<u4")])             # bm_volume_result
+
+
+@dataclass
+class VolumeResults:
+    """Results of Scene.query_volumes, one row per record, in the input's kind (torch CUDA tensors or numpy arrays): solid (voxels counted;
+    torch: int64), lo / hi (tight half-open bounds, int32 x 3, -1 when solid == 0), unresolved (brick cells that are not resident), status
+    (1 = malformed record; both int32 in torch).  `packed`: the bm_volume_result records themselves (torch: uint8 [n, 40] on the device;
+    numpy: VOLUME_RESULT_DTYPE)."""
+    solid: object
+    lo: object
+    hi: object
+    unresolved: object
+    status: object
+    packed: object = None
+
+    def __len__(self):
+        return len(self.solid)
+
+
+def volume_box(lo, hi):
+    """bm_volume records (a VOLUME_DTYPE array) of boxes lo <= v < hi: lo and hi are (x, y, z), or N x 3 for N boxes."""
+    lo, hi = np.asarray(lo, np.int32).reshape(-1, 3), np.asarray(hi, np.int32).reshape(-1, 3)
+    assert len(lo) == len(hi), "one hi per lo"
+    out = np.zeros(len(lo), VOLUME_DTYPE)
+    out["shape"], out["lo"], out["hi"] = BM_EDIT_BOX, lo, hi
+    return out
+
+
+def volume_sphere(center, radius):
+    """bm_volume records of spheres sum((v - center)^2) <= radius^2: center is (x, y, z) or N x 3, radius a scalar or one per sphere."""
+    center = np.asarray(center, np.int32).reshape(-1, 3)
+    out = np.zeros(len(center), VOLUME_DTYPE)
+    out["shape"], out["center"], out["radius"] = BM_EDIT_SPHERE, center, np.asarray(radius, np.int32)
+    return out
 
 
 def probe_streams(count, device=0):
@@ -691,6 +730,86 @@ class Scene:
         if int(h["level"]) < 0:
             return None
         return RayHit(float(h["distance"]), tuple(float(v) for v in h["normal"]), tuple(int(v) for v in h["voxel"]), int(h["level"]))
+
+    # ---- volume queries (bm_scene_query_volumes): issued like a ray query, asynchronous to the host
+    def query_volumes_raw(self, n, volumes_ptr, results_ptr, flags=0, stream=None):
+        """bm_scene_query_volumes on device pointers (ints): n bm_volume records in, n bm_volume_result records out."""
+        check(self._L.bm_scene_query_volumes(self.gpuScene, int(n), C.c_void_p(volumes_ptr), C.c_void_p(results_ptr), int(flags), self._stream(stream)))
+
+    def query_volumes(self, volumes, any=False, stream=None):
+        """Solid voxels, their tight bounds and the unresolved brick cells of each box or sphere.  volumes: a VOLUME_DTYPE array
+        (volume_box / volume_sphere; np.concatenate joins them), or the records as a contiguous uint8 CUDA tensor of 48 n bytes (used
+        as it is, no copy).  any=True: the yes / no probe BM_VOLUME_ANY (solid 0 / 1, bounds -1).  stream: a raw HIP stream handle
+        (None = torch's current stream); the query runs there, behind the work already queued on the current stream.  A tensor gives
+        tensors on the device, ready in stream order on `stream`, and the host does not wait; an array makes the call wait and gives arrays."""
+        import torch
+        flags = BM_VOLUME_ANY if any else 0
+        dev = volumes.device if isinstance(volumes, torch.Tensor) else torch.device("cuda", self.device)
+        current = torch.cuda.current_stream(dev)
+        target = current if stream is None else torch.cuda.ExternalStream(int(stream), device=dev)
+        other = target.cuda_stream != current.cuda_stream
+        if other:
+            target.wait_stream(current)
+        with torch.cuda.stream(target):  # (what the query touches is made on the stream it runs on, as in cast_rays)
+            if isinstance(volumes, torch.Tensor):
+                assert volumes.is_cuda and volumes.dtype == torch.uint8 and volumes.is_contiguous() and volumes.numel() % 48 == 0, "packed volumes: contiguous uint8, 48 bytes per record, on the GPU"
+                if other:
+                    volumes.record_stream(target)
+                n = volumes.numel() // 48
+                res = torch.empty((n, 40), dtype=torch.uint8, device=dev)
+                self.query_volumes_raw(n, volumes.data_ptr(), res.data_ptr(), flags, target.cuda_stream)
+                return VolumeResults(res[:, 0:8].view(torch.int64).reshape(n), res[:, 8:20].view(torch.int32), res[:, 20:32].view(torch.int32),
+                                     res[:, 32:36].view(torch.int32).reshape(n), res[:, 36:40].view(torch.int32).reshape(n), res)
+            volumes = np.ascontiguousarray(volumes)
+            assert volumes.dtype == VOLUME_DTYPE, "packed volumes: a VOLUME_DTYPE array"
+            n = volumes.size
+            out = np.zeros(n, VOLUME_RESULT_DTYPE)
+            if n:
+                d_vol = torch.from_numpy(volumes.reshape(n).view(np.uint8).reshape(n, 48)).to(dev)
+                d_res = torch.empty((n, 40), dtype=torch.uint8, device=dev)
+                self.query_volumes_raw(n, d_vol.data_ptr(), d_res.data_ptr(), flags, target.cuda_stream)
+                target.synchronize()
+                out = d_res.cpu().numpy().view(VOLUME_RESULT_DTYPE).reshape(n)
+            return VolumeResults(out["solid"], out["lo"], out["hi"], out["unresolved"], out["status"], out)
+
+    def count_box(self, lo, hi):
+        """Solid voxels in the box lo <= v < hi (one query, then the host waits); in a streaming scene only resident bricks count."""
+        return int(self.query_volumes(volume_box(lo, hi)).solid[0])
+
+    def count_sphere(self, center, radius):
+        """Solid voxels in the sphere sum((v - center)^2) <= radius^2 (one query, then the host waits)."""
+        return int(self.query_volumes(volume_sphere(center, radius)).solid[0])
+
+    def is_free(self, lo, hi):
+        """True when no resident solid voxel lies in the box lo <= v < hi (the early-out probe BM_VOLUME_ANY)."""
+        return int(self.query_volumes(volume_box(lo, hi), any=True).solid[0]) == 0
+
+    def sweep_box(self, lo, hi, axis, sign, max_distance):
+        """How far the box lo <= v < hi can move along sign * axis (axis 0 / 1 / 2 = x / y / z, sign +1 / -1): the largest d in
+        [0, max_distance] such that the box moved by k voxels meets no solid voxel for every 1 <= k <= d.  One box query per sweep, over
+        everything the moved boxes cover -- the box moved by one voxel, stretched by max_distance - 1 more along the direction; d follows
+        from the bounds of the solid voxels found there, exactly: the nearest one beyond the leading face stops the box in front of it,
+        and one inside the box moved by one voxel (a box that starts in something solid) gives 0.  All arguments are scalars / (x, y, z),
+        or arrays of N (N x 3 for lo and hi).  Returns (d, unresolved): numpy arrays of N, or two ints for one box; unresolved counts the
+        brick cells of the queried space that are not resident (a streaming scene)."""
+        single = np.ndim(lo) == 1 and all(np.ndim(v) == 0 for v in (axis, sign, max_distance))
+        lo, hi = np.asarray(lo, np.int64).reshape(-1, 3), np.asarray(hi, np.int64).reshape(-1, 3)
+        n = max(len(lo), np.size(axis), np.size(sign), np.size(max_distance))
+        lo, hi = np.broadcast_to(lo, (n, 3)), np.broadcast_to(hi, (n, 3))
+        axis, sign, dist = (np.broadcast_to(np.asarray(v, np.int64), (n,)) for v in (axis, sign, max_distance))
+        assert ((axis >= 0) & (axis <= 2)).all() and (np.abs(sign) == 1).all() and (dist >= 0).all(), "axis 0 ... 2, sign +1 / -1, max_distance >= 0"
+        rows = np.arange(n)
+        face_hi, face_lo = hi[rows, axis], lo[rows, axis]
+        elo, ehi = lo.copy(), hi.copy()
+        elo[rows, axis] = np.where(sign > 0, face_lo + 1, face_lo - dist)
+        ehi[rows, axis] = np.where(sign > 0, face_hi + dist, face_hi - 1)
+        ehi[dist == 0] = elo[dist == 0]  # nothing to ask
+        lim = np.iinfo(np.int32)
+        res = self.query_volumes(volume_box(np.clip(elo, lim.min, lim.max), np.clip(ehi, lim.min, lim.max)))
+        hit = res.solid > 0
+        d = np.where(hit, np.maximum(np.where(sign > 0, res.lo[rows, axis] - face_hi, face_lo - res.hi[rows, axis]), 0), dist)
+        unresolved = res.unresolved.astype(np.int64)
+        return (int(d[0]), int(unresolved[0])) if single else (d, unresolved)
 
     def synchronize(self):
         check(self._L.bm_synchronize(self.gpuScene))

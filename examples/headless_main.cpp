@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -11,6 +11,8 @@
 // world streams, so while the pick lands on a brick that is not resident yet (level 3) the load queue is serviced and the pick repeated
 // (at most 8 times).  Prints `picked voxel x,y,z level L`; after the carve, what the same pixel sees now.  A pick that stays
 // unresolved (level 3) digs nothing.
+// --ground x,y prints the height of the highest solid voxel of that column after the digging (one box query, Scene::query_volume): the
+// world streams, so bricks that are not resident yet are reported as unresolved cells, not counted.
 // With `wavefront` the frames are rendered with the reference's own queue schedule (one segment per call); with `ring` the
 // world is made resident first and all frames are ONE launch of the persistent kernel (launch_frames, the frame ring).
 #include <cstdint>
@@ -28,6 +30,7 @@ int main(int argc_in, char** argv_in) {
 	std::vector<char*> args;
 	int dig[4] = {0, 0, 0, -1};
 	int dig_at[3] = {0, 0, -1};
+	int ground[2] = {-1, -1};
 	const char* voxels_path = nullptr;
 	std::string paste_path;
 	int paste_size[3] = {0, 0, 0}, paste_at[3] = {0, 0, 0};
@@ -50,6 +53,13 @@ int main(int argc_in, char** argv_in) {
 		if (std::string(argv_in[i]) == "--dig-at" && i + 1 < argc_in) {
 			if (std::sscanf(argv_in[++i], "%d,%d,%d", &dig_at[0], &dig_at[1], &dig_at[2]) != 3 || dig_at[2] < 0) {
 				std::cerr << "--dig-at wants px,py,r (r >= 0)\n";
+				return 2;
+			}
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--ground" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d", &ground[0], &ground[1]) != 2 || ground[0] < 0 || ground[1] < 0) {
+				std::cerr << "--ground wants x,y (>= 0)\n";
 				return 2;
 			}
 			continue;
@@ -120,6 +130,12 @@ int main(int argc_in, char** argv_in) {
 			std::printf("carved radius %d at %d,%d,%d; the pixel now sees voxel %d,%d,%d level %d\n", dig_at[2], hit.voxel[0], hit.voxel[1],
 						hit.voxel[2], now.voxel[0], now.voxel[1], now.voxel[2], now.level);
 		}
+	}
+	if (ground[0] >= 0) {
+		const int lo[3] = {ground[0], ground[1], 0}, hi[3] = {ground[0] + 1, ground[1] + 1, grid_height};
+		const bm_volume_result column = scene.query_volume(Scene::Volume::box(lo, hi));
+		std::printf("ground at %d,%d: height %d (%llu solid voxels in the column, %u brick cells not resident)\n", ground[0], ground[1], column.hi[2],
+					static_cast<unsigned long long>(column.solid), column.unresolved);
 	}
 
 	if (wavefront) {

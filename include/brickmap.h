@@ -322,6 +322,45 @@ BM_API int bm_scene_cast_rays(bm_scene* scene, int64_t n, const bm_ray* rays_dev
  * frames; tmax = +inf. */
 BM_API int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t n, const float* px, const float* py, bm_ray* out);
 
+/* ---- volume queries against the live scene (no reference counterpart): how much is solid in a box or a sphere, and where.
+ * Is this box free, how much does this sphere hold, where is the ground under this column, how far can this box move before it
+ * touches something -- questions a ray, which has no width, answers badly.  For each of n records in device memory: the number of
+ * solid voxels inside the shape, their tight bounding box, and how many brick cells could not be answered.  All integers, all exact.
+ *  - The shape is clipped to the world exactly like an edit's shape; one wholly outside gives zeros and -1 bounds, and so does an
+ *    empty box.  Per brick cell, with cover = the clipped shape's voxels in the cell: a resident cell (the device index word has
+ *    BM_BRICK_LOADED_BIT; the brick is at arena[pool_base + slot]) contributes popcount(brick & cover) and the bounds of those bits;
+ *    a cell that is empty in the world contributes nothing; a cell that holds a brick which is not resident adds 1 to `unresolved`,
+ *    provided cover is not empty.  In a preloaded scene unresolved is always 0 and the answer is exact.
+ *  - BM_VOLUME_ANY: a yes / no probe that may stop early.  solid = 1 if any solid voxel would be counted, else 0; the bounds are all
+ *    -1; unresolved = 1 if solid == 0 and at least one cell was unresolved, else 0 -- whatever the order of evaluation.
+ *  - Malformed records are marked, not refused (the records live in device memory and the call stays asynchronous, as for
+ *    bm_ray.reserved): status = 1, solid = 0, bounds -1, unresolved = 0 for an unknown shape, a box with hi < lo on an axis, a
+ *    sphere with radius < 0 (the checks of bm_scene_edit), or reserved != 0.  Other records are not affected.
+ *  - The call writes every byte of every result record.  It files no brick request and writes no index word: it only reads the world.
+ *  - Ordering: issued like a ray query on hip_stream -- it sees every edit, region write and upload issued before it, on any
+ *    stream; later edits and bm_scene_process_load_queue order themselves behind it; asynchronous to the host.  Volume queries of one
+ *    scene run one after another, also when issued on different streams (they share the temporary memory below).
+ *  - n == 0 is a no-op.  n < 0, n > 2^24, NULL buffers, unknown flag bits, volumes_dev not 4-byte or results_dev not 8-byte aligned:
+ *    BM_EINVAL; a scene not on the device, or a failed one: BM_ESTATE.  Nothing is launched on an error.
+ *  - Temporary device memory: 8 bytes per record and 8 per 256 records (at least 64 KiB; 128.5 MiB for 2^24 records), kept and
+ *    grown on demand. */
+typedef struct bm_volume {        /* 48 bytes -- the shape part of bm_edit, same meaning field by field */
+	int32_t shape;                /* BM_EDIT_BOX / BM_EDIT_SPHERE */
+	int32_t lo[3], hi[3];         /* box: lo <= v < hi */
+	int32_t center[3];            /* sphere: sum (v - center)^2 <= radius^2, 64-bit integers, as bm_edit */
+	int32_t radius;
+	uint32_t reserved;            /* 0 */
+} bm_volume;
+typedef struct bm_volume_result { /* 40 bytes */
+	uint64_t solid;               /* solid voxels of the shape, clipped to the world, in resident bricks */
+	int32_t lo[3], hi[3];         /* tight half-open bounds of those voxels; all six -1 when solid == 0 */
+	uint32_t unresolved;          /* brick cells that hold a brick in the world, contain a voxel of the clipped shape, and are not resident */
+	uint32_t status;              /* 0 ok; 1 malformed record (then solid = 0, bounds -1, unresolved = 0) */
+} bm_volume_result;
+#define BM_VOLUME_ANY 1u
+BM_API int bm_scene_query_volumes(bm_scene* scene, int64_t n, const bm_volume* volumes_dev, bm_volume_result* results_dev, uint32_t flags,
+                                  void* hip_stream);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

@@ -173,6 +173,39 @@ public:
 		return hit;
 	}
 
+	// volume queries (no counterpart in the reference; bm_scene_query_volumes): solid voxels, their bounds and the unresolved brick cells
+	// of n boxes or spheres, device buffers in and out, issued like a ray query on hip_stream, asynchronous to the host
+	struct Volume : bm_volume {
+		static Volume box(const int lo_[3], const int hi_[3]) {
+			Volume v{};
+			v.shape = BM_EDIT_BOX;
+			for (int k = 0; k < 3; ++k) { v.lo[k] = lo_[k]; v.hi[k] = hi_[k]; }
+			return v;
+		}
+		static Volume sphere(const int center_[3], int radius_) {
+			Volume v{};
+			v.shape = BM_EDIT_SPHERE; v.radius = radius_;
+			for (int k = 0; k < 3; ++k) v.center[k] = center_[k];
+			return v;
+		}
+	};
+	void query_volumes(int64_t n, const bm_volume* volumes_dev, bm_volume_result* results_dev, uint32_t flags = 0, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_query_volumes(gpuScene.handle, n, volumes_dev, results_dev, flags, hip_stream));
+	}
+	// one shape, one query, then the host waits
+	bm_volume_result query_volume(const bm_volume& volume, uint32_t flags = 0) {
+		void* buf = nullptr;
+		BM_CHECKED(bm_buffer_alloc(device_, sizeof(bm_volume) + sizeof(bm_volume_result), &buf));
+		bm_volume_result* d_result = static_cast<bm_volume_result*>(buf);
+		bm_volume* d_volume = reinterpret_cast<bm_volume*>(static_cast<char*>(buf) + sizeof(bm_volume_result));
+		BM_CHECKED(bm_buffer_write(device_, d_volume, &volume, sizeof volume));
+		query_volumes(1, d_volume, d_result, flags);
+		bm_volume_result result{};
+		BM_CHECKED(bm_buffer_read(device_, &result, d_result, sizeof result)); // (waits for the device)
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return result;
+	}
+
 private:
 	int device_;
 };
