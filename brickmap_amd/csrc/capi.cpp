@@ -395,6 +395,7 @@ int bm_frame_plan_of(const bm_frame_params* params, int hit_records, bm_frame_pl
 	out->refill_min_in_ring = bm::ring_refill_min(fc.refill_min, fc.helpers != 0, bm::tuning().refill_min);
 	out->tiles_x = fc.tiles_x; out->tiles_y = fc.tiles_y; out->local_rows = fc.local_rows;
 	out->instrumented = (hit_records || (fc.flags & BM_FLAG_COUNTERS)) ? 1 : 0;
+	out->ring_group = bm::ring_group_of(fc, bm::kMaxRingGroup); // (of a launch long enough for a whole group)
 	return 0;
 }
 int bm_trace_waves_per_simd(int device, int instrumented, int xcd_handout, int helpers, int* waves) {
@@ -414,6 +415,7 @@ int bm_tuning_overrides(char* buf, size_t buflen) {
 	if (t.xcd_handout == 0 || t.xcd_handout == 1) add("BM_XCD_HANDOUT", t.xcd_handout);
 	if (t.helpers == 0 || t.helpers == 1) add("BM_HELPERS", t.helpers);
 	if (t.blocks_per_cu > 0) add("BM_TRACE_BLOCKS_PER_CU", t.blocks_per_cu);
+	if (t.ring_group >= 1 && t.ring_group <= bm::kMaxRingGroup) add("BM_RING_GROUP", t.ring_group);
 	if (s.size() + 1 > buflen) { set_error("buffer too small"); return BM_EINVAL; }
 	std::memcpy(buf, s.c_str(), s.size() + 1);
 	return 0;

@@ -94,6 +94,10 @@ struct FrameConstants {
 	int ring_uniform;
 	int ring_sample_stride;      // sample_base of frame i = sample_base + i * ring_sample_stride
 	uint32_t ring_pixel_stride;  // pixel record of frame i = accum + (local pixel + i * ring_pixel_stride) float4s
+	// ... and their frames are handed out in GROUPS of ring_group consecutive frames (trace.hip "FRAME GROUPS"): the work item is (chunk,
+	// pixel part, frame of the group), every group has its own block of ticket counters, and the launch's last group may be shorter
+	int ring_group;              // F >= 1 (1: frame after frame)
+	int ring_groups_after;       // groups that follow the first one: ceil(frames / F) - 1
 };
 
 struct DeviceCounters { // v: same order as bm_counters; sched: same order as bm_sched_stats

@@ -42,7 +42,7 @@ void division_magic(uint32_t d, uint32_t* magic, int* shift) {
 }
 
 // Tuning overrides, read from the environment ONCE per process (A/B runs, tools/): BM_REFILL_MIN (1 ... 64), BM_XCD_HANDOUT (0 / 1),
-// BM_HELPERS (0 / 1), BM_TRACE_BLOCKS_PER_CU (> 0).  None set = the product's own rules.  bm_tuning_overrides() reports them, so that
+// BM_HELPERS (0 / 1), BM_TRACE_BLOCKS_PER_CU (> 0), BM_RING_GROUP (1 ... 64).  None set = the product's own rules.  bm_tuning_overrides() reports them, so that
 // a measurement can say what it ran under (bench.py echoes them into its line and refuses to go on under BM_BENCH_STRICT=1).
 const Tuning& tuning() {
 	static const Tuning t = [] {
@@ -52,9 +52,42 @@ const Tuning& tuning() {
 		v.xcd_handout = num("BM_XCD_HANDOUT", -1);
 		v.helpers = num("BM_HELPERS", -1);
 		v.blocks_per_cu = num("BM_TRACE_BLOCKS_PER_CU", 0);
+		v.ring_group = num("BM_RING_GROUP", 0);
 		return v;
 	}();
 	return t;
+}
+
+// The hand-out counts tickets in 32 bits (trace.hip: `my_tickets`, `base + want`).  The busiest counter owns a 1/8 share of the
+// units -- groups of four chunks, or 256x256-pixel super-tiles of 4096 chunks -- times `per_chunk` tickets per chunk: 16, times the
+// samples with (chunk, sample) items, times the frames of a group in a uniform launch; every wave may overshoot a used-up counter
+// once by up to 64.
+static bool tickets_fit(int tiles_x, int tiles_y, bool xcd, long long per_chunk) {
+	long long share;
+	if (xcd) {
+		const long long st = static_cast<long long>((tiles_x + 15) / 16) * ((tiles_y + 15) / 16);
+		share = ((st + 7) / 8) * 4096ll * per_chunk;
+	} else {
+		share = ((static_cast<long long>(tiles_x) * tiles_y * 4 + 7) / 8) * 4ll * per_chunk;
+	}
+	return share < (1ll << 30) - (1ll << 24); // (2^30: the hand-out divides ticket numbers with 30-bit-exact multiply-high constants)
+}
+
+// How many consecutive frames of a UNIFORM launch (scene.cpp render_frames) are handed out together, as (chunk, pixel part, frame)
+// items (trace.hip "FRAME GROUPS")?  The one place that decides it.  Frames that add every event with float atomics -- helper lanes
+// on -- leave the order of a pixel's additions free already, so their frames may run side by side in a wave: kRingGroup, or
+// BM_RING_GROUP (1 = frame after frame, for A/B runs), at most the frames there are.  Ordered frames write back with plain stores and
+// compare bit for bit with single launches: 1.  Frames with (chunk, sample) items of two or more samples hold a pixel's samples in
+// neighbouring lanes as it is, and the ticket has one field for "which sample of the chunk": 1.  And 1 where the tickets of a group
+// would not fit their counter.
+int ring_group_of(const FrameConstants& fc, int frames) {
+	const bool several_sample_items = (fc.flags & BM_FLAG_SAMPLE_ITEMS) && fc.spp >= 2;
+	if (!fc.helpers || several_sample_items || frames < 2) return 1;
+	const int chosen = tuning().ring_group;
+	int group = chosen >= 1 && chosen <= kMaxRingGroup ? chosen : kRingGroup;
+	group = std::min(group, frames);
+	if (!tickets_fit(fc.tiles_x, fc.tiles_y, fc.xcd_handout != 0, 16ll * group)) group = 1;
+	return group;
 }
 
 int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_in, FrameConstants* fc, bool hit_records) {
@@ -93,21 +126,8 @@ int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_
 	// 24.05 -> 23.90; on a 1080p frame (40 super-tiles) the shares are too uneven: +8 % (profiles/r04_xcd_handout.txt)
 	int geo_xcd = (static_cast<long long>(geo_tiles_x) * geo_tiles_y >= 32000) ? 1 : 0;
 	if (tuning().xcd_handout == 0 || tuning().xcd_handout == 1) geo_xcd = tuning().xcd_handout;
-	// The hand-out counts tickets in 32 bits (trace.hip: `my_tickets`, `base + want`).  The busiest counter owns a 1/8 share of the
-	// units -- groups of four chunks, or 256x256-pixel super-tiles of 4096 chunks -- times 16 tickets per chunk and, with (chunk,
-	// sample) items, per sample; every wave may overshoot a used-up counter once by up to 64.
-	auto tickets_fit = [&](bool sample_items) {
-		const long long tiles = static_cast<long long>(geo_tiles_x) * geo_tiles_y;
-		const long long per_chunk = 16ll * (sample_items ? std::max(fp->spp, 1) : 1);
-		long long share;
-		if (geo_xcd) {
-			const long long st = static_cast<long long>((geo_tiles_x + 15) / 16) * ((geo_tiles_y + 15) / 16);
-			share = ((st + 7) / 8) * 4096ll * per_chunk;
-		} else {
-			share = ((tiles * 4 + 7) / 8) * 4ll * per_chunk;
-		}
-		return share < (1ll << 30) - (1ll << 24); // (2^30: the hand-out divides ticket numbers with 30-bit-exact multiply-high constants)
-	};
+	// the ticket counters are 32 bits wide (tickets_fit, above): 16 tickets per chunk and, with (chunk, sample) items, per sample
+	auto tickets_fit = [&](bool sample_items) { return bm::tickets_fit(geo_tiles_x, geo_tiles_y, geo_xcd != 0, 16ll * (sample_items ? std::max(fp->spp, 1) : 1)); };
 	if (!tickets_fit((promoted.flags & BM_FLAG_SAMPLE_ITEMS) != 0)) { // what the caller asked for does not fit: refuse
 		set_error("frame too large for the 32-bit ticket counters: tiles x samples per launch (lower spp per call, or render row-band shards)");
 		return BM_EINVAL;
@@ -192,7 +212,16 @@ int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_
 		set(static_cast<uint32_t>(fc->band_rows), &fc->div_band_magic, &fc->div_band_shift);
 		set(static_cast<uint32_t>((fc->tiles_x + 15) / 16), &fc->div_st_x_magic, &fc->div_st_x_shift);
 	}
+	fc->ring_group = 1; // (a launch of one frame; Scene::render_frames sets the groups of a uniform launch)
 	return 0;
+}
+
+// the hand-out's division by the samples of a (chunk, sample) ticket group, times the frames of a group of a uniform launch
+void set_ring_group(FrameConstants* fc, int group, int frames) {
+	fc->ring_group = group;
+	fc->ring_groups_after = (frames + group - 1) / group - 1;
+	const uint32_t d = ((fc->flags & BM_FLAG_SAMPLE_ITEMS) ? static_cast<uint32_t>(std::max(fc->spp, 1)) : 1u) * static_cast<uint32_t>(group);
+	if (d <= 1u) { fc->div_samples_magic = 0u; fc->div_samples_shift = 0; } else division_magic(d, &fc->div_samples_magic, &fc->div_samples_shift);
 }
 
 } // namespace bm

@@ -1340,6 +1340,8 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 			fcs[0].ring_uniform = 1;
 			fcs[0].ring_sample_stride = static_cast<int>(sample_stride);
 			fcs[0].ring_pixel_stride = static_cast<uint32_t>(byte_stride / 16);
+			// ... and frames that add with float atomics are handed out several at a time (trace.hip "FRAME GROUPS")
+			set_ring_group(&fcs[0], ring_group_of(fcs[0], count), count);
 		}
 		if (shared_digest && !uniform) digest_ok = false;
 	}
@@ -1348,6 +1350,15 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 		// sample_base and its first-hit record is written once -- which only a uniform launch (one view, stepping sample_base) defines
 		set_error("bm_render_frames: ray-digest frames may share one hit-record buffer only in a uniform launch (one view and sun, sample_base stepping by a constant, one accumulation buffer)");
 		return BM_EINVAL;
+	}
+	if (shared_digest) {
+		// ... and that digest counts the pixel's rays of ALL the frames in 16 bits (word 6) and keys them with 24 bits of sample index
+		// counted from the first frame's sample_base: fill_frame_constants checked one frame's share of either
+		const long long sample_stride = fc.ring_sample_stride; // (a shared digest is a uniform launch; the entries' own sample_base all read like the first by now)
+		if (static_cast<long long>(count) * fc.spp * (fc.max_bounces + 1) >= 65536 || sample_stride * (count - 1) + fc.spp >= (1ll << 24)) {
+			set_error("bm_render_frames: ray-digest frames that share one hit-record buffer: frames x spp x segments < 65536 and sample_base stride x (frames - 1) + spp < 2^24 (the digest counts the launch's rays per pixel in 16 bits and keys them with 24 bits of sample)");
+			return BM_EINVAL;
+		}
 	}
 	{ // the kernel's hang guard is a 64-bit product (trace.hip round_budget): a launch for which it would wrap -- it would end before it has
 	  // traced anything -- is refused (such a launch is weeks of GPU time anyway)
@@ -1381,8 +1392,10 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 			waited = owner;
 		}
 	}
-	uint32_t* const work_counter = d_work_counter_ + static_cast<size_t>(first) * (kWorkCounterBytes / sizeof(uint32_t)); // one block per frame
-	BM_HIP(hipMemsetAsync(work_counter, 0, kWorkCounterBytes * static_cast<size_t>(count), stream)); // ticket counters of the persistent kernel
+	// (one block per frame; a uniform launch uses one per GROUP of frames, the first of them)
+	uint32_t* const work_counter = d_work_counter_ + static_cast<size_t>(first) * (kWorkCounterBytes / sizeof(uint32_t));
+	const int counter_blocks = fc.ring_uniform ? fc.ring_groups_after + 1 : count;
+	BM_HIP(hipMemsetAsync(work_counter, 0, kWorkCounterBytes * static_cast<size_t>(counter_blocks), stream)); // ticket counters of the persistent kernel
 	std::memcpy(h_frame_constants_ + first, fcs.data(), sizeof(FrameConstants) * static_cast<size_t>(count));
 	BM_HIP(hipMemcpyAsync(d_frame_constants_ + first, h_frame_constants_ + first, sizeof(FrameConstants) * static_cast<size_t>(count), hipMemcpyHostToDevice, stream));
 	BM_HIP(hipEventRecord(ev_start_[slot], stream));

@@ -27,9 +27,14 @@ inline int ring_refill_min(int single_frame_refill_min, bool helpers, int overri
 
 // tuning overrides from the environment (frame_plan.cpp tuning()): 0 / -1 = not set
 struct Tuning {
-	int refill_min = 0, xcd_handout = -1, helpers = -1, blocks_per_cu = 0;
+	int refill_min = 0, xcd_handout = -1, helpers = -1, blocks_per_cu = 0, ring_group = 0;
 };
 const Tuning& tuning();
+
+// the frames of a uniform launch are handed out in groups of this many (trace.hip "FRAME GROUPS"; frame_plan.cpp ring_group_of)
+constexpr int kRingGroup = 4, kMaxRingGroup = 64;
+int ring_group_of(const FrameConstants& fc, int frames); // the group size a uniform launch of `frames` such frames gets (1: frame after frame)
+void set_ring_group(FrameConstants* fc, int group, int frames); // ... written into the launch's first constants, with the hand-out's division by samples x group
 
 class Scene {
 public:

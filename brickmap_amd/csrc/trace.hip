@@ -170,11 +170,11 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 	// counter, round budget) is recomputed there.  The frame is an INDEX into the `__restrict__` array, never a pointer carried
 	// round the loop: only then does the compiler prove that the kernel's stores leave the constants alone (scalar loads).
 	const FrameConstants& fg = *fcp;     // what all frames of the launch share
-	int ring_pos = 0;                    // the frame of the launch this wave is in (RING; otherwise the constant 0)
+	int ring_pos = 0;                    // the frame of the launch this wave is in (RING; otherwise the constant 0) -- UNIFORM launches: the GROUP of frames (below)
 	constexpr bool kRing = RING != 0, kUniform = RING == 2;
 #define fc (fcp[RING == 1 ? ring_pos : 0])
-	// are there frames after the one this wave is in?  (uniform: the first entry knows how many follow IT)
-	auto more_frames = [&]() { return kUniform ? ring_pos < fg.frames_after : fc.frames_after > 0; };
+	// are there frames after the one this wave is in?  (uniform: the first entry knows how many GROUPS follow the first one)
+	auto more_frames = [&]() { return kUniform ? ring_pos < fg.ring_groups_after : fc.frames_after > 0; };
 	float4* accum = reinterpret_cast<float4*>(fc.accum);
 	uint32_t* dbg = DBG ? fc.dbg : nullptr;
 	__shared__ unsigned long long lds_brick[8 * 256]; // 16 KiB: one 64-byte brick per thread (traverse.h brick_dma_to_lds: word k of thread t at u32 word k * 256 + t)
@@ -188,7 +188,14 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 	// reference does (kernel.cu:319-322,341-343), so radiance is equal up to summation order.
 	const bool sample_items = (fg.flags & 4u) != 0u; // BM_FLAG_SAMPLE_ITEMS
 	constexpr uint32_t kParts = 16u / BM_ITEM_LANES; // tickets per chunk and sample
-	const uint32_t items_per_chunk = (sample_items ? static_cast<uint32_t>(fg.spp > 0 ? fg.spp : 1) : 1u) * kParts;
+	// FRAME GROUPS (uniform launches, FrameConstants::ring_group = F): the frames are dealt F at a time, and the item is (chunk, pixel
+	// part, frame of the group), exactly as (chunk, sample) items are dealt: consecutive tickets run through the F frames of one chunk,
+	// so a wave's 64 lanes trace 16 pixels x F frames -- to the kernel, F samples of the same pixels -- whose rays share field rows,
+	// index words and bricks and whose walks are of similar length, instead of 64 different pixels of one frame.  Every group has
+	// its own block of ticket counters, `ring_pos` counts groups, and everything the ring does at the end of a frame it does at the
+	// end of a group.  F > 1 only where an item is one sample of a pixel or all of them (frame_plan.cpp ring_group_of): then the
+	// ticket's middle field is the frame of the group where it is the sample otherwise, and one division serves both.
+	const uint32_t items_per_chunk = (sample_items ? static_cast<uint32_t>(fg.spp > 0 ? fg.spp : 1) : 1u) * (kUniform ? static_cast<uint32_t>(fg.ring_group) : 1u) * kParts;
 	const bool atomic_acc = HELP || sample_items; // other lanes may add to the pixel while this one holds it: add, never overwrite
 
 	// per-pixel state
@@ -342,10 +349,17 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 			const int rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(idle >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(idle), 0u));
 			if (state == ST_IDLE && rank < want * BM_ITEM_LANES) {
 				const uint32_t item = base + static_cast<uint32_t>(rank / BM_ITEM_LANES);
-				// items_per_chunk = samples x kParts: divide by the power of two first, then by the samples (a prepared constant)
+				// items_per_chunk = samples x kParts (x frames of a group): divide by the power of two first, then by the samples (a prepared constant)
 				static_assert((kParts & (kParts - 1u)) == 0u, "kParts is a power of two");
 				const uint32_t ticket = div_const(item / kParts, fg.div_samples_magic, fg.div_samples_shift), item_sub = item - ticket * items_per_chunk;
-				const uint32_t item_sample = item_sub / kParts, part = item_sub % kParts; // (kParts == 1: part 0)
+				uint32_t item_sample = item_sub / kParts;
+				const uint32_t part = item_sub % kParts; // (kParts == 1: part 0)
+				int item_frame = ring_at_refill; // (uniform launches: the lane's frame)
+				if (kUniform) {
+					const int group = fg.ring_group;
+					item_frame *= group;
+					if (group > 1) { item_frame += static_cast<int>(item_sample); item_sample = 0u; } // (grouped: the field is the frame of the group)
+				}
 				uint32_t k;
 				int tile_x, tile_y;
 				bool in_frame;
@@ -365,6 +379,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					tile_x = static_cast<int>(tile - static_cast<uint32_t>(tile_y) * static_cast<uint32_t>(fg.tiles_x));
 					in_frame = chunk < total_chunks;
 				}
+				if (kUniform) in_frame = in_frame && item_frame <= fg.frames_after; // (a short last group: its missing frames' items are dropped)
 				if (item < my_tickets && in_frame) {
 					const int cx = static_cast<int>((k & 1u) | ((k >> 1) & 2u)), cy = static_cast<int>(((k >> 1) & 1u) | ((k >> 2) & 2u));
 					const uint32_t q = part * BM_ITEM_LANES + (static_cast<uint32_t>(rank) % BM_ITEM_LANES); // pixel of the 4x4 chunk
@@ -379,9 +394,9 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 						s = sample_items ? static_cast<int>(item_sample) : 0;
 						s_end = sample_items ? s + 1 : fg.spp;
 						if (kUniform) { // the frame as an offset of the sample index and of the pixel record
-							const int sample_off = __mul24(ring_at_refill, fg.ring_sample_stride);
+							const int sample_off = __mul24(item_frame, fg.ring_sample_stride);
 							s += sample_off; s_end += sample_off;
-							local_pixel += static_cast<uint32_t>(ring_at_refill) * fg.ring_pixel_stride;
+							local_pixel += static_cast<uint32_t>(item_frame) * fg.ring_pixel_stride;
 						}
 						pstate = P_GEN;
 						state = ST_NEED;

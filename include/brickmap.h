@@ -434,7 +434,11 @@ BM_API int bm_render_frame(bm_scene* scene, const bm_camera* camera, const bm_fr
  * NULL or a hit-record buffer of its own (BM_FLAG_RAY_DIGEST frames of one view whose sample_base steps by a constant and that share
  * their accumulation buffer may also share ONE hit-record buffer: it then holds the digest of the whole launch, samples counted from
  * the first frame's sample_base -- for sample_base stepping by spp, the digest of one frame of count x spp samples).  Results of ordered
- * frames are bit-identical to `count` single launches.  Bricks
+ * frames are bit-identical to `count` single launches.  Production frames of one view whose sample_base and buffers step by
+ * constants (a resting camera accumulating) are handed out in GROUPS of bm_frame_plan.ring_group consecutive frames, whose lanes
+ * share a wave: such frames complete group by group rather than one after the other, and no frame of a group is complete before the
+ * launch is -- as with every launch, read results only after the launch has finished.  Ray-digest frames that share one hit-record
+ * buffer must keep count x spp x (max_bounces + 1) < 65536 and sample_base stride x (count - 1) + spp < 2^24 (BM_EINVAL otherwise).  Bricks
  * requested by any frame of the launch are serviced by the next bm_scene_process_load_queue.  bm_render_times /
  * bm_last_render_ms report the launch as one duration. */
 BM_API int bm_render_frames(bm_scene* scene, int count, const bm_camera* cameras, const bm_frame_params* params,
@@ -453,13 +457,15 @@ typedef struct bm_frame_plan {
 	int32_t refill_min_in_ring; /* ... when the frame is one of several of a bm_render_frames launch (later: its end is covered)     */
 	int32_t instrumented;  /* 1: the instrumented instantiation (hit records / BM_FLAG_COUNTERS) runs                             */
 	int32_t tiles_x, tiles_y, local_rows;
+	int32_t ring_group;    /* frames handed out together, as (chunk, pixel part, frame) items, when such frames make a uniform
+	                          bm_render_frames launch (one view, sample_base and buffers stepping by constants); 1: frame after frame */
 } bm_frame_plan;
 BM_API int bm_frame_plan_of(const bm_frame_params* params, int hit_records, bm_frame_plan* out);
 /* resident waves per SIMD of the trace_paths instantiation <instrumented, xcd_handout, helpers> on `device` (what the register
  * budget allows: hipOccupancyMaxActiveBlocksPerMultiprocessor of the 256-thread workgroup = one wave per SIMD each) */
 BM_API int bm_trace_waves_per_simd(int device, int instrumented, int xcd_handout, int helpers, int* waves);
 /* The tuning overrides this process runs under, as "NAME=value NAME=value" ("" when none is set): BM_REFILL_MIN,
- * BM_XCD_HANDOUT, BM_HELPERS, BM_TRACE_BLOCKS_PER_CU -- A/B knobs read from the environment once; a measurement should echo them. */
+ * BM_XCD_HANDOUT, BM_HELPERS, BM_TRACE_BLOCKS_PER_CU, BM_RING_GROUP -- A/B knobs read from the environment once; a measurement should echo them. */
 BM_API int bm_tuning_overrides(char* buf, size_t buflen);
 
 /* blit_onto_framebuffer (kernel.cu:348-364) into an offscreen float4 buffer: rgb/a, a=1, gamma 1/2.2 */
