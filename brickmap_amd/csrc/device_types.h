@@ -1,8 +1,34 @@
 // device_types.h -- kernel argument blocks shared by the host scene code and the HIP kernels.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
+#if defined(__HIPCC__)
+#define BM_VHD __host__ __device__ inline
+#else
+#define BM_VHD inline // world.cpp also builds with a plain host compiler (tools/sim)
+#endif
+
 namespace bm {
+
+// ---- the index word and a cell's place (the layout below), for host and device code: the one copy of each rule
+constexpr uint32_t kIndexBits = 0x00000FFFu; // BM_BRICK_INDEX_BITS: the brick's slot in its supercell's pool
+constexpr uint32_t kLoadedBit = 0x80000000u; // BM_BRICK_LOADED_BIT: the slot names a brick (world.h asserts both against brickmap.h)
+
+// The brick cell (cx, cy, cz) -- brick coordinates in the world, not negative: its supercell ...
+BM_VHD uint32_t supercell_of(int sg_xy, int sg_xy2, int cx, int cy, int cz) {
+	return static_cast<uint32_t>((cx >> 4) + (cy >> 4) * sg_xy + (cz >> 4) * sg_xy2);
+}
+// ... and the offset of its word in index_grid: supercell-major, word lx + 16 ly + 256 lz inside (64-bit additions, in this order)
+BM_VHD size_t index_word_at(int sg_xy, int sg_xy2, int cx, int cy, int cz) {
+	return static_cast<size_t>(supercell_of(sg_xy, sg_xy2, cx, cy, cz)) * 4096 + (cx & 15) + (cy & 15) * 16 + (cz & 15) * 256;
+}
+// its place among the 4096 words of its supercell: the same sum without a supercell
+BM_VHD uint32_t cell_local_index(int cx, int cy, int cz) { return static_cast<uint32_t>(index_word_at(0, 0, cx & 15, cy & 15, cz & 15)); }
+// offset of a brick's first word in the arena, from its supercell's pool_base entry and its index word
+BM_VHD size_t brick_first_word(uint32_t pool_base_value, uint32_t index_word) {
+	return (static_cast<size_t>(pool_base_value) + (index_word & kIndexBits)) << 4;
+}
 
 // Device view of the scene (the reference passes Scene::GPUScene by value, Scene.h:9-17).
 //

@@ -12,18 +12,11 @@
 // changed cells' bounding box grown by 254 cells on every side, clipped to the grid (FieldUpdate, kernels.h).
 #include <hip/hip_runtime.h>
 
+#include "global_mem.h"
 #include "kernels.h"
 
 namespace bm {
 namespace {
-
-// plain global-memory accesses: buffers named through a struct or computed addresses would otherwise be generic (flat_*) to the compiler
-typedef __attribute__((address_space(1))) uint32_t g_u32;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-__device__ __forceinline__ uint32_t ld32(const uint32_t* p, size_t i) { return ((const g_u32*)p)[i]; }
-__device__ __forceinline__ void st32(uint32_t* p, size_t i, uint32_t v) { ((g_u32*)p)[i] = v; }
-__device__ __forceinline__ uint32_t ld8(const uint8_t* p, size_t i) { return ((const g_u8*)p)[i]; }
-__device__ __forceinline__ void st8(uint8_t* p, size_t i, uint32_t v) { ((g_u8*)p)[i] = static_cast<uint8_t>(v); }
 
 constexpr int kFieldCap = 254; // largest cube edge the field stores (world.cpp)
 
@@ -40,6 +33,7 @@ __global__ void edit_scatter(const uint32_t* __restrict__ cells, const uint32_t*
 
 // is the brick cell at bordered coordinates (x, y, z) (1 ... cells) occupied, i.e. is its index word non-zero?
 __device__ __forceinline__ bool occupied(const uint32_t* index_grid, const FieldUpdate& u, int x, int y, int z) {
+	// index_word_at (device_types.h), written out: here the supercell is computed in 64 bits, and the pass is compiled from that
 	const uint32_t cx = x - 1, cy = y - 1, cz = z - 1;
 	const size_t sc = (cx >> 4) + (cy >> 4) * static_cast<size_t>(u.sg_xy) + (cz >> 4) * static_cast<size_t>(u.sg_xy2);
 	return ld32(index_grid, (sc << 12) + ((cx & 15) | ((cy & 15) << 4) | ((cz & 15) << 8))) != 0;

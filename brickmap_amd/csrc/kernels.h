@@ -1,10 +1,20 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip.
+// What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
+// (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
 
 namespace bm {
+// resident workgroups of `threads` threads per compute unit of a kernel, at least 1 (host code of the file that defines the kernel)
+template <class K>
+int resident_blocks_per_cu(K kernel, int threads = 256) {
+	int n = 0;
+	const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0);
+	return e == hipSuccess && n > 0 ? n : 1;
+}
+
 constexpr size_t kWorkCounterBytes = 64 * 32 * sizeof(uint32_t); // up to 64 chunk counters, one 128-byte line each
 int trace_blocks_per_cu(bool instrumented, bool xcd_handout, bool helpers, int ring = 0); // resident workgroups per CU of that instantiation (ring: 0 = a launch of one frame, 1 = of several, 2 = of several uniform ones)
 // blocks_per_cu_cap: 0 = as many workgroups per CU as the instantiation keeps resident; > 0 = at most that many (tuning runs)

@@ -10,36 +10,22 @@
 //              the host reads to size the arena
 //   pack     : a second read of the volume (brick rows without a brick are skipped); bricks go to arena[pool_base[sc] + slot]
 //
-// Shape of classify and pack: one workgroup per BRICK ROW -- the 16 brick cells of a supercell that share (by, bz).  Its voxels are
-// 64 x-rows (y, z = 0 ... 7) of 128 contiguous bytes each, so a lane's 16-byte load covers two bricks' rows and eight neighbouring
-// lanes cover one whole 128-byte line; a wave instruction requests eight full lines.  The row's 8 + 8 voxels become byte (y + 8 z) of
-// the two bricks (voxel_bits.h); the 16 bricks of the row are assembled in 1 KiB of LDS and leave it as 16 lanes x 4 bytes per brick.
+// Shape of classify and pack: one workgroup per BRICK ROW -- the 16 brick cells of a supercell that share (by, bz) -- read as 512
+// chunks of 16 bytes and assembled in 1 KiB of LDS (brick_rows.h).
 // Temporary device memory: 4 bytes per supercell (the counts) and 8 bytes for the total; the cube-field passes that follow
 // (edit.hip) take their 6 bytes per brick cell.
 #include <hip/hip_runtime.h>
 
+#include "brick_rows.h"
 #include "kernels.h"
-#include "voxel_bits.h"
 
 namespace bm {
 namespace {
 
-// plain global-memory accesses (see edit.hip)
-typedef __attribute__((address_space(1))) uint32_t g_u32;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-__device__ __forceinline__ uint32_t ld32(const uint32_t* p, size_t i) { return ((const g_u32*)p)[i]; }
-__device__ __forceinline__ void st32(uint32_t* p, size_t i, uint32_t v) { ((g_u32*)p)[i] = v; }
-__device__ __forceinline__ u32x4 ld128(const void* p, size_t byte) { return *(const g_u32x4*)((const g_u8*)p + byte); }
-__device__ __forceinline__ void st128(void* p, size_t byte, u32x4 v) { *(g_u32x4*)((g_u8*)p + byte) = v; }
 __device__ __forceinline__ uint32_t ld8x4(const uint8_t* p, size_t byte) { // four bytes of an unaligned volume, as the little-endian word
 	const g_u8* q = (const g_u8*)p + byte;
 	return q[0] | (static_cast<uint32_t>(q[1]) << 8) | (static_cast<uint32_t>(q[2]) << 16) | (static_cast<uint32_t>(q[3]) << 24);
 }
-
-constexpr uint32_t kLoaded = 0x80000000u; // BM_BRICK_LOADED_BIT
-constexpr uint32_t kSlotBits = 0xFFFu;    // BM_BRICK_INDEX_BITS
 
 // The workgroup's brick row (blockIdx.x = supercell * 256 + bz * 16 + by) -> rows[256]: word t = word (t & 15) of brick (t >> 4).
 // ALIGNED: the volume starts on a 16-byte boundary (every row then does: grid_size is a multiple of 128).
@@ -51,14 +37,14 @@ __device__ __forceinline__ void read_brick_row(const uint8_t* __restrict__ vox, 
 	uint8_t* bytes = reinterpret_cast<uint8_t*>(rows);
 #pragma unroll
 	for (int h = 0; h < 2; ++h) {
-		const uint32_t i = threadIdx.x + 256 * h; // 512 chunks of 16 bytes: x-row (i >> 3), chunk (i & 7) of its 128 bytes
-		const uint32_t r = i >> 3, k = i & 7, y = r & 7, z = r >> 3;
-		const size_t at = (static_cast<size_t>(sz * 128 + bz * 8 + z) * g + (sy * 128 + by * 8 + y)) * g + sx * 128 + 16 * k;
+		const RowChunk c = row_chunk(threadIdx.x + 256 * h);
+		const size_t at = (static_cast<size_t>(sz * 128 + bz * 8 + c.z()) * g + (sy * 128 + by * 8 + c.y())) * g + sx * 128 + 16 * c.k;
 		u32x4 v;
 		if (ALIGNED) v = ld128(vox, at);
 		else { v.x = ld8x4(vox, at); v.y = ld8x4(vox, at + 4); v.z = ld8x4(vox, at + 8); v.w = ld8x4(vox, at + 12); }
-		bytes[(2 * k) * 64 + r] = static_cast<uint8_t>(brick_row_bits(v.x, v.y));
-		bytes[(2 * k + 1) * 64 + r] = static_cast<uint8_t>(brick_row_bits(v.z, v.w));
+		// stage_chunk (brick_rows.h), written out: through the call load_pack is compiled with the operands of one OR exchanged
+		bytes[(2 * c.k) * 64 + c.r] = static_cast<uint8_t>(brick_row_bits(v.x, v.y));
+		bytes[(2 * c.k + 1) * 64 + c.r] = static_cast<uint8_t>(brick_row_bits(v.z, v.w));
 	}
 	__syncthreads();
 }
@@ -102,7 +88,7 @@ __global__ __launch_bounds__(256) void load_number(uint32_t* __restrict__ index_
 	uint32_t slot = inc - mine;
 	for (uint32_t v = 0; v < wave; ++v) slot += wave_total[v];
 	if (threadIdx.x == 255) st32(counts, blockIdx.x, slot + mine);
-#define BM_NUMBER(v) if (v) { (v) |= slot | kLoaded; ++slot; }
+#define BM_NUMBER(v) if (v) { (v) |= slot | kLoadedBit; ++slot; }
 	BM_EACH_WORD(BM_NUMBER)
 #undef BM_NUMBER
 #undef BM_EACH_WORD
@@ -137,7 +123,8 @@ __global__ __launch_bounds__(256) void load_pack(const uint8_t* __restrict__ vox
 	const uint32_t iw = ld32(index_grid, static_cast<size_t>(blockIdx.x) * 16 + (threadIdx.x >> 4));
 	if (!__syncthreads_or(iw != 0)) return; // no brick in this row: nothing to read
 	read_brick_row<ALIGNED>(vox, d, rows);
-	if (iw) st32(arena, (static_cast<size_t>(ld32(pool_base, blockIdx.x >> 8) + (iw & kSlotBits)) << 4) + (threadIdx.x & 15), rows[threadIdx.x]);
+	// brick_first_word (device_types.h), written out: base and slot are added in 32 bits here, as in the walk (traverse.h)
+	if (iw) st32(arena, (static_cast<size_t>(ld32(pool_base, blockIdx.x >> 8) + (iw & kIndexBits)) << 4) + (threadIdx.x & 15), rows[threadIdx.x]);
 }
 
 } // namespace

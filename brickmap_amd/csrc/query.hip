@@ -168,10 +168,7 @@ __global__ __launch_bounds__(256, BM_QUERY_WAVES) void query_rays(const DeviceSc
 
 // ---- host-callable launchers (kernels.h)
 int query_blocks_per_cu(bool request) {
-	int n = 0;
-	const hipError_t e = request ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, query_rays<true>, 256, 0)
-								 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, query_rays<false>, 256, 0);
-	return e == hipSuccess && n > 0 ? n : 1;
+	return request ? resident_blocks_per_cu(query_rays<true>) : resident_blocks_per_cu(query_rays<false>);
 }
 
 void launch_query(const DeviceScene& sc, const int campos[3], const void* rays, void* hits, uint32_t n, uint32_t* ticket, int resident_blocks,

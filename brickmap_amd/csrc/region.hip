@@ -8,32 +8,18 @@
 //   patch  : a list of (cell, brick) pairs -> the box's part of those cells (the bricks a streaming scene does not hold on the device)
 //   zero   : a sub-box of the volume set to 0 (the parts of a read that lie outside the world)
 //
-// Shape of pack and unpack, as in load.hip: one workgroup per run of 16 brick cells along x that starts at a multiple of 128 voxels,
-// i.e. 64 x-rows (y, z = 0 ... 7) of 128 bytes; a lane owns 16-byte chunks that start at multiples of 16 voxels, so a chunk is the
-// rows of two bricks and eight neighbouring lanes cover a 128-byte line.  ALIGNED: V[0][0][0] lies at a world x that is a multiple of
-// 16 and the base and both pitches are multiples of 16 bytes, so every chunk is a 16-byte aligned address: chunks wholly inside the box
-// move as one 16-byte access, the (at most two per row) partial ones byte by byte.  The general instantiation moves every chunk byte
-// by byte.  Nothing outside the box is read or written.  The bricks of a run pass through 1 KiB of LDS.
+// Shape of pack and unpack: one workgroup per run of 16 brick cells along x that starts at a multiple of 128 voxels, moved as 512
+// chunks of 16 bytes through 1 KiB of LDS (brick_rows.h).  ALIGNED: V[0][0][0] lies at a world x that is a multiple of 16 and the base
+// and both pitches are multiples of 16 bytes, so every chunk is a 16-byte aligned address: chunks wholly inside the box move as one
+// 16-byte access, the (at most two per row) partial ones byte by byte.  The general instantiation moves every chunk byte by byte.
+// Nothing outside the box is read or written.
 #include <hip/hip_runtime.h>
 
+#include "brick_rows.h"
 #include "kernels.h"
-#include "voxel_bits.h"
 
 namespace bm {
 namespace {
-
-// plain global-memory accesses (see edit.hip)
-typedef __attribute__((address_space(1))) uint32_t g_u32;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-__device__ __forceinline__ uint32_t ld32(const uint32_t* p, size_t i) { return ((const g_u32*)p)[i]; }
-__device__ __forceinline__ void st32(uint32_t* p, size_t i, uint32_t v) { ((g_u32*)p)[i] = v; }
-__device__ __forceinline__ u32x4 ld128(const void* p, int64_t byte) { return *(const g_u32x4*)((const g_u8*)p + byte); }
-__device__ __forceinline__ void st128(void* p, int64_t byte, u32x4 v) { *(g_u32x4*)((g_u8*)p + byte) = v; }
-
-constexpr uint32_t kLoaded = 0x80000000u; // BM_BRICK_LOADED_BIT
-constexpr uint32_t kSlotBits = 0xFFFu;    // BM_BRICK_INDEX_BITS
 
 // four voxel bytes at world x ... x + 3 of a row (at = the volume offset of world x), those outside [x0, x1) read as 0 and are not touched
 __device__ __forceinline__ uint32_t ld_bytes(const uint8_t* p, int64_t at, int x, int x0, int x1) {
@@ -51,19 +37,18 @@ __device__ __forceinline__ void st_bytes(uint8_t* p, int64_t at, int x, int x0, 
 		if (x + j >= x0 && x + j < x1) q[j] = static_cast<uint8_t>(v >> (8 * j));
 }
 
-// chunk i (0 ... 511) of the workgroup's run: x-row r = i >> 3 (y = r & 7, z = r >> 3), bytes 16 k ... 16 k + 15 of its 128 (k = i & 7)
+// a chunk of the workgroup's run (brick_rows.h) in the world and in the volume
 struct Chunk {
-	uint32_t r, k;
+	RowChunk rc;
 	int x;         // world x of its first voxel
 	bool row;      // the row lies in the box
 	int64_t at;    // volume offset of world voxel (x, y, z)
 };
 __device__ __forceinline__ Chunk chunk_of(const RegionDims& d, uint32_t i) {
 	Chunk c;
-	c.r = i >> 3;
-	c.k = i & 7;
-	const int y = (d.c0[1] + static_cast<int>(blockIdx.y)) * 8 + static_cast<int>(c.r & 7), z = (d.c0[2] + static_cast<int>(blockIdx.z)) * 8 + static_cast<int>(c.r >> 3);
-	c.x = (d.g0 + static_cast<int>(blockIdx.x)) * 128 + 16 * static_cast<int>(c.k);
+	c.rc = row_chunk(i);
+	const int y = (d.c0[1] + static_cast<int>(blockIdx.y)) * 8 + static_cast<int>(c.rc.y()), z = (d.c0[2] + static_cast<int>(blockIdx.z)) * 8 + static_cast<int>(c.rc.z());
+	c.x = (d.g0 + static_cast<int>(blockIdx.x)) * 128 + 16 * static_cast<int>(c.rc.k);
 	c.row = y >= d.lo[1] && y < d.hi[1] && z >= d.lo[2] && z < d.hi[2];
 	c.at = (static_cast<int64_t>(z) - d.org[2]) * d.slice_pitch + (static_cast<int64_t>(y) - d.org[1]) * d.row_pitch + (static_cast<int64_t>(c.x) - d.org[0]);
 	return c;
@@ -78,8 +63,7 @@ __device__ __forceinline__ int64_t box_cell(const RegionDims& d, uint32_t t) {
 
 template <bool ALIGNED>
 __global__ __launch_bounds__(256) void region_pack(const uint8_t* __restrict__ vox, uint32_t* __restrict__ bricks, const RegionDims d) {
-	__shared__ uint32_t rows[256]; // word t = word (t & 15) of brick (t >> 4)
-	uint8_t* bytes = reinterpret_cast<uint8_t*>(rows);
+	__shared__ uint32_t rows[256];
 #pragma unroll
 	for (int h = 0; h < 2; ++h) {
 		const Chunk c = chunk_of(d, threadIdx.x + 256 * h);
@@ -93,8 +77,7 @@ __global__ __launch_bounds__(256) void region_pack(const uint8_t* __restrict__ v
 				v.w = ld_bytes(vox, c.at + 12, c.x + 12, d.lo[0], d.hi[0]);
 			}
 		}
-		bytes[(2 * c.k) * 64 + c.r] = static_cast<uint8_t>(brick_row_bits(v.x, v.y));
-		bytes[(2 * c.k + 1) * 64 + c.r] = static_cast<uint8_t>(brick_row_bits(v.z, v.w));
+		stage_chunk(rows, c.rc, v);
 	}
 	__syncthreads();
 	const int64_t cell = box_cell(d, threadIdx.x);
@@ -110,22 +93,20 @@ __global__ __launch_bounds__(256) void region_unpack(uint8_t* __restrict__ vox, 
 		if (box_cell(d, threadIdx.x) >= 0) { // a cell of the clipped box: inside the world
 			const uint32_t cx = static_cast<uint32_t>(d.g0 + static_cast<int>(blockIdx.x)) * 16 + (threadIdx.x >> 4), cy = static_cast<uint32_t>(d.c0[1]) + blockIdx.y,
 						   cz = static_cast<uint32_t>(d.c0[2]) + blockIdx.z;
+			// supercell_of and index_word_at (device_types.h), written out: through them the run's supercell is no longer found to be the
+			// same for the whole workgroup, and the kernel computes it per lane
 			const uint32_t sc = (cx >> 4) + (cy >> 4) * d.sg_xy + (cz >> 4) * d.sg_xy2;
 			const uint32_t iw = ld32(index_grid, static_cast<size_t>(sc) * 4096 + (cx & 15) + (cy & 15) * 16 + (cz & 15) * 256);
-			if (iw & kLoaded) word = ld32(arena, ((static_cast<size_t>(ld32(pool_base, sc)) + (iw & kSlotBits)) << 4) + (threadIdx.x & 15));
+			if (iw & kLoadedBit) word = ld32(arena, brick_first_word(ld32(pool_base, sc), iw) + (threadIdx.x & 15));
 		}
 		rows[threadIdx.x] = word;
 	}
 	__syncthreads();
-	const uint8_t* bytes = reinterpret_cast<const uint8_t*>(rows);
 #pragma unroll
 	for (int h = 0; h < 2; ++h) {
 		const Chunk c = chunk_of(d, threadIdx.x + 256 * h);
 		if (!(c.row && c.x < d.hi[0] && c.x + 16 > d.lo[0])) continue;
-		uint32_t a, b, e, f;
-		brick_row_bytes(bytes[(2 * c.k) * 64 + c.r], &a, &b);
-		brick_row_bytes(bytes[(2 * c.k + 1) * 64 + c.r], &e, &f);
-		const u32x4 v = {a, b, e, f};
+		const u32x4 v = staged_chunk(rows, c.rc);
 		if (ALIGNED && c.x >= d.lo[0] && c.x + 16 <= d.hi[0]) st128(vox, c.at, v);
 		else {
 			st_bytes(vox, c.at, c.x, d.lo[0], d.hi[0], v.x);
@@ -141,8 +122,7 @@ __global__ __launch_bounds__(256) void region_patch(uint8_t* __restrict__ vox, c
 													const RegionDims d) {
 	const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6), r = threadIdx.x & 63;
 	if (i >= count) return;
-	const int x = ((const __attribute__((address_space(1))) int*)cells)[3 * i] * 8, y = ((const __attribute__((address_space(1))) int*)cells)[3 * i + 1] * 8 + static_cast<int>(r & 7),
-			  z = ((const __attribute__((address_space(1))) int*)cells)[3 * i + 2] * 8 + static_cast<int>(r >> 3);
+	const int x = ldi32(cells, 3 * i) * 8, y = ldi32(cells, 3 * i + 1) * 8 + static_cast<int>(r & 7), z = ldi32(cells, 3 * i + 2) * 8 + static_cast<int>(r >> 3);
 	if (!(y >= d.lo[1] && y < d.hi[1] && z >= d.lo[2] && z < d.hi[2])) return;
 	const uint32_t word = ld32(bricks, static_cast<size_t>(i) * 16 + (r >> 2));
 	uint32_t a, b;

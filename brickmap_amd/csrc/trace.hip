@@ -863,11 +863,7 @@ __global__ void debug_sky_kernel(const FrameConstants fc, int n, const float* __
 // resident 256-thread workgroups per compute unit of one instantiation (asked once per instantiation)
 template <bool DBG, bool XCD, bool HELP, int RING>
 static int occupancy_of() {
-	static const int cached = [] {
-		int n = 0;
-		const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_paths<DBG, XCD, HELP, RING>, 256, 0);
-		return e == hipSuccess && n > 0 ? n : 1;
-	}();
+	static const int cached = resident_blocks_per_cu(trace_paths<DBG, XCD, HELP, RING>);
 	return cached;
 }
 // run `f` with the four instantiation choices as compile-time constants (ring: 0 = one frame, 1 = frame ring, 2 = uniform frame ring)

@@ -16,9 +16,7 @@ namespace {
 
 constexpr float kPi = 3.1415926535897932f;       // variables.h:3
 constexpr float kEpsilon = 0.001f;               // variables.h:22
-constexpr uint32_t kIndexBits = 0xFFFu;          // variables.h:29-33
-constexpr uint32_t kLodBits = 0xFF000u;
-constexpr uint32_t kLoadedBit = 0x80000000u;
+constexpr uint32_t kLodBits = 0xFF000u;          // variables.h:29-33; kIndexBits and kLoadedBit: device_types.h
 constexpr uint32_t kUnloadedBit = 0x40000000u;
 constexpr uint32_t kRequestedBit = 0x20000000u;
 
@@ -465,6 +463,7 @@ __device__ __forceinline__ int process_candidate(const DeviceScene& sc, const in
 	const int sx = r.sx, sy = step_sign(r.stepy), sz = step_sign(r.stepz); // step signs back from the offset increments
 	// inside the grid 0 <= pos < cells, so >>4 and &15 equal the reference's signed /16 and %16
 	// (24-bit multiplies: all operands are far below 2^24; a 32-bit v_mul_lo_u32 issues at a quarter of the rate)
+	// index_word_at (device_types.h), specialised: the supercell id is kept for the pool base
 	const uint32_t sci = static_cast<uint32_t>((px >> 4) + __mul24(py >> 4, sc.sg_xy) + __mul24(pz >> 4, sc.sg_xy2));
 	const uint32_t flat = (sci << 12) + static_cast<uint32_t>((px & 15) + ((py & 15) << 4) + ((pz & 15) << 8));
 	// the reference's addressing (voxel.cuh:222): pool of the supercell + the 12-bit slot carried by the index word.  The

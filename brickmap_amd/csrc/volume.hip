@@ -22,6 +22,7 @@
 
 #include <climits>
 
+#include "global_mem.h"
 #include "kernels.h"
 #include "voxel_bits.h"
 
@@ -33,20 +34,6 @@ namespace bm {
 
 namespace {
 
-// plain global-memory accesses (see edit.hip)
-typedef __attribute__((address_space(1))) uint32_t g_u32;
-typedef __attribute__((address_space(1))) int g_i32;
-typedef __attribute__((address_space(1))) uint64_t g_u64;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-__device__ __forceinline__ uint32_t ld32(const uint32_t* p, size_t i) { return ((const g_u32*)p)[i]; }
-__device__ __forceinline__ void st32(uint32_t* p, size_t i, uint32_t v) { ((g_u32*)p)[i] = v; }
-__device__ __forceinline__ uint64_t ld64(const uint64_t* p, size_t i) { return ((const g_u64*)p)[i]; }
-__device__ __forceinline__ void st64(uint64_t* p, size_t i, uint64_t v) { ((g_u64*)p)[i] = v; }
-
-constexpr uint32_t kLoaded = 0x80000000u; // BM_BRICK_LOADED_BIT
-constexpr uint32_t kSlotBits = 0xFFFu;    // BM_BRICK_INDEX_BITS
 constexpr int kBox = 1, kSphere = 2;      // BM_EDIT_BOX, BM_EDIT_SPHERE
 constexpr int kRecordWords = 12, kResultWords = 10; // bm_volume, bm_volume_result
 
@@ -61,17 +48,17 @@ struct Shape {
 };
 
 __device__ __forceinline__ Shape load_shape(const int* __restrict__ volumes, size_t i, int size, int height) {
-	const g_i32* p = (const g_i32*)volumes + i * kRecordWords;
+	const auto p = [&](int k) { return ldi32(volumes, i * kRecordWords + k); };
 	Shape s;
-	const int shape = p[0];
-	s.radius = p[10];
+	const int shape = p(0);
+	s.radius = p(10);
 	s.sphere = shape == kSphere;
-	s.ok = (shape == kBox || shape == kSphere) && p[11] == 0 && !(s.sphere && s.radius < 0);
+	s.ok = (shape == kBox || shape == kSphere) && p(11) == 0 && !(s.sphere && s.radius < 0);
 	bool inside = s.ok;
 #pragma unroll
 	for (int k = 0; k < 3; ++k) {
-		s.c[k] = p[7 + k];
-		long long a = p[1 + k], b = p[4 + k];
+		s.c[k] = p(7 + k);
+		long long a = p(1 + k), b = p(4 + k);
 		if (!s.sphere && b < a) { s.ok = false; inside = false; }
 		if (s.sphere) { a = static_cast<long long>(s.c[k]) - s.radius; b = static_cast<long long>(s.c[k]) + s.radius + 1; }
 		const long long top = k == 2 ? height : size;
@@ -209,7 +196,7 @@ __global__ __launch_bounds__(256, BM_VOLUME_WAVES) void volume_count(const Devic
 			const int cy = (s.lo[1] >> 3) + static_cast<int>(q % s.ncy), cz = (s.lo[2] >> 3) + static_cast<int>(q / s.ncy);
 			const int cc[3] = {cx, cy, cz};
 			if (cx >= (s.lo[0] >> 3) && cx <= ((s.hi[0] - 1) >> 3) &&
-				((const g_u8*)sc.cube_field)[static_cast<size_t>(cz + 1) * sc.cf_pxy + (static_cast<size_t>(cy + 1) << sc.cf_shift) + static_cast<size_t>(cx + 1)] == 0) {
+				ld8(sc.cube_field, static_cast<size_t>(cz + 1) * sc.cf_pxy + (static_cast<size_t>(cy + 1) << sc.cf_shift) + static_cast<size_t>(cx + 1)) == 0) {
 				// the clipped shape's part of the cell: [v0, v1) per axis, in voxels of the cell
 				int v0[3], v1[3];
 				uint64_t near2 = 0, far2 = 0;
@@ -225,19 +212,18 @@ __global__ __launch_bounds__(256, BM_VOLUME_WAVES) void volume_count(const Devic
 					}
 				}
 				if (!s.sphere || near2 <= r2) { // the shape has a voxel in the cell
-					const uint32_t scell = static_cast<uint32_t>((cx >> 4) + (cy >> 4) * sc.sg_xy + (cz >> 4) * sc.sg_xy2);
-					const uint32_t iw = ld32(sc.index_grid, static_cast<size_t>(scell) * 4096 + (cx & 15) + (cy & 15) * 16 + (cz & 15) * 256);
-					if (!(iw & kLoaded)) {
+					const uint32_t iw = ld32(sc.index_grid, index_word_at(sc.sg_xy, sc.sg_xy2, cx, cy, cz));
+					if (!(iw & kLoadedBit)) {
 						unres = 1;
 					} else {
-						const g_u32x4* brick = (const g_u32x4*)sc.brick_arena + ((static_cast<size_t>(ld32(sc.pool_base, scell)) + (iw & kSlotBits)) << 2);
+						const size_t brick = brick_first_word(ld32(sc.pool_base, supercell_of(sc.sg_xy, sc.sg_xy2, cx, cy, cz)), iw);
 						uint32_t or_even = 0, or_odd = 0, zbits = 0; // the covered solid bits of words 0, 2, ... (y 0-3) and 1, 3, ... (y 4-7); slices that hold one
 						if (!s.sphere || far2 <= r2) {
 							const uint32_t xm = bit_range(v0[0], v1[0]), ym = bit_range(v0[1], v1[1]), zm = bit_range(v0[2], v1[2]);
 							const uint32_t even = bits4_to_bytes(ym) * xm, odd = bits4_to_bytes(ym >> 4) * xm;
 							u32x4 v[4];
 #pragma unroll
-							for (int h = 0; h < 4; ++h) v[h] = brick[h];
+							for (int h = 0; h < 4; ++h) v[h] = ld128(sc.brick_arena, (brick + 4 * h) * sizeof(uint32_t));
 #pragma unroll
 							for (int h = 0; h < 4; ++h) {
 								const uint32_t m0 = (zm >> (2 * h)) & 1u ? 0xFFFFFFFFu : 0u, m1 = (zm >> (2 * h + 1)) & 1u ? 0xFFFFFFFFu : 0u;
@@ -251,7 +237,6 @@ __global__ __launch_bounds__(256, BM_VOLUME_WAVES) void volume_count(const Devic
 							// voxel (x, y, z) of the cell lies at e + (x, y, z) from the centre: (e0 + x)^2 + (e1 + y)^2 + (e2 + z)^2 <= r^2  <=>
 							// x (2 e0 + x) + y (2 e1 + y) + z (2 e2 + z) <= room, room = r^2 - |e|^2
 							const long long e0 = 8ll * cx - s.c[0], e1 = 8ll * cy - s.c[1], e2 = 8ll * cz - s.c[2];
-							const g_u32* words = (const g_u32*)brick;
 							const long long lim = 1ll << 24;
 							const bool small = e0 > -lim && e0 < lim && e1 > -lim && e1 < lim && e2 > -lim && e2 < lim;
 #pragma unroll 1
@@ -274,7 +259,7 @@ __global__ __launch_bounds__(256, BM_VOLUME_WAVES) void volume_count(const Devic
 									for (int b = 0; b < 32; ++b)
 										m |= (sq(e0 + (b & 7)) + sq(e1 + 4 * (w & 1) + (b >> 3)) + sq(e2 + (w >> 1)) <= r2 ? 1u : 0u) << b;
 								}
-								m &= words[w];
+								m &= ld32(sc.brick_arena, brick + w);
 								cnt += __popc(m);
 								if (w & 1) or_odd |= m; else or_even |= m;
 								zbits |= (m != 0 ? 1u : 0u) << (w >> 1);
@@ -354,10 +339,7 @@ __global__ __launch_bounds__(256) void volume_finish(uint32_t* __restrict__ resu
 } // namespace
 
 int volume_blocks_per_cu(bool any) {
-	int n = 0;
-	const hipError_t e = any ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, volume_count<true>, 256, 0)
-							 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, volume_count<false>, 256, 0);
-	return e == hipSuccess && n > 0 ? n : 1;
+	return any ? resident_blocks_per_cu(volume_count<true>) : resident_blocks_per_cu(volume_count<false>);
 }
 
 size_t volume_tmp_bytes(uint32_t n) { return (static_cast<size_t>(n) + (n + 255) / 256 + 1) * sizeof(uint64_t); }

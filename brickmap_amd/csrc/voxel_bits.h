@@ -1,14 +1,10 @@
 // voxel_bits.h -- dense voxels (one byte each, non-zero = solid) <-> brick bits; shared by the host routes (world.cpp) and the device
-// routes (load.hip, region.hip) of bm_scene_load_voxels, bm_scene_write_region and bm_scene_read_region, so that all of them pack and
+// routes (load.hip and region.hip through brick_rows.h, volume.hip) of bm_scene_load_voxels, bm_scene_write_region and bm_scene_read_region, so that all of them pack and
 // unpack a row of voxels with the same arithmetic.
 #pragma once
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define BM_VHD __host__ __device__ inline
-#else
-#define BM_VHD inline // world.cpp also builds with a plain host compiler (tools/sim)
-#endif
+#include "device_types.h" // BM_VHD
 
 namespace bm {
 

@@ -519,13 +519,8 @@ __global__ __launch_bounds__(1024) void wf_scan(uint2* __restrict__ block_counts
 
 // ---- host-callable launchers (kernels.h)
 int wavefront_blocks_per_cu(bool connect, bool instrumented) {
-	int n = 0;
-	hipError_t e;
-	if (connect) e = instrumented ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, BM_WF_TRACE<true, true>, 256, 0)
-								  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, BM_WF_TRACE<true, false>, 256, 0);
-	else e = instrumented ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, BM_WF_TRACE<false, true>, 256, 0)
-						  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, BM_WF_TRACE<false, false>, 256, 0);
-	return e == hipSuccess && n > 0 ? n : 1;
+	if (connect) return instrumented ? resident_blocks_per_cu(BM_WF_TRACE<true, true>) : resident_blocks_per_cu(BM_WF_TRACE<true, false>);
+	return instrumented ? resident_blocks_per_cu(BM_WF_TRACE<false, true>) : resident_blocks_per_cu(BM_WF_TRACE<false, false>);
 }
 
 void launch_wf_primary(WfState* st, WfRay* work, const FrameConstants* fc_dev, uint32_t queue_size, uint32_t pixels, hipStream_t stream) {

@@ -163,7 +163,7 @@ void World::build_supercell(int sx, int sy, int sz, const float* heights) {
 				}
 				cell.bricks.push_back(brick);
 				cell.indices[bx + by * kSupercell + bz * kSupercell * kSupercell] =
-					static_cast<uint32_t>(cell.bricks.size() - 1) | 0x80000000u | (lod << 12); // Scene.cpp:104
+					static_cast<uint32_t>(cell.bricks.size() - 1) | BM_BRICK_LOADED_BIT | (lod << 12); // Scene.cpp:104
 			}
 	}
 }
@@ -390,13 +390,13 @@ void World::edit_supercell(const WorldDims& dims, HostSupercell& c, int sx, int 
 								c.bricks.emplace_back();
 							}
 							std::memset(c.bricks[slot].data, 0, sizeof(Brick));
-							word = slot | 0x80000000u;
+							word = slot | BM_BRICK_LOADED_BIT;
 						}
-						Brick& b = c.bricks[word & 0xFFFu];
+						Brick& b = c.bricks[word & BM_BRICK_INDEX_BITS];
 						for (int w = 0; w < kBrickWords; ++w) b.data[w] |= mask[w];
-						word = (word & 0xFFFu) | 0x80000000u | (brick_lod(b) << 12); // Scene.cpp:104
+						word = (word & BM_BRICK_INDEX_BITS) | BM_BRICK_LOADED_BIT | (brick_lod(b) << 12); // Scene.cpp:104
 					} else {
-						const uint32_t slot = word & 0xFFFu;
+						const uint32_t slot = word & BM_BRICK_INDEX_BITS;
 						Brick& b = c.bricks[slot];
 						uint32_t left = 0;
 						for (int w = 0; w < kBrickWords; ++w) left |= (b.data[w] &= ~mask[w]);
@@ -404,7 +404,7 @@ void World::edit_supercell(const WorldDims& dims, HostSupercell& c, int sx, int 
 							c.free_slots.push_back(slot);
 							word = 0;
 						} else {
-							word = slot | 0x80000000u | (brick_lod(b) << 12);
+							word = slot | BM_BRICK_LOADED_BIT | (brick_lod(b) << 12);
 						}
 					}
 				}

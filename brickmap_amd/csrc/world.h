@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/brickmap.h"
+#include "device_types.h" // the index word and a cell's place: kIndexBits, kLoadedBit, cell_local_index
 
 namespace bm {
 
@@ -45,10 +46,7 @@ struct WorldDims {
 	bool set(int grid_size_, int grid_height_);
 	int supercell_id(int sx, int sy, int sz) const { return sx + sy * supergrid_xy + sz * supergrid_xy * supergrid_xy; }
 };
-// index of the brick cell (px, py, pz) -- brick coordinates in the world -- among the 4096 words of its supercell
-inline uint32_t cell_local_index(int px, int py, int pz) {
-	return static_cast<uint32_t>((px % kSupercell) + (py % kSupercell) * kSupercell + (pz % kSupercell) * kSupercell * kSupercell);
-}
+static_assert(kIndexBits == BM_BRICK_INDEX_BITS && kLoadedBit == BM_BRICK_LOADED_BIT, "device_types.h and brickmap.h name one index word");
 
 // 2-D simplex noise + fBm exactly as the reference's terrain uses it (SimplexNoise.cpp:216-292,
 // 435-450 with SimplexNoise(1,1,2,0.5), Scene.cpp:45,53).  Pure fp32, no contraction.
