@@ -1,0 +1,87 @@
+// steps.h -- the two innermost bodies of the walk, in the form the kernels run them: one Amanatides-Woo move (src/voxel.cuh:122-130,
+// 249-258) and the packed cell of the 8^3 / 2^3 brick walk with its occupancy test; and what a byte of the cube field means.
+// Plain C++ (host + device) like jump.h: tests/step_check.cpp replays these very functions against a literal transcription of the
+// reference's move and cell arithmetic.
+//
+// The move stays in compare / select form.  Its mask form (0 / -1 masks from the sign of fp32 differences, `bits(tdelta) & mask`,
+// (sx & mx) | (sy & my) | (sz & mz)) is bit-identical on its domain but not faster: the brick loop is a chain of dependent
+// instructions around one LDS read and the mask form makes that chain longer, the single move waits for its cube-field byte either
+// way (tools/variants/mask_moves.patch, profiles/r07_inner_steps.txt).
+#pragma once
+#include "jump.h"
+
+namespace bm {
+
+// The reference's choice of the axis (ties: z before y before x); exactly one flag is set.  Any fp32 input: a NaN compares false,
+// -0 equals +0.
+struct StepAxis {
+	bool x, y, z;
+};
+BM_JHD StepAxis step_choose(float tx, float ty, float tz) {
+	StepAxis m;
+	m.x = tx < ty && tx < tz;
+	m.y = ty <= tx && ty < tz; // x implies !y
+	m.z = !(m.x || m.y);
+	return m;
+}
+// select-style (no per-axis branches)
+BM_JHD int step_pick(const StepAxis& m, int sx, int sy, int sz) { return m.x ? sx : (m.y ? sy : sz); }
+// `t += mask ? delta : 0` is the reference's `tmax += mask * tdelta` for finite deltas
+BM_JHD float step_add(float t, float d, bool mask) { return t + (mask ? d : 0.f); }
+
+// ---- the cell of the brick walk (N = 8: the 8^3 bitmask of a brick; N = 2: the 2^3 LoD mask of the index word), ONE register:
+//     bits 5 ...        the voxel's linear index  v = x + N*y + N*N*z  (9 bits for N = 8, 3 for N = 2)
+//     bits 15-19, 20-24, 25-29   guard copies of the coordinates, each as (coordinate + 8)
+// A move adds ONE per-axis constant, sign * (linear stride << 5 | 1 << guard field).  A coordinate that leaves [0, N) shows in the
+// upper bits of its guard field -- "still inside" is one AND and one XOR for all three axes -- and only then may a carry or borrow
+// of the linear part run into its neighbours: the walk is over, nothing reads them.  (A borrow that leaves the linear part ends in
+// the x guard field, which holds at least 8; a carry ends in the zero bit above the linear part.  An exit's own guard field is 16 or
+// 7, one less at most after such a borrow: outside either way.)
+// The bitmask of a brick is sixteen 32-bit words, word w = bits 32w ... 32w + 31 of the linear order: the voxel's bit is bit (v & 31)
+// of word (v >> 5).  With v at bit 5 the word number sits at bits 10-13 -- for a staging layout that keeps word w of a thread at
+// byte w * 1024 + 4 * thread (traverse.h) `cell & 0x3C00` IS the word's address offset -- and the bit number is the low five bits
+// of cell >> 5, which is all a 32-bit shift looks at.
+template <int N>
+struct BrickCell {
+	static constexpr int kLog = N == 8 ? 3 : 1;
+	static constexpr uint32_t kLin = 5, kGx = 15, kGy = 20, kGz = 25;
+	static constexpr uint32_t kOnes = (1u << kGx) | (1u << kGy) | (1u << kGz);
+	static constexpr uint32_t kGuard = (~static_cast<uint32_t>(N - 1) & 0x1Fu) * kOnes, kInside = 8u * kOnes;
+	static constexpr int kStepX = static_cast<int>((1u << kLin) | (1u << kGx));
+	static constexpr int kStepY = static_cast<int>((1u << (kLin + kLog)) | (1u << kGy));
+	static constexpr int kStepZ = static_cast<int>((1u << (kLin + 2 * kLog)) | (1u << kGz));
+	static constexpr uint32_t kWordMask = 0xFu << (kLin + 5); // N = 8: the word number, in place
+
+	// start cell of a walk from voxel (px, py, pz) (`% N`, then `& (N - 1)`: the latter only defines what the reference leaves
+	// undefined, a negative start cell)
+	static BM_JHD uint32_t start(int px, int py, int pz) {
+		const uint32_t x = static_cast<uint32_t>(px % N) & (N - 1), y = static_cast<uint32_t>(py % N) & (N - 1), z = static_cast<uint32_t>(pz % N) & (N - 1);
+		return ((x | (y << kLog) | (z << (2 * kLog))) << kLin) + ((x << kGx) | (y << kGy) | (z << kGz)) + kInside;
+	}
+	// 0: still inside the block; otherwise bits of the guard fields only (never bit 0)
+	static BM_JHD uint32_t outside(uint32_t cell) { return (cell & kGuard) ^ kInside; }
+	static BM_JHD uint32_t linear(uint32_t cell) { return (cell >> kLin) & (N * N * N - 1); }
+	static BM_JHD uint32_t word(uint32_t cell) { return (cell >> (kLin + 5)) & 0xFu; }
+	// occupancy bit of the cell in `w`: its 32-bit word of the brick (N = 8) or the LoD mask (N = 2)
+	static BM_JHD uint32_t bit(uint32_t cell, uint32_t w) { return (w >> ((cell >> kLin) & (N == 8 ? 31u : 7u))) & 1u; }
+};
+
+// ---- what a byte of the cube field means (traverse.h "cube-field walk"): 0 = the cell holds a brick, 255 = border cell outside the
+// grid, n = edge of the empty cube ahead.  `cube` keeps the byte for the walk pass that follows, with a flag when the current tmax is
+// outside the range jump.h handles.
+enum : int { ST_NEED = 0, ST_OUTER = 1, ST_CAND = 2, ST_JUMP = 3 };
+#ifndef BM_JUMP_MIN
+#define BM_JUMP_MIN 4 // smallest cube edge worth a jump (a jump costs about four single steps)
+#endif
+constexpr uint32_t kCubeNoJump = 0x100u; // RayState::cube flag: tmax is outside the range of jump.h, take single moves
+BM_JHD int field_state(uint32_t v, bool possible, uint32_t& cube) {
+	// select-style, no short-circuit: a branchy version costs its full instruction count in a divergent wave anyway
+	cube = possible ? v : (v | kCubeNoJump); // remembered for the walk pass, which may be several scheduler rounds away
+	const int jump = static_cast<int>(v >= static_cast<uint32_t>(BM_JUMP_MIN)) & static_cast<int>(possible);
+	int st = jump ? ST_JUMP : ST_OUTER;
+	st = v == 0u ? ST_CAND : st;
+	st = v == 255u ? ST_NEED : st; // left the grid (voxel.cuh:256): a miss
+	return st;
+}
+
+} // namespace bm

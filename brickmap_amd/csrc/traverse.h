@@ -9,6 +9,7 @@
 #include "detmath.h"
 #include "device_types.h"
 #include "jump.h"
+#include "steps.h"
 
 namespace bm {
 
@@ -61,16 +62,15 @@ struct HitInfo {
 
 // ---- 8^3 bitmask DDA (voxel.cuh:79-133) and 2^3 LoD DDA (voxel.cuh:26-77): one body, N = 8 or 2.
 // `brick` holds the 64-byte brick (N == 8); `byte` is the LoD mask from the index word (N == 2).
-// The brick is fetched once, as four 16-byte loads in flight together, and staged in LDS: a z-slice of the
-// brick is exactly one 64-bit word (bit x + 8y), re-read only when the walk changes z.
+// The brick is fetched once and staged in LDS; the walk reads the one 32-bit word that holds its voxel (steps.h BrickCell).
 struct BrickRegs {
 	uint4 q0, q1, q2, q3;
 };
 
-// Brick staging in LDS: the 64-byte bitmask of the brick under test is written to the workgroup's LDS once and the
-// walk re-reads one 8-byte z-slice whenever it changes z.  Slice z of thread t lives at lds_brick[z * 256 + t]:
-// consecutive lanes hit consecutive 8-byte slots, so the eight stores and the per-z-move loads are free of bank
-// conflicts whatever z each lane wants (a 14-instruction register select tree per z-move measured 5 % slower).
+// Brick staging in LDS through registers (-DBM_LDS_DMA=0): the 64-byte bitmask of the brick under test is written to the
+// workgroup's LDS once.  Slice z of thread t lives at lds_brick[z * 256 + t]: consecutive lanes hit consecutive 8-byte
+// slots, so the eight stores and the walk's loads are free of bank conflicts whatever z each lane wants (a 14-instruction
+// register select tree per z-move measured 5 % slower).
 __device__ __forceinline__ void brick_to_lds(unsigned long long* lds_brick, const BrickRegs& b) {
 	const int t = threadIdx.x;
 	lds_brick[0 * 256 + t] = static_cast<unsigned long long>(b.q0.x) | (static_cast<unsigned long long>(b.q0.y) << 32);
@@ -87,8 +87,8 @@ __device__ __forceinline__ void brick_to_lds(unsigned long long* lds_brick, cons
 // global_load_lds_dword moves 4 bytes per lane from the lane's own global address to LDS at M0 + offset + lane * 4 -- lane-
 // contiguous words, which is exactly a bank-conflict-free layout: word k (0...15) of thread t's brick at word k * 256 + t of
 // the staging area.  Sixteen such loads (M0 steps by 1020 bytes between them: the instruction offset, k * 4, counts for the
-// global AND the LDS address) replace four 16-byte loads + a wait + eight ds_write_b64; a z-slice is the two words 2z, 2z + 1,
-// one ds_read2st64_b32.  The staging sits on the candidate pass's critical path -- staging the brick a second time cost 2.9 % of
+// global AND the LDS address) replace four 16-byte loads + a wait + eight ds_write_b64; the walk reads one word per voxel step,
+// at the address its cell names (brick_word below).  The staging sits on the candidate pass's critical path -- staging the brick a second time cost 2.9 % of
 // the 1080p frame (profiles/r05_brick_staging.txt) -- and inactive lanes write nothing, as with any masked store.
 #ifndef BM_LDS_DMA
 #define BM_LDS_DMA 1
@@ -127,14 +127,18 @@ __device__ __forceinline__ float& staging_word(unsigned long long* lds_brick, ui
 	return f[((j >> 1) * 256u + t) * 2u + (j & 1u)];                      // half j & 1 of slice j / 2 of thread t
 }
 
-// z-slice (one 64-bit word: bit x + 8y) of the calling thread's staged brick
-__device__ __forceinline__ unsigned long long brick_slice(const unsigned long long* lds_brick, uint32_t z) {
-	if (BM_LDS_DMA == 2) return lds_brick[(z >> 1) * 512u + threadIdx.x * 2u + (z & 1u)];
-	if (BM_LDS_DMA) {
-		const uint32_t* w = reinterpret_cast<const uint32_t*>(lds_brick) + z * 512u + threadIdx.x;
-		return static_cast<unsigned long long>(w[0]) | (static_cast<unsigned long long>(w[256]) << 32);
+// The 32-bit word of the calling thread's staged brick that holds the walk cell's voxel (steps.h BrickCell: word v >> 5 of the linear
+// order, i.e. half y >> 2 of z-slice z).  In the default layout the word number is an address field of the cell as it stands.
+__device__ __forceinline__ uint32_t brick_word(const unsigned long long* lds_brick, uint32_t cell) {
+	typedef BrickCell<8> C;
+	if (BM_LDS_DMA == 1) {
+		static_assert(C::kWordMask == 0x3C00u, "word w of thread t at byte w * 1024 + t * 4");
+		return reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(lds_brick) + (cell & C::kWordMask))[threadIdx.x];
 	}
-	return lds_brick[z * 256u + threadIdx.x];
+	const uint32_t w = C::word(cell);
+	const uint32_t* f = reinterpret_cast<const uint32_t*>(lds_brick);
+	if (BM_LDS_DMA == 2) return f[(w >> 2) * 1024u + threadIdx.x * 4u + (w & 3u)]; // chunk w / 4 of thread t
+	return f[((w >> 1) * 256u + threadIdx.x) * 2u + (w & 1u)];                       // half w & 1 of slice w / 2 of thread t
 }
 template <int N, bool DBG>
 __device__ __forceinline__ bool intersect_grid(f3 origin, f3 dir, int sx, int sy, int sz, float dx, float dy, float dz, f3& normal, float& distance,
@@ -150,19 +154,14 @@ __device__ __forceinline__ bool intersect_grid(f3 origin, f3 dir, int sx, int sy
 	float ty = dir.y != 0.f ? (cby - origin.y) * ry : 1000000.f;
 	float tz = dir.z != 0.f ? (cbz - origin.z) * rz : 1000000.f;
 	distance = 0.f;
-	// The walk cell is ONE register: three 5-bit fields, each holding (coordinate % N) + 8, so a coordinate that
-	// leaves [0, N) shows up as a change of its field's upper bits -- "still inside" is one AND + one compare for all
-	// three axes, a move is one add of a per-axis constant, and the loop below has a single exit condition (a divergent
-	// loop with several breaks spends more scalar instructions on exit-mask bookkeeping than vector ones on the walk).
-	// (`& (N - 1)` only defines what the reference leaves undefined, a negative start cell; no effect otherwise.)
-	constexpr uint32_t kOnes = 1u | (1u << 5) | (1u << 10);
-	constexpr uint32_t kGuard = (~static_cast<uint32_t>(N - 1) & 0x1Fu) * kOnes, kInside = 8u * kOnes;
-	uint32_t cell = ((static_cast<uint32_t>(px % N) & (N - 1)) | ((static_cast<uint32_t>(py % N) & (N - 1)) << 5) | ((static_cast<uint32_t>(pz % N) & (N - 1)) << 10)) + kInside;
-	const int step_x = sx, step_y = sy * 32, step_z = sz * 1024;
-	auto test = [&](uint32_t c, unsigned long long slice) -> bool {
-		if (N == 8) return static_cast<uint32_t>(slice >> ((c & 7u) | ((c >> 2) & 0x38u))) & 1u;          // bit x + 8y of the z-slice
-		return (byte >> ((c & 1u) | ((c >> 4) & 2u) | ((c >> 8) & 4u))) & 1u;                                  // bit x + 2y + 4z of the LoD mask
-	};
+	// The walk cell is ONE register (steps.h BrickCell): the voxel's linear index x + N*y + N*N*z -- the bit number in the mask -- and a
+	// guard copy of each coordinate as (coordinate + 8) in a 5-bit field, so a coordinate that leaves [0, N) shows up as a change
+	// of its field's upper bits -- "still inside" is one AND + one XOR for all three axes, a move is one add of a per-axis constant,
+	// and the loop below has a single exit condition (a divergent loop with several breaks spends more scalar instructions on
+	// exit-mask bookkeeping than vector ones on the walk).
+	typedef BrickCell<N> C;
+	uint32_t cell = C::start(px, py, pz);
+	const int step_x = sx * C::kStepX, step_y = sy * C::kStepY, step_z = sz * C::kStepZ;
 	if (N == 8) {
 		if (BM_LDS_DMA == 2) {
 			brick_dma4_to_lds(lds_brick, brick_words);
@@ -172,36 +171,37 @@ __device__ __forceinline__ bool intersect_grid(f3 origin, f3 dir, int sx, int sy
 			brick_to_lds(lds_brick, brick);
 		}
 	}
-	unsigned long long slice = N == 8 ? brick_slice(lds_brick, (cell >> 10) & 7u) : 0ull;
+	// occupancy of a cell: ONE 32-bit word of the staged brick (or the LoD mask), shifted by the cell's own low bits.  A cell that
+	// has left the block still names a word of the thread's own slot (its fields are masked): any value is safe to test.
+	auto occupied = [&](uint32_t c) -> uint32_t { return C::bit(c, N == 8 ? brick_word(lds_brick, c) : byte); };
 	if (DBG) tally.voxel_steps++;
-	bool solid = test(cell, slice);
-	bool inside = true;
+	// stop: 0 = empty voxel inside the block, walk on; 1 = solid voxel inside the block; anything else = left the block (guard-field
+	// bits, with or without bit 0).  `inside` is folded into `solid` without a select or a second compare.
+	uint32_t stop = occupied(cell);
 	int last = 0; // packed increment of the last move: which axis it was
 	// at most 3N-2 cells lie on a line through an N^3 block; the bound only guards against NaN input
 	int guard = 3 * N + 1;
-	for (; !solid && inside && guard > 0; --guard) {
-		// select-style move (voxel.cuh:122-130); `t += mask ? delta : 0` is `tmax += mask * tdelta` for finite deltas
-		const bool mx = tx < ty && tx < tz;
-		const bool my = ty <= tx && ty < tz; // mx implies !my
-		const bool mz = !(mx || my);
-		last = mx ? step_x : (my ? step_y : step_z);
+	for (; stop == 0u && guard > 0; --guard) {
+		// the move (voxel.cuh:122-130), select-style: steps.h
+		const StepAxis m = step_choose(tx, ty, tz);
+		last = step_pick(m, step_x, step_y, step_z);
 		cell += static_cast<uint32_t>(last);
-		inside = (cell & kGuard) == kInside; // false: left the block (the values below are then unused)
-		tx += mx ? dx : 0.f;
-		ty += my ? dy : 0.f;
-		tz += mz ? dz : 0.f;
-		if (N == 8) slice = brick_slice(lds_brick, (cell >> 10) & 7u);
-		if (DBG && inside) tally.voxel_steps++;
-		solid = static_cast<bool>(static_cast<int>(inside) & static_cast<int>(test(cell, slice))); // no branch: (cell's fields are masked, any value is safe to test)
+		tx = step_add(tx, dx, m.x);
+		ty = step_add(ty, dy, m.y);
+		tz = step_add(tz, dz, m.z);
+		const uint32_t out = C::outside(cell); // nonzero: left the block (the values below are then unused)
+		if (DBG && out == 0u) tally.voxel_steps++;
+		stop = out | occupied(cell);
 	}
+	const bool solid = stop == 1u;
 	if (trips) *trips = static_cast<uint32_t>(3 * N + 2 - guard); // profiling builds: cells tested by this lane
 	if (!solid) return false;
 	// voxel.cuh:114-118, by select; a hit in the very first cell (no move) keeps distance 0 and the caller's normal
-	const int a = last < 0 ? -last : last; // 0 = no move, 1 = x, 32 = y, 1024 = z
-	normal = mk(a == 0 ? normal.x : (a == 1 ? -static_cast<float>(sx) : 0.f), a == 0 ? normal.y : (a == 32 ? -static_cast<float>(sy) : 0.f),
-				a == 0 ? normal.z : (a == 1024 ? -static_cast<float>(sz) : 0.f));
-	distance = a == 0 ? 0.f : (a == 1 ? tx - dx : (a == 32 ? ty - dy : tz - dz));
-	sub_id = static_cast<int>((cell & (N - 1)) + ((cell >> 5) & (N - 1)) * N + ((cell >> 10) & (N - 1)) * N * N);
+	const int a = last < 0 ? -last : last; // 0 = no move, else the axis' step constant
+	const float ns = last < 0 ? 1.f : -1.f; // minus the sign of the move
+	normal = mk(a == 0 ? normal.x : (a == C::kStepX ? ns : 0.f), a == 0 ? normal.y : (a == C::kStepY ? ns : 0.f), a == 0 ? normal.z : (a == C::kStepZ ? ns : 0.f));
+	distance = a == 0 ? 0.f : (a == C::kStepX ? tx - dx : (a == C::kStepY ? ty - dy : tz - dz));
+	sub_id = static_cast<int>(C::linear(cell)); // x + N*y + N*N*z
 	return true;
 }
 
@@ -229,7 +229,7 @@ struct RayState {
 	bool hit;
 };
 
-enum : int { ST_NEED = 0, ST_OUTER = 1, ST_CAND = 2, ST_JUMP = 3 };
+// lane states ST_NEED / ST_OUTER / ST_CAND / ST_JUMP: steps.h
 
 // The current cell is kept as the byte offset of its entry in the ray's octant plane of the cube field (DeviceScene::cube_field):
 //     offset = octant * cf_plane + ((z + 1) * (cells + 2) + (y + 1)) * 2^cf_shift + (x + 1)
@@ -265,10 +265,7 @@ __device__ __forceinline__ int move_axis(const DeviceScene& sc, int last_step) {
 // moved n cells, so the walk may take up to that many steps without looking at the grid: field_jump does it in one go,
 // landing on the bit-exact tmax values of the reference's cell-by-cell walk (jump.h); cubes too small to pay for a jump
 // are crossed by single steps.  One byte per visited cell replaces the 16-byte block record + bit test of the mask walk.
-#ifndef BM_JUMP_MIN
-#define BM_JUMP_MIN 4 // smallest cube edge worth a jump (a jump costs about four single steps)
-#endif
-constexpr uint32_t kCubeNoJump = 0x100u; // RayState::cube flag: tmax is outside the range of jump.h, take single moves
+// (BM_JUMP_MIN, the smallest cube edge worth a jump, and kCubeNoJump, the RayState::cube flag "take single moves": steps.h)
 // The lookup in three pieces -- where the cell's byte lives, whether a jump may start from the current tmax, what the byte means;
 // field_lookup is their sum.
 __device__ __forceinline__ uint32_t field_index(const DeviceScene& sc, const RayState& r) {
@@ -278,15 +275,7 @@ __device__ __forceinline__ bool field_jump_possible(const RayState& r) { // jump
 	const float m = fminf(fminf(r.tx, r.ty), r.tz);
 	return __float_as_uint(m) - kJumpMinBits < kJumpMaxBits - kJumpMinBits;
 }
-__device__ __forceinline__ int field_state(uint32_t v, bool possible, uint32_t& cube) {
-	// select-style, no short-circuit: a branchy version costs its full instruction count in a divergent wave anyway
-	cube = possible ? v : (v | kCubeNoJump); // remembered for the walk pass, which may be several scheduler rounds away
-	const int jump = static_cast<int>(v >= static_cast<uint32_t>(BM_JUMP_MIN)) & static_cast<int>(possible);
-	int st = jump ? ST_JUMP : ST_OUTER;
-	st = v == 0u ? ST_CAND : st;
-	st = v == 255u ? ST_NEED : st; // left the grid (voxel.cuh:256): a miss
-	return st;
-}
+// field_state(byte, possible, cube): steps.h
 __device__ __forceinline__ int field_lookup(const DeviceScene& sc, RayState& r) {
 	const uint32_t v = sc.cube_field[field_index(sc, r)];
 	return field_state(v, field_jump_possible(r), r.cube);
@@ -296,16 +285,14 @@ __device__ __forceinline__ int field_lookup(const DeviceScene& sc, RayState& r) 
 // the reference's `tmax += mask * tdelta` for finite deltas.
 __device__ __forceinline__ void step_advance(RayState& r) {
 	const float tx = r.tx, ty = r.ty, tz = r.tz;
-	const bool mx = tx < ty && tx < tz;
-	const bool my = ty <= tx && ty < tz; // mx implies !my
-	const bool mz = !(mx || my);
 	const int step_x = r.sx, step_y = r.stepy, step_z = r.stepz; // scalar copies: selects between struct members pin the struct in scratch
-	const int step = mx ? step_x : (my ? step_y : step_z);
+	const StepAxis m = step_choose(tx, ty, tz);
+	const int step = step_pick(m, step_x, step_y, step_z);
 	r.p += static_cast<uint32_t>(step);
 	r.last_step = step;
-	r.tx = tx + (mx ? r.dx : 0.f);
-	r.ty = ty + (my ? r.dy : 0.f);
-	r.tz = tz + (mz ? r.dz : 0.f);
+	r.tx = step_add(tx, r.dx, m.x);
+	r.ty = step_add(ty, r.dy, m.y);
+	r.tz = step_add(tz, r.dz, m.z);
 }
 // ... then the new cell's byte
 template <bool DBG>

@@ -47,7 +47,7 @@ def main():
         if re.match(r"\tif \(DBG && counters\) \{ // wave-level sum", line):
             regions.append((i, "epilogue"))
     starts = [r[0] for r in regions]
-    funcs = {f: function_ranges(os.path.join(CSRC, f)) for f in ("traverse.h", "jump.h", "detmath.h")}
+    funcs = {f: function_ranges(os.path.join(CSRC, f)) for f in ("traverse.h", "jump.h", "steps.h", "detmath.h")}
     with tempfile.TemporaryDirectory() as tmp:
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-gline-tables-only", *FLAGS, "-save-temps", "-x", "hip", src, "-c", "-o", "trace.o"], cwd=tmp,
                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
