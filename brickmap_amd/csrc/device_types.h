@@ -44,6 +44,7 @@ BM_VHD size_t brick_first_word(uint32_t pool_base_value, uint32_t index_word) {
 //   brick_arena 64 B * arena capacity    one allocation that all pools live in (power-of-two regions, free lists per
 //                                         size; grows by residency, not by world size)
 //   cube_field  8 planes, 1 B per cell   octant cube field (below): what the walk reads while it crosses empty space
+//   escape      u32[8 * cf_pxy]          escape heights of the walk (below, escape.h)
 //   load_queue  int3[queue_cap] + count  brick-request ring (voxel.cuh:228-245)
 struct DeviceScene {
 	uint32_t* index_grid;
@@ -68,6 +69,9 @@ struct DeviceScene {
 	int sg_xy, sg_xy2;       // supercells per axis, squared
 	float grid_size_f, grid_height_f;
 	int lod_distance_8x8x8, lod_distance_2x2x2;
+	// escape heights (escape.h): per octant and cell column, the cube-field offset of the first slice in which a ray of that octant
+	// that started in the column can no longer meet a brick; entry (x, y) of octant o at o * cf_pxy + ((y + 1) << cf_shift) + (x + 1)
+	const uint32_t* escape;
 };
 
 // a pool that has grown: `count` bricks move from arena slot `src` to `dst` (upload path, Scene.cpp:231-251)

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -45,6 +45,18 @@ size_t field_update_tmp_bytes(const FieldUpdate& u); // intermediate planes of t
 void launch_edit_scatter(const uint32_t* cells, const uint32_t* words, const uint32_t* slots, const uint32_t* bricks, uint32_t count,
 						 uint32_t* index_grid, uint32_t* arena, hipStream_t stream);
 void launch_field_update(const uint32_t* index_grid, uint8_t* field, uint8_t* tmp, const FieldUpdate& u, hipStream_t stream);
+
+// escape heights (escape.hip; escape.h has the rule): the table the walk reads -- escape_entries() words -- rebuilt from the index grid.
+// [x0, x1) x [y0, y1): the columns (unbordered cells) whose tops and bottoms are scanned again; the quadrant passes always cover the whole table.
+// cols: escape_columns_bytes() bytes that keep every column's top and bottom between updates.
+struct EscapeUpdate {
+	int x0, x1, y0, y1;
+	int cells, cells_height, sg_xy, sg_xy2;
+	int cf_shift;
+	uint32_t cf_pxy, cf_plane;
+};
+size_t escape_columns_bytes(int cells);
+void launch_escape_update(const uint32_t* index_grid, int32_t* cols, uint32_t* table, const EscapeUpdate& u, hipStream_t stream);
 
 // dense voxels -> scene (load.hip): the volume is V[z][y][x], one byte per voxel, in device memory.  classify leaves lod << 12 in every
 // cell's index word; number turns the words into slot | loaded | lod << 12 (slots in local cell order), fills counts[supercells] and

@@ -14,6 +14,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "escape.h"
 #include "kernels.h"
 
 namespace bm {
@@ -216,6 +217,8 @@ void Scene::free_device() {
 	(void)d_pool_base_.release();
 	arena_.close();
 	(void)d_cube_field_.release();
+	(void)d_escape_.release();
+	(void)d_escape_cols_.release();
 	on_device_ = false;
 }
 
@@ -260,7 +263,12 @@ int Scene::allocate_device() {
 	}
 	set_view_dims();
 	on_device_ = true;
-	return reset_residency();
+	if (int e = reset_residency()) return e;
+	// the escape heights, from the index words reset_residency has just written: which words are non-zero never changes with residency
+	launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(0, d.cells, 0, d.cells), load_stream_);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipStreamSynchronize(load_stream_));
+	return 0;
 }
 
 // the flat index grid and one pool-base word per supercell
@@ -290,7 +298,24 @@ int Scene::alloc_cube_field() {
 	view_.cf_plane = static_cast<uint32_t>(l.plane);
 	division_magic(view_.cf_pxy, &view_.cf_magic, &view_.cf_magic_shift);
 	view_.cube_field = d_cube_field_;
+	// ... and the escape heights that go with it (escape.h)
+	if (int e = d_escape_.alloc(escape_entries(view_.cf_pxy) * sizeof(uint32_t))) return e;
+	BM_HIP(hipMemset(d_escape_, 0, d_escape_.bytes())); // (border and padding entries: never read, never written)
+	if (int e = d_escape_cols_.alloc(escape_columns_bytes(world.dims.cells))) return e;
+	view_.escape = d_escape_;
 	return 0;
+}
+
+EscapeUpdate Scene::escape_update_box(int x0, int x1, int y0, int y1) const {
+	const WorldDims& d = world.dims;
+	EscapeUpdate u{};
+	u.x0 = std::max(0, x0); u.x1 = std::min(d.cells, x1); u.y0 = std::max(0, y0); u.y1 = std::min(d.cells, y1);
+	if (u.x1 < u.x0) u.x1 = u.x0;
+	if (u.y1 < u.y0) u.y1 = u.y0;
+	u.cells = d.cells; u.cells_height = d.cells_height;
+	u.sg_xy = d.supergrid_xy; u.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
+	u.cf_shift = view_.cf_shift; u.cf_pxy = view_.cf_pxy; u.cf_plane = view_.cf_plane;
+	return u;
 }
 
 void Scene::set_view_dims() {
@@ -487,6 +512,8 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	BM_HIP(hipEventRecord(ev_load_time_[3], load_stream_));
 	// ---- field
 	launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
+	BM_HIP(hipGetLastError());
+	launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(0, d.cells, 0, d.cells), load_stream_);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(ev_load_time_[4], load_stream_));
 	// ---- mirror: the host world becomes what World::load_voxels builds, in the state preload_all leaves it in
@@ -795,6 +822,7 @@ int Scene::info(bm_scene_info* out) {
 	out->brick_bytes = on_device_ ? arena_.capacity() * 64 : 0;
 	out->pool_bytes = on_device_ ? arena_.pool_bricks() * 64 : 0;
 	out->cube_field_bytes = on_device_ ? d_cube_field_.bytes() : 0;
+	out->escape_bytes = on_device_ ? d_escape_.bytes() : 0;
 	out->arena_growths = arena_.growths();
 	out->arena_copy_growths = arena_.copy_growths();
 	out->arena_virtual = arena_.is_virtual() ? 1 : 0;
@@ -998,6 +1026,9 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 		BM_HIP(hipEventRecord(times[1], load_stream_));
 		if (field) {
 			launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
+			BM_HIP(hipGetLastError());
+			// the escape heights: the columns of the cells whose occupancy changed, then the quadrant passes over the whole table
+			launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(b.box_lo[0], b.box_hi[0] + 1, b.box_lo[1], b.box_hi[1] + 1), load_stream_);
 			BM_HIP(hipGetLastError());
 		}
 		BM_HIP(hipEventRecord(times[2], load_stream_));
@@ -1233,6 +1264,24 @@ int Scene::device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
 	BM_HIP(hipDeviceSynchronize());
 	// every plane is Z slices of X rows padded to 2^cf_shift bytes, and the planes follow each other: 8 X Z rows in all
 	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_, static_cast<size_t>(1) << view_.cf_shift, X, 8 * X * Z, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int Scene::escape_table(int32_t* dst, size_t capacity, size_t* count) {
+	if (int e = require_on_device()) return e;
+	const WorldDims& d = world.dims;
+	const size_t plane = static_cast<size_t>(d.cells) * d.cells, need = 8 * plane;
+	if (count) *count = need;
+	if (!dst) return 0;
+	if (capacity < need) { set_error("escape table buffer too small"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipDeviceSynchronize());
+	std::vector<uint32_t> entries(escape_entries(view_.cf_pxy));
+	BM_HIP(hipMemcpy(entries.data(), d_escape_, entries.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	for (int o = 0; o < 8; ++o)
+		for (int y = 0; y < d.cells; ++y)
+			for (int x = 0; x < d.cells; ++x)
+				dst[o * plane + static_cast<size_t>(y) * d.cells + x] = escape_height_of(o, entries[escape_index(o, view_.cf_shift, view_.cf_pxy, x, y)], view_.cf_pxy, view_.cf_plane);
 	return 0;
 }
 

@@ -58,6 +58,7 @@ public:
 	int edit(int count, const bm_edit* edits, hipStream_t stream);
 	int device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
+	int escape_table(int32_t* dst, size_t capacity, size_t* count); // the device's escape heights (escape.h), as thresholds [8][cells][cells]
 	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
 	// dense regions (region.hip / scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
 	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
@@ -100,6 +101,7 @@ private:
 	int allocate_device();
 	int alloc_index_grid();   // the pieces of allocate_device that the device route of load_voxels shares with it
 	int alloc_cube_field();
+	EscapeUpdate escape_update_box(int x0, int x1, int y0, int y1) const; // the columns [x0, x1) x [y0, y1) of the escape-height table (escape.hip)
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
 	bool device_span_ok(const uint8_t* p, size_t bytes) const;
@@ -158,6 +160,10 @@ private:
 	// device memory (DeviceScene view)
 	DeviceBuffer<uint32_t> d_index_grid_, d_pool_base_;
 	DeviceBuffer<uint8_t> d_cube_field_;
+	// escape heights (escape.h): the table the walk reads, and every column's top and bottom, kept for the updates after edits.  Valid and
+	// rebuilt wherever the cube field is, on the same stream right behind it.
+	DeviceBuffer<uint32_t> d_escape_;
+	DeviceBuffer<int32_t> d_escape_cols_;
 	// two request rings: the blocking (reference-order) mode only uses ring 0; the overlapped mode alternates them so
 	// that a frame can raise requests while the previous frame's ring is being copied out and serviced
 	DeviceBuffer<int> d_load_queue_[2];

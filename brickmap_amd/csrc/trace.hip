@@ -112,6 +112,16 @@ enum : int { ST_IDLE = 4, ST_CONN = 5 };
 #ifndef BM_QUORUM_SHADE_DIV
 #define BM_QUORUM_SHADE_DIV 4
 #endif
+// Escape heights (escape.h): a production ray that has left the occupied part of its octant's box ends as a miss at its set-up or at
+// its next jump landing instead of walking to the world's border.  -DBM_ESCAPE=0 builds the kernels without the rule (the table is
+// built and kept either way): the same-tree A/B.  The instrumented instantiations never escape -- their index_loads stay the
+// reference's cell visits, and every parity test that renders with both instantiations checks the rule.
+#ifndef BM_ESCAPE
+#define BM_ESCAPE 1
+#endif
+#ifndef BM_ESCAPE_XCD // 0: only the instantiations without the XCD-aware hand-out escape (the A/B of the big frames)
+#define BM_ESCAPE_XCD 1
+#endif
 #ifndef BM_STEPS_PER_ROUND
 #define BM_STEPS_PER_ROUND 4
 #endif
@@ -214,6 +224,8 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 	uint32_t ray_key = 0, ray_loads0 = 0; // of the ray in flight
 
 	RayState r;
+	constexpr bool kEscape = BM_ESCAPE != 0 && !DBG && (BM_ESCAPE_XCD != 0 || !XCD);
+	uint32_t esc = 0; // kEscape: the escape threshold of the ray in flight (ray_setup)
 	r.hit = false;
 	r.n = mk(0.f, 0.f, 0.f);
 	int state = ST_IDLE;
@@ -681,7 +693,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					ray_loads0 = tally.index_loads;
 				}
 				pstate = shadow ? ((HELP && pstate == P_HELPER) ? P_HELPER : P_SHD_DONE) : P_EXT_DONE;
-				const int st = ray_setup<DBG>(sc, ro, rd, r, tally);
+				const int st = ray_setup<DBG, kEscape>(sc, ro, rd, r, tally, &esc);
 				state = (st == ST_NEED && shadow) ? ST_CONN : st;
 			}
 			BM_MARK(4, t_sub); // ray set-up
@@ -742,7 +754,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					if (BM_TIMED) { runsJ++; lanesJ += walkers; }
 					if (state == ST_JUMP || state == ST_OUTER) {
 						int st;
-						if (!(r.cube & kCubeNoJump)) st = field_jump<DBG>(sc, r, tally);
+						if (!(r.cube & kCubeNoJump)) st = field_jump<DBG, true, kEscape>(sc, r, tally, esc);
 						else st = field_step<DBG>(sc, r, tally); // tmax outside the range jump.h handles (first move of a ray that starts on a cell face)
 						state = (st == ST_NEED && shadow) ? ST_CONN : st;
 					}

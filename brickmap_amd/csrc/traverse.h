@@ -8,6 +8,7 @@
 
 #include "detmath.h"
 #include "device_types.h"
+#include "escape.h"
 #include "jump.h"
 #include "steps.h"
 
@@ -326,10 +327,13 @@ __device__ __forceinline__ uint32_t jump_advance(RayState& r) {
 	r.last_step = axis == 0 ? step_x : (axis == 1 ? step_y : step_z); // (only read after a cube exit, where it is the exit axis)
 	return cx + cy + cz;
 }
-template <bool DBG, bool DIR = true>
-__device__ __forceinline__ int field_jump(const DeviceScene& sc, RayState& r, Tally& tally) {
+// ESC: the landing is tested against the ray's escape threshold `esc` (escape.h; read once by ray_setup) -- a ray that has left the
+// occupied part of its octant's box is what a border byte would make it, a miss, without walking to the border.
+template <bool DBG, bool DIR = true, bool ESC = false>
+__device__ __forceinline__ int field_jump(const DeviceScene& sc, RayState& r, Tally& tally, uint32_t esc = 0u) {
 	const uint32_t cells = jump_advance<DIR>(r);
-	const int st = field_lookup(sc, r);
+	int st = field_lookup(sc, r);
+	if (ESC) st = escape_reached(r.p, esc, r.stepz) ? ST_NEED : st;
 	if (DBG) tally.index_loads += cells - (st == ST_NEED ? 1u : 0u); // the cells the reference would have loaded: all but a final one outside the grid
 	return st;
 }
@@ -380,8 +384,13 @@ __device__ __forceinline__ int walk_round(const DeviceScene& sc, RayState& r, in
 
 // voxel.cuh:136-189: clip against the world box, move onto it, set up the Amanatides-Woo state.
 // Returns the lane's next state: ST_OUTER / ST_CAND, or ST_NEED with r.hit = false when the ray misses the box.
-template <bool DBG>
-__device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally) {
+// ESC: *esc becomes the ray's escape threshold (escape.h), the table entry of its octant at its start column -- one load, next to the
+// field byte's -- and a ray whose start cell is already past it is a miss there and then.  (By select: the field byte's load is still
+// issued, both loads are in flight together, and the byte is dropped -- a branch round the lookup would put the two load latencies of
+// the set-up one behind the other for every lane that does not escape.)  The threshold is the caller's lane
+// variable, not a field of RayState: the queue kernels and the ray queries share that record and do not escape.
+template <bool DBG, bool ESC = false>
+__device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally, uint32_t* esc = nullptr) {
 	r.hit = false;
 	r.d = dir;
 	// intersect_aabb_branchless2 (voxel.cuh:13-24).  For an origin strictly inside the box every slab entry time is
@@ -422,6 +431,7 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 	const uint32_t oct = (dir.x < 0.f ? 1u : 0u) | (dir.y < 0.f ? 2u : 0u) | (dir.z < 0.f ? 4u : 0u);
 	r.field_off = oct * sc.cf_plane;
 	r.p = cell_offset(sc, r.field_off, px, py, pz);
+	if (ESC) *esc = sc.escape[__umul24(oct, sc.cf_pxy) + (static_cast<uint32_t>(py + 1) << sc.cf_shift) + static_cast<uint32_t>(px + 1)]; // escape_index
 	const float cbx = dir.x > 0.f ? static_cast<float>(px + 1) : static_cast<float>(px);
 	const float cby = dir.y > 0.f ? static_cast<float>(py + 1) : static_cast<float>(py);
 	const float cbz = dir.z > 0.f ? static_cast<float>(pz + 1) : static_cast<float>(pz);
@@ -436,7 +446,8 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 	r.dx = static_cast<float>(sx) * rx; r.dy = static_cast<float>(sy) * ry; r.dz = static_cast<float>(sz) * rz;
 	r.last_step = 0;
 	if (DBG) tally.index_loads++; // one per visited cell = the reference's index loads (algorithmic count)
-	return field_lookup(sc, r); // inside the grid: never a border cell
+	const int st = field_lookup(sc, r); // inside the grid: never a border cell
+	return ESC && escape_reached(r.p, *esc, r.stepz) ? ST_NEED : st;
 }
 
 // voxel.cuh:200-247: the current cell holds a non-empty brick -- read its index word and resolve it.

@@ -593,6 +593,15 @@ class Scene:
         """bm_scene_host_cube_field: the cube field of the scene's current host world (same layout)."""
         return self._cube_field(self._L.bm_scene_host_cube_field)
 
+    def escape_table(self):
+        """bm_scene_escape_table: the device's escape heights as thresholds, int32 [8, cells, cells] (octant, y, x)."""
+        n = C.c_size_t(0)
+        check(self._L.bm_scene_escape_table(self.gpuScene, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        check(self._L.bm_scene_escape_table(self.gpuScene, out.ctypes.data, out.size, C.byref(n)))
+        c = self.grid_size // 8
+        return out.reshape(8, c, c)
+
     def last_edit_ms(self):
         """(scatter_ms, field_ms) of the last edit batch that changed the scene (hipEvents on the load stream)."""
         a, b = C.c_float(0), C.c_float(0)

@@ -115,6 +115,7 @@ typedef struct bm_scene_info {
 	int32_t failed;                 /* 1: a streaming batch could not be completed; frames are refused until the residency is reset */
 	uint64_t stream_batches;        /* upload batches queued since the residency was last reset                                   */
 	uint64_t stream_host_ns;        /* host time spent staging them (validate, copy bricks to pinned memory, hand out slots, queue) */
+	uint64_t escape_bytes;          /* escape heights of the walk: 8 octants x one 32-bit entry per cell column, in rows padded like the cube field's                    */
 } bm_scene_info;
 
 /* one voxel edit (bm_scene_edit).  Voxel coordinates are integers; a batch applies its edits in order. */
@@ -215,8 +216,14 @@ BM_API int bm_scene_set_voxels(bm_scene* scene, int n, const int32_t* xyz, const
 BM_API int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes);
 /* the cube field built on the host from the scene's current host world (bm_host_cube_field's layout) */
 BM_API int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes);
+/* the device's escape heights (waits for the device): per direction octant o (bit 0 / 1 / 2 = direction negative in x / y / z) and
+ * brick-cell column (x, y), dst[(o * cells + y) * cells + x] = the threshold E of the walk's escape rule -- octants 0-3: the highest
+ * occupied cell z over the columns x' >= x (octant bit 0 clear; x' <= x if set), y' likewise, -1 if there is none: a ray of the octant
+ * in a cell above E is a miss; octants 4-7: the lowest such z, cells_height if none: a miss below E.  *count = entries (8 * cells^2),
+ * also when dst is null.  Kept exact by bm_scene_load_voxels, edits and region writes, like the cube field. */
+BM_API int bm_scene_escape_table(bm_scene* scene, int32_t* dst, size_t capacity, size_t* count);
 /* device time of the last batch that changed the scene (hipEvents on the load stream): the scatter (pool moves, bricks, words)
- * and the cube-field update (0 when no cell's occupancy changed); waits for that batch */
+ * and the cube-field update with the escape-height update behind it (0 when no cell's occupancy changed); waits for that batch */
 BM_API int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms);
 
 /* ---- a scene from the caller's own voxels (no reference counterpart: the reference's only world is its terrain).
@@ -240,7 +247,7 @@ BM_API int bm_scene_load_voxels(bm_scene* scene, const uint8_t* voxels, size_t b
 /* the host world as a dense volume of 0 / 1 in the layout above (host only); *bytes = size needed (dst = NULL to query) */
 BM_API int bm_scene_host_voxels(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes);
 /* device time of the last BM_VOXELS_DEVICE load (hipEvents on the load stream): pack = classify + number + pack kernels (without the
- * host's round trip that sizes the arena), the cube-field passes, and the copy back into the host world.  BM_ESTATE when the last load
+ * host's round trip that sizes the arena), the cube-field passes with the escape-height build behind them, and the copy back into the host world.  BM_ESTATE when the last load
  * was not from device memory. */
 BM_API int bm_scene_last_load_ms(bm_scene* scene, float* pack_ms, float* field_ms, float* mirror_ms);
 
@@ -279,7 +286,7 @@ typedef struct bm_region {
 BM_API int bm_scene_write_region(bm_scene* scene, const bm_region* region, int op, const uint8_t* voxels, int where, void* hip_stream);
 BM_API int bm_scene_read_region(bm_scene* scene, const bm_region* region, uint8_t* voxels, int where, void* hip_stream);
 /* times of the last bm_scene_write_region that reached the device, in ms (hipEvents on the load stream; waits for that write): the
- * pack kernel and the copy of the packed bricks to the host (both 0 for BM_VOXELS_HOST), the scatter and the cube-field update (0 when
+ * pack kernel and the copy of the packed bricks to the host (both 0 for BM_VOXELS_HOST), the scatter and the cube-field update with the escape-height update behind it (0 when
  * no cell changed / no cell's occupancy changed).  BM_ESTATE before the first write. */
 BM_API int bm_scene_last_region_ms(bm_scene* scene, float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms);
 
