@@ -92,7 +92,7 @@ class bm_scene_info(C.Structure):
                 ("index_bytes", C.c_uint64), ("brick_bytes", C.c_uint64),
                 ("pool_bytes", C.c_uint64), ("cube_field_bytes", C.c_uint64),
                 ("arena_growths", C.c_uint64), ("arena_copy_growths", C.c_uint64), ("arena_virtual", C.c_int32), ("failed", C.c_int32),
-                ("stream_batches", C.c_uint64), ("stream_host_ns", C.c_uint64), ("escape_bytes", C.c_uint64)]
+                ("stream_batches", C.c_uint64), ("stream_host_ns", C.c_uint64), ("escape_bytes", C.c_uint64), ("sun_plane_bytes", C.c_uint64)]
 
 
 COUNTER_NAMES = ("index_loads", "brick_tests", "byte_tests", "voxel_steps", "extend_rays",
@@ -141,6 +141,8 @@ SIGNATURES = {
     "bm_scene_device_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_scene_host_cube_field": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bm_scene_escape_table": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bm_scene_sun_plane": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
+    "bm_scene_sun_plane_stats": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "bm_scene_last_edit_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bm_scene_load_voxels": (_i, [_vp, _vp, C.c_size_t, _i, _vp]),
     "bm_scene_host_voxels": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -114,6 +114,9 @@ struct FrameConstants {
 	int div_samples_shift, div_tiles_x_shift, div_band_shift, div_st_x_shift;
 	int helpers;          // 1: shadow rays may be traced by idle lanes of the wave and added with float atomics (trace.hip HELP); 0: every pixel's events
 	                      // are accumulated in path order by the one lane that owns it (BM_FLAG_ORDERED, and every frame that writes hit records)
+	// the sun plane (sunfield.h): byte offset of the cube-field plane this frame's shadow rays read, 8 * cf_plane, or 0 -- they keep their octant
+	// plane -- when the scene's sun plane was not built for this frame's cone (scene.cpp render_frames)
+	uint32_t shadow_field_off;
 	// the frame ring (trace.hip): where this frame's results go, and how many frames of the launch follow it (the queue kernels of
 	// wavefront.hip take their buffers as arguments)
 	float* accum;          // float4 per pixel of the shard

@@ -1,10 +1,11 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
+#include "sunfield.h"
 
 namespace bm {
 // resident workgroups of `threads` threads per compute unit of a kernel, at least 1 (host code of the file that defines the kernel)
@@ -57,6 +58,19 @@ struct EscapeUpdate {
 };
 size_t escape_columns_bytes(int cells);
 void launch_escape_update(const uint32_t* index_grid, int32_t* cols, uint32_t* table, const EscapeUpdate& u, hipStream_t stream);
+
+// the sun plane (sunfield.hip; sunfield.h has the rules): plane 8 of `field`, every interior byte, rebuilt from the index grid, the column
+// tops in `cols` and the escape table (both as launch_escape_update leaves them).  nd / n1 / n2: cells along the plan's dominant and minor
+// axes.  tmp: sun_build_tmp_bytes() bytes that no other launch uses until this one has finished.
+struct SunBuild {
+	SunPlan plan; // valid
+	int cells, cells_height, sg_xy, sg_xy2;
+	int nd, n1, n2;
+	int cf_shift;
+	uint32_t cf_pxy, cf_plane;
+};
+size_t sun_build_tmp_bytes(const SunBuild& u);
+void launch_sun_build(const uint32_t* index_grid, const int32_t* cols, const uint32_t* escape, uint8_t* field, uint8_t* tmp, const SunBuild& u, hipStream_t stream);
 
 // dense voxels -> scene (load.hip): the volume is V[z][y][x], one byte per voxel, in device memory.  classify leaves lod << 12 in every
 // cell's index word; number turns the words into slot | loaded | lod << 12 (slots in local cell order), fills counts[supercells] and

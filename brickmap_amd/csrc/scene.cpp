@@ -43,7 +43,7 @@ namespace {
 struct CubeFieldLayout {
 	int shift;
 	uint64_t pxy, plane;
-	bool fits;
+	bool fits, ninth;
 };
 CubeFieldLayout cube_field_layout(const WorldDims& d) {
 	int shift = 2;
@@ -53,6 +53,7 @@ CubeFieldLayout cube_field_layout(const WorldDims& d) {
 	l.pxy = static_cast<uint64_t>(d.cells + 2) << shift;
 	l.plane = l.pxy * static_cast<uint64_t>(d.cells_height + 2);
 	l.fits = l.pxy < (1ull << 23) && l.plane * 8 < (1ull << 32);
+	l.ninth = BM_SUNFIELD != 0 && l.fits && l.plane * 9 < (1ull << 32); // the sun plane's offsets fit 32 bits as well
 	return l;
 }
 
@@ -217,6 +218,7 @@ void Scene::free_device() {
 	(void)d_pool_base_.release();
 	arena_.close();
 	(void)d_cube_field_.release();
+	sun_plane_ = sun_built_ = false;
 	(void)d_escape_.release();
 	(void)d_escape_cols_.release();
 	on_device_ = false;
@@ -291,8 +293,16 @@ int Scene::alloc_index_grid() {
 int Scene::alloc_cube_field() {
 	const CubeFieldLayout l = cube_field_layout(world.dims);
 	if (!l.fits) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
-	if (int e = d_cube_field_.alloc(l.plane * 8)) return e;
-	BM_HIP(hipMemset(d_cube_field_, 255, l.plane * 8)); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
+	// a ninth plane behind the eight is the sun plane of shadow rays (sunfield.h), where it can be had: a scene without it renders as before
+	sun_plane_ = false;
+	if (l.ninth) {
+		if (d_cube_field_.alloc(l.plane * 9) == 0) sun_plane_ = true;
+		else { (void)hipGetLastError(); set_error(""); } // (doing without the plane is no error: neither HIP's slot nor ours keeps it)
+	}
+	if (!sun_plane_) { if (int e = d_cube_field_.alloc(l.plane * 8)) return e; }
+	sun_built_ = false; // (whoever fills the field afterwards has a new world)
+	sun_dirty_ = true;
+	BM_HIP(hipMemset(d_cube_field_, 255, d_cube_field_.bytes())); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
 	view_.cf_shift = l.shift;
 	view_.cf_pxy = static_cast<uint32_t>(l.pxy);
 	view_.cf_plane = static_cast<uint32_t>(l.plane);
@@ -821,8 +831,9 @@ int Scene::info(bm_scene_info* out) {
 	out->index_bytes = on_device_ ? static_cast<uint64_t>(d.supercells) * kCellsPerSupercell * 4 : 0;
 	out->brick_bytes = on_device_ ? arena_.capacity() * 64 : 0;
 	out->pool_bytes = on_device_ ? arena_.pool_bricks() * 64 : 0;
-	out->cube_field_bytes = on_device_ ? d_cube_field_.bytes() : 0;
+	out->cube_field_bytes = on_device_ ? 8 * static_cast<uint64_t>(view_.cf_plane) : 0; // (the octant planes; the sun plane, where there is one, is one more plane)
 	out->escape_bytes = on_device_ ? d_escape_.bytes() : 0;
+	out->sun_plane_bytes = on_device_ && sun_plane_ ? static_cast<uint64_t>(view_.cf_plane) + d_sun_tmp_.bytes() : 0;
 	out->arena_growths = arena_.growths();
 	out->arena_copy_growths = arena_.copy_growths();
 	out->arena_virtual = arena_.is_virtual() ? 1 : 0;
@@ -1030,6 +1041,7 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 			// the escape heights: the columns of the cells whose occupancy changed, then the quadrant passes over the whole table
 			launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(b.box_lo[0], b.box_hi[0] + 1, b.box_lo[1], b.box_hi[1] + 1), load_stream_);
 			BM_HIP(hipGetLastError());
+			sun_dirty_ = true; // the sun plane is rebuilt before the next frame that reads it (ensure_sun_plane): a run of batches pays once
 		}
 		BM_HIP(hipEventRecord(times[2], load_stream_));
 		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
@@ -1285,6 +1297,78 @@ int Scene::escape_table(int32_t* dst, size_t capacity, size_t* count) {
 	return 0;
 }
 
+// ---- the sun plane (sunfield.h, sunfield.hip): plane 8 of the cube field, for the cone of ONE sun.  The sun is a scene setting that stays
+// put from frame to frame (the reference sets it from a slider), so the plane is keyed on the cone and rebuilt only when a production
+// frame is about to read it and the cone or the field has changed since it was built.
+int Scene::ensure_sun_plane(const FrameConstants& fc, bool* usable) {
+	*usable = false;
+	if (!sun_plane_) return 0;
+	const SunPlan plan = sun_plan(fc.cone_dir, fc.cone_extent);
+	if (!plan.valid) return 0; // (the plane of another sun, if any, stays: the frames of this one keep their octant planes)
+	const float key[4] = {fc.cone_dir[0], fc.cone_dir[1], fc.cone_dir[2], fc.cone_extent};
+	*usable = true;
+	if (sun_built_ && !sun_dirty_ && std::memcmp(key, sun_key_, sizeof key) == 0) return 0;
+	const WorldDims& d = world.dims;
+	const int n[3] = {d.cells, d.cells, d.cells_height};
+	SunBuild u{};
+	u.plan = plan;
+	u.cells = d.cells; u.cells_height = d.cells_height;
+	u.sg_xy = d.supergrid_xy; u.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
+	u.nd = n[plan.dom]; u.n1 = n[plan.m1]; u.n2 = n[plan.m2];
+	u.cf_shift = view_.cf_shift; u.cf_pxy = view_.cf_pxy; u.cf_plane = view_.cf_plane;
+	*usable = false;
+	for (Event& ev : ev_sun_time_) if (int e = ev.create()) return e;
+	if (sun_build_tmp_bytes(u) > d_sun_tmp_.bytes()) {
+		BM_HIP(hipStreamSynchronize(load_stream_)); // an earlier build may still use the scratch
+		if (d_sun_tmp_.reserve(sun_build_tmp_bytes(u)) != 0) { (void)hipGetLastError(); set_error(""); return 0; } // no scratch, no plane: not an error
+	}
+	// behind every frame in flight (their shadow rays read the plane) and, on the load stream, behind the field and escape updates it reads
+	if (int e = order_load_stream_behind_frames()) return e;
+	BM_HIP(hipEventRecord(ev_sun_time_[0], load_stream_));
+	launch_sun_build(d_index_grid_, d_escape_cols_, d_escape_, d_cube_field_, d_sun_tmp_, u, load_stream_);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_sun_time_[1], load_stream_));
+	BM_HIP(hipEventRecord(ev_upload_, load_stream_)); // frames wait for it like for an upload batch (frame_begin)
+	upload_seq_++;
+	std::memcpy(sun_key_, key, sizeof key);
+	sun_plan_ = plan;
+	sun_built_ = true;
+	sun_dirty_ = false;
+	sun_builds_++;
+	*usable = true;
+	return 0;
+}
+
+int Scene::sun_plane(uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12) {
+	if (int e = require_on_device()) return e;
+	const WorldDims& d = world.dims;
+	const bool have = sun_plane_ && sun_built_;
+	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = have ? X * X * Z : 0;
+	if (bytes) *bytes = need;
+	if (plan12) {
+		const SunPlan p = have ? sun_plan_ : SunPlan{};
+		const int32_t v[12] = {p.valid, p.octant, p.dom, p.m1, p.m2, p.lo1, p.hi1, p.lo2, p.hi2, p.clear, p.rise, kSunBins};
+		std::memcpy(plan12, v, sizeof v);
+	}
+	if (!dst || !have) return 0;
+	if (capacity < need) { set_error("sun plane buffer too small"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipDeviceSynchronize());
+	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_ + 8 * static_cast<size_t>(view_.cf_plane), static_cast<size_t>(1) << view_.cf_shift, X, X * Z, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int Scene::sun_plane_stats(uint64_t* builds, float* last_build_ms) {
+	if (!builds || !last_build_ms) { set_error("null argument"); return BM_EINVAL; }
+	*builds = sun_builds_;
+	*last_build_ms = 0.0f;
+	if (sun_builds_ == 0) return 0;
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipEventSynchronize(ev_sun_time_[1]));
+	BM_HIP(hipEventElapsedTime(last_build_ms, ev_sun_time_[0], ev_sun_time_[1]));
+	return 0;
+}
+
 int Scene::host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
 	const WorldDims& d = world.dims;
 	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = 8 * X * X * Z;
@@ -1420,10 +1504,18 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 		}
 	}
 	BM_HIP(hipSetDevice(device_));
+	const bool instrumented = hit_records || (fc.flags & BM_FLAG_COUNTERS);
+	// the sun plane, for the first frame's sun: built now if it is not there; frames of the launch with another sun keep their octant planes
+	if (!instrumented && !(fc.flags & BM_FLAG_PRIMARY_ONLY) && fc.spp >= 1) {
+		bool usable = false;
+		if (int e = ensure_sun_plane(fc, &usable)) return e;
+		if (usable)
+			for (FrameConstants& f : fcs)
+				if (std::memcmp(f.cone_dir, sun_key_, 3 * sizeof(float)) == 0 && f.cone_extent == sun_key_[3]) f.shadow_field_off = 8u * view_.cf_plane;
+	}
 	// `stream` is used as given: nullptr is HIP's default stream (what the reference's <<<>>> launches use), which is
 	// ordered with the caller's other default-stream work (e.g. torch's fill kernels on the accumulation buffer).
 	if (int e = frame_begin(stream)) return e; // bricks uploaded on the load stream must be visible to these frames
-	const bool instrumented = hit_records || (fc.flags & BM_FLAG_COUNTERS);
 	const int slot = static_cast<int>(launches_ % kTimingRing);
 	// the event pair of this slot is reused every kTimingRing launches: wait for the launch that used it last (almost always done)
 	if (launches_ >= kTimingRing) BM_HIP(hipEventSynchronize(ev_stop_[slot]));

@@ -60,6 +60,10 @@ public:
 	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int escape_table(int32_t* dst, size_t capacity, size_t* count); // the device's escape heights (escape.h), as thresholds [8][cells][cells]
 	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
+	// the sun plane (sunfield.h): the device's plane as it was last built, [z][y][x] with its border, and the plan it was built for; how often it
+	// has been built and what the last build took
+	int sun_plane(uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12);
+	int sun_plane_stats(uint64_t* builds, float* last_build_ms);
 	// dense regions (region.hip / scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
 	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
 	int read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream);
@@ -101,6 +105,7 @@ private:
 	int allocate_device();
 	int alloc_index_grid();   // the pieces of allocate_device that the device route of load_voxels shares with it
 	int alloc_cube_field();
+	int ensure_sun_plane(const FrameConstants& fc, bool* usable); // builds the sun plane for the frame's cone unless it stands; *usable: shadow rays of that cone may read it
 	EscapeUpdate escape_update_box(int x0, int x1, int y0, int y1) const; // the columns [x0, x1) x [y0, y1) of the escape-height table (escape.hip)
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
@@ -164,6 +169,14 @@ private:
 	// rebuilt wherever the cube field is, on the same stream right behind it.
 	DeviceBuffer<uint32_t> d_escape_;
 	DeviceBuffer<int32_t> d_escape_cols_;
+	// the sun plane (sunfield.h): plane 8 of d_cube_field_ where alloc_cube_field got nine planes; built for the cone in sun_key_ (cone_dir,
+	// cone_extent), stale once the field has changed (every field change sets sun_dirty_), rebuilt by the next production frame that reads it
+	bool sun_plane_ = false, sun_built_ = false, sun_dirty_ = true;
+	float sun_key_[4] = {0.f, 0.f, 0.f, 0.f};
+	SunPlan sun_plan_{};
+	uint64_t sun_builds_ = 0;
+	DeviceBuffer<uint8_t> d_sun_tmp_;
+	Event ev_sun_time_[2];
 	// two request rings: the blocking (reference-order) mode only uses ring 0; the overlapped mode alternates them so
 	// that a frame can raise requests while the previous frame's ring is being copied out and serviced
 	DeviceBuffer<int> d_load_queue_[2];

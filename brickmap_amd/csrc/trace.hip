@@ -122,6 +122,9 @@ enum : int { ST_IDLE = 4, ST_CONN = 5 };
 #ifndef BM_ESCAPE_XCD // 0: only the instantiations without the XCD-aware hand-out escape (the A/B of the big frames)
 #define BM_ESCAPE_XCD 1
 #endif
+// The sun plane (sunfield.h, with the build switches BM_SUNFIELD and BM_SUNFIELD_XCD): a shadow ray of a production frame whose sun has
+// one walks that plane instead of its octant's.  The instrumented instantiations never do -- their index_loads stay the reference's
+// cell visits, and every parity test that renders with both instantiations checks the plane.
 #ifndef BM_STEPS_PER_ROUND
 #define BM_STEPS_PER_ROUND 4
 #endif
@@ -225,6 +228,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 
 	RayState r;
 	constexpr bool kEscape = BM_ESCAPE != 0 && !DBG && (BM_ESCAPE_XCD != 0 || !XCD);
+	constexpr bool kSun = BM_SUNFIELD != 0 && kEscape && (BM_SUNFIELD_XCD != 0 || !XCD); // (the plane's stamps stand in for the escape test: only where that is compiled in)
 	uint32_t esc = 0; // kEscape: the escape threshold of the ray in flight (ray_setup)
 	r.hit = false;
 	r.n = mk(0.f, 0.f, 0.f);
@@ -693,7 +697,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					ray_loads0 = tally.index_loads;
 				}
 				pstate = shadow ? ((HELP && pstate == P_HELPER) ? P_HELPER : P_SHD_DONE) : P_EXT_DONE;
-				const int st = ray_setup<DBG, kEscape>(sc, ro, rd, r, tally, &esc);
+				const int st = ray_setup<DBG, kEscape>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u);
 				state = (st == ST_NEED && shadow) ? ST_CONN : st;
 			}
 			BM_MARK(4, t_sub); // ray set-up

@@ -224,7 +224,7 @@ struct RayState {
 	float tminn;
 	f3 n;               // normal carried in/out of the traversal (voxel.cuh:135 `normal`)
 	int last_step;      // offset increment of the last move (0 before the first): which axis it was, see move_axis
-	uint32_t field_off;      // byte offset of the ray's octant plane in DeviceScene::cube_field
+	uint32_t field_off;      // byte offset in DeviceScene::cube_field of the plane the ray walks: its octant's, or the sun plane for a shadow ray that has one (ray_setup)
 	uint32_t cube;           // edge of the empty cube ahead of the current cell (its cube_field byte)
 	float distance;     // result
 	bool hit;
@@ -243,7 +243,7 @@ __device__ __forceinline__ uint32_t cell_offset(const DeviceScene& sc, uint32_t 
 	return field_off + __umul24(static_cast<uint32_t>(z + 1), sc.cf_pxy) + (static_cast<uint32_t>(y + 1) << sc.cf_shift) + static_cast<uint32_t>(x + 1);
 }
 __device__ __forceinline__ void cell_coords(const DeviceScene& sc, const RayState& r, int& x, int& y, int& z) {
-	const uint32_t rel = r.p - r.field_off;                               // < cf_plane < 2^30
+	const uint32_t rel = r.p - r.field_off;                               // < cf_plane < 2^29 (the eight or nine planes together stay below 2^32)
 	const uint32_t fz = __umulhi(rel, sc.cf_magic) >> sc.cf_magic_shift;  // floor(rel / cf_pxy), exact (frame_plan.cpp division_magic)
 	const uint32_t low = rel - __umul24(fz, sc.cf_pxy);
 	x = static_cast<int>(low & ((1u << sc.cf_shift) - 1u)) - 1;
@@ -389,8 +389,11 @@ __device__ __forceinline__ int walk_round(const DeviceScene& sc, RayState& r, in
 // issued, both loads are in flight together, and the byte is dropped -- a branch round the lookup would put the two load latencies of
 // the set-up one behind the other for every lane that does not escape.)  The threshold is the caller's lane
 // variable, not a field of RayState: the queue kernels and the ray queries share that record and do not escape.
+// sun_plane: non-zero for a shadow ray whose frame has a sun plane (sunfield.h; FrameConstants::shadow_field_off) -- the ray walks that
+// plane instead of its octant's, by one select here; the plane's 255 stamps hold the escape rule, so the threshold becomes the plane's
+// end, which escape_reached never sees reached (such a ray moves up: the plan of a sun below the horizon is not valid).
 template <bool DBG, bool ESC = false>
-__device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally, uint32_t* esc = nullptr) {
+__device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally, uint32_t* esc = nullptr, uint32_t sun_plane = 0u) {
 	r.hit = false;
 	r.d = dir;
 	// intersect_aabb_branchless2 (voxel.cuh:13-24).  For an origin strictly inside the box every slab entry time is
@@ -429,9 +432,10 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 	if (px < 0 || px >= cells || py < 0 || py >= cells || pz < 0 || pz >= cells_h) return ST_NEED;
 	// octant of the direction: a zero component never moves, either plane is valid for it
 	const uint32_t oct = (dir.x < 0.f ? 1u : 0u) | (dir.y < 0.f ? 2u : 0u) | (dir.z < 0.f ? 4u : 0u);
-	r.field_off = oct * sc.cf_plane;
+	r.field_off = sun_plane ? sun_plane : oct * sc.cf_plane;
 	r.p = cell_offset(sc, r.field_off, px, py, pz);
 	if (ESC) *esc = sc.escape[__umul24(oct, sc.cf_pxy) + (static_cast<uint32_t>(py + 1) << sc.cf_shift) + static_cast<uint32_t>(px + 1)]; // escape_index
+	if (ESC) *esc = sun_plane ? sun_plane + sc.cf_plane : *esc;
 	const float cbx = dir.x > 0.f ? static_cast<float>(px + 1) : static_cast<float>(px);
 	const float cby = dir.y > 0.f ? static_cast<float>(py + 1) : static_cast<float>(py);
 	const float cbz = dir.z > 0.f ? static_cast<float>(pz + 1) : static_cast<float>(pz);

@@ -593,6 +593,27 @@ class Scene:
         """bm_scene_host_cube_field: the cube field of the scene's current host world (same layout)."""
         return self._cube_field(self._L.bm_scene_host_cube_field)
 
+    def sun_plane(self):
+        """bm_scene_sun_plane: (plane, plan) -- the sun plane as last built, uint8 [cells_z + 2, cells + 2, cells + 2] with its border, or None
+        when none has been built; and the plan it was built for as a dict (valid, octant, dom, m1, m2, lo1, hi1, lo2, hi2, clear, rise, bins)."""
+        n = C.c_size_t(0)
+        plan = (C.c_int32 * 12)()
+        check(self._L.bm_scene_sun_plane(self.gpuScene, None, 0, C.byref(n), plan))
+        names = ("valid", "octant", "dom", "m1", "m2", "lo1", "hi1", "lo2", "hi2", "clear", "rise", "bins")
+        plan = dict(zip(names, (int(v) for v in plan)))
+        if n.value == 0:
+            return None, plan
+        out = np.zeros(n.value, np.uint8)
+        check(self._L.bm_scene_sun_plane(self.gpuScene, out.ctypes.data, out.size, C.byref(n), None))
+        c = self.grid_size // 8 + 2
+        return out.reshape(-1, c, c), plan
+
+    def sun_plane_stats(self):
+        """bm_scene_sun_plane_stats: (builds so far, device ms of the last build)."""
+        builds, ms = C.c_uint64(0), C.c_float(0)
+        check(self._L.bm_scene_sun_plane_stats(self.gpuScene, C.byref(builds), C.byref(ms)))
+        return int(builds.value), float(ms.value)
+
     def escape_table(self):
         """bm_scene_escape_table: the device's escape heights as thresholds, int32 [8, cells, cells] (octant, y, x)."""
         n = C.c_size_t(0)

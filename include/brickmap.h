@@ -107,7 +107,7 @@ typedef struct bm_scene_info {
 	uint64_t resident_bricks;       /* bricks currently in the device arena              */
 	uint64_t index_bytes, brick_bytes; /* device allocations: index grid; brick arena as allocated (grows by residency) */
 	uint64_t pool_bytes;            /* part of the arena handed to supercell pools (16-brick pools that double, Scene.cpp:231-251) */
-	uint64_t cube_field_bytes;      /* octant cube field of the walk (8 bytes per brick cell) */
+	uint64_t cube_field_bytes;      /* octant cube field of the walk (8 bytes per brick cell; the sun plane is counted in sun_plane_bytes) */
 	uint64_t arena_growths;         /* times the brick arena grew while bricks were resident (pool growth, Scene.cpp:231-251)      */
 	uint64_t arena_copy_growths;    /* ... of which by device synchronisation + reallocation + copy: 0 when the arena is a virtual
 	                                   address range that physical chunks are mapped into (arena_virtual)                        */
@@ -116,6 +116,8 @@ typedef struct bm_scene_info {
 	uint64_t stream_batches;        /* upload batches queued since the residency was last reset                                   */
 	uint64_t stream_host_ns;        /* host time spent staging them (validate, copy bricks to pinned memory, hand out slots, queue) */
 	uint64_t escape_bytes;          /* escape heights of the walk: 8 octants x one 32-bit entry per cell column, in rows padded like the cube field's                    */
+	uint64_t sun_plane_bytes;       /* the sun plane of shadow rays: a ninth plane of the cube field's size (not part of cube_field_bytes) plus the scratch of its
+	                                   builds so far (32 bytes per cell of a slab, 4 per cell column); 0 for a scene that has no ninth plane */
 } bm_scene_info;
 
 /* one voxel edit (bm_scene_edit).  Voxel coordinates are integers; a batch applies its edits in order. */
@@ -222,6 +224,19 @@ BM_API int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capaci
  * in a cell above E is a miss; octants 4-7: the lowest such z, cells_height if none: a miss below E.  *count = entries (8 * cells^2),
  * also when dst is null.  Kept exact by bm_scene_load_voxels, edits and region writes, like the cube field. */
 BM_API int bm_scene_escape_table(bm_scene* scene, int32_t* dst, size_t capacity, size_t* count);
+/* ---- the sun plane: a ninth plane of the cube field that only shadow rays read, built for the cone of ONE sun (the first production frame
+ * that needs it builds it on the device; it is rebuilt before the next such frame after the sun or the world has changed, and scenes
+ * whose ninth plane could not be allocated, suns below the horizon and cones that touch an octant boundary or a diagonal do without).
+ * bm_scene_sun_plane copies the plane as it was last built (waits for the device): dst[(z * X + y) * X + x] over the bordered grid, X =
+ * cells + 2 (border bytes 255), one byte per brick cell -- 0: the cell holds a brick; 255: no ray of the cone can hit anything from here
+ * on; n: no ray of the cone, from anywhere in the cell, enters an occupied cell before one of its axes has moved n cells.  *bytes = the
+ * size needed, 0 when no plane has been built (also when dst is null).  plan12 (may be null) gets the plan it was built for: valid,
+ * octant, dominant axis, minor axes m1 and m2, bins moved per slab along m1 (least, most) and along m2 (least, most), whether clear
+ * heights were built, rise per slab in 1/256 cells, bins per cell. */
+BM_API int bm_scene_sun_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12);
+/* how often the sun plane has been built since the scene was created, and the device time of the last build in ms (0 before the first;
+ * waits for that build) */
+BM_API int bm_scene_sun_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms);
 /* device time of the last batch that changed the scene (hipEvents on the load stream): the scatter (pool moves, bricks, words)
  * and the cube-field update with the escape-height update behind it (0 when no cell's occupancy changed); waits for that batch */
 BM_API int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms);

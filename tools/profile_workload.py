@@ -125,7 +125,12 @@ def main():
     #    exactly what bench.py does with the committed file: the same function, pointed at the new file
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     shutil.copy(os.path.join(OUT, f"{tag}_pmc_summary_{workload}.json"), os.path.join(ROOT, "profiles", f"{tag}_pmc_summary_{workload}.json"))
-    assert bench_mod.PROFILE_ROUNDS[0] == tag, f"bench.py PROFILE_ROUNDS must start with {tag}"
+    if bench_mod.PROFILE_ROUNDS[0] != tag:
+        # a tag bench.py does not read its roofline from (a parent's checkout, a round that leaves bench.py alone): the summary and the kernel
+        # stats above are the result; the bench line is kept as measured, without counter-derived fields
+        json.dump(bench_json, open(os.path.join(OUT, f"{tag}_bench_{workload}.json"), "w"), indent=1)
+        print(f"bench.py reads its counters from round {bench_mod.PROFILE_ROUNDS[0]}, not {tag}: bench line written as measured")
+        return
     rf = bench_json["roofline"]
     rf.update(bench_mod.counter_figures(workload, rf["kernel_ms_per_step"] * 1e-3, sum(rf["frames_per_launch"]) / len(rf["frames_per_launch"])))
     json.dump(bench_json, open(os.path.join(OUT, f"{tag}_bench_{workload}.json"), "w"), indent=1)
