@@ -7,6 +7,7 @@
 #include <vector>
 #include <new>
 
+#include "denoise.h"
 #include "kernels.h"
 #include "scene.h"
 #include "wavefront.h"
@@ -186,6 +187,31 @@ int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t
 		r.reserved = 0;
 	}
 	return 0;
+}
+
+int bm_camera_pixel_rays_device(bm_scene* scene, const bm_camera* camera, int width, int height, bm_ray* rays_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.pixel_rays(camera, width, height, rays_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+// (bm_host_denoise is csrc/denoise_host.cpp: host code that needs nothing of the library)
+int bm_denoise_workspace_bytes(int width, int height, size_t* bytes) {
+	if (!bytes || width < 1 || height < 1 || width > 65535 || height > 65535) { set_error("bm_denoise_workspace_bytes: bad argument"); return BM_EINVAL; }
+	*bytes = bm::denoise_workspace_bytes(width, height);
+	return 0;
+}
+
+int bm_denoise(bm_scene* scene, const bm_denoise_params* params, const float* accum_dev, const bm_ray_hit* hits_dev, float* out_dev, void* workspace_dev,
+			   size_t workspace_bytes, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.denoise(params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_denoise_times(bm_scene* scene, const bm_denoise_params* params, const float* accum_dev, const bm_ray_hit* hits_dev, float* out_dev,
+						   void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms) {
+	BM_NEED(scene);
+	if (!kernel_ms) { set_error("bm_debug_denoise_times: null argument"); return BM_EINVAL; }
+	return scene->impl.denoise(params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
 }
 
 int bm_scene_column_heights(bm_scene* scene, int sx, int sy, float* heights) {

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, denoise.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -113,6 +113,20 @@ void launch_query(const DeviceScene& sc, const int campos[3], const void* rays, 
 int volume_blocks_per_cu(bool any);
 size_t volume_tmp_bytes(uint32_t n);
 void launch_volume_query(const DeviceScene& sc, const void* volumes, void* results, uint32_t n, bool any, uint64_t* tmp, int resident_blocks, hipStream_t stream);
+
+// the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
+// bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.
+// tiled_max_step: a-trous passes up to this stride (1, 2; 0 = none) stage their taps in LDS, the others read them from global memory.
+// marks: null, or 2 + max(iterations, 1) events, recorded before the first kernel and after every kernel (prepare, moments, the passes).
+constexpr int kDenoiseTiledMaxStep = 2;
+void launch_denoise(int width, int height, int iterations, float sigma_l, const float* accum, const void* hits, float* out, void* workspace,
+					int tiled_max_step, hipStream_t stream, hipEvent_t* marks = nullptr);
+// pixel-centre rays of a width x height frame (denoise.hip): width * height bm_ray records; the basis is that of fill_frame_constants
+struct PixelRayBasis {
+	float right[3], up[3], dir[3], origin[3];
+	int width, height;
+};
+void launch_pixel_rays(const PixelRayBasis& basis, void* rays, hipStream_t stream);
 
 // wavefront mode (wavefront.hip)
 int wavefront_blocks_per_cu(bool connect, bool instrumented);

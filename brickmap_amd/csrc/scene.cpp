@@ -14,6 +14,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "denoise.h"
 #include "escape.h"
 #include "kernels.h"
 
@@ -1651,6 +1652,63 @@ int Scene::resolve(const float* accum, float* out, long long n, hipStream_t stre
 	if (!accum || !out || n < 0) { set_error("bad argument"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
 	launch_resolve(accum, out, n, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- the a-trous filter (bm_denoise): image passes on the caller's stream over the caller's buffers; nothing of the world is read
+int Scene::denoise(const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream,
+				   float* kernel_ms) {
+	if (!params || !accum || !hits || !out || !workspace) { set_error("bm_denoise: null argument"); return BM_EINVAL; }
+	const DenoiseParamsView pv = {params->width, params->height, params->iterations, params->sigma_l, params->flags, params->reserved};
+	if (const char* why = denoise_params_problem(pv)) { set_error(std::string("bm_denoise: ") + why); return BM_EINVAL; }
+	const size_t need = denoise_workspace_bytes(params->width, params->height);
+	if (workspace_bytes < need) { set_error("bm_denoise: the workspace is smaller than bm_denoise_workspace_bytes"); return BM_EINVAL; }
+	const uintptr_t pa = reinterpret_cast<uintptr_t>(accum), ph = reinterpret_cast<uintptr_t>(hits), po = reinterpret_cast<uintptr_t>(out), pw = reinterpret_cast<uintptr_t>(workspace);
+	if ((pa | ph | po | pw) % 16 != 0) { set_error("bm_denoise: buffers must be 16-byte aligned"); return BM_EINVAL; }
+	const size_t image = need / 36 * 16;
+	auto overlaps_workspace = [&](uintptr_t p, size_t bytes) { return p < pw + need && pw < p + bytes; };
+	if (overlaps_workspace(pa, image) || overlaps_workspace(po, image) || overlaps_workspace(ph, 2 * image)) { set_error("bm_denoise: the workspace overlaps an image"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	static const int tiled_max_step = [] { // experiment knob: the largest a-trous stride that stages its taps in LDS (0, 1, 2)
+		const char* e = std::getenv("BM_DENOISE_TILED_MAX");
+		return e && *e ? std::atoi(e) : kDenoiseTiledMaxStep;
+	}();
+	if (!kernel_ms) {
+		launch_denoise(params->width, params->height, params->iterations, params->sigma_l, accum, hits, out, workspace, tiled_max_step, stream);
+		BM_HIP(hipGetLastError());
+		return 0;
+	}
+	const int kernels = params->iterations == 0 ? 1 : 2 + params->iterations;
+	Event marks[3 + kDenoiseMaxIterations];
+	hipEvent_t raw[3 + kDenoiseMaxIterations];
+	for (int i = 0; i <= kernels; ++i) {
+		if (int e = marks[i].create(hipEventDefault)) return e;
+		raw[i] = marks[i];
+	}
+	launch_denoise(params->width, params->height, params->iterations, params->sigma_l, accum, hits, out, workspace, tiled_max_step, stream, raw);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventSynchronize(raw[kernels]));
+	for (int i = 0; i < 2 + params->iterations; ++i) kernel_ms[i] = 0.f;
+	for (int i = 0; i < kernels; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
+	return 0;
+}
+
+int Scene::pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream) {
+	if (!cam || !rays || width < 1 || height < 1 || width > 65535 || height > 65535 || reinterpret_cast<uintptr_t>(rays) % 16 != 0) {
+		set_error("bm_camera_pixel_rays_device: bad argument (null, a size outside 1 ... 65535, or rays not 16-byte aligned)");
+		return BM_EINVAL;
+	}
+	// the camera basis of the frames, as bm_camera_pixel_rays takes it
+	bm_frame_params p{};
+	p.width = width; p.height = height; p.spp = 1; p.band_rows = height; p.shard_count = 1;
+	FrameConstants fc;
+	if (int e = fill_frame_constants(cam, &p, &fc)) return e;
+	PixelRayBasis b;
+	for (int k = 0; k < 3; ++k) { b.right[k] = fc.right[k]; b.up[k] = fc.up[k]; b.dir[k] = fc.dir[k]; b.origin[k] = fc.origin[k]; }
+	b.width = width; b.height = height;
+	BM_HIP(hipSetDevice(device_));
+	launch_pixel_rays(b, rays, stream);
 	BM_HIP(hipGetLastError());
 	return 0;
 }

@@ -80,6 +80,12 @@ public:
 	// `count` consecutive frames as one launch (the frame ring, trace.hip); dbgs may be null, and so may any of its entries
 	int render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream);
 	int resolve(const float* accum, float* out, long long n, hipStream_t stream);
+	// the a-trous filter (denoise.hip): the workspace is the caller's, the scene keeps no state for it -- calls on different streams are independent
+	// kernel_ms: null, or 2 + iterations durations -- prepare, moments, every pass (the call then waits; bm_debug_denoise_times)
+	int denoise(const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream,
+				float* kernel_ms = nullptr);
+	// pixel-centre rays of a frame, written on the device (denoise.hip)
+	int pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
 	int synchronize();
 	int last_render_ms(float* ms);
 	int render_times(float* ms, int capacity, int* count); // durations of the most recent launches, oldest first

@@ -335,6 +335,30 @@ def camera_pixel_rays(camera, width, height, px, py):
     return out
 
 
+def denoise_workspace_bytes(width, height):
+    """bm_denoise_workspace_bytes: device memory bm_denoise needs beside its images (36 bytes per pixel)."""
+    n = C.c_size_t(0)
+    check(_lib.load().bm_denoise_workspace_bytes(int(width), int(height), C.byref(n)))
+    return int(n.value)
+
+
+def host_denoise(accum, hits, width=None, height=None, iterations=5, sigma_l=4.0, flags=0, reserved=0):
+    """bm_host_denoise (host only, no device): the a-trous filter of Scene.denoise as plain loops.  accum: float32 [height, width, 4]
+    (R, G, B, n); hits: a RAY_HIT_DTYPE array of height * width records (or float32 [height * width, 8]).  width / height default to
+    accum's shape.  Returns float32 [height, width, 4] = (c, 1)."""
+    accum = np.ascontiguousarray(accum, np.float32)
+    if width is None or height is None:
+        assert accum.ndim == 3 and accum.shape[2] == 4, "accum: [height, width, 4], or pass width and height"
+        height, width = accum.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    n = max(int(width), 0) * max(int(height), 0)
+    assert accum.size == 4 * n and hits.nbytes == 32 * n, "accum: 4 floats per pixel; hits: one 32-byte record per pixel"
+    out = np.zeros((max(int(height), 0), max(int(width), 0), 4), np.float32)
+    par = _lib.bm_denoise_params(int(width), int(height), int(iterations), float(sigma_l), int(flags), int(reserved))
+    check(_lib.load().bm_host_denoise(C.byref(par), accum.ctypes.data, hits.ctypes.data, out.ctypes.data))
+    return out
+
+
 def pack_rays(origins, directions, tmax=None):
     """numpy RAY_DTYPE records from N x 3 origins and directions (tmax: None = unbounded, a scalar, or one per ray)."""
     o = np.asarray(origins, np.float32).reshape(-1, 3)
@@ -751,6 +775,77 @@ class Scene:
                 target.synchronize()
                 out = d_hits.cpu().numpy().view(RAY_HIT_DTYPE).reshape(n)
             return RayHits(out["distance"], out["normal"], out["voxel"], out["level"], out)
+
+    def _target_stream(self, dev, stream):
+        """(target, other): the torch stream a call runs on -- `stream` (a raw handle) or the current one -- made to wait for the work queued
+        on the current stream so far; other: it is not the current stream (inputs then need record_stream)"""
+        import torch
+        current = torch.cuda.current_stream(dev)
+        target = current if stream is None else torch.cuda.ExternalStream(int(stream), device=dev)
+        other = target.cuda_stream != current.cuda_stream
+        if other:
+            target.wait_stream(current)
+        return target, other
+
+    def pixel_rays(self, camera, width, height, stream=None):
+        """bm_camera_pixel_rays_device: the pixel-centre rays of a width x height frame of `camera`, written on the device -- a float32
+        [height * width, 8] CUDA tensor of packed bm_ray records, ray y * width + x through pixel (x, y), bit for bit what
+        camera_pixel_rays gives for (x + 0.5, y + 0.5).  Ready in stream order on `stream` (None = torch's current stream)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        target, _ = self._target_stream(dev, stream)
+        with torch.cuda.stream(target):
+            rays = torch.empty((int(height) * int(width), 8), dtype=torch.float32, device=dev)
+            c = camera.to_c()
+            check(self._L.bm_camera_pixel_rays_device(self.gpuScene, C.byref(c), int(width), int(height), C.c_void_p(rays.data_ptr()), C.c_void_p(target.cuda_stream)))
+        return rays
+
+    def pixel_hits(self, camera, width, height, lod_origin="camera", stream=None):
+        """The first hit of every pixel's centre ray -- the guides of Scene.denoise: rays made on the device (pixel_rays), then cast_rays.
+        lod_origin: "camera" (default) = the frames' LoD rule around the camera position, so the guides see the geometry the frame sees;
+        None = exact (every brick at voxel level); or a point.  Returns RayHits (torch); .packed is the [height * width, 8] record tensor."""
+        if isinstance(lod_origin, str):
+            assert lod_origin == "camera", "lod_origin: 'camera', None or a point"
+            lod_origin = tuple(float(v) for v in camera.position)
+        rays = self.pixel_rays(camera, width, height, stream=stream)
+        return self.cast_rays(rays, lod_origin=lod_origin, stream=stream)
+
+    def _denoise_args(self, accum, hits, width, height, iterations, sigma_l, out, stream):
+        import torch
+        hits = hits.packed if isinstance(hits, RayHits) else hits
+        n = int(width) * int(height)
+        assert accum.is_cuda and accum.dtype == torch.float32 and accum.is_contiguous() and accum.numel() == 4 * n, "accum: float32 [height, width, 4] on the GPU"
+        assert hits.is_cuda and hits.dtype == torch.float32 and hits.is_contiguous() and hits.numel() == 8 * n, "hits: the packed records, float32 [height * width, 8]"
+        target, other = self._target_stream(accum.device, stream)
+        with torch.cuda.stream(target):
+            if out is None:
+                out = torch.empty_like(accum)
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 4 * n, "out: like accum"
+            ws = torch.empty(denoise_workspace_bytes(width, height), dtype=torch.uint8, device=accum.device)
+        if other:
+            for x in (accum, hits, out):
+                x.record_stream(target)
+        par = _lib.bm_denoise_params(int(width), int(height), int(iterations), float(sigma_l), 0, 0)
+        return par, hits, out, ws, target
+
+    def denoise(self, accum, hits, width, height, iterations=5, sigma_l=4.0, out=None, stream=None):
+        """bm_denoise: the edge-avoiding a-trous filter of an accumulation buffer `accum` (float32 [height, width, 4]: R, G, B,
+        n), guided by `hits` (Scene.pixel_hits, or its .packed tensor).  Returns (c, 1) per pixel -- what Scene.resolve takes -- in `out`
+        (None = a new tensor; may be accum itself).  The workspace comes from torch's pool on the stream the filter runs on: `stream` (a raw
+        HIP stream handle; None = torch's current stream), which first waits for the work queued on the current stream.  The host does not wait."""
+        par, hits, out, ws, target = self._denoise_args(accum, hits, width, height, iterations, sigma_l, out, stream)
+        check(self._L.bm_denoise(self.gpuScene, C.byref(par), C.c_void_p(accum.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_void_p(out.data_ptr()),
+                                 C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(target.cuda_stream)))
+        return out
+
+    def denoise_times(self, accum, hits, width, height, iterations=5, sigma_l=4.0, out=None, stream=None):
+        """bm_debug_denoise_times: Scene.denoise with a hipEvent between its kernels; waits.  Returns (out, [ms of prepare, the variance pass,
+        every a-trous pass])."""
+        par, hits, out, ws, target = self._denoise_args(accum, hits, width, height, iterations, sigma_l, out, stream)
+        ms = (C.c_float * (2 + max(int(iterations), 0)))()
+        check(self._L.bm_debug_denoise_times(self.gpuScene, C.byref(par), C.c_void_p(accum.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(target.cuda_stream), ms))
+        return out, [float(v) for v in ms]
 
     def pick(self, camera, x, y, width, height, lod_origin=None):
         """The voxel under pixel (x, y) of a width x height frame of `camera`: one ray through the pixel's centre, one query, then the host

@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -13,6 +13,8 @@
 // unresolved (level 3) digs nothing.
 // --ground x,y prints the height of the highest solid voxel of that column after the digging (one box query, Scene::query_volume): the
 // world streams, so bricks that are not resident yet are reported as unresolved cells, not counted.
+// --denoise filters the accumulated frame before the resolve (Scene::denoise: the a-trous filter guided by the first hits of the
+// pixel-centre rays, Scene::pixel_rays + Scene::cast_rays with the frames' LoD rule around the camera) -- for runs of a few frames.
 // With `wavefront` the frames are rendered with the reference's own queue schedule (one segment per call); with `ring` the
 // world is made resident first and all frames are ONE launch of the persistent kernel (launch_frames, the frame ring).
 #include <cstdint>
@@ -32,9 +34,14 @@ int main(int argc_in, char** argv_in) {
 	int dig_at[3] = {0, 0, -1};
 	int ground[2] = {-1, -1};
 	const char* voxels_path = nullptr;
+	bool denoise = false;
 	std::string paste_path;
 	int paste_size[3] = {0, 0, 0}, paste_at[3] = {0, 0, 0};
 	for (int i = 0; i < argc_in; ++i) {
+		if (std::string(argv_in[i]) == "--denoise") {
+			denoise = true;
+			continue;
+		}
 		if (std::string(argv_in[i]) == "--voxels" && i + 1 < argc_in) {
 			voxels_path = argv_in[++i];
 			continue;
@@ -157,8 +164,22 @@ int main(int argc_in, char** argv_in) {
 	// blit_onto_framebuffer (kernel.cu:348-364) into an offscreen buffer instead of the GL surface
 	void* resolved = nullptr;
 	BM_CHECKED(bm_buffer_alloc(0, width * height * sizeof(vec4), &resolved));
-	BM_CHECKED(bm_resolve(scene.gpuScene.handle, reinterpret_cast<const float*>(state.blit_buffer), static_cast<float*>(resolved),
-						  static_cast<int64_t>(width * height), nullptr));
+	const float* to_resolve = reinterpret_cast<const float*>(state.blit_buffer);
+	void* guides = nullptr; // rays, then hits, then the filter's workspace; the filtered frame goes to `resolved`, which is then resolved in place
+	if (denoise) {
+		const int w = static_cast<int>(width), h = static_cast<int>(height);
+		const size_t n = width * height, ws_bytes = Scene::denoise_workspace_bytes(w, h);
+		BM_CHECKED(bm_buffer_alloc(0, n * (sizeof(bm_ray) + sizeof(bm_ray_hit)) + ws_bytes, &guides));
+		bm_ray* rays = static_cast<bm_ray*>(guides);
+		bm_ray_hit* hits = reinterpret_cast<bm_ray_hit*>(rays + n);
+		const float lod_origin[3] = {camera.position.x, camera.position.y, camera.position.z};
+		scene.pixel_rays(camera, w, h, rays);
+		scene.cast_rays(static_cast<int64_t>(n), rays, hits, BM_QUERY_LOD | BM_QUERY_NO_REQUESTS, lod_origin);
+		scene.denoise(w, h, to_resolve, hits, static_cast<float*>(resolved), hits + n, ws_bytes);
+		to_resolve = static_cast<const float*>(resolved);
+		std::cout << "denoised: 5 a-trous iterations, sigma_l 4\n";
+	}
+	BM_CHECKED(bm_resolve(scene.gpuScene.handle, to_resolve, static_cast<float*>(resolved), static_cast<int64_t>(width * height), nullptr));
 	std::vector<vec4> host(width * height);
 	BM_CHECKED(bm_buffer_read(0, host.data(), resolved, host.size() * sizeof(vec4)));
 	std::ofstream f(out, std::ios::binary);
@@ -173,5 +194,6 @@ int main(int argc_in, char** argv_in) {
 	BM_CHECKED(bm_scene_get_info(scene.gpuScene.handle, &info));
 	std::cout << "wrote " << out << ": " << frames << " frames, " << info.resident_bricks << " of " << info.total_bricks << " bricks resident\n";
 	bm_buffer_free(0, resolved);
+	if (guides) bm_buffer_free(0, guides);
 	return 0;
 }

@@ -344,6 +344,54 @@ BM_API int bm_scene_cast_rays(bm_scene* scene, int64_t n, const bm_ray* rays_dev
  * frames; tmax = +inf. */
 BM_API int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t n, const float* px, const float* py, bm_ray* out);
 
+/* the same rays for EVERY pixel of a width x height frame, written on the device: ray y * width + x passes through the centre of pixel
+ * (x, y), bit for bit what bm_camera_pixel_rays gives for (x + 0.5, y + 0.5) -- same operation order, tmax = +inf.  rays_dev: width * height
+ * records of device memory, 16-byte aligned.  Asynchronous on hip_stream; reads nothing of the world.  (What a frame's guide query would
+ * otherwise build on the host and upload: two million rays per 1080p frame.) */
+BM_API int bm_camera_pixel_rays_device(bm_scene* scene, const bm_camera* camera, int width, int height, bm_ray* rays_dev, void* hip_stream);
+
+/* ---- denoising a frame of few samples (no reference counterpart: the reference only accumulates, so a moving camera shows raw 1-spp
+ * noise): an edge-avoiding a-trous filter guided by the first hit of every pixel's centre ray (bm_camera_pixel_rays_device +
+ * bm_scene_cast_rays with BM_QUERY_LOD around the camera: the geometry the frame sees).  All arithmetic is fp32 IEEE + - * / sqrt in a
+ * fixed order, without contraction, so bm_denoise and bm_host_denoise agree bit for bit (csrc/denoise.h holds the rules once).
+ * Per pixel of the width x height image, row-major: the accumulation value (R, G, B, n) and one bm_ray_hit.
+ *  - radiance c = (R/n, G/n, B/n) when n > 0, else 0; luminance l(c) = (0.2126 r + 0.7152 g) + 0.0722 b.
+ *  - surface key: a pixel is SPECIAL when n <= 0, level is -1 or 3, or the normal is (0, 0, 0); else, with a = the first axis whose normal
+ *    component is not zero, s = normal[a] > 0 and size = 1 / 4 / 8 for levels 2 / 1 / 0: plane = voxel[a] + (s ? size : 0), the plane of
+ *    the entry face, and key = plane * 8 + a * 2 + s.  Pixels that see one face plane from one side share a key, whatever their LoD.
+ *  - special pixels are never filtered and never a tap: their output is (c, 1).
+ *  - a tap q of pixel p counts when it lies inside the image and key_q == key_p; other taps are skipped (nothing is added).  Every sum
+ *    runs left to right within a row of taps starting from 0.0f; the row sums are added top to bottom onto 0.0f.
+ *  - variance pass, 7 x 7 taps at stride 1: N = taps, S1 = sum l_q, S2 = sum l_q * l_q, var_p = max(0, S2/N - (S1/N) * (S1/N)).
+ *  - a-trous pass i = 0 ... iterations - 1, 5 x 5 taps at stride 2^i, h = (1/16, 1/4, 3/8, 1/4, 1/16): den_p = sigma_l * sqrt(var_p) + 1e-4;
+ *    per tap x = |l(c_p) - l(c_q)| / den_p, t = 1 + x, w = (h[dy] * h[dx]) / (t * t); W += w, C += w * c_q, V += (w * w) * var_q;
+ *    then c_p = C / W, var_p = V / (W * W).
+ *  - output (c, 1) per pixel, so bm_resolve takes it unchanged; iterations == 0 gives the unfiltered (c, 1).
+ * The guides of a gathered frame: denoise the whole frame, not a row shard of it. */
+typedef struct bm_denoise_params {
+	int32_t width, height;
+	int32_t iterations;   /* 0 ... 8; 5 is a good default */
+	float sigma_l;        /* finite, > 0; 4 is a good default */
+	uint32_t flags;       /* 0 */
+	uint32_t reserved;    /* 0 */
+} bm_denoise_params;
+/* bytes of device memory bm_denoise needs beside its images: two float4 images and the keys, 36 bytes per pixel */
+BM_API int bm_denoise_workspace_bytes(int width, int height, size_t* bytes);
+/* accum_dev: width * height float4 (R, G, B, n) as bm_render_frame leaves them; hits_dev: one bm_ray_hit per pixel; out_dev: width * height
+ * float4, may be accum_dev itself; workspace_dev: the caller's, not used by anything else until the call has finished on its stream -- the
+ * scene holds no state for a denoise, so calls on different streams with workspaces of their own are independent.  Asynchronous on
+ * hip_stream like bm_resolve.  Refused with BM_EINVAL, launching nothing: iterations outside 0 ... 8, sigma_l not finite or <= 0, width or
+ * height < 1 or > 65535, non-zero flags or reserved, a NULL buffer, a workspace smaller than bm_denoise_workspace_bytes, a buffer that is
+ * not 16-byte aligned, a workspace that overlaps an image. */
+BM_API int bm_denoise(bm_scene* scene, const bm_denoise_params* params, const float* accum_dev, const bm_ray_hit* hits_dev, float* out_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+/* measuring door: bm_denoise with a hipEvent between its kernels; waits, then kernel_ms[0 ... 1 + iterations] = the durations in ms of
+ * prepare, the variance pass and every a-trous pass (iterations == 0: prepare alone, the second entry 0) */
+BM_API int bm_debug_denoise_times(bm_scene* scene, const bm_denoise_params* params, const float* accum_dev, const bm_ray_hit* hits_dev, float* out_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms);
+/* the same filter on host memory, as plain loops (no device needed); the refusals of bm_denoise that concern params and NULL buffers */
+BM_API int bm_host_denoise(const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out);
+
 /* ---- volume queries against the live scene (no reference counterpart): how much is solid in a box or a sphere, and where.
  * Is this box free, how much does this sphere hold, where is the ground under this column, how far can this box move before it
  * touches something -- questions a ray, which has no width, answers badly.  For each of n records in device memory: the number of

@@ -155,6 +155,24 @@ public:
 				   void* hip_stream = nullptr) {
 		BM_CHECKED(bm_scene_cast_rays(gpuScene.handle, n, rays_dev, hits_dev, flags, lod_origin, hip_stream));
 	}
+	// the pixel-centre rays of a width x height frame of `cam`, written on the device (bm_camera_pixel_rays_device): width * height records
+	void pixel_rays(const Camera& cam, int width, int height, bm_ray* rays_dev, void* hip_stream = nullptr) {
+		const bm_camera c = cam.to_c();
+		BM_CHECKED(bm_camera_pixel_rays_device(gpuScene.handle, &c, width, height, rays_dev, hip_stream));
+	}
+	// the edge-avoiding a-trous filter of a frame of few samples (no counterpart in the reference; bm_denoise): accum_dev = (R, G, B, n) per
+	// pixel, hits_dev = the first hit of every pixel's centre ray (pixel_rays + cast_rays with BM_QUERY_LOD around the camera), out_dev =
+	// (c, 1) per pixel, which bm_resolve takes (may be accum_dev); workspace_dev: denoise_workspace_bytes() bytes of the caller's
+	static size_t denoise_workspace_bytes(int width, int height) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_denoise_workspace_bytes(width, height, &bytes));
+		return bytes;
+	}
+	void denoise(int width, int height, const float* accum_dev, const bm_ray_hit* hits_dev, float* out_dev, void* workspace_dev, size_t workspace_bytes,
+				 int iterations = 5, float sigma_l = 4.f, void* hip_stream = nullptr) {
+		const bm_denoise_params p = {width, height, iterations, sigma_l, 0u, 0u};
+		BM_CHECKED(bm_denoise(gpuScene.handle, &p, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, hip_stream));
+	}
 	// the hit under pixel (x, y) of a width x height frame of `cam`: one ray through the pixel's centre, one query, then the host waits.
 	// level -1 = nothing there; level 3 = the brick is not resident yet (service the load queue, pick again)
 	bm_ray_hit pick(const Camera& cam, int width, int height, int x, int y) {
