@@ -75,6 +75,10 @@ class bm_ray_hit(C.Structure):
     _fields_ = [("distance", C.c_float), ("normal", C.c_float * 3), ("voxel", C.c_int32 * 3), ("level", C.c_int32)]
 
 
+class bm_reproject_params(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_history", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class bm_denoise_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("sigma_l", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -162,6 +166,9 @@ SIGNATURES = {
     "bm_denoise": (_i, [_vp, C.POINTER(bm_denoise_params), _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bm_debug_denoise_times": (_i, [_vp, C.POINTER(bm_denoise_params), _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_float)]),
     "bm_host_denoise": (_i, [C.POINTER(bm_denoise_params), _vp, _vp, _vp]),
+    "bm_history_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),
+    "bm_reproject": (_i, [_vp, C.POINTER(bm_reproject_params), C.POINTER(bm_camera), C.POINTER(bm_camera), _vp, _vp, _vp, _vp, _vp]),
+    "bm_host_reproject": (_i, [C.POINTER(bm_reproject_params), C.POINTER(bm_camera), C.POINTER(bm_camera), _vp, _vp, _vp, _vp]),
     "bm_host_column_heights": (_i, [_i, _i, _i, _i, _vp]),
     "bm_host_generate_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32]),
     "bm_host_edit_supercell": (_i, [_i, _i, _i, _i, _i, _vp, _u32p, _vp, C.c_uint32, _i, C.POINTER(bm_edit)]),

@@ -7,8 +7,10 @@
 #include <vector>
 #include <new>
 
+#include "camera_rays.h"
 #include "denoise.h"
 #include "kernels.h"
+#include "reproject.h"
 #include "scene.h"
 #include "wavefront.h"
 
@@ -171,18 +173,9 @@ int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t
 	if (int e = bm::Scene::fill_frame_constants(camera, &p, &fc)) return e;
 	const float W = static_cast<float>(width), H = static_cast<float>(height);
 	for (int64_t i = 0; i < n; ++i) {
-		// primary_ray (csrc/traverse.h) with the jitter (jx, jy) replaced: pixel x covers ppx in (x - 1, x], so ppx = px - 1
-		const float ppx = px[i] - 1.f, ppy = py[i] - 1.f;
-		const float ni = (ppx / W) - 0.5f;
-		const float nj = ((H - ppy) / H) - 0.5f;
-		float v[3];
-		for (int k = 0; k < 3; ++k) v[k] = (fc.dir[k] + fc.right[k] * ni) + fc.up[k] * nj;
-		const float inv = 1.0f / std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
 		bm_ray& r = out[i];
-		for (int k = 0; k < 3; ++k) {
-			r.origin[k] = fc.origin[k];
-			r.direction[k] = v[k] * inv;
-		}
+		bm::pixel_ray_direction(fc.dir, fc.right, fc.up, W, H, px[i], py[i], r.direction); // (csrc/camera_rays.h: the rule, written once)
+		for (int k = 0; k < 3; ++k) r.origin[k] = fc.origin[k];
 		r.tmax = std::numeric_limits<float>::infinity();
 		r.reserved = 0;
 	}
@@ -212,6 +205,19 @@ int bm_debug_denoise_times(bm_scene* scene, const bm_denoise_params* params, con
 	BM_NEED(scene);
 	if (!kernel_ms) { set_error("bm_debug_denoise_times: null argument"); return BM_EINVAL; }
 	return scene->impl.denoise(params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+}
+
+// (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)
+int bm_history_bytes(int width, int height, size_t* bytes) {
+	if (!bytes || width < 1 || height < 1 || width > 65535 || height > 65535) { set_error("bm_history_bytes: bad argument"); return BM_EINVAL; }
+	*bytes = bm::history_bytes(width, height);
+	return 0;
+}
+
+int bm_reproject(bm_scene* scene, const bm_reproject_params* params, const bm_camera* camera, const bm_camera* camera_prev, const float* accum_dev,
+				 const bm_ray_hit* hits_dev, const void* history_prev_dev, void* history_out_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.reproject(params, camera, camera_prev, accum_dev, hits_dev, history_prev_dev, history_out_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 int bm_scene_column_heights(bm_scene* scene, int sx, int sy, float* heights) {

@@ -12,6 +12,7 @@
 // A staged pixel outside the image gets the special key, which no filtered pixel carries: the bounds test of a tap is its key test.
 #include "denoise.h"
 
+#include "camera_rays.h"
 #include "kernels.h"
 
 namespace bm {
@@ -185,24 +186,18 @@ __global__ __launch_bounds__(kThreads) void denoise_atrous_far(const float4* __r
 	dst[p] = v;
 }
 
-// ray i = y * width + x: the frames' primary ray through the centre of pixel (x, y) without jitter and lens, in the operation order
-// of bm_camera_pixel_rays (capi.cpp) with px = x + 0.5, py = y + 0.5; two float4 per ray (origin, direction.x | direction.y, direction.z, tmax, reserved)
+// ray i = y * width + x: the frames' primary ray through the centre of pixel (x, y) without jitter and lens -- pixel_ray_direction
+// (camera_rays.h), which bm_camera_pixel_rays (capi.cpp) calls as well, with px = x + 0.5, py = y + 0.5; two float4 per ray (origin, direction.x | direction.y, direction.z, tmax, reserved)
 __global__ __launch_bounds__(kThreads) void pixel_rays(const PixelRayBasis b, float4* __restrict__ rays, size_t n) {
 	const size_t i = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x;
 	if (i >= n) return;
 	const uint32_t width = static_cast<uint32_t>(b.width);
 	const uint32_t y = static_cast<uint32_t>(i / width), x = static_cast<uint32_t>(i - static_cast<size_t>(y) * width);
 	const float W = static_cast<float>(b.width), H = static_cast<float>(b.height);
-	const float px = static_cast<float>(x) + 0.5f, py = static_cast<float>(y) + 0.5f;
-	const float ppx = px - 1.f, ppy = py - 1.f;
-	const float ni = (ppx / W) - 0.5f;
-	const float nj = ((H - ppy) / H) - 0.5f;
-	float v[3];
-#pragma unroll
-	for (int k = 0; k < 3; ++k) v[k] = (b.dir[k] + b.right[k] * ni) + b.up[k] * nj;
-	const float inv = 1.0f / sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-	rays[2 * i] = make_float4(b.origin[0], b.origin[1], b.origin[2], v[0] * inv);
-	rays[2 * i + 1] = make_float4(v[1] * inv, v[2] * inv, __int_as_float(0x7F800000), 0.f);
+	float d[3];
+	pixel_ray_direction(b.dir, b.right, b.up, W, H, static_cast<float>(x) + 0.5f, static_cast<float>(y) + 0.5f, d);
+	rays[2 * i] = make_float4(b.origin[0], b.origin[1], b.origin[2], d[0]);
+	rays[2 * i + 1] = make_float4(d[1], d[2], __int_as_float(0x7F800000), 0.f);
 }
 
 // ---- host-callable launchers (kernels.h)

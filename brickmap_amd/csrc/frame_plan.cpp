@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "camera_rays.h"
 #include "scene.h"
 
 namespace bm {
@@ -136,16 +137,12 @@ int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_
 	// do at this point (helper lanes work with either: atomic_acc = HELP)
 	if (!ordered && promoted.spp >= 2 && tickets_fit(true)) promoted.flags |= BM_FLAG_SAMPLE_ITEMS;
 	std::memset(fc, 0, sizeof *fc);
-	const V3 dir{cam->direction[0], cam->direction[1], cam->direction[2]};
-	const V3 upv{cam->up[0], cam->up[1], cam->up[2]};
-	const float aspect = static_cast<float>(fp->width) / static_cast<float>(fp->height);
-	const V3 right = (normalize3(cross3(dir, upv)) * 1.5f) * aspect;   // launch_kernels:384
-	const V3 up = normalize3(cross3(right, dir)) * 1.5f;               // launch_kernels:385
-	fc->right[0] = right.x; fc->right[1] = right.y; fc->right[2] = right.z;
-	fc->up[0] = up.x; fc->up[1] = up.y; fc->up[2] = up.z;
+	const CameraBasis basis = camera_basis(cam->position, cam->direction, cam->up, fp->width, fp->height); // launch_kernels:384-385
 	for (int i = 0; i < 3; ++i) {
-		fc->dir[i] = cam->direction[i];
-		fc->origin[i] = cam->position[i];
+		fc->right[i] = basis.right[i];
+		fc->up[i] = basis.up[i];
+		fc->dir[i] = basis.dir[i];
+		fc->origin[i] = basis.origin[i];
 		fc->campos[i] = static_cast<int>(cam->position[i] / 8.f); // kernel.cu:418
 	}
 	fc->focal3 = cam->focal_distance * 3; // kernel.cu:191-192 (int 3)

@@ -1,10 +1,11 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, denoise.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
+#include "reproject.h"
 #include "sunfield.h"
 
 namespace bm {
@@ -127,6 +128,16 @@ struct PixelRayBasis {
 	int width, height;
 };
 void launch_pixel_rays(const PixelRayBasis& basis, void* rays, hipStream_t stream);
+// temporal accumulation (reproject.hip; reproject.h has the rules): accum and hits of the frame of camera `cur`, the history of the frame
+// of camera `prev` (history_prev, or null: no history) -> history_out; a history is history_bytes() bytes, every pointer 16-byte aligned,
+// history_out overlaps no input.  Both bases travel by value as a kernel argument.
+struct ReprojectCameras {
+	CameraBasis cur;
+	RpPrevCamera prev;
+	int width, height;
+};
+void launch_reproject(const ReprojectCameras& cams, float max_history, const float* accum, const void* hits, const void* history_prev, void* history_out,
+					  hipStream_t stream);
 
 // wavefront mode (wavefront.hip)
 int wavefront_blocks_per_cu(bool connect, bool instrumented);

@@ -14,6 +14,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "camera_rays.h"
 #include "denoise.h"
 #include "escape.h"
 #include "kernels.h"
@@ -1709,6 +1710,34 @@ int Scene::pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays,
 	b.width = width; b.height = height;
 	BM_HIP(hipSetDevice(device_));
 	launch_pixel_rays(b, rays, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- temporal accumulation (bm_reproject): like the filter, nothing of the world is read and nothing is kept
+int Scene::reproject(const bm_reproject_params* params, const bm_camera* cam, const bm_camera* cam_prev, const float* accum, const bm_ray_hit* hits,
+					 const void* history_prev, void* history_out, hipStream_t stream) {
+	if (!params || !cam || !accum || !hits || !history_out) { set_error("bm_reproject: null argument"); return BM_EINVAL; }
+	if (history_prev && !cam_prev) { set_error("bm_reproject: a previous history needs the camera it was made with"); return BM_EINVAL; }
+	const ReprojectParamsView pv = {params->width, params->height, params->max_history, params->flags, params->reserved};
+	if (const char* why = reproject_params_problem(pv)) { set_error(std::string("bm_reproject: ") + why); return BM_EINVAL; }
+	const uintptr_t pa = reinterpret_cast<uintptr_t>(accum), ph = reinterpret_cast<uintptr_t>(hits), pp = reinterpret_cast<uintptr_t>(history_prev),
+					po = reinterpret_cast<uintptr_t>(history_out);
+	if ((pa | ph | pp | po) % 16 != 0) { set_error("bm_reproject: buffers must be 16-byte aligned"); return BM_EINVAL; }
+	const size_t history = history_bytes(params->width, params->height), image = history / 20 * 16;
+	auto overlaps_out = [&](uintptr_t p, size_t bytes) { return p < po + history && po < p + bytes; };
+	if ((history_prev && overlaps_out(pp, history)) || overlaps_out(pa, image) || overlaps_out(ph, 2 * image)) {
+		set_error("bm_reproject: history_out overlaps an input (taps read neighbours: ping-pong two histories)");
+		return BM_EINVAL;
+	}
+	ReprojectCameras cams;
+	cams.cur = camera_basis(cam->position, cam->direction, cam->up, params->width, params->height);
+	// (without a history the previous camera is not read; the current one stands in so that the argument holds defined values)
+	const bm_camera* before = history_prev ? cam_prev : cam;
+	cams.prev = reproject_prev_camera(camera_basis(before->position, before->direction, before->up, params->width, params->height));
+	cams.width = params->width; cams.height = params->height;
+	BM_HIP(hipSetDevice(device_));
+	launch_reproject(cams, params->max_history, accum, hits, history_prev, history_out, stream);
 	BM_HIP(hipGetLastError());
 	return 0;
 }

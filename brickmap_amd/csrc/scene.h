@@ -86,6 +86,9 @@ public:
 				float* kernel_ms = nullptr);
 	// pixel-centre rays of a frame, written on the device (denoise.hip)
 	int pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
+	// temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers; the scene keeps no state for it
+	int reproject(const bm_reproject_params* params, const bm_camera* cam, const bm_camera* cam_prev, const float* accum, const bm_ray_hit* hits, const void* history_prev,
+				  void* history_out, hipStream_t stream);
 	int synchronize();
 	int last_render_ms(float* ms);
 	int render_times(float* ms, int capacity, int* count); // durations of the most recent launches, oldest first

@@ -8,7 +8,7 @@ C-ABI of libbrickmap_hip.so; torch only provides device tensors and streams.
 import ctypes as C
 import math
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -356,6 +356,53 @@ def host_denoise(accum, hits, width=None, height=None, iterations=5, sigma_l=4.0
     out = np.zeros((max(int(height), 0), max(int(width), 0), 4), np.float32)
     par = _lib.bm_denoise_params(int(width), int(height), int(iterations), float(sigma_l), int(flags), int(reserved))
     check(_lib.load().bm_host_denoise(C.byref(par), accum.ctypes.data, hits.ctypes.data, out.ctypes.data))
+    return out
+
+
+def history_bytes(width, height):
+    """bm_history_bytes: bytes of a history of Scene.reproject -- a float4 image, then the surface keys (20 bytes per pixel)."""
+    n = C.c_size_t(0)
+    check(_lib.load().bm_history_bytes(int(width), int(height), C.byref(n)))
+    return int(n.value)
+
+
+class History:
+    """A history of Scene.reproject / host_reproject: `buffer`, 5 * height * width 32-bit words (a float32 torch CUDA tensor or numpy
+    array), and two views of it -- `image`, float32 [height, width, 4] = (R, G, B, n), an accumulation buffer that Scene.denoise and
+    Scene.resolve take unchanged, and `keys`, the surface keys [height, width] (torch: int32 bits; numpy: uint32)."""
+
+    def __init__(self, buffer, width, height):
+        n = int(width) * int(height)
+        assert buffer.ndim == 1 and buffer.shape[0] == 5 * n, "a history: 5 float32 words per pixel"
+        self.buffer, self.width, self.height = buffer, int(width), int(height)
+        self.image = buffer[:4 * n].reshape(int(height), int(width), 4)
+        if isinstance(buffer, np.ndarray):
+            self.keys = buffer[4 * n:].view(np.uint32).reshape(int(height), int(width))
+        else:
+            import torch
+            self.keys = buffer[4 * n:].view(torch.int32).reshape(int(height), int(width))
+
+
+def host_reproject(accum, hits, camera, prev_camera=None, history_prev=None, width=None, height=None, max_history=32.0, flags=0, reserved=0):
+    """bm_host_reproject (host only, no device): the temporal accumulation of Scene.reproject as plain loops.  accum: float32 [height,
+    width, 4] (R, G, B, n) of the frame of `camera`; hits: a RAY_HIT_DTYPE array of height * width records; history_prev: the History
+    (numpy) of the frame of `prev_camera`, or None.  width / height default to accum's shape.  Returns a History (numpy)."""
+    accum = np.ascontiguousarray(accum, np.float32)
+    if width is None or height is None:
+        assert accum.ndim == 3 and accum.shape[2] == 4, "accum: [height, width, 4], or pass width and height"
+        height, width = accum.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    n = max(int(width), 0) * max(int(height), 0)
+    assert accum.size == 4 * n and hits.nbytes == 32 * n, "accum: 4 floats per pixel; hits: one 32-byte record per pixel"
+    prev = None
+    if history_prev is not None:
+        prev = np.ascontiguousarray(history_prev.buffer if isinstance(history_prev, History) else history_prev, np.float32)
+        assert prev.size == 5 * n, "history_prev: 5 words per pixel"
+    out = History(np.zeros(5 * n, np.float32), max(int(width), 0), max(int(height), 0))
+    par = _lib.bm_reproject_params(int(width), int(height), float(max_history), int(flags), int(reserved))
+    c, cp = camera.to_c(), (prev_camera.to_c() if prev_camera is not None else None)
+    check(_lib.load().bm_host_reproject(C.byref(par), C.byref(c), C.byref(cp) if cp is not None else None, accum.ctypes.data, hits.ctypes.data,
+                                        prev.ctypes.data if prev is not None else None, out.buffer.ctypes.data))
     return out
 
 
@@ -847,6 +894,34 @@ class Scene:
                                              C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(target.cuda_stream), ms))
         return out, [float(v) for v in ms]
 
+    def reproject(self, accum, hits, camera, prev_camera, history_prev, width, height, max_history=32.0, out=None, stream=None):
+        """bm_reproject: temporal accumulation for a moving camera.  `accum` (float32 [height, width, 4]: R, G, B, n) is the
+        frame just rendered with `camera`, `hits` its guides (Scene.pixel_hits, or its .packed tensor); `history_prev` is the History of the
+        frame before, rendered with `prev_camera`, or None (no history: the result is accum and its keys).  Returns the new History -- `out`,
+        or a new one; never history_prev itself: the taps read neighbours, so two histories take turns.  Its .image is an accumulation buffer
+        of up to max_history + the frame's own samples per pixel, which Scene.denoise and Scene.resolve take.  Stream handling as in
+        Scene.denoise; the host does not wait."""
+        import torch
+        hits = hits.packed if isinstance(hits, RayHits) else hits
+        n = int(width) * int(height)
+        assert accum.is_cuda and accum.dtype == torch.float32 and accum.is_contiguous() and accum.numel() == 4 * n, "accum: float32 [height, width, 4] on the GPU"
+        assert hits.is_cuda and hits.dtype == torch.float32 and hits.is_contiguous() and hits.numel() == 8 * n, "hits: the packed records, float32 [height * width, 8]"
+        assert history_prev is None or (history_prev.buffer.is_cuda and history_prev.buffer.numel() == 5 * n), "history_prev: a History of this size on the GPU"
+        target, other = self._target_stream(accum.device, stream)
+        with torch.cuda.stream(target):
+            if out is None:
+                out = History(torch.empty(5 * n, dtype=torch.float32, device=accum.device), width, height)
+        assert out.buffer.is_cuda and out.buffer.dtype == torch.float32 and out.buffer.numel() == 5 * n, "out: a History of this size on the GPU"
+        if other:
+            for x in (accum, hits, out.buffer) + ((history_prev.buffer,) if history_prev is not None else ()):
+                x.record_stream(target)
+        par = _lib.bm_reproject_params(int(width), int(height), float(max_history), 0, 0)
+        c, cp = camera.to_c(), (prev_camera.to_c() if prev_camera is not None else None)
+        check(self._L.bm_reproject(self.gpuScene, C.byref(par), C.byref(c), C.byref(cp) if cp is not None else None, C.c_void_p(accum.data_ptr()),
+                                   C.c_void_p(hits.data_ptr()), C.c_void_p(history_prev.buffer.data_ptr()) if history_prev is not None else None,
+                                   C.c_void_p(out.buffer.data_ptr()), C.c_void_p(target.cuda_stream)))
+        return out
+
     def pick(self, camera, x, y, width, height, lod_origin=None):
         """The voxel under pixel (x, y) of a width x height frame of `camera`: one ray through the pixel's centre, one query, then the host
         waits.  Returns a RayHit, or None on a miss.  (A level-3 hit means the brick is not resident yet: service the load queue and pick again.)"""
@@ -1026,6 +1101,38 @@ class Scene:
         check(self._L.bm_resolve(self.gpuScene, C.c_void_p(accum.data_ptr()), C.c_void_p(out.data_ptr()), accum.numel() // 4,
                                  C.c_void_p(stream)))
         return out
+
+
+class TemporalAccumulator:
+    """Temporal accumulation over the frames of a moving camera: owns two histories, which take turns, and the previous camera.
+    add(camera, accum, hits=None) reprojects the history of the frame before into the frame just rendered (`accum`, 1 spp or a few into a
+    zeroed buffer; hits: its guides, made with Scene.pixel_hits when not given) and returns the new history's image -- an accumulation
+    buffer of up to max_history + the frame's own samples per pixel, for Scene.denoise and Scene.resolve; it stays valid until the
+    add after the next.  reset() forgets the history: after a moved sun or an edit, which change the light without changing a key."""
+
+    def __init__(self, scene, width, height, max_history=32.0):
+        self.scene, self.width, self.height, self.max_history = scene, int(width), int(height), float(max_history)
+        self._histories = [None, None]
+        self._turn = 0
+        self._camera = None  # of the newest history; None = no history
+
+    def reset(self):
+        self._camera = None
+
+    @property
+    def history(self):
+        """the newest History, or None"""
+        return self._histories[self._turn ^ 1] if self._camera is not None else None
+
+    def add(self, camera, accum, hits=None):
+        if hits is None:
+            hits = self.scene.pixel_hits(camera, self.width, self.height)
+        out = self.scene.reproject(accum, hits, camera, self._camera, self.history, self.width, self.height, self.max_history,
+                                   out=self._histories[self._turn])
+        self._histories[self._turn] = out
+        self._turn ^= 1
+        self._camera = replace(camera)
+        return out.image
 
 
 # numpy views of the queue records (variables.h:43-52 RayQueue, :54-59 ShadowQueue)

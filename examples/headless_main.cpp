@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -15,8 +15,13 @@
 // world streams, so bricks that are not resident yet are reported as unresolved cells, not counted.
 // --denoise filters the accumulated frame before the resolve (Scene::denoise: the a-trous filter guided by the first hits of the
 // pixel-centre rays, Scene::pixel_rays + Scene::cast_rays with the frames' LoD rule around the camera) -- for runs of a few frames.
+// --temporal moves the camera: it advances by a fixed small step (half a voxel sideways) per frame, every frame is 1 spp with samples of
+// its own into a zeroed buffer and is reprojected into the history of the frames before (Scene::reproject: the samples of earlier
+// frames carried to where the same surface point is now, tested by exact surface keys); the last history is what --denoise and the
+// resolve get.  Not with `wavefront` or `ring`.
 // With `wavefront` the frames are rendered with the reference's own queue schedule (one segment per call); with `ring` the
 // world is made resident first and all frames are ONE launch of the persistent kernel (launch_frames, the frame ring).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <fstream>
@@ -34,12 +39,16 @@ int main(int argc_in, char** argv_in) {
 	int dig_at[3] = {0, 0, -1};
 	int ground[2] = {-1, -1};
 	const char* voxels_path = nullptr;
-	bool denoise = false;
+	bool denoise = false, temporal = false;
 	std::string paste_path;
 	int paste_size[3] = {0, 0, 0}, paste_at[3] = {0, 0, 0};
 	for (int i = 0; i < argc_in; ++i) {
 		if (std::string(argv_in[i]) == "--denoise") {
 			denoise = true;
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--temporal") {
+			temporal = true;
 			continue;
 		}
 		if (std::string(argv_in[i]) == "--voxels" && i + 1 < argc_in) {
@@ -145,7 +154,44 @@ int main(int argc_in, char** argv_in) {
 					static_cast<unsigned long long>(column.solid), column.unresolved);
 	}
 
-	if (wavefront) {
+	if (temporal && (wavefront || ring)) {
+		std::cerr << "--temporal renders its frames one by one: not with wavefront or ring\n";
+		return 2;
+	}
+	const int w = static_cast<int>(width), h = static_cast<int>(height);
+	const size_t n_pixels = width * height;
+	const float* to_resolve = reinterpret_cast<const float*>(state.blit_buffer);
+	void* temporal_buffers = nullptr; // rays, then hits, then the two histories that take turns
+	if (temporal) {
+		const size_t hist_bytes = (Scene::history_bytes(w, h) + 15) / 16 * 16;
+		BM_CHECKED(bm_buffer_alloc(0, n_pixels * (sizeof(bm_ray) + sizeof(bm_ray_hit)) + 2 * hist_bytes, &temporal_buffers));
+		bm_ray* rays = static_cast<bm_ray*>(temporal_buffers);
+		bm_ray_hit* hits = reinterpret_cast<bm_ray_hit*>(rays + n_pixels);
+		char* histories[2] = {reinterpret_cast<char*>(hits + n_pixels), reinterpret_cast<char*>(hits + n_pixels) + hist_bytes};
+		float* frame = reinterpret_cast<float*>(state.blit_buffer);
+		// the step: half a voxel along cross(direction, up), the view's right axis
+		const vec3 d = camera.direction;
+		const float len = std::sqrt(d.x * d.x + d.y * d.y);
+		const vec3 step = {0.5f * d.y / len, -0.5f * d.x / len, 0.f};
+		Camera before;
+		for (int f = 0; f < frames; ++f) {
+			bm_frame_params fp = detail::frame_params(state, 3);
+			fp.sample_base = f; // samples of its own: the noise of consecutive frames must not be the same
+			const bm_camera cam = camera.to_c();
+			const float lod_origin[3] = {camera.position.x, camera.position.y, camera.position.z};
+			BM_CHECKED(bm_buffer_zero(0, frame, n_pixels * sizeof(vec4), nullptr));
+			BM_CHECKED(bm_render_frame(scene.gpuScene.handle, &cam, &fp, frame, nullptr, nullptr));
+			scene.pixel_rays(camera, w, h, rays);
+			scene.cast_rays(static_cast<int64_t>(n_pixels), rays, hits, BM_QUERY_LOD | BM_QUERY_NO_REQUESTS, lod_origin);
+			scene.reproject(w, h, camera, f ? &before : nullptr, frame, hits, f ? histories[(f + 1) & 1] : nullptr, histories[f & 1]);
+			BM_CHECKED(bm_synchronize(scene.gpuScene.handle));
+			scene.process_load_queue();
+			to_resolve = reinterpret_cast<const float*>(histories[f & 1]);
+			before = camera;
+			if (f + 1 < frames) camera.position = {camera.position.x + step.x, camera.position.y + step.y, camera.position.z + step.z};
+		}
+		std::cout << "temporal: " << frames << " frames of 1 spp, the camera half a voxel sideways per frame, max_history 32\n";
+	} else if (wavefront) {
 		Wavefront queues(scene.gpuScene); // state.h:19-21: ray_buffer_work / ray_buffer_next / shadow_queue_buffer
 		for (int frame = 0; frame < frames; ++frame) {
 			launch_kernels(state, state.blit_buffer, scene.gpuScene, queues); // main.cpp:142
@@ -164,11 +210,9 @@ int main(int argc_in, char** argv_in) {
 	// blit_onto_framebuffer (kernel.cu:348-364) into an offscreen buffer instead of the GL surface
 	void* resolved = nullptr;
 	BM_CHECKED(bm_buffer_alloc(0, width * height * sizeof(vec4), &resolved));
-	const float* to_resolve = reinterpret_cast<const float*>(state.blit_buffer);
 	void* guides = nullptr; // rays, then hits, then the filter's workspace; the filtered frame goes to `resolved`, which is then resolved in place
 	if (denoise) {
-		const int w = static_cast<int>(width), h = static_cast<int>(height);
-		const size_t n = width * height, ws_bytes = Scene::denoise_workspace_bytes(w, h);
+		const size_t n = n_pixels, ws_bytes = Scene::denoise_workspace_bytes(w, h);
 		BM_CHECKED(bm_buffer_alloc(0, n * (sizeof(bm_ray) + sizeof(bm_ray_hit)) + ws_bytes, &guides));
 		bm_ray* rays = static_cast<bm_ray*>(guides);
 		bm_ray_hit* hits = reinterpret_cast<bm_ray_hit*>(rays + n);
@@ -195,5 +239,6 @@ int main(int argc_in, char** argv_in) {
 	std::cout << "wrote " << out << ": " << frames << " frames, " << info.resident_bricks << " of " << info.total_bricks << " bricks resident\n";
 	bm_buffer_free(0, resolved);
 	if (guides) bm_buffer_free(0, guides);
+	if (temporal_buffers) bm_buffer_free(0, temporal_buffers);
 	return 0;
 }

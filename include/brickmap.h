@@ -392,6 +392,52 @@ BM_API int bm_debug_denoise_times(bm_scene* scene, const bm_denoise_params* para
 /* the same filter on host memory, as plain loops (no device needed); the refusals of bm_denoise that concern params and NULL buffers */
 BM_API int bm_host_denoise(const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out);
 
+/* ---- temporal accumulation for a moving camera (no reference counterpart: the reference accumulates only while the camera rests):
+ * the samples of earlier frames are carried to where the same surface point is now.  A surface is the exact integer key of the denoise
+ * (face plane, axis, side), and the previous camera's ray through a point P of an axis-aligned plane meets that plane only in P, so "the
+ * previous pixel carries the same key" is an exact disocclusion test -- no depth or normal threshold.  All arithmetic is fp32 IEEE
+ * + - * / sqrt floor in a fixed order, without contraction, so bm_reproject and bm_host_reproject agree bit for bit (csrc/reproject.h
+ * holds the rules once).
+ * A HISTORY of a width x height image is one buffer, 16-byte aligned: width * height float4 (R, G, B, n) row-major -- an accumulation
+ * buffer, which bm_denoise and bm_resolve take unchanged -- then width * height uint32 surface keys: 20 bytes per pixel.
+ * Both cameras' bases (origin o, dir D, right Rt, up U) are those of the frames for this width and height; for the previous camera
+ * (marked ') also dd = (D.x*D.x + D.y*D.y) + D.z*D.z, and rr, uu likewise for Rt, U.  Per pixel p = (x, y):
+ *  1. key_p = the denoise's surface key of (accum n, hit); history_out.key[p] = key_p always.
+ *  2. without history_prev, or with the special key: history_out.image[p] = accum[p], all four words unchanged ("no history").
+ *  3. dhat = the direction of bm_camera_pixel_rays for (x + 0.5, y + 0.5); P[k] = o[k] + dhat[k] * distance.
+ *  4. e[k] = P[k] - o'[k]; t = ((e.x*D'.x + e.y*D'.y) + e.z*D'.z) / dd; !(t > 0): no history.  a = ((e.x*Rt'.x + e.y*Rt'.y) + e.z*Rt'.z) / (t * rr),
+ *     b likewise with U', uu.  u = (a + 0.5) * W + 0.5, v = (H - (b + 0.5) * H) + 0.5: continuous coordinates in which pixel centres
+ *     are integers.
+ *  5. x0f = floor(u), fx = u - x0f, y0f = floor(v), fy = v - y0f; !(x0f >= -1 && x0f <= W - 1 && y0f >= -1 && y0f <= H - 1), tested in
+ *     float: no history.  Four taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with weights (1-fx)*(1-fy), fx*(1-fy), (1-fx)*fy,
+ *     fx*fy.  A tap counts when it lies inside the image, prev.key[q] == key_p, prev.n[q] > 0 and its weight > 0; any other tap is skipped,
+ *     not multiplied by zero.  From 0 in tap order: Ws += w, C += w * (prev.rgb[q] / prev.n[q]), N += w * prev.n[q].
+ *  6. no tap counted: no history.  Else c_h = C / Ws, n_h = N / Ws, n_h = n_h < max_history ? n_h : max_history,
+ *     out.rgb = c_h * n_h + accum.rgb (a multiply, then an add), out.n = n_h + accum.n.
+ * So a surface that was hidden, off-screen or behind the previous camera starts again at the frame's own samples.  A moved sun, or an
+ * edit that changes the light without changing keys, is the caller's reason to pass a NULL history_prev. */
+typedef struct bm_reproject_params {
+	int32_t width, height;
+	float max_history;    /* finite, >= 1: the most samples a pixel takes over from the history; 32 is a good default */
+	uint32_t flags;       /* 0 */
+	uint32_t reserved;    /* 0 */
+} bm_reproject_params;
+/* bytes of a history: 20 per pixel */
+BM_API int bm_history_bytes(int width, int height, size_t* bytes);
+/* accum_dev: the frame just rendered with `camera`, width * height float4 (R, G, B, n); hits_dev: one bm_ray_hit per pixel for that
+ * camera's pixel-centre rays (what bm_denoise takes); history_prev_dev: the history of the frame before, made with camera_prev, or NULL
+ * (camera_prev may then be NULL too); history_out_dev: the new history.  Asynchronous on hip_stream like bm_denoise; the scene keeps no
+ * state, so calls on different streams are independent.  Refused with BM_EINVAL, launching nothing: width or height < 1 or > 65535,
+ * max_history not finite or < 1, non-zero flags or reserved, a NULL camera, accum, hits or history_out, a NULL camera_prev with a
+ * history_prev, a buffer that is not 16-byte aligned, history_out overlapping history_prev, accum or hits (taps read neighbours: the
+ * caller ping-pongs two histories).  A degenerate camera (dir parallel to up) is not refused: its NaNs fail every comparison, which
+ * gives "no history". */
+BM_API int bm_reproject(bm_scene* scene, const bm_reproject_params* params, const bm_camera* camera, const bm_camera* camera_prev,
+                        const float* accum_dev, const bm_ray_hit* hits_dev, const void* history_prev_dev, void* history_out_dev, void* hip_stream);
+/* the same on host memory, as plain loops (no device needed); the refusals of bm_reproject that concern params and NULL pointers */
+BM_API int bm_host_reproject(const bm_reproject_params* params, const bm_camera* camera, const bm_camera* camera_prev, const float* accum,
+                             const bm_ray_hit* hits, const void* history_prev, void* history_out);
+
 /* ---- volume queries against the live scene (no reference counterpart): how much is solid in a box or a sphere, and where.
  * Is this box free, how much does this sphere hold, where is the ground under this column, how far can this box move before it
  * touches something -- questions a ray, which has no width, answers badly.  For each of n records in device memory: the number of

@@ -173,6 +173,23 @@ public:
 		const bm_denoise_params p = {width, height, iterations, sigma_l, 0u, 0u};
 		BM_CHECKED(bm_denoise(gpuScene.handle, &p, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, hip_stream));
 	}
+	// temporal accumulation for a moving camera (no counterpart in the reference; bm_reproject): accum_dev = the frame just rendered with
+	// `cam`, hits_dev = its guides as for denoise, history_prev_dev = the history of the frame before, rendered with `cam_prev`, or null
+	// (no history); history_out_dev = the new history, history_bytes() bytes, never the previous one: two histories take turns.  A history
+	// begins with an accumulation buffer of up to max_history + the frame's own samples per pixel, which denoise and bm_resolve take.
+	static size_t history_bytes(int width, int height) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_history_bytes(width, height, &bytes));
+		return bytes;
+	}
+	void reproject(int width, int height, const Camera& cam, const Camera* cam_prev, const float* accum_dev, const bm_ray_hit* hits_dev,
+				   const void* history_prev_dev, void* history_out_dev, float max_history = 32.f, void* hip_stream = nullptr) {
+		const bm_reproject_params p = {width, height, max_history, 0u, 0u};
+		const bm_camera c = cam.to_c();
+		bm_camera before{};
+		if (cam_prev) before = cam_prev->to_c();
+		BM_CHECKED(bm_reproject(gpuScene.handle, &p, &c, cam_prev ? &before : nullptr, accum_dev, hits_dev, history_prev_dev, history_out_dev, hip_stream));
+	}
 	// the hit under pixel (x, y) of a width x height frame of `cam`: one ray through the pixel's centre, one query, then the host waits.
 	// level -1 = nothing there; level 3 = the brick is not resident yet (service the load queue, pick again)
 	bm_ray_hit pick(const Camera& cam, int width, int height, int x, int y) {
