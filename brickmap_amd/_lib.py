@@ -49,6 +49,11 @@ class bm_frame_plan(C.Structure):
                 ("refill_min", C.c_int32), ("refill_min_in_ring", C.c_int32), ("instrumented", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("local_rows", C.c_int32), ("ring_group", C.c_int32)]
 
 
+class bm_launch_plan(C.Structure):
+    _fields_ = [("ring_mode", C.c_int32), ("ring_group", C.c_int32), ("sample_stride", C.c_int32), ("pixel_stride", C.c_uint32), ("shared_digest", C.c_int32),
+                ("instrumented", C.c_int32), ("counter_blocks", C.c_int32), ("refill_min", C.c_int32), ("workgroups", C.c_int64)]
+
+
 BM_EDIT_SET = 1
 BM_EDIT_CLEAR = 2
 BM_EDIT_BOX = 1
@@ -184,6 +189,7 @@ SIGNATURES = {
     "bm_render_frame": (_i, [_vp, C.POINTER(bm_camera), C.POINTER(bm_frame_params), _vp, _vp, _vp]),
     "bm_render_frames": (_i, [_vp, _i, C.POINTER(bm_camera), C.POINTER(bm_frame_params), C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "bm_frame_plan_of": (_i, [C.POINTER(bm_frame_params), _i, C.POINTER(bm_frame_plan)]),
+    "bm_launch_plan_of": (_i, [_i, C.POINTER(bm_camera), C.POINTER(bm_frame_params), _vp, _vp, _i, _i, C.POINTER(bm_launch_plan)]),
     "bm_trace_waves_per_simd": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int)]),
     "bm_tuning_overrides": (_i, [C.c_char_p, C.c_size_t]),
     "bm_resolve": (_i, [_vp, _vp, _vp, C.c_int64, _vp]),

@@ -1,5 +1,5 @@
 // camera_rays.h -- the view basis of a frame and the direction of the ray through a pixel position, each written once.
-// Plain C++ (host + device) like denoise.h.  The basis is the frames' (Scene::fill_frame_constants calls camera_basis); the direction is
+// Plain C++ (host + device) like denoise.h.  The basis is the frames' (fill_frame_constants calls camera_basis); the direction is
 // the frames' primary ray without jitter and lens, which bm_camera_pixel_rays (capi.cpp), the pixel_rays kernel (denoise.hip) and the
 // reprojection (reproject.h) share: fp32 IEEE operations in the order written here, no contraction (-ffp-contract=off).
 #pragma once

@@ -166,11 +166,11 @@ int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t
 		set_error("bm_camera_pixel_rays: bad argument");
 		return BM_EINVAL;
 	}
-	// the camera basis of the frames (Scene::fill_frame_constants, this translation unit is built with -ffp-contract=off like it)
+	// the camera basis of the frames (fill_frame_constants, this translation unit is built with -ffp-contract=off like it)
 	bm_frame_params p{};
 	p.width = width; p.height = height; p.spp = 1; p.band_rows = height; p.shard_count = 1;
 	bm::FrameConstants fc;
-	if (int e = bm::Scene::fill_frame_constants(camera, &p, &fc)) return e;
+	if (int e = bm::fill_frame_constants(camera, &p, &fc)) return e;
 	const float W = static_cast<float>(width), H = static_cast<float>(height);
 	for (int64_t i = 0; i < n; ++i) {
 		bm_ray& r = out[i];
@@ -419,7 +419,7 @@ int bm_frame_plan_of(const bm_frame_params* params, int hit_records, bm_frame_pl
 	bm_camera cam{};
 	cam.direction[0] = 1.f; cam.up[2] = 1.f; cam.focal_distance = 1.f; // (the plan does not depend on the view)
 	bm::FrameConstants fc;
-	if (int e = bm::Scene::fill_frame_constants(&cam, params, &fc, hit_records != 0)) return e;
+	if (int e = bm::fill_frame_constants(&cam, params, &fc, hit_records != 0)) return e;
 	std::memset(out, 0, sizeof *out);
 	out->flags = fc.flags;
 	out->helpers = fc.helpers;
@@ -429,8 +429,28 @@ int bm_frame_plan_of(const bm_frame_params* params, int hit_records, bm_frame_pl
 	out->refill_min = fc.refill_min;
 	out->refill_min_in_ring = bm::ring_refill_min(fc.refill_min, fc.helpers != 0, bm::tuning().refill_min);
 	out->tiles_x = fc.tiles_x; out->tiles_y = fc.tiles_y; out->local_rows = fc.local_rows;
-	out->instrumented = (hit_records || (fc.flags & BM_FLAG_COUNTERS)) ? 1 : 0;
+	out->instrumented = bm::instrumented_frame(fc.flags, hit_records != 0) ? 1 : 0;
 	out->ring_group = bm::ring_group_of(fc, bm::kMaxRingGroup); // (of a launch long enough for a whole group)
+	return 0;
+}
+int bm_launch_plan_of(int count, const bm_camera* cameras, const bm_frame_params* params, float* const* accum_dev, uint32_t* const* debug_dev, int grid_size,
+					  int grid_height, bm_launch_plan* out) {
+	if (!out) { set_error("null argument"); return BM_EINVAL; }
+	std::memset(out, 0, sizeof *out); // (a refused plan reads all zero)
+	bm::WorldDims dims;
+	if (!dims.set(grid_size, grid_height)) { set_error("bad world dimensions"); return BM_EINVAL; }
+	bm::LaunchPlan plan;
+	if (int e = bm::plan_launch(count, cameras, params, accum_dev, debug_dev, dims.cells, dims.cells_height, &plan)) return e;
+	const bm::FrameConstants& fc = plan.frames[0];
+	out->ring_mode = plan.ring_mode;
+	out->ring_group = fc.ring_group;
+	out->sample_stride = fc.ring_sample_stride;
+	out->pixel_stride = fc.ring_pixel_stride;
+	out->shared_digest = plan.shared_digest ? 1 : 0;
+	out->instrumented = plan.instrumented ? 1 : 0;
+	out->counter_blocks = plan.counter_blocks;
+	out->refill_min = fc.refill_min;
+	out->workgroups = plan.workgroups;
 	return 0;
 }
 int bm_trace_waves_per_simd(int device, int instrumented, int xcd_handout, int helpers, int* waves) {
@@ -533,7 +553,7 @@ int bm_debug_sky(int device, const float sun_position[2], int n, const float* vi
 	fp.width = 16; fp.height = 16; fp.spp = 1; fp.max_bounces = 3; fp.base_frame = 1; fp.band_rows = 16; fp.shard_count = 1;
 	fp.sun_position[0] = sun_position[0]; fp.sun_position[1] = sun_position[1];
 	bm::FrameConstants fc;
-	if (int e = bm::Scene::fill_frame_constants(&cam, &fp, &fc)) return e;
+	if (int e = bm::fill_frame_constants(&cam, &fp, &fc)) return e;
 	BM_HIP(hipSetDevice(device));
 	const size_t bytes = static_cast<size_t>(n) * 3 * sizeof(float);
 	float* d[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -1,13 +1,15 @@
-// frame_plan.cpp -- the pure-host plan of a frame: FrameConstants from a camera and frame parameters (view basis, sky constants, the
-// hand-out's geometry, refill and helper-lane rules), the tuning overrides of the environment and the multiply-high division constants.
-// Calls no HIP function.
+// frame_plan.cpp -- the pure-host plans (frame_plan.h).  Of a frame: FrameConstants from a camera and frame parameters (view basis, sky
+// constants, the hand-out's geometry, refill and helper-lane rules), the tuning overrides of the environment and the multiply-high division
+// constants.  Of a launch (plan_launch): which frames may go out together, in which ring mode, with what grid.  Calls no HIP function.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstddef>
 #include <cstring>
 
 #include "camera_rays.h"
-#include "scene.h"
+#include "error.h"
+#include "frame_plan.h"
 
 namespace bm {
 
@@ -74,7 +76,7 @@ static bool tickets_fit(int tiles_x, int tiles_y, bool xcd, long long per_chunk)
 	return share < (1ll << 30) - (1ll << 24); // (2^30: the hand-out divides ticket numbers with 30-bit-exact multiply-high constants)
 }
 
-// How many consecutive frames of a UNIFORM launch (scene.cpp render_frames) are handed out together, as (chunk, pixel part, frame)
+// How many consecutive frames of a UNIFORM launch (plan_launch, below) are handed out together, as (chunk, pixel part, frame)
 // items (trace.hip "FRAME GROUPS")?  The one place that decides it.  Frames that add every event with float atomics -- helper lanes
 // on -- leave the order of a pixel's additions free already, so their frames may run side by side in a wave: kRingGroup, or
 // BM_RING_GROUP (1 = frame after frame, for A/B runs), at most the frames there are.  Ordered frames write back with plain stores and
@@ -91,7 +93,7 @@ int ring_group_of(const FrameConstants& fc, int frames) {
 	return group;
 }
 
-int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_in, FrameConstants* fc, bool hit_records) {
+int fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_in, FrameConstants* fc, bool hit_records) {
 	if (!fp_in) { set_error("null argument"); return BM_EINVAL; }
 	if (fp_in->flags & ~(BM_FLAG_PRIMARY_ONLY | BM_FLAG_COUNTERS | BM_FLAG_SAMPLE_ITEMS | BM_FLAG_ORDERED | BM_FLAG_RAY_DIGEST)) {
 		set_error("unknown frame flag (bit 8 was the retired K-slot schedule's)");
@@ -209,7 +211,7 @@ int Scene::fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp_
 		set(static_cast<uint32_t>(fc->band_rows), &fc->div_band_magic, &fc->div_band_shift);
 		set(static_cast<uint32_t>((fc->tiles_x + 15) / 16), &fc->div_st_x_magic, &fc->div_st_x_shift);
 	}
-	fc->ring_group = 1; // (a launch of one frame; Scene::render_frames sets the groups of a uniform launch)
+	fc->ring_group = 1; // (a launch of one frame; plan_launch sets the groups of a uniform launch)
 	return 0;
 }
 
@@ -219,6 +221,136 @@ void set_ring_group(FrameConstants* fc, int group, int frames) {
 	fc->ring_groups_after = (frames + group - 1) / group - 1;
 	const uint32_t d = ((fc->flags & BM_FLAG_SAMPLE_ITEMS) ? static_cast<uint32_t>(std::max(fc->spp, 1)) : 1u) * static_cast<uint32_t>(group);
 	if (d <= 1u) { fc->div_samples_magic = 0u; fc->div_samples_shift = 0; } else division_magic(d, &fc->div_samples_magic, &fc->div_samples_shift);
+}
+
+// ---------------------------------------------------------------- the plan of a launch
+// `count` consecutive frames -- the reference's per-frame loop (main.cpp:117-147: one launch_kernels call per frame) -- as ONE launch
+// of the persistent kernel (trace.hip "FRAME RING"): every decision about it that needs no device.  Scene::render_frames issues it.
+int plan_launch(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, int cells, int cells_height, LaunchPlan* out) {
+	if (count < 1 || count > kMaxFramesPerLaunch) { set_error("bm_render_frames: 1 ... 256 frames per launch"); return BM_EINVAL; }
+	if (!cams || !fps || !accums) { set_error("null argument"); return BM_EINVAL; }
+	bool hit_records = false;
+	for (int i = 0; i < count; ++i) {
+		if (!accums[i]) { set_error("null accumulation buffer"); return BM_EINVAL; }
+		hit_records = hit_records || (dbgs && dbgs[i]);
+	}
+	// ---- constants of every frame; what shapes the hand-out must be the same for all frames of a launch
+	std::vector<FrameConstants>& fcs = out->frames;
+	fcs.assign(static_cast<size_t>(count), FrameConstants{});
+	for (int i = 0; i < count; ++i) {
+		if (int e = fill_frame_constants(cams + i, fps + i, &fcs[static_cast<size_t>(i)], hit_records)) return e;
+		FrameConstants& f = fcs[static_cast<size_t>(i)];
+		f.accum = accums[i];
+		f.dbg = dbgs ? dbgs[i] : nullptr;
+		f.frames_after = count - 1 - i;
+		const FrameConstants& g = fcs[0];
+		if (f.width != g.width || f.height != g.height || f.spp != g.spp || f.max_bounces != g.max_bounces || f.flags != g.flags || f.band_rows != g.band_rows ||
+			f.shard_rank != g.shard_rank || f.shard_count != g.shard_count) {
+			set_error("bm_render_frames: the frames of one launch must agree in width, height, spp, max_bounces, flags and shard (camera, sun, sample_base, base_frame and buffers may differ)");
+			return BM_EINVAL;
+		}
+	}
+	// In a launch of several frames a wave refills later: what argues for an early refill in a lone frame -- the paths started last are what
+	// the frame's end waits for -- does not count when the next frame covers that end (ring of 20, kernel ms per frame: 24 idle lanes 0.7514,
+	// 32: 0.7478, 36: 0.7481, 40: 0.7515; 1080p at 4 spp 2.937 / 2.905 / 2.894 / 2.899; profiles/r06_frame_ring.txt)
+	if (count > 1)
+		for (FrameConstants& f : fcs) f.refill_min = ring_refill_min(f.refill_min, f.helpers != 0, tuning().refill_min);
+	const FrameConstants& fc = fcs[0];
+	bool shared_digest = false; // ray-digest frames that all write ONE hit-record buffer (and one accumulation buffer)
+	if (count > 1) {
+		// Frames of a launch overlap in time.  Hit records are written with plain stores, and so are the pixels of frames that neither
+		// run helper lanes nor (chunk, sample) items (read when a lane takes the pixel, written back when it is done): such frames
+		// need buffers of their own.  Frames that add with float atomics may share one buffer, like consecutive frames of the
+		// reference's accumulation (kernel.cu:319-322,341-343).
+		const size_t pixels = static_cast<size_t>(fc.local_rows) * static_cast<size_t>(fc.width);
+		const bool plain_pixels = !(fc.helpers || (fc.flags & BM_FLAG_SAMPLE_ITEMS));
+		for (int i = 0; i < count; ++i)
+			for (int k = 0; k < i; ++k) {
+				const char *a = reinterpret_cast<const char*>(accums[i]), *b = reinterpret_cast<const char*>(accums[k]);
+				if (plain_pixels && a < b + pixels * 16 && b < a + pixels * 16) {
+					set_error("bm_render_frames: ordered frames of one launch need accumulation buffers of their own (they overlap in time and write pixels back with plain stores)");
+					return BM_EINVAL;
+				}
+				const char *c = dbgs ? reinterpret_cast<const char*>(dbgs[i]) : nullptr, *d = dbgs ? reinterpret_cast<const char*>(dbgs[k]) : nullptr;
+				if (c && d && c == d && a == b && (fc.flags & BM_FLAG_RAY_DIGEST)) { shared_digest = true; continue; } // (allowed for uniform launches: below)
+				if (c && d && c < d + pixels * 32 && d < c + pixels * 32) {
+					set_error("bm_render_frames: the frames of one launch need hit-record buffers of their own");
+					return BM_EINVAL;
+				}
+			}
+	}
+	// ---- a UNIFORM launch?  Frames that differ only in sample_base and buffers, both stepping by constants (a resting camera: the
+	// reference's progressive accumulation; bench.py's steps; a rank's batch into one allocation): lanes of consecutive frames may then
+	// share a wave (trace.hip), because nothing a lane reads after it took its item depends on the frame any more.
+	bool uniform = false, digest_ok = false;
+	if (shared_digest) { // every frame names the same two buffers?
+		digest_ok = true;
+		for (int i = 0; i < count; ++i) digest_ok = digest_ok && dbgs[i] == dbgs[0] && accums[i] == accums[0];
+	}
+	if (count > 1 && (!hit_records || digest_ok)) {
+		auto same_view = [&](const FrameConstants& a, const FrameConstants& b) {
+			// everything up to `width` is the view, the sun and the sky (device_types.h); base_frame seeds the RNG
+			return std::memcmp(&a, &b, offsetof(FrameConstants, width)) == 0 && a.base_frame == b.base_frame;
+		};
+		const long long sample_stride = static_cast<long long>(fcs[1].sample_base) - fcs[0].sample_base;
+		const long long byte_stride = reinterpret_cast<const char*>(accums[1]) - reinterpret_cast<const char*>(accums[0]);
+		const unsigned long long pixels = static_cast<unsigned long long>(fc.local_rows) * static_cast<unsigned long long>(fc.width);
+		uniform = sample_stride >= 0 && sample_stride < (1 << 20) && byte_stride >= 0 && byte_stride % 16 == 0 &&
+				  static_cast<unsigned long long>(byte_stride / 16) * static_cast<unsigned long long>(count - 1) + pixels < (1ull << 32) &&
+				  static_cast<long long>(fcs[0].sample_base) + sample_stride * (count - 1) + fc.spp < (1ll << 31);
+		for (int i = 1; i < count && uniform; ++i)
+			uniform = same_view(fcs[static_cast<size_t>(i)], fcs[0]) && static_cast<long long>(fcs[static_cast<size_t>(i)].sample_base) == fcs[0].sample_base + sample_stride * i &&
+					  reinterpret_cast<const char*>(accums[i]) == reinterpret_cast<const char*>(accums[0]) + byte_stride * i;
+		if (uniform) {
+			for (int i = 0; i < count; ++i) { // every entry reads like the first; the frame is an offset the lanes add themselves
+				fcs[static_cast<size_t>(i)].sample_base = fcs[0].sample_base;
+				fcs[static_cast<size_t>(i)].accum = fcs[0].accum;
+			}
+			fcs[0].ring_uniform = 1;
+			fcs[0].ring_sample_stride = static_cast<int>(sample_stride);
+			fcs[0].ring_pixel_stride = static_cast<uint32_t>(byte_stride / 16);
+			// ... and frames that add with float atomics are handed out several at a time (trace.hip "FRAME GROUPS")
+			set_ring_group(&fcs[0], ring_group_of(fcs[0], count), count);
+		}
+		if (shared_digest && !uniform) digest_ok = false;
+	}
+	if (shared_digest && !digest_ok) {
+		// One hit-record buffer for several frames is the digest of the WHOLE launch: its keys count samples from the first frame's
+		// sample_base and its first-hit record is written once -- which only a uniform launch (one view, stepping sample_base) defines
+		set_error("bm_render_frames: ray-digest frames may share one hit-record buffer only in a uniform launch (one view and sun, sample_base stepping by a constant, one accumulation buffer)");
+		return BM_EINVAL;
+	}
+	if (shared_digest) {
+		// ... and that digest counts the pixel's rays of ALL the frames in 16 bits (word 6) and keys them with 24 bits of sample index
+		// counted from the first frame's sample_base: fill_frame_constants checked one frame's share of either
+		const long long sample_stride = fc.ring_sample_stride; // (a shared digest is a uniform launch; the entries' own sample_base all read like the first by now)
+		if (static_cast<long long>(count) * fc.spp * (fc.max_bounces + 1) >= 65536 || sample_stride * (count - 1) + fc.spp >= (1ll << 24)) {
+			set_error("bm_render_frames: ray-digest frames that share one hit-record buffer: frames x spp x segments < 65536 and sample_base stride x (frames - 1) + spp < 2^24 (the digest counts the launch's rays per pixel in 16 bits and keys them with 24 bits of sample)");
+			return BM_EINVAL;
+		}
+	}
+	{ // the kernel's hang guard is a 64-bit product (trace.hip round_budget): a launch for which it would wrap -- it would end before it has
+	  // traced anything -- is refused (such a launch is weeks of GPU time anyway)
+		const unsigned __int128 rounds = static_cast<unsigned __int128>(static_cast<unsigned long long>(fc.tiles_x) * static_cast<unsigned long long>(fc.tiles_y) * 16ull + 64ull) *
+										 static_cast<unsigned long long>(fc.spp + 1) * static_cast<unsigned long long>(fc.max_bounces + 2) *
+										 static_cast<unsigned long long>(2ll * cells + cells_height + 64) * static_cast<unsigned long long>(count);
+		if (rounds >= (static_cast<unsigned __int128>(1) << 62)) {
+			set_error("launch too large: tiles x samples x segments x frames overflows the kernel's round budget (render fewer samples or frames per launch)");
+			return BM_EINVAL;
+		}
+	}
+	out->ring_mode = count > 1 ? (uniform ? 2 : 1) : 0;
+	out->instrumented = instrumented_frame(fc.flags, hit_records);
+	out->shared_digest = shared_digest;
+	// (one block of ticket counters per frame; a uniform launch uses one per GROUP of frames, the first of them)
+	out->counter_blocks = uniform ? fc.ring_groups_after + 1 : count;
+	// never more waves than a frame has 64-item groups: an item is a pixel, or ONE sample of a pixel with (chunk, sample) items -- a
+	// 1/8 shard of a 1080p frame at 8 spp is 276 480 pixels but 2.2 M items, and sizing its launch by pixels left 40 % of the
+	// GPU's wave slots empty (1080 of 1792 workgroups: 1.16 -> 0.95 ms per shard step).  A launch of several frames may start a
+	// second frame's worth of waves: those that find the first frame's counters used up go straight on to the next one.
+	const long long items = static_cast<long long>(fc.tiles_x) * fc.tiles_y * 256 * ((fc.flags & BM_FLAG_SAMPLE_ITEMS) ? std::max(fc.spp, 1) : 1);
+	out->workgroups = (items + 255) / 256 * (count > 1 ? 2 : 1);
+	return 0;
 }
 
 } // namespace bm

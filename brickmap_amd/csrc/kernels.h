@@ -19,11 +19,12 @@ int resident_blocks_per_cu(K kernel, int threads = 256) {
 
 constexpr size_t kWorkCounterBytes = 64 * 32 * sizeof(uint32_t); // up to 64 chunk counters, one 128-byte line each
 int trace_blocks_per_cu(bool instrumented, bool xcd_handout, bool helpers, int ring = 0); // resident workgroups per CU of that instantiation (ring: 0 = a launch of one frame, 1 = of several, 2 = of several uniform ones)
-// blocks_per_cu_cap: 0 = as many workgroups per CU as the instantiation keeps resident; > 0 = at most that many (tuning runs)
 // fc_dev[0], fc_dev[1], ... are the constants of the frames of this launch (the frame ring, trace.hip; the last entry has frames_after == 0): each
-// names its own accumulation / hit-record buffers; work_counter is the first of as many zeroed blocks of kWorkCounterBytes (a uniform launch uses one per GROUP of frames, FrameConstants::ring_group); fc = host copy of fc_dev[0]
-void launch_trace(const DeviceScene& sc, const FrameConstants& fc, const FrameConstants* fc_dev, DeviceCounters* counters,
-				  uint32_t* work_counter, bool instrumented, int compute_units, int blocks_per_cu_cap, hipStream_t stream);
+// names its own accumulation / hit-record buffers; work_counter is the first of as many zeroed blocks of kWorkCounterBytes (a uniform launch uses one per GROUP of frames, FrameConstants::ring_group).
+// instrumented ... ring name the instantiation and `workgroups` is the grid, both as planned (frame_plan.h LaunchPlan), the grid capped here by what the
+// device keeps resident; blocks_per_cu_cap: 0 = as many workgroups per CU as the instantiation keeps resident; > 0 = at most that many (tuning runs)
+void launch_trace(const DeviceScene& sc, const FrameConstants* fc_dev, DeviceCounters* counters, uint32_t* work_counter, bool instrumented, bool xcd_handout, bool helpers,
+				  int ring, long long workgroups, int compute_units, int blocks_per_cu_cap, hipStream_t stream);
 void launch_upload(const DeviceScene& sc, const uint32_t* bricks_queue, const uint32_t* indices_queue, uint32_t* arena, uint32_t count,
 				   hipStream_t stream);
 void launch_pool_moves(const PoolMove* moves, uint32_t count, uint32_t* arena, uint32_t* pool_base, hipStream_t stream);

@@ -1394,121 +1394,13 @@ int Scene::render(const bm_camera* cam, const bm_frame_params* fp, float* accum,
 // scene's rings, and every wave walks from frame to frame by itself.
 int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream) {
 	if (int e = require_on_device()) return e;
-	if (count < 1 || count > kMaxFramesPerLaunch) { set_error("bm_render_frames: 1 ... 256 frames per launch"); return BM_EINVAL; }
-	if (!cams || !fps || !accums) { set_error("null argument"); return BM_EINVAL; }
-	bool hit_records = false;
-	for (int i = 0; i < count; ++i) {
-		if (!accums[i]) { set_error("null accumulation buffer"); return BM_EINVAL; }
-		hit_records = hit_records || (dbgs && dbgs[i]);
-	}
-	// ---- constants of every frame; what shapes the hand-out must be the same for all frames of a launch
-	std::vector<FrameConstants> fcs(static_cast<size_t>(count));
-	for (int i = 0; i < count; ++i) {
-		if (int e = fill_frame_constants(cams + i, fps + i, &fcs[static_cast<size_t>(i)], hit_records)) return e;
-		FrameConstants& f = fcs[static_cast<size_t>(i)];
-		f.accum = accums[i];
-		f.dbg = dbgs ? dbgs[i] : nullptr;
-		f.frames_after = count - 1 - i;
-		const FrameConstants& g = fcs[0];
-		if (f.width != g.width || f.height != g.height || f.spp != g.spp || f.max_bounces != g.max_bounces || f.flags != g.flags || f.band_rows != g.band_rows ||
-			f.shard_rank != g.shard_rank || f.shard_count != g.shard_count) {
-			set_error("bm_render_frames: the frames of one launch must agree in width, height, spp, max_bounces, flags and shard (camera, sun, sample_base, base_frame and buffers may differ)");
-			return BM_EINVAL;
-		}
-	}
-	// In a launch of several frames a wave refills later: what argues for an early refill in a lone frame -- the paths started last are what
-	// the frame's end waits for -- does not count when the next frame covers that end (ring of 20, kernel ms per frame: 24 idle lanes 0.7514,
-	// 32: 0.7478, 36: 0.7481, 40: 0.7515; 1080p at 4 spp 2.937 / 2.905 / 2.894 / 2.899; profiles/r06_frame_ring.txt)
-	if (count > 1)
-		for (FrameConstants& f : fcs) f.refill_min = ring_refill_min(f.refill_min, f.helpers != 0, tuning().refill_min);
+	LaunchPlan plan; // every decision that needs no device: frame_plan.cpp
+	if (int e = plan_launch(count, cams, fps, accums, dbgs, world.dims.cells, world.dims.cells_height, &plan)) return e;
+	std::vector<FrameConstants>& fcs = plan.frames;
 	const FrameConstants& fc = fcs[0];
-	bool shared_digest = false; // ray-digest frames that all write ONE hit-record buffer (and one accumulation buffer)
-	if (count > 1) {
-		// Frames of a launch overlap in time.  Hit records are written with plain stores, and so are the pixels of frames that neither
-		// run helper lanes nor (chunk, sample) items (read when a lane takes the pixel, written back when it is done): such frames
-		// need buffers of their own.  Frames that add with float atomics may share one buffer, like consecutive frames of the
-		// reference's accumulation (kernel.cu:319-322,341-343).
-		const size_t pixels = static_cast<size_t>(fc.local_rows) * static_cast<size_t>(fc.width);
-		const bool plain_pixels = !(fc.helpers || (fc.flags & BM_FLAG_SAMPLE_ITEMS));
-		for (int i = 0; i < count; ++i)
-			for (int k = 0; k < i; ++k) {
-				const char *a = reinterpret_cast<const char*>(accums[i]), *b = reinterpret_cast<const char*>(accums[k]);
-				if (plain_pixels && a < b + pixels * 16 && b < a + pixels * 16) {
-					set_error("bm_render_frames: ordered frames of one launch need accumulation buffers of their own (they overlap in time and write pixels back with plain stores)");
-					return BM_EINVAL;
-				}
-				const char *c = dbgs ? reinterpret_cast<const char*>(dbgs[i]) : nullptr, *d = dbgs ? reinterpret_cast<const char*>(dbgs[k]) : nullptr;
-				if (c && d && c == d && a == b && (fc.flags & BM_FLAG_RAY_DIGEST)) { shared_digest = true; continue; } // (allowed for uniform launches: below)
-				if (c && d && c < d + pixels * 32 && d < c + pixels * 32) {
-					set_error("bm_render_frames: the frames of one launch need hit-record buffers of their own");
-					return BM_EINVAL;
-				}
-			}
-	}
-	// ---- a UNIFORM launch?  Frames that differ only in sample_base and buffers, both stepping by constants (a resting camera: the
-	// reference's progressive accumulation; bench.py's steps; a rank's batch into one allocation): lanes of consecutive frames may then
-	// share a wave (trace.hip), because nothing a lane reads after it took its item depends on the frame any more.
-	bool digest_ok = false;
-	if (shared_digest) { // every frame names the same two buffers?
-		digest_ok = true;
-		for (int i = 0; i < count; ++i) digest_ok = digest_ok && dbgs[i] == dbgs[0] && accums[i] == accums[0];
-	}
-	if (count > 1 && (!hit_records || digest_ok)) {
-		auto same_view = [&](const FrameConstants& a, const FrameConstants& b) {
-			// everything up to `width` is the view, the sun and the sky (device_types.h); base_frame seeds the RNG
-			return std::memcmp(&a, &b, offsetof(FrameConstants, width)) == 0 && a.base_frame == b.base_frame;
-		};
-		const long long sample_stride = static_cast<long long>(fcs[1].sample_base) - fcs[0].sample_base;
-		const long long byte_stride = reinterpret_cast<const char*>(accums[1]) - reinterpret_cast<const char*>(accums[0]);
-		const unsigned long long pixels = static_cast<unsigned long long>(fc.local_rows) * static_cast<unsigned long long>(fc.width);
-		bool uniform = sample_stride >= 0 && sample_stride < (1 << 20) && byte_stride >= 0 && byte_stride % 16 == 0 &&
-					   static_cast<unsigned long long>(byte_stride / 16) * static_cast<unsigned long long>(count - 1) + pixels < (1ull << 32) &&
-					   static_cast<long long>(fcs[0].sample_base) + sample_stride * (count - 1) + fc.spp < (1ll << 31);
-		for (int i = 1; i < count && uniform; ++i)
-			uniform = same_view(fcs[static_cast<size_t>(i)], fcs[0]) && static_cast<long long>(fcs[static_cast<size_t>(i)].sample_base) == fcs[0].sample_base + sample_stride * i &&
-					  reinterpret_cast<const char*>(accums[i]) == reinterpret_cast<const char*>(accums[0]) + byte_stride * i;
-		if (uniform) {
-			for (int i = 0; i < count; ++i) { // every entry reads like the first; the frame is an offset the lanes add themselves
-				fcs[static_cast<size_t>(i)].sample_base = fcs[0].sample_base;
-				fcs[static_cast<size_t>(i)].accum = fcs[0].accum;
-			}
-			fcs[0].ring_uniform = 1;
-			fcs[0].ring_sample_stride = static_cast<int>(sample_stride);
-			fcs[0].ring_pixel_stride = static_cast<uint32_t>(byte_stride / 16);
-			// ... and frames that add with float atomics are handed out several at a time (trace.hip "FRAME GROUPS")
-			set_ring_group(&fcs[0], ring_group_of(fcs[0], count), count);
-		}
-		if (shared_digest && !uniform) digest_ok = false;
-	}
-	if (shared_digest && !digest_ok) {
-		// One hit-record buffer for several frames is the digest of the WHOLE launch: its keys count samples from the first frame's
-		// sample_base and its first-hit record is written once -- which only a uniform launch (one view, stepping sample_base) defines
-		set_error("bm_render_frames: ray-digest frames may share one hit-record buffer only in a uniform launch (one view and sun, sample_base stepping by a constant, one accumulation buffer)");
-		return BM_EINVAL;
-	}
-	if (shared_digest) {
-		// ... and that digest counts the pixel's rays of ALL the frames in 16 bits (word 6) and keys them with 24 bits of sample index
-		// counted from the first frame's sample_base: fill_frame_constants checked one frame's share of either
-		const long long sample_stride = fc.ring_sample_stride; // (a shared digest is a uniform launch; the entries' own sample_base all read like the first by now)
-		if (static_cast<long long>(count) * fc.spp * (fc.max_bounces + 1) >= 65536 || sample_stride * (count - 1) + fc.spp >= (1ll << 24)) {
-			set_error("bm_render_frames: ray-digest frames that share one hit-record buffer: frames x spp x segments < 65536 and sample_base stride x (frames - 1) + spp < 2^24 (the digest counts the launch's rays per pixel in 16 bits and keys them with 24 bits of sample)");
-			return BM_EINVAL;
-		}
-	}
-	{ // the kernel's hang guard is a 64-bit product (trace.hip round_budget): a launch for which it would wrap -- it would end before it has
-	  // traced anything -- is refused (such a launch is weeks of GPU time anyway)
-		const unsigned __int128 rounds = static_cast<unsigned __int128>(static_cast<unsigned long long>(fc.tiles_x) * static_cast<unsigned long long>(fc.tiles_y) * 16ull + 64ull) *
-										 static_cast<unsigned long long>(fc.spp + 1) * static_cast<unsigned long long>(fc.max_bounces + 2) *
-										 static_cast<unsigned long long>(2ll * world.dims.cells + world.dims.cells_height + 64) * static_cast<unsigned long long>(count);
-		if (rounds >= (static_cast<unsigned __int128>(1) << 62)) {
-			set_error("launch too large: tiles x samples x segments x frames overflows the kernel's round budget (render fewer samples or frames per launch)");
-			return BM_EINVAL;
-		}
-	}
 	BM_HIP(hipSetDevice(device_));
-	const bool instrumented = hit_records || (fc.flags & BM_FLAG_COUNTERS);
 	// the sun plane, for the first frame's sun: built now if it is not there; frames of the launch with another sun keep their octant planes
-	if (!instrumented && !(fc.flags & BM_FLAG_PRIMARY_ONLY) && fc.spp >= 1) {
+	if (!plan.instrumented && !(fc.flags & BM_FLAG_PRIMARY_ONLY) && fc.spp >= 1) {
 		bool usable = false;
 		if (int e = ensure_sun_plane(fc, &usable)) return e;
 		if (usable)
@@ -1535,23 +1427,29 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 			waited = owner;
 		}
 	}
-	// (one block per frame; a uniform launch uses one per GROUP of frames, the first of them)
 	uint32_t* const work_counter = d_work_counter_ + static_cast<size_t>(first) * (kWorkCounterBytes / sizeof(uint32_t));
-	const int counter_blocks = fc.ring_uniform ? fc.ring_groups_after + 1 : count;
-	BM_HIP(hipMemsetAsync(work_counter, 0, kWorkCounterBytes * static_cast<size_t>(counter_blocks), stream)); // ticket counters of the persistent kernel
-	std::memcpy(h_frame_constants_ + first, fcs.data(), sizeof(FrameConstants) * static_cast<size_t>(count));
-	BM_HIP(hipMemcpyAsync(d_frame_constants_ + first, h_frame_constants_ + first, sizeof(FrameConstants) * static_cast<size_t>(count), hipMemcpyHostToDevice, stream));
-	BM_HIP(hipEventRecord(ev_start_[slot], stream));
 #ifdef BM_PHASE_TIMING
-	DeviceCounters* const counters_arg = d_counters_; // profiling build: the plain kernel reports its phase timers too
+	DeviceCounters* const counters = d_counters_; // profiling build: the plain kernel reports its phase timers too
 #else
-	DeviceCounters* const counters_arg = (fc.flags & BM_FLAG_COUNTERS) ? d_counters_.get() : nullptr;
+	DeviceCounters* const counters = (fc.flags & BM_FLAG_COUNTERS) ? d_counters_.get() : nullptr;
 #endif
-	launch_trace(view_, fc, d_frame_constants_ + first, counters_arg, work_counter, instrumented,
-				 compute_units_, blocks_per_cu_[instrumented ? 1 : 0], stream);
-	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_stop_[slot], stream));
-	if (int e = frame_end(stream)) return e; // what process_load_queue orders itself behind
+	auto enqueue = [&]() -> int {
+		BM_HIP(hipMemsetAsync(work_counter, 0, kWorkCounterBytes * static_cast<size_t>(plan.counter_blocks), stream)); // ticket counters of the persistent kernel
+		std::memcpy(h_frame_constants_ + first, fcs.data(), sizeof(FrameConstants) * static_cast<size_t>(count));
+		BM_HIP(hipMemcpyAsync(d_frame_constants_ + first, h_frame_constants_ + first, sizeof(FrameConstants) * static_cast<size_t>(count), hipMemcpyHostToDevice, stream));
+		BM_HIP(hipEventRecord(ev_start_[slot], stream));
+		launch_trace(view_, d_frame_constants_ + first, counters, work_counter, plan.instrumented, fc.xcd_handout != 0, fc.helpers != 0, plan.ring_mode, plan.workgroups,
+					 compute_units_, blocks_per_cu_[plan.instrumented ? 1 : 0], stream);
+		BM_HIP(hipGetLastError());
+		BM_HIP(hipEventRecord(ev_stop_[slot], stream));
+		return frame_end(stream); // what process_load_queue orders itself behind
+	};
+	if (int e = enqueue()) {
+		// part of the launch may be queued, and nothing records that it uses the ring entries and the pinned constants: wait for it
+		// here, so that no later launch writes them under a copy that is still pending
+		(void)hipStreamSynchronize(stream);
+		return e;
+	}
 	for (int e = first; e < first + count; ++e) ring_owner_[e] = launches_;
 	ring_next_ = first + count;
 	launches_++;
@@ -1700,13 +1598,9 @@ int Scene::pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays,
 		set_error("bm_camera_pixel_rays_device: bad argument (null, a size outside 1 ... 65535, or rays not 16-byte aligned)");
 		return BM_EINVAL;
 	}
-	// the camera basis of the frames, as bm_camera_pixel_rays takes it
-	bm_frame_params p{};
-	p.width = width; p.height = height; p.spp = 1; p.band_rows = height; p.shard_count = 1;
-	FrameConstants fc;
-	if (int e = fill_frame_constants(cam, &p, &fc)) return e;
+	const CameraBasis basis = camera_basis(cam->position, cam->direction, cam->up, width, height); // the frames' basis, as bm_camera_pixel_rays takes it
 	PixelRayBasis b;
-	for (int k = 0; k < 3; ++k) { b.right[k] = fc.right[k]; b.up[k] = fc.up[k]; b.dir[k] = fc.dir[k]; b.origin[k] = fc.origin[k]; }
+	for (int k = 0; k < 3; ++k) { b.right[k] = basis.right[k]; b.up[k] = basis.up[k]; b.dir[k] = basis.dir[k]; b.origin[k] = basis.origin[k]; }
 	b.width = width; b.height = height;
 	BM_HIP(hipSetDevice(device_));
 	launch_pixel_rays(b, rays, stream);

@@ -11,30 +11,12 @@
 #include "arena.h"
 #include "device_types.h"
 #include "error.h"
+#include "frame_plan.h"
 #include "hip_owned.h"
 #include "kernels.h"
 #include "world.h"
 
 namespace bm {
-
-void division_magic(uint32_t d, uint32_t* magic, int* shift); // floor(n / d) = umulhi(n, magic) >> shift for n < 2^30 (frame_plan.cpp)
-
-// a wave of a multi-frame launch (the frame ring) with helper lanes takes new items once this many of its lanes are idle (scene.cpp render_frames)
-constexpr int kRingRefillMin = 32;
-inline int ring_refill_min(int single_frame_refill_min, bool helpers, int override_refill_min) {
-	return (helpers && !(override_refill_min >= 1 && override_refill_min <= 64)) ? kRingRefillMin : single_frame_refill_min;
-}
-
-// tuning overrides from the environment (frame_plan.cpp tuning()): 0 / -1 = not set
-struct Tuning {
-	int refill_min = 0, xcd_handout = -1, helpers = -1, blocks_per_cu = 0, ring_group = 0;
-};
-const Tuning& tuning();
-
-// the frames of a uniform launch are handed out in groups of this many (trace.hip "FRAME GROUPS"; frame_plan.cpp ring_group_of)
-constexpr int kRingGroup = 4, kMaxRingGroup = 64;
-int ring_group_of(const FrameConstants& fc, int frames); // the group size a uniform launch of `frames` such frames gets (1: frame after frame)
-void set_ring_group(FrameConstants* fc, int group, int frames); // ... written into the launch's first constants, with the hand-out's division by samples x group
 
 class Scene {
 public:
@@ -105,10 +87,6 @@ public:
 
 	World world;
 	int device() const { return device_; }
-
-	// hit_records: the frame writes per-pixel hit records, which makes it an ORDERED frame (frame_plan.cpp)
-	static int fill_frame_constants(const bm_camera* cam, const bm_frame_params* fp, FrameConstants* fc, bool hit_records = false);
-
 
 private:
 	int allocate_device();
@@ -193,7 +171,7 @@ private:
 	DeviceBuffer<uint32_t> d_bricks_queue_, d_indices_queue_;
 	DeviceBuffer<DeviceCounters> d_counters_;
 	// the frame ring: constants and ticket counters of the frames in flight -- a launch takes as many consecutive entries as it has frames
-	static constexpr int kFrameRing = 1024, kMaxFramesPerLaunch = 256;
+	static constexpr int kFrameRing = 1024; // (a launch takes at most kMaxFramesPerLaunch, frame_plan.h)
 	DeviceBuffer<FrameConstants> d_frame_constants_; // kFrameRing device copies
 	PinnedBuffer<FrameConstants> h_frame_constants_; // pinned source of the copies
 	DeviceBuffer<uint32_t> d_work_counter_; // chunk counters of the persistent trace kernel: kFrameRing blocks of kWorkCounterBytes, zeroed before the launch that uses them

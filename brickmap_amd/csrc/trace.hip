@@ -895,36 +895,19 @@ int trace_blocks_per_cu(bool instrumented, bool xcd, bool help, int ring) {
 	return with_instantiation(instrumented, xcd, help, ring, [](auto d, auto x, auto h, auto r) { return occupancy_of<decltype(d)::value, decltype(x)::value, decltype(h)::value, decltype(r)::value>(); });
 }
 
-// Persistent launch: exactly as many 256-thread workgroups as the device keeps resident (compute_units x
-// blocks per CU); the waves pull 4x4-pixel chunks from the ticket counters behind work_counter -- one block of kWorkCounterBytes
-// per frame of the launch (fc_dev[0], fc_dev[1], ... up to the entry with frames_after == 0), all zero at launch.  fc = the host
-// copy of the first frame's constants (fc_dev[0]).
-void launch_trace(const DeviceScene& sc, const FrameConstants& fc, const FrameConstants* fc_dev, DeviceCounters* counters,
-				  uint32_t* work_counter, bool instrumented, int compute_units, int blocks_per_cu_cap, hipStream_t stream) {
-	const long long chunks = static_cast<long long>(fc.tiles_x) * fc.tiles_y * 16;
-	if (chunks <= 0) return;
-	const bool xcd = fc.xcd_handout != 0, help = fc.helpers != 0;
-	const int ring = fc.frames_after > 0 ? (fc.ring_uniform ? 2 : 1) : 0;
+// Persistent launch: as many 256-thread workgroups as the plan asks for (frame_plan.cpp plan_launch), at most what the device keeps
+// resident (compute_units x blocks per CU); the waves pull 4x4-pixel chunks from the ticket counters behind work_counter -- one block
+// of kWorkCounterBytes per frame of the launch (fc_dev[0], fc_dev[1], ... up to the entry with frames_after == 0), all zero at launch.
+void launch_trace(const DeviceScene& sc, const FrameConstants* fc_dev, DeviceCounters* counters, uint32_t* work_counter, bool instrumented, bool xcd, bool help,
+				  int ring, long long workgroups, int compute_units, int blocks_per_cu_cap, hipStream_t stream) {
+	if (workgroups <= 0) return;
 	int per_cu = trace_blocks_per_cu(instrumented, xcd, help, ring); // what THIS instantiation keeps resident
 	if (blocks_per_cu_cap > 0 && per_cu > blocks_per_cu_cap) per_cu = blocks_per_cu_cap;
 	const long long resident_blocks = static_cast<long long>(compute_units) * per_cu;
-	// never more waves than a frame has 64-item groups: an item is a pixel, or ONE sample of a pixel with (chunk, sample) items -- a
-	// 1/8 shard of a 1080p frame at 8 spp is 276 480 pixels but 2.2 M items, and sizing its launch by pixels left 40 % of the
-	// GPU's wave slots empty (1080 of 1792 workgroups: 1.16 -> 0.95 ms per shard step).  A launch of several frames may start a
-	// second frame's worth of waves: those that find the first frame's counters used up go straight on to the next one.
-	const long long items = chunks * 16 * ((fc.flags & 4u /* BM_FLAG_SAMPLE_ITEMS */) ? (fc.spp > 0 ? fc.spp : 1) : 1);
-	long long blocks = (items + 255) / 256;
-	if (ring) blocks *= 2;
-	if (blocks > resident_blocks) blocks = resident_blocks;
+	const long long blocks = workgroups < resident_blocks ? workgroups : resident_blocks;
 	const dim3 grid(static_cast<unsigned>(blocks)), block(256);
-#ifdef BM_PHASE_TIMING
-	DeviceCounters* const plain_counters = counters; // profiling build: the plain kernel reports its phase timers too
-#else
-	DeviceCounters* const plain_counters = nullptr;
-#endif
-	DeviceCounters* const cnt = instrumented ? counters : plain_counters;
 	with_instantiation(instrumented, xcd, help, ring, [&](auto d, auto x, auto h, auto r) {
-		hipLaunchKernelGGL((trace_paths<decltype(d)::value, decltype(x)::value, decltype(h)::value, decltype(r)::value>), grid, block, 0, stream, sc, fc_dev, cnt, work_counter);
+		hipLaunchKernelGGL((trace_paths<decltype(d)::value, decltype(x)::value, decltype(h)::value, decltype(r)::value>), grid, block, 0, stream, sc, fc_dev, counters, work_counter);
 		return 0;
 	});
 }

@@ -55,7 +55,7 @@ int Wavefront::frame(const bm_camera* cam, const bm_frame_params* fp, float* acc
 	p.spp = 1; p.sample_base = 0;
 	p.band_rows = 16; p.shard_rank = 0; p.shard_count = 1; // the queue schedule does not shard: replicas only
 	FrameConstants fc;
-	if (int e = Scene::fill_frame_constants(cam, &p, &fc)) return e;
+	if (int e = fill_frame_constants(cam, &p, &fc)) return e;
 	const unsigned long long pixels = static_cast<unsigned long long>(fp->width) * static_cast<unsigned long long>(fp->height);
 	if (pixels > 0xFFFFFFFFull) { set_error("frame too large"); return BM_EINVAL; }
 	DeviceScene view;

@@ -120,6 +120,25 @@ def frame_plan(params: FrameParams, hit_records=False):
     return {name: int(getattr(plan, name)) for name, _ in _lib.bm_frame_plan._fields_}
 
 
+def launch_plan(cameras, params, accum_ptrs, debug_ptrs=None, grid_size=256, grid_height=256):
+    """bm_launch_plan_of: what the library decides for a bm_render_frames launch of `len(params)` frames (host only, no scene): the ring
+    mode (0 one frame, 1 frame ring, 2 uniform frame ring), the frame group and strides of a uniform launch, shared_digest, instrumented,
+    counter_blocks, refill_min and the workgroups before the residency cap.  cameras: one Camera or one per frame; accum_ptrs: one
+    address or one per frame; debug_ptrs: None or one entry per frame (None or an address).  The addresses are integers -- a tensor's
+    data_ptr() -- and are only compared, never read.  Raises what Scene.render_frames would raise on a world of that size."""
+    n = len(params)
+    cams = list(cameras) if isinstance(cameras, (list, tuple)) else [cameras] * n
+    accs = list(accum_ptrs) if isinstance(accum_ptrs, (list, tuple)) else [accum_ptrs] * n
+    assert len(cams) == n and len(accs) == n and (debug_ptrs is None or len(debug_ptrs) == n)
+    cam_c = (_lib.bm_camera * n)(*[c.to_c() for c in cams])
+    par_c = (_lib.bm_frame_params * n)(*[p.to_c() for p in params])
+    acc_p = (C.c_void_p * n)(*accs)
+    dbg_p = (C.c_void_p * n)(*debug_ptrs) if debug_ptrs is not None else None
+    plan = _lib.bm_launch_plan()
+    check(_lib.load().bm_launch_plan_of(n, cam_c, par_c, acc_p, dbg_p, grid_size, grid_height, C.byref(plan)))
+    return {name: int(getattr(plan, name)) for name, _ in _lib.bm_launch_plan._fields_}
+
+
 def trace_waves_per_simd(instrumented=False, xcd_handout=False, helpers=True, device=0):
     """bm_trace_waves_per_simd: resident waves per SIMD of the trace_paths instantiation on `device`."""
     n = C.c_int(0)

@@ -577,6 +577,24 @@ typedef struct bm_frame_plan {
 	                          bm_render_frames launch (one view, sample_base and buffers stepping by constants); 1: frame after frame */
 } bm_frame_plan;
 BM_API int bm_frame_plan_of(const bm_frame_params* params, int hit_records, bm_frame_plan* out);
+/* What the library decides for a bm_render_frames launch with these arguments (host only: no device, no scene; grid_size and
+ * grid_height are the world's, as for bm_scene_create).  This is how a host learns the ring mode its launch gets -- which the
+ * library decides from the frames' views and from the ADDRESSES of the buffers, never by reading them: accum_dev / debug_dev
+ * are only compared and subtracted here.  Accepts and refuses exactly what bm_render_frames does on a scene of that world, with
+ * the same error text; a refused plan leaves *out all zero. */
+typedef struct bm_launch_plan {
+	int32_t  ring_mode;       /* 0: one frame; 1: frame ring, waves change frame when idle; 2: uniform frame ring, frames share waves */
+	int32_t  ring_group;      /* frames handed out together (1 unless ring_mode == 2)                                                 */
+	int32_t  sample_stride;   /* ring_mode 2: sample_base step from frame to frame                                                    */
+	uint32_t pixel_stride;    /* ring_mode 2: buffer step from frame to frame, in pixels                                              */
+	int32_t  shared_digest;   /* 1: ray-digest frames that all write one hit-record buffer                                            */
+	int32_t  instrumented;    /* 1: the instrumented instantiation (hit records / BM_FLAG_COUNTERS) runs                              */
+	int32_t  counter_blocks;  /* ticket-counter blocks the launch zeroes: one per frame, or per group of frames when ring_mode == 2   */
+	int32_t  refill_min;      /* a wave takes new work items once this many of its lanes are idle                                     */
+	int64_t  workgroups;      /* before the cap by what the device keeps resident                                                     */
+} bm_launch_plan;
+BM_API int bm_launch_plan_of(int count, const bm_camera* cameras, const bm_frame_params* params, float* const* accum_dev,
+                             uint32_t* const* debug_dev, int grid_size, int grid_height, bm_launch_plan* out);
 /* resident waves per SIMD of the trace_paths instantiation <instrumented, xcd_handout, helpers> on `device` (what the register
  * budget allows: hipOccupancyMaxActiveBlocksPerMultiprocessor of the 256-thread workgroup = one wave per SIMD each) */
 BM_API int bm_trace_waves_per_simd(int device, int instrumented, int xcd_handout, int helpers, int* waves);

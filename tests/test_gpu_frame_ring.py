@@ -265,3 +265,47 @@ def test_bad_launches_are_refused(bm, orc, torch_cuda, scene256):
     scene256.render_frames(cam, [p, p], acc)  # production frames may share the buffer
     torch.cuda.synchronize()
     assert torch.all(acc[..., 3] == 2)
+
+
+def test_render_frames_runs_the_plan_it_reports(bm, orc, torch_cuda, scene256):
+    """bm.launch_plan (host only) and Scene.render_frames decide with one function: on the real buffers' addresses both accept -- the
+    launch then renders every frame, in whichever ring mode the plan names -- or both refuse with the same message."""
+    torch = torch_cuda
+    W, H, K = 64, 48, 5
+    cam, cam2 = cameras(bm, orc, 256)[0], fly(bm, orc, 3)[0]
+    zeros = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device="cuda:0")
+    prod = [bm.FrameParams(W, H, spp=1, sample_base=k, max_bounces=3) for k in range(K)]
+    ordered = [bm.FrameParams(W, H, spp=1, sample_base=k, max_bounces=3, flags=bm.BM_FLAG_ORDERED) for k in range(K)]
+    digest = [bm.FrameParams(W, H, spp=1, sample_base=k, max_bounces=3, flags=bm.BM_FLAG_RAY_DIGEST) for k in range(K)]
+    shared, batch, dig = zeros(H, W, 4), zeros(K, H, W, 4), zeros(H, W, 8, dtype=torch.int32)
+    own = [batch[k] for k in range(K)]
+    # (cameras, params, accums, debugs, the plan's ring_mode / ring_group / counter_blocks or None = refused, frames that write each production buffer)
+    launches = [
+        (cam, prod, [shared] * K, None, (2, 4, 2), K),             # uniform, one buffer: groups of four frames
+        (cam, prod, own, None, (2, 4, 2), 1),                      # uniform, image after image of one allocation
+        ([cam, cam2] * 2 + [cam], prod, [shared] * K, None, (1, 1, K), K),  # two views: a plain ring
+        (cam, ordered, own, None, (2, 1, K), None),                # ordered, buffers of their own: uniform, frame after frame
+        (cam, digest, [shared] * K, [dig] * K, (2, 4, 2), K),      # one digest of the whole launch
+        (cam, ordered, [shared] * K, None, None, None),            # refused: plain stores into one buffer
+        ([cam, cam2] * 2 + [cam], digest, [shared] * K, [dig] * K, None, None),  # refused: a shared digest of two views
+    ]
+    for cams, params, accs, dbgs, want, frames_per_buffer in launches:
+        batch.zero_(), shared.zero_(), dig.zero_()
+        said = []
+        for call in (lambda: bm.launch_plan(cams, params, [a.data_ptr() for a in accs], [d.data_ptr() for d in dbgs] if dbgs else None, grid_size=256, grid_height=256),
+                     lambda: scene256.render_frames(cams, params, accs, debugs=dbgs)):
+            try:
+                said.append(call())
+            except bm.BrickmapError as e:
+                said.append(str(e))
+        torch.cuda.synchronize()
+        plan, rendered = said
+        if want is None:
+            assert isinstance(plan, str) and "bm_render_frames" in plan and rendered == plan
+            assert not batch.any() and not shared.any() and not dig.any()
+            continue
+        assert rendered is None and (plan["ring_mode"], plan["ring_group"], plan["counter_blocks"]) == want
+        assert plan["shared_digest"] == plan["instrumented"] == (1 if dbgs else 0)
+        if frames_per_buffer is not None:
+            for a in {a.data_ptr(): a for a in accs}.values():
+                assert torch.all(a[..., 3] == frames_per_buffer)
