@@ -128,6 +128,7 @@ int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, s
 int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.host_cube_field(dst, capacity, bytes); }
 int bm_scene_escape_table(bm_scene* scene, int32_t* dst, size_t capacity, size_t* count) { BM_NEED(scene); return scene->impl.escape_table(dst, capacity, count); }
 int bm_scene_sun_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12) { BM_NEED(scene); return scene->impl.sun_plane(dst, capacity, bytes, plan12); }
+int bm_scene_shadow_heights(bm_scene* scene, uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4) { BM_NEED(scene); return scene->impl.shadow_heights(dst, capacity, count, bytes, plan4); }
 int bm_scene_sun_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms) { BM_NEED(scene); return scene->impl.sun_plane_stats(builds, last_build_ms); }
 int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms) { BM_NEED(scene); return scene->impl.last_edit_ms(scatter_ms, field_ms); }
 

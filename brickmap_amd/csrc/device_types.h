@@ -44,7 +44,7 @@ BM_VHD size_t brick_first_word(uint32_t pool_base_value, uint32_t index_word) {
 //   brick_arena 64 B * arena capacity    one allocation that all pools live in (power-of-two regions, free lists per
 //                                         size; grows by residency, not by world size)
 //   cube_field  8 planes, 1 B per cell   octant cube field (below): what the walk reads while it crosses empty space
-//   escape      u32[8 * cf_pxy]          escape heights of the walk (below, escape.h)
+//   escape      u32[9 * cf_pxy]          escape heights of the walk (below, escape.h); slice 8: the shadow heights of the sun plane's cone (shadowheight.h)
 //   load_queue  int3[queue_cap] + count  brick-request ring (voxel.cuh:228-245)
 struct DeviceScene {
 	uint32_t* index_grid;
@@ -70,7 +70,8 @@ struct DeviceScene {
 	float grid_size_f, grid_height_f;
 	int lod_distance_8x8x8, lod_distance_2x2x2;
 	// escape heights (escape.h): per octant and cell column, the cube-field offset of the first slice in which a ray of that octant
-	// that started in the column can no longer meet a brick; entry (x, y) of octant o at o * cf_pxy + ((y + 1) << cf_shift) + (x + 1)
+	// that started in the column can no longer meet a brick; entry (x, y) of octant o at o * cf_pxy + ((y + 1) << cf_shift) + (x + 1).
+	// Slice 8, same layout (shadowheight.h): the sun-plane offset of the column's first slice from which a shadow ray may reach the sun, or 0
 	const uint32_t* escape;
 };
 

@@ -6,6 +6,7 @@
 
 #include "device_types.h"
 #include "reproject.h"
+#include "shadowheight.h"
 #include "sunfield.h"
 
 namespace bm {
@@ -64,15 +65,22 @@ void launch_escape_update(const uint32_t* index_grid, int32_t* cols, uint32_t* t
 // the sun plane (sunfield.hip; sunfield.h has the rules): plane 8 of `field`, every interior byte, rebuilt from the index grid, the column
 // tops in `cols` and the escape table (both as launch_escape_update leaves them).  nd / n1 / n2: cells along the plan's dominant and minor
 // axes.  tmp: sun_build_tmp_bytes() bytes that no other launch uses until this one has finished.
+// The shadow heights (shadowheight.h) are built on the same occasion, by the clear-heights kernel of every slab: slice 8 of the escape
+// table, from a scan of the columns' full bricks (index words, pool bases and the arena as they stand on the stream); where the plan has
+// none (shadow.valid == 0) the slice is zeroed.  field = false: the slice alone, the plane stands (bricks changed, no cell's occupancy did).
 struct SunBuild {
 	SunPlan plan; // valid
+	ShadowPlan shadow;
+	int fx0, fx1, fy0, fy1; // the columns (unbordered cells, half-open, inside the grid) whose full tops are scanned again; the others keep what tmp_shadow holds
 	int cells, cells_height, sg_xy, sg_xy2;
 	int nd, n1, n2;
 	int cf_shift;
 	uint32_t cf_pxy, cf_plane;
 };
 size_t sun_build_tmp_bytes(const SunBuild& u);
-void launch_sun_build(const uint32_t* index_grid, const int32_t* cols, const uint32_t* escape, uint8_t* field, uint8_t* tmp, const SunBuild& u, hipStream_t stream);
+size_t shadow_build_tmp_bytes(const SunBuild& u); // tmp_shadow: the scratch of the shadow heights, under the same condition
+void launch_sun_build(const uint32_t* index_grid, const uint32_t* pool_base, const uint32_t* arena, const int32_t* cols, uint32_t* escape, uint8_t* field, uint8_t* tmp,
+					  uint8_t* tmp_shadow, const SunBuild& u, bool with_field, hipStream_t stream);
 
 // dense voxels -> scene (load.hip): the volume is V[z][y][x], one byte per voxel, in device memory.  classify leaves lod << 12 in every
 // cell's index word; number turns the words into slot | loaded | lod << 12 (slots in local cell order), fills counts[supercells] and

@@ -167,6 +167,8 @@ void Scene::residency_rebuilt(bool preloaded) {
 	use_ring(0);
 	snapshot_pending_ = false;
 	preloaded_ = preloaded;
+	shadow_dirty_ = true; // the shadow heights count resident bricks, and only where all of them are (ensure_sun_plane)
+	shadow_full_valid_ = false;
 	staging_busy_ = false;
 	failed_ = false;
 	stream_batches_ = stream_host_ns_ = 0;
@@ -303,6 +305,8 @@ int Scene::alloc_cube_field() {
 	}
 	if (!sun_plane_) { if (int e = d_cube_field_.alloc(l.plane * 8)) return e; }
 	sun_built_ = false; // (whoever fills the field afterwards has a new world)
+	shadow_full_valid_ = false;
+	shadow_zero_ = true; // (the memset of the escape allocation below)
 	sun_dirty_ = true;
 	BM_HIP(hipMemset(d_cube_field_, 255, d_cube_field_.bytes())); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
 	view_.cf_shift = l.shift;
@@ -311,7 +315,8 @@ int Scene::alloc_cube_field() {
 	division_magic(view_.cf_pxy, &view_.cf_magic, &view_.cf_magic_shift);
 	view_.cube_field = d_cube_field_;
 	// ... and the escape heights that go with it (escape.h)
-	if (int e = d_escape_.alloc(escape_entries(view_.cf_pxy) * sizeof(uint32_t))) return e;
+	// (a ninth slice behind the octants' eight holds the shadow heights of the sun plane's cone, shadowheight.h: zero = no dark cell)
+	if (int e = d_escape_.alloc((escape_entries(view_.cf_pxy) + (BM_SHADOWHEIGHT != 0 ? view_.cf_pxy : 0u)) * sizeof(uint32_t))) return e;
 	BM_HIP(hipMemset(d_escape_, 0, d_escape_.bytes())); // (border and padding entries: never read, never written)
 	if (int e = d_escape_cols_.alloc(escape_columns_bytes(world.dims.cells))) return e;
 	view_.escape = d_escape_;
@@ -834,7 +839,7 @@ int Scene::info(bm_scene_info* out) {
 	out->brick_bytes = on_device_ ? arena_.capacity() * 64 : 0;
 	out->pool_bytes = on_device_ ? arena_.pool_bricks() * 64 : 0;
 	out->cube_field_bytes = on_device_ ? 8 * static_cast<uint64_t>(view_.cf_plane) : 0; // (the octant planes; the sun plane, where there is one, is one more plane)
-	out->escape_bytes = on_device_ ? d_escape_.bytes() : 0;
+	out->escape_bytes = on_device_ ? escape_entries(view_.cf_pxy) * sizeof(uint32_t) : 0; // (the octants' slices; the shadow heights' slice: bm_scene_shadow_heights)
 	out->sun_plane_bytes = on_device_ && sun_plane_ ? static_cast<uint64_t>(view_.cf_plane) + d_sun_tmp_.bytes() : 0;
 	out->arena_growths = arena_.growths();
 	out->arena_copy_growths = arena_.copy_growths();
@@ -940,6 +945,11 @@ int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const 
 	for (int j = 0; j < kCellsPerSupercell; ++j) {
 		if (!touched[j]) continue;
 		const uint32_t ow = old_words[j], nw = c.indices[j];
+		{
+			const int gx = sx * kSupercell + (j & 15), gy = sy * kSupercell + ((j >> 4) & 15);
+			b.touch_lo[0] = std::min(b.touch_lo[0], gx); b.touch_hi[0] = std::max(b.touch_hi[0], gx);
+			b.touch_lo[1] = std::min(b.touch_lo[1], gy); b.touch_hi[1] = std::max(b.touch_hi[1], gy);
+		}
 		const uint16_t ods = ow ? old_dev[ow & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
 		if (ods != kNoDeviceSlot) {
 			if (nw) dev[nw & BM_BRICK_INDEX_BITS] = ods; // resident stays resident, rewritten in place
@@ -1037,6 +1047,10 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 							load_stream_);
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipEventRecord(times[1], load_stream_));
+		// a brick's bits changed: the shadow heights count full bricks (shadowheight.h); rebuilt like the plane, before the next frame that reads
+		// them, from a scan of the touched columns alone
+		shadow_dirty_ = true;
+		for (int k = 0; k < 2; ++k) { shadow_box_[k] = std::min(shadow_box_[k], b.touch_lo[k]); shadow_box_[2 + k] = std::max(shadow_box_[2 + k], b.touch_hi[k]); }
 		if (field) {
 			launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
 			BM_HIP(hipGetLastError());
@@ -1309,11 +1323,20 @@ int Scene::ensure_sun_plane(const FrameConstants& fc, bool* usable) {
 	if (!plan.valid) return 0; // (the plane of another sun, if any, stays: the frames of this one keep their octant planes)
 	const float key[4] = {fc.cone_dir[0], fc.cone_dir[1], fc.cone_dir[2], fc.cone_extent};
 	*usable = true;
-	if (sun_built_ && !sun_dirty_ && std::memcmp(key, sun_key_, sizeof key) == 0) return 0;
+	const bool stands = sun_built_ && !sun_dirty_ && std::memcmp(key, sun_key_, sizeof key) == 0; // the plane does; the shadow heights may still be stale
+	if (stands && !(BM_SHADOWHEIGHT != 0 && shadow_dirty_)) return 0;
 	const WorldDims& d = world.dims;
 	const int n[3] = {d.cells, d.cells, d.cells_height};
 	SunBuild u{};
 	u.plan = plan;
+	// shadow heights only where every brick is resident: a ray that ends at set-up requests nothing, and in a streaming scene the requests of
+	// the shadow rays' walks are part of what brings the bricks in (the steady state must be the resident scene's) -- there the slice is zeroed
+	u.shadow = BM_SHADOWHEIGHT != 0 && preloaded_ ? shadow_plan(fc.cone_dir, fc.cone_extent) : ShadowPlan{};
+	if (stands && !u.shadow.valid && shadow_zero_) { // (an edit batch of a streaming scene, or under a sun without shadow heights: the slice is zero and stays so, nothing to launch)
+		shadow_dirty_ = false;
+		shadow_plan_ = u.shadow;
+		return 0;
+	}
 	u.cells = d.cells; u.cells_height = d.cells_height;
 	u.sg_xy = d.supergrid_xy; u.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
 	u.nd = n[plan.dom]; u.n1 = n[plan.m1]; u.n2 = n[plan.m2];
@@ -1324,10 +1347,22 @@ int Scene::ensure_sun_plane(const FrameConstants& fc, bool* usable) {
 		BM_HIP(hipStreamSynchronize(load_stream_)); // an earlier build may still use the scratch
 		if (d_sun_tmp_.reserve(sun_build_tmp_bytes(u)) != 0) { (void)hipGetLastError(); set_error(""); return 0; } // no scratch, no plane: not an error
 	}
+	if (u.shadow.valid && shadow_build_tmp_bytes(u) > d_shadow_tmp_.bytes()) {
+		BM_HIP(hipStreamSynchronize(load_stream_));
+		shadow_full_valid_ = false;
+		if (d_shadow_tmp_.reserve(shadow_build_tmp_bytes(u)) != 0) { (void)hipGetLastError(); set_error(""); return 0; }
+	}
+	// the full tops do not depend on the sun: a scan of the whole world once, afterwards of the columns that batches have touched since
+	if (!shadow_full_valid_) { u.fx0 = u.fy0 = 0; u.fx1 = u.fy1 = d.cells; }
+	else {
+		u.fx0 = std::max(0, shadow_box_[0]); u.fy0 = std::max(0, shadow_box_[1]);
+		u.fx1 = std::min(d.cells, shadow_box_[2] + 1); u.fy1 = std::min(d.cells, shadow_box_[3] + 1);
+		if (u.fx1 <= u.fx0 || u.fy1 <= u.fy0) u.fx0 = u.fx1 = u.fy0 = u.fy1 = 0;
+	}
 	// behind every frame in flight (their shadow rays read the plane) and, on the load stream, behind the field and escape updates it reads
 	if (int e = order_load_stream_behind_frames()) return e;
 	BM_HIP(hipEventRecord(ev_sun_time_[0], load_stream_));
-	launch_sun_build(d_index_grid_, d_escape_cols_, d_escape_, d_cube_field_, d_sun_tmp_, u, load_stream_);
+	launch_sun_build(d_index_grid_, d_pool_base_, arena_.base(), d_escape_cols_, d_escape_, d_cube_field_, d_sun_tmp_, d_shadow_tmp_, u, !stands, load_stream_);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(ev_sun_time_[1], load_stream_));
 	BM_HIP(hipEventRecord(ev_upload_, load_stream_)); // frames wait for it like for an upload batch (frame_begin)
@@ -1336,7 +1371,14 @@ int Scene::ensure_sun_plane(const FrameConstants& fc, bool* usable) {
 	sun_plan_ = plan;
 	sun_built_ = true;
 	sun_dirty_ = false;
-	sun_builds_++;
+	shadow_dirty_ = false;
+	shadow_plan_ = u.shadow;
+	shadow_zero_ = !u.shadow.valid;
+	if (u.shadow.valid) { // the scan has run
+		shadow_full_valid_ = true;
+		shadow_box_[0] = shadow_box_[1] = 1 << 30; shadow_box_[2] = shadow_box_[3] = -1;
+	}
+	if (!stands) sun_builds_++;
 	*usable = true;
 	return 0;
 }
@@ -1357,6 +1399,31 @@ int Scene::sun_plane(uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
 	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_ + 8 * static_cast<size_t>(view_.cf_plane), static_cast<size_t>(1) << view_.cf_shift, X, X * Z, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+// the shadow heights as last built: the table's entries per (y, x) -- the sun plane's offset of the column's first slice that is not dark, or 0; *bytes = what they take on the device (the slice and the build's scratch)
+int Scene::shadow_heights(uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4) {
+	if (int e = require_on_device()) return e;
+	const WorldDims& d = world.dims;
+	const bool have = BM_SHADOWHEIGHT != 0 && sun_plane_ && sun_built_;
+	const size_t need = have ? static_cast<size_t>(d.cells) * d.cells : 0;
+	if (count) *count = need;
+	if (bytes) *bytes = BM_SHADOWHEIGHT != 0 && on_device_ ? static_cast<uint64_t>(view_.cf_pxy) * sizeof(uint32_t) + d_shadow_tmp_.bytes() : 0;
+	if (plan4) {
+		const ShadowPlan p = have ? shadow_plan_ : ShadowPlan{};
+		const int32_t v[4] = {p.valid, p.sun.rise, p.rise_hi, kSunHeightUnit};
+		std::memcpy(plan4, v, sizeof v);
+	}
+	if (!dst || !have) return 0;
+	if (capacity < need) { set_error("shadow heights buffer too small"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipDeviceSynchronize());
+	std::vector<uint32_t> slice(view_.cf_pxy);
+	BM_HIP(hipMemcpy(slice.data(), d_escape_ + escape_entries(view_.cf_pxy), slice.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	for (int y = 0; y < d.cells; ++y)
+		for (int x = 0; x < d.cells; ++x)
+			dst[static_cast<size_t>(y) * d.cells + x] = slice[escape_index(0, view_.cf_shift, view_.cf_pxy, x, y)];
 	return 0;
 }
 

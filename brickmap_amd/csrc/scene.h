@@ -46,6 +46,7 @@ public:
 	// has been built and what the last build took
 	int sun_plane(uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12);
 	int sun_plane_stats(uint64_t* builds, float* last_build_ms);
+	int shadow_heights(uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4);
 	// dense regions (region.hip / scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
 	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
 	int read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream);
@@ -103,6 +104,7 @@ private:
 		std::vector<Brick> bricks;
 		std::vector<PoolMove> moves;
 		int box_lo[3] = {1 << 30, 1 << 30, 1 << 30}, box_hi[3] = {-1, -1, -1}; // cells whose occupancy changed (unbordered, inclusive)
+		int touch_lo[2] = {1 << 30, 1 << 30}, touch_hi[2] = {-1, -1};          // columns of every touched cell (x, y): what the shadow heights scan again
 	};
 	int wait_edit_staging();
 	int stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b);
@@ -161,8 +163,15 @@ private:
 	bool sun_plane_ = false, sun_built_ = false, sun_dirty_ = true;
 	float sun_key_[4] = {0.f, 0.f, 0.f, 0.f};
 	SunPlan sun_plan_{};
+	// the shadow heights (shadowheight.h): slice 8 of d_escape_, built with the plane and for its cone; stale once a brick's bits have changed
+	// (shadow_dirty_), also where no cell's occupancy did and the plane stands -- then ensure_sun_plane rebuilds the slice alone
+	bool shadow_dirty_ = true;
+	bool shadow_zero_ = true;        // the slice holds zeros only (as allocated, or built for a sun or a scene without shadow heights)
+	bool shadow_full_valid_ = false; // d_shadow_tmp_ holds every column's full top of the world as it was at the last scan; the full tops do not depend on the sun
+	int shadow_box_[4] = {1 << 30, 1 << 30, -1, -1}; // ... and the columns touched since (x0, y0, x1, y1; unbordered, inclusive): the next build scans these alone
+	ShadowPlan shadow_plan_{};
 	uint64_t sun_builds_ = 0;
-	DeviceBuffer<uint8_t> d_sun_tmp_;
+	DeviceBuffer<uint8_t> d_sun_tmp_, d_shadow_tmp_;
 	Event ev_sun_time_[2];
 	// two request rings: the blocking (reference-order) mode only uses ring 0; the overlapped mode alternates them so
 	// that a frame can raise requests while the previous frame's ring is being copied out and serviced

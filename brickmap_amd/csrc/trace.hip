@@ -229,6 +229,8 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 	RayState r;
 	constexpr bool kEscape = BM_ESCAPE != 0 && !DBG && (BM_ESCAPE_XCD != 0 || !XCD);
 	constexpr bool kSun = BM_SUNFIELD != 0 && kEscape && (BM_SUNFIELD_XCD != 0 || !XCD); // (the plane's stamps stand in for the escape test: only where that is compiled in)
+	// shadow heights (shadowheight.h, BM_SHADOWHEIGHT / BM_SHADOWHEIGHT_XCD): production shadow rays on the sun plane end at set-up where no ray of the cone reaches the sun
+	constexpr bool kShade = BM_SHADOWHEIGHT != 0 && kSun && !DBG && (BM_SHADOWHEIGHT_XCD != 0 || !XCD);
 	uint32_t esc = 0; // kEscape: the escape threshold of the ray in flight (ray_setup)
 	r.hit = false;
 	r.n = mk(0.f, 0.f, 0.f);
@@ -697,7 +699,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					ray_loads0 = tally.index_loads;
 				}
 				pstate = shadow ? ((HELP && pstate == P_HELPER) ? P_HELPER : P_SHD_DONE) : P_EXT_DONE;
-				const int st = ray_setup<DBG, kEscape>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u);
+				const int st = ray_setup<DBG, kEscape, kShade>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u);
 				state = (st == ST_NEED && shadow) ? ST_CONN : st;
 			}
 			BM_MARK(4, t_sub); // ray set-up

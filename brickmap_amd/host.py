@@ -698,6 +698,21 @@ class Scene:
         c = self.grid_size // 8 + 2
         return out.reshape(-1, c, c), plan
 
+    def shadow_heights(self):
+        """bm_scene_shadow_heights: (entries, plan, bytes) -- the table of shadow heights as last built, uint32 [cells, cells] (y, x): 0 = no
+        dark cell, otherwise the sun plane's byte offset of the column's first slice that is not dark; None when nothing has been built.  plan:
+        dict (valid, rise, rise_hi, unit); bytes: device memory of the slice and the build's scratch."""
+        n, nbytes = C.c_size_t(0), C.c_uint64(0)
+        plan = (C.c_int32 * 4)()
+        check(self._L.bm_scene_shadow_heights(self.gpuScene, None, 0, C.byref(n), C.byref(nbytes), plan))
+        plan = dict(zip(("valid", "rise", "rise_hi", "unit"), (int(v) for v in plan)))
+        if n.value == 0:
+            return None, plan, int(nbytes.value)
+        out = np.zeros(n.value, np.uint32)
+        check(self._L.bm_scene_shadow_heights(self.gpuScene, out.ctypes.data, out.size, C.byref(n), None, None))
+        c = self.grid_size // 8
+        return out.reshape(c, c), plan, int(nbytes.value)
+
     def sun_plane_stats(self):
         """bm_scene_sun_plane_stats: (builds so far, device ms of the last build)."""
         builds, ms = C.c_uint64(0), C.c_float(0)

@@ -234,8 +234,16 @@ BM_API int bm_scene_escape_table(bm_scene* scene, int32_t* dst, size_t capacity,
  * octant, dominant axis, minor axes m1 and m2, bins moved per slab along m1 (least, most) and along m2 (least, most), whether clear
  * heights were built, rise per slab in 1/256 cells, bins per cell. */
 BM_API int bm_scene_sun_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12);
+/* ---- shadow heights: with the sun plane, and for the same cone, the scene keeps per brick-cell column the height below which no ray of
+ * the cone can reach the sun (only for cones whose dominant axis is horizontal, and only while every brick is resident: a scene that
+ * streams its bricks in has none, its table is zero); production shadow rays that start below it end at once, occluded.  Rebuilt with the plane, and alone after a change that left every cell's occupancy as it was.  bm_scene_shadow_heights
+ * copies the 32-bit table entries as last built (waits for the device): dst[y * cells + x] = 0 where the column has no dark cell,
+ * otherwise the sun plane's byte offset of the first slice that is not dark, 8 * plane + (Zd + 1) * slice pitch.  *count = entries needed
+ * (cells^2; 0 when nothing has been built), also when dst is null; *bytes = device memory of the table's slice and the build's scratch (not
+ * part of escape_bytes or sun_plane_bytes); plan4: valid, least and most rise per slab, height units per cell. */
+BM_API int bm_scene_shadow_heights(bm_scene* scene, uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4);
 /* how often the sun plane has been built since the scene was created, and the device time of the last build in ms (0 before the first;
- * waits for that build) */
+ * waits for that build).  A rebuild of the shadow heights alone (above) is not counted as a build, but last_build_ms is then its time. */
 BM_API int bm_scene_sun_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms);
 /* device time of the last batch that changed the scene (hipEvents on the load stream): the scatter (pool moves, bricks, words)
  * and the cube-field update with the escape-height update behind it (0 when no cell's occupancy changed); waits for that batch */
