@@ -166,6 +166,11 @@ SIGNATURES = {
     "bm_scene_last_region_ms": (_i, [_vp] + [C.POINTER(C.c_float)] * 4),
     "bm_scene_cast_rays": (_i, [_vp, C.c_int64, _vp, _vp, C.c_uint32, _vp, _vp]),
     "bm_scene_query_volumes": (_i, [_vp, C.c_int64, _vp, _vp, C.c_uint32, _vp]),
+    "bm_scene_label_region": (_i, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_int32 * 3), C.c_uint32, _vp, _vp, _vp]),
+    "bm_scene_label_components": (_i, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_int32 * 3), _vp, _vp, C.c_int64, _vp]),
+    "bm_scene_label_mask": (_i, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_int32 * 3), _vp, _vp, C.c_int64, _vp, _vp, _vp]),
+    "bm_scene_last_label_ms": (_i, [_vp] + [C.POINTER(C.c_float)] * 3),
+    "bm_host_label_volume": (_i, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.POINTER(C.c_uint64)]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

@@ -162,6 +162,23 @@ int bm_scene_query_volumes(bm_scene* scene, int64_t n, const bm_volume* volumes_
 	return scene->impl.query_volumes(n, volumes_dev, results_dev, flags, static_cast<hipStream_t>(hip_stream));
 }
 
+// (bm_host_label_volume is csrc/label_host.cpp: host code that needs nothing of the library)
+int bm_scene_label_region(bm_scene* scene, const int32_t lo[3], const int32_t hi[3], uint32_t flags, int32_t* labels_dev, uint64_t* count_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.label_region(lo, hi, flags, labels_dev, count_dev, static_cast<hipStream_t>(hip_stream));
+}
+int bm_scene_label_components(bm_scene* scene, const int32_t lo[3], const int32_t hi[3], const int32_t* labels_dev, bm_component* comps_dev, int64_t capacity,
+							  void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.label_components(lo, hi, labels_dev, comps_dev, capacity, static_cast<hipStream_t>(hip_stream));
+}
+int bm_scene_label_mask(bm_scene* scene, const int32_t lo[3], const int32_t hi[3], const int32_t* labels_dev, const bm_component* comps_dev, int64_t n,
+						const uint8_t* chosen_dev, uint8_t* mask_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.label_mask(lo, hi, labels_dev, comps_dev, n, chosen_dev, mask_dev, static_cast<hipStream_t>(hip_stream));
+}
+int bm_scene_last_label_ms(bm_scene* scene, float* local_ms, float* merge_ms, float* flatten_ms) { BM_NEED(scene); return scene->impl.last_label_ms(local_ms, merge_ms, flatten_ms); }
+
 int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t n, const float* px, const float* py, bm_ray* out) {
 	if (!camera || width <= 0 || height <= 0 || width > 65535 || height > 65535 || n < 0 || (n > 0 && (!px || !py || !out))) {
 		set_error("bm_camera_pixel_rays: bad argument");

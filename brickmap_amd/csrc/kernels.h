@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -123,6 +123,25 @@ void launch_query(const DeviceScene& sc, const int campos[3], const void* rays, 
 int volume_blocks_per_cu(bool any);
 size_t volume_tmp_bytes(uint32_t n);
 void launch_volume_query(const DeviceScene& sc, const void* volumes, void* results, uint32_t n, bool any, uint64_t* tmp, int resident_blocks, hipStream_t stream);
+
+// connected components (label.hip; label.h has the rules): the label volume L[z][y][x] of the box [org, org + (nx, ny, nz)) is tight, one
+// int32 per voxel.  [lo, hi) = the box clipped to the world (lo == hi == 0 when nothing is left: then c0 / nc are not used), c0 / nc = the
+// brick cells it overlaps
+struct LabelDims {
+	int lo[3], hi[3], org[3];
+	uint32_t nx, ny, nz;
+	int c0[3], nc[3];
+	uint32_t sg_xy, sg_xy2;
+};
+// local, merge, flatten over the clipped box (not empty; the voxels outside the world are zeroed by the caller): labels as the contract
+// of bm_scene_label_region has them, and the number of components added to *count.  patch_cells / patch_bricks: `patches` listed cells
+// (as launch_region_patch takes them) whose bricks the device does not hold.  marks: null, or 4 events around local, merge and flatten.
+void launch_label_region(const DeviceScene& sc, uint32_t* labels, uint64_t* count, const LabelDims& d, const int* patch_cells, const uint32_t* patch_bricks,
+						 uint32_t patches, hipStream_t stream, hipEvent_t* marks = nullptr);
+// tmp of launch_label_components: one 64-bit word per 1024 voxels, plus one, that no other launch uses until this one has finished
+size_t label_tmp_bytes(uint32_t voxels);
+void launch_label_components(const uint32_t* labels, void* comps, uint64_t capacity, const LabelDims& d, uint64_t* tmp, hipStream_t stream);
+void launch_label_mask(const uint32_t* labels, uint32_t voxels, const void* comps, uint64_t records, const uint8_t* chosen, uint8_t* mask, hipStream_t stream);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

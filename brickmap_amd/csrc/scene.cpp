@@ -18,6 +18,7 @@
 #include "denoise.h"
 #include "escape.h"
 #include "kernels.h"
+#include "label.h"
 
 namespace bm {
 
@@ -1220,26 +1221,8 @@ int Scene::last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, flo
 	return 0;
 }
 
-// The host world is authoritative, so a host read is World::store_region.  A device read is issued like a query: the unpack kernel reads
-// the device words and bricks; bricks that are not resident (a streaming scene) are staged from the host world and written by a second
-// small launch; what lies outside the world is zeroed.
-int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream) {
-	bm_region r;
-	uint64_t span = 0;
-	if (int e = check_region("bm_scene_read_region", region, voxels, where, &r, &span)) return e;
-	if (span == 0) return 0;
+int Scene::stage_absent_bricks(bool inside, const int lo[3], const int hi[3], size_t* count, size_t* bricks_at, size_t* total) {
 	const WorldDims& d = world.dims;
-	int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-	const bool inside = World::region_bounds(d, r, lo, hi);
-	if (where == BM_VOXELS_HOST) {
-		for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
-			for (int64_t z = z0; z < z1; ++z)
-				for (int64_t y = y0; y < y1; ++y) std::memset(voxels + region_offset(r, x0, y, z), 0, static_cast<size_t>(x1 - x0));
-		});
-		if (inside) world.store_region(lo, hi, r.lo, voxels, r.row_pitch, r.slice_pitch, 16);
-		return 0;
-	}
-	// ---- the bricks of the box that the device does not hold, from the host world
 	std::vector<int> cells;
 	std::vector<Brick> bricks;
 	if (inside && !preloaded_)
@@ -1261,6 +1244,31 @@ int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipS
 		std::memcpy(h_patch_, cells.data(), n * 3 * sizeof(int));
 		std::memcpy(h_patch_ + o_bricks, bricks.data(), n * sizeof(Brick));
 	}
+	*count = n; *bricks_at = o_bricks; *total = bytes;
+	return 0;
+}
+
+// The host world is authoritative, so a host read is World::store_region.  A device read is issued like a query: the unpack kernel reads
+// the device words and bricks; bricks that are not resident (a streaming scene) are staged from the host world and written by a second
+// small launch; what lies outside the world is zeroed.
+int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream) {
+	bm_region r;
+	uint64_t span = 0;
+	if (int e = check_region("bm_scene_read_region", region, voxels, where, &r, &span)) return e;
+	if (span == 0) return 0;
+	const WorldDims& d = world.dims;
+	int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+	const bool inside = World::region_bounds(d, r, lo, hi);
+	if (where == BM_VOXELS_HOST) {
+		for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
+			for (int64_t z = z0; z < z1; ++z)
+				for (int64_t y = y0; y < y1; ++y) std::memset(voxels + region_offset(r, x0, y, z), 0, static_cast<size_t>(x1 - x0));
+		});
+		if (inside) world.store_region(lo, hi, r.lo, voxels, r.row_pitch, r.slice_pitch, 16);
+		return 0;
+	}
+	size_t n = 0, o_bricks = 0, bytes = 0;
+	if (int e = stage_absent_bricks(inside, lo, hi, &n, &o_bricks, &bytes)) return e;
 	DeviceScene view;
 	if (int e = begin_frame(stream, &view, nullptr)) return e;
 	for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
@@ -1278,6 +1286,184 @@ int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipS
 	}
 	BM_HIP(hipGetLastError());
 	end_frame(stream);
+	return 0;
+}
+
+// ---------------------------------------------------------------- connected components (bm_scene_label_region / _components / _mask)
+int Scene::check_label_box(const char* who, const int32_t lo[3], const int32_t hi[3], LabelDims* d, bool* empty) {
+	const std::string at = std::string(who) + ": ";
+	if (!lo || !hi) { set_error(at + "null box"); return BM_EINVAL; }
+	int64_t n[3];
+	for (int k = 0; k < 3; ++k) {
+		n[k] = static_cast<int64_t>(hi[k]) - lo[k];
+		if (n[k] < 0) { set_error(at + "hi < lo"); return BM_EINVAL; }
+	}
+	*empty = n[0] == 0 || n[1] == 0 || n[2] == 0;
+	// (64 bits: each factor is below 2^32, so the first product is below 2^63 once n[0] has passed, and the second is formed only below 2^31 * 2^32)
+	if (!*empty && (n[0] > kLabelMaxVoxels || n[0] * n[1] > kLabelMaxVoxels || n[0] * n[1] * n[2] > kLabelMaxVoxels)) { set_error(at + "the box holds more than 2^31 - 2 voxels"); return BM_EINVAL; }
+	*d = LabelDims{};
+	for (int k = 0; k < 3; ++k) d->org[k] = lo[k];
+	d->nx = static_cast<uint32_t>(n[0]); d->ny = static_cast<uint32_t>(n[1]); d->nz = static_cast<uint32_t>(n[2]);
+	d->sg_xy = static_cast<uint32_t>(world.dims.supergrid_xy);
+	d->sg_xy2 = d->sg_xy * d->sg_xy;
+	return 0;
+}
+
+int Scene::label_turn(hipStream_t stream) {
+	if (int e = ev_label_.create(hipEventDisableTiming)) return e;
+	if (label_busy_) BM_HIP(hipStreamWaitEvent(stream, ev_label_, 0));
+	return 0;
+}
+
+namespace {
+// the box clipped to the world, as World::region_bounds gives it, and the cells it overlaps
+bool label_clip(const WorldDims& wd, const int32_t lo[3], const int32_t hi[3], LabelDims* d) {
+	bm_region r{};
+	for (int k = 0; k < 3; ++k) { r.lo[k] = lo[k]; r.hi[k] = hi[k]; }
+	int clo[3] = {0, 0, 0}, chi[3] = {0, 0, 0};
+	const bool inside = World::region_bounds(wd, r, clo, chi);
+	for (int k = 0; k < 3; ++k) {
+		d->lo[k] = inside ? clo[k] : 0;
+		d->hi[k] = inside ? chi[k] : 0;
+		d->c0[k] = inside ? clo[k] >> 3 : 0;
+		d->nc[k] = inside ? ((chi[k] - 1) >> 3) - d->c0[k] + 1 : 0;
+	}
+	return inside;
+}
+} // namespace
+
+// Issued like a device read of the same box (read_region): zero what lies outside the world, label the cells the device holds and then
+// the staged ones, merge across cell faces, flatten and count.  Only the caller's volume is written.
+int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags, int32_t* labels, uint64_t* count, hipStream_t stream) {
+	const char* who = "bm_scene_label_region";
+	LabelDims ld;
+	bool empty = false;
+	if (flags != 0) { set_error("bm_scene_label_region: unknown flags (must be 0)"); return BM_EINVAL; }
+	if (int e = check_label_box(who, lo, hi, &ld, &empty)) return e;
+	if (!count || (!empty && !labels)) { set_error("bm_scene_label_region: null label volume or count"); return BM_EINVAL; }
+	if (reinterpret_cast<uintptr_t>(count) % 8 != 0 || (!empty && reinterpret_cast<uintptr_t>(labels) % 4 != 0)) {
+		set_error("bm_scene_label_region: labels must be 4-byte aligned, count 8-byte aligned");
+		return BM_EINVAL;
+	}
+	if (int e = require_on_device()) return e;
+	if (int e = require_not_failed()) return e;
+	BM_HIP(hipSetDevice(device_));
+	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
+	if (!device_span_ok(reinterpret_cast<const uint8_t*>(count), sizeof(uint64_t)) ||
+		(!empty && !device_span_ok(reinterpret_cast<const uint8_t*>(labels), voxels * sizeof(int32_t)))) {
+		set_error("bm_scene_label_region: the label volume's whole span and the count must lie inside one allocation each of the scene's device");
+		return BM_EINVAL;
+	}
+	const bool inside = !empty && label_clip(world.dims, lo, hi, &ld);
+	size_t n = 0, o_bricks = 0, bytes = 0;
+	if (int e = stage_absent_bricks(inside, ld.lo, ld.hi, &n, &o_bricks, &bytes)) return e;
+	for (Event& ev : ev_label_time_) if (int e = ev.create()) return e;
+	DeviceScene view;
+	if (int e = begin_frame(stream, &view, nullptr)) return e;
+	if (int e = label_turn(stream)) return e;
+	BM_HIP(hipMemsetAsync(count, 0, sizeof(uint64_t), stream));
+	label_timed_ = false;
+	if (!empty) {
+		uint8_t* bytes_out = reinterpret_cast<uint8_t*>(labels);
+		const int64_t row = static_cast<int64_t>(ld.nx) * 4, slice = row * ld.ny;
+		for_outside_slabs(lo, hi, inside, ld.lo, ld.hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
+			launch_region_zero(bytes_out + (z0 - lo[2]) * slice + (y0 - lo[1]) * row + (x0 - lo[0]) * 4, row, slice, (x1 - x0) * 4, y1 - y0, z1 - z0, stream);
+		});
+		if (inside) {
+			if (n > 0) BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));
+			hipEvent_t marks[4] = {ev_label_time_[0], ev_label_time_[1], ev_label_time_[2], ev_label_time_[3]};
+			launch_label_region(view, reinterpret_cast<uint32_t*>(labels), count, ld, reinterpret_cast<const int*>(d_patch_.get()),
+								reinterpret_cast<const uint32_t*>(d_patch_.get() + o_bricks), static_cast<uint32_t>(n), stream, marks);
+			label_timed_ = true;
+			if (n > 0) {
+				BM_HIP(hipEventRecord(ev_region_read_, stream));
+				region_read_busy_ = true;
+			}
+		}
+	}
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_label_, stream));
+	label_busy_ = true;
+	end_frame(stream);
+	return 0;
+}
+
+int Scene::last_label_ms(float* local_ms, float* merge_ms, float* flatten_ms) {
+	if (!local_ms || !merge_ms || !flatten_ms) { set_error("null argument"); return BM_EINVAL; }
+	if (!label_timed_) { set_error("the last bm_scene_label_region launched nothing, or there was none"); return BM_ESTATE; }
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipEventSynchronize(ev_label_time_[3]));
+	BM_HIP(hipEventElapsedTime(local_ms, ev_label_time_[0], ev_label_time_[1]));
+	BM_HIP(hipEventElapsedTime(merge_ms, ev_label_time_[1], ev_label_time_[2]));
+	BM_HIP(hipEventElapsedTime(flatten_ms, ev_label_time_[2], ev_label_time_[3]));
+	return 0;
+}
+
+// Reads the label volume alone, so it is not a frame: ordered on its stream, and behind the label call before it (the root counts are
+// one buffer, which grows only once that call has finished).
+int Scene::label_components(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, bm_component* comps, int64_t capacity, hipStream_t stream) {
+	const char* who = "bm_scene_label_components";
+	LabelDims ld;
+	bool empty = false;
+	if (int e = check_label_box(who, lo, hi, &ld, &empty)) return e;
+	if (capacity < 0) { set_error("bm_scene_label_components: negative capacity"); return BM_EINVAL; }
+	if (empty || capacity == 0) return 0;
+	if (!labels || !comps) { set_error("bm_scene_label_components: null label volume or table"); return BM_EINVAL; }
+	if (reinterpret_cast<uintptr_t>(labels) % 4 != 0 || reinterpret_cast<uintptr_t>(comps) % 8 != 0) {
+		set_error("bm_scene_label_components: labels must be 4-byte aligned, the table 8-byte aligned");
+		return BM_EINVAL;
+	}
+	if (int e = require_on_device()) return e;
+	if (int e = require_not_failed()) return e;
+	BM_HIP(hipSetDevice(device_));
+	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
+	const size_t records = static_cast<size_t>(std::min<int64_t>(capacity, static_cast<int64_t>(voxels))); // (no more components than voxels)
+	if (!device_span_ok(reinterpret_cast<const uint8_t*>(labels), voxels * sizeof(int32_t)) ||
+		!device_span_ok(reinterpret_cast<const uint8_t*>(comps), records * sizeof(bm_component))) {
+		set_error("bm_scene_label_components: the label volume and min(capacity, voxels) records must lie inside one allocation each of the scene's device");
+		return BM_EINVAL;
+	}
+	label_clip(world.dims, lo, hi, &ld);
+	const size_t need = label_tmp_bytes(static_cast<uint32_t>(voxels));
+	if (d_label_tmp_.bytes() < need) {
+		if (label_busy_) { BM_HIP(hipEventSynchronize(ev_label_)); label_busy_ = false; }
+		if (int e = d_label_tmp_.reserve(std::max<size_t>(need, 1 << 16))) return e;
+	}
+	if (int e = label_turn(stream)) return e;
+	launch_label_components(reinterpret_cast<const uint32_t*>(labels), comps, static_cast<uint64_t>(capacity), ld, d_label_tmp_, stream);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_label_, stream));
+	label_busy_ = true;
+	return 0;
+}
+
+int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* mask,
+					  hipStream_t stream) {
+	const char* who = "bm_scene_label_mask";
+	LabelDims ld;
+	bool empty = false;
+	if (int e = check_label_box(who, lo, hi, &ld, &empty)) return e;
+	if (n < 0) { set_error("bm_scene_label_mask: negative record count"); return BM_EINVAL; }
+	if (empty) return 0;
+	if (!labels || !mask || (n > 0 && (!comps || !chosen))) { set_error("bm_scene_label_mask: null buffer"); return BM_EINVAL; }
+	if (reinterpret_cast<uintptr_t>(labels) % 4 != 0 || reinterpret_cast<uintptr_t>(comps) % 8 != 0) {
+		set_error("bm_scene_label_mask: labels must be 4-byte aligned, the table 8-byte aligned");
+		return BM_EINVAL;
+	}
+	if (int e = require_on_device()) return e;
+	if (int e = require_not_failed()) return e;
+	BM_HIP(hipSetDevice(device_));
+	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
+	if (!device_span_ok(reinterpret_cast<const uint8_t*>(labels), voxels * sizeof(int32_t)) || !device_span_ok(mask, voxels) ||
+		(n > 0 && (!device_span_ok(reinterpret_cast<const uint8_t*>(comps), static_cast<size_t>(n) * sizeof(bm_component)) || !device_span_ok(chosen, static_cast<size_t>(n))))) {
+		set_error("bm_scene_label_mask: every buffer's whole span must lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (int e = label_turn(stream)) return e;
+	launch_label_mask(reinterpret_cast<const uint32_t*>(labels), static_cast<uint32_t>(voxels), comps, static_cast<uint64_t>(n), chosen, mask, stream);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_label_, stream));
+	label_busy_ = true;
 	return 0;
 }
 

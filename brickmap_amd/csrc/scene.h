@@ -59,6 +59,12 @@ public:
 	int cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream);
 	// volume queries (volume.hip): issued like a ray query
 	int query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* results, uint32_t flags, hipStream_t stream);
+	// connected components (label.hip): label_region is issued like a query; the other two only read the caller's label volume
+	int label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags, int32_t* labels, uint64_t* count, hipStream_t stream);
+	int label_components(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, bm_component* comps, int64_t capacity, hipStream_t stream);
+	int label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* mask,
+				   hipStream_t stream);
+	int last_label_ms(float* local_ms, float* merge_ms, float* flatten_ms);
 	int render(const bm_camera* cam, const bm_frame_params* fp, float* accum, uint32_t* dbg, hipStream_t stream);
 	// `count` consecutive frames as one launch (the frame ring, trace.hip); dbgs may be null, and so may any of its entries
 	int render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream);
@@ -111,6 +117,12 @@ private:
 	int submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* scattered, bool* field_updated);
 	int check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span);
 	RegionDims region_dims(const bm_region& r, const int lo[3], const int hi[3]) const;
+	// the bricks of the clipped box [lo, hi) that the device does not hold, from the host world into h_patch_ / d_patch_'s layout: *n of them,
+	// the bricks from byte *o_bricks on, *bytes in all (a preloaded scene, or inside == false: none)
+	int stage_absent_bricks(bool inside, const int lo[3], const int hi[3], size_t* n, size_t* o_bricks, size_t* bytes);
+	// what the three label calls refuse about their box, before anything is launched; *d gets the box's dimensions
+	int check_label_box(const char* who, const int32_t lo[3], const int32_t hi[3], LabelDims* d, bool* empty);
+	int label_turn(hipStream_t stream);  // a label call waits for the one before it
 	void free_device();
 	int alloc_queue();
 	int service_ring(int ring, uint32_t count, uint32_t* serviced);
@@ -233,6 +245,11 @@ private:
 	Event ev_volume_;
 	bool volume_busy_ = false;
 	int volume_blocks_per_cu_[2] = {0, 0};
+	// connected components: the root counts of one bm_scene_label_components (label_tmp_bytes, grown on demand); label calls of a scene run
+	// one after another, each waits for the one before it.  ev_label_time_: around local, merge and flatten of the last label_region
+	DeviceBuffer<uint64_t> d_label_tmp_;
+	Event ev_label_, ev_label_time_[4];
+	bool label_busy_ = false, label_timed_ = false;
 	int queue_cap_ = 1024;                       // variables.h:35
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27
 	DeviceScene view_{};

@@ -313,6 +313,75 @@ def host_write_region_supercell(grid_size, grid_height, sx, sy, sz, indices, bri
     return idx, buf[: n.value].copy()
 
 
+# ---- connected components (bm_scene_label_region / bm_scene_label_components / bm_scene_label_mask)
+COMPONENT_DTYPE = np.dtype([("label", "<i4"), ("faces", "<u4"), ("voxels", "<u8"), ("lo", "<i4", 3), ("hi", "<i4", 3)])  # bm_component, 40 bytes
+FACE_BITS = {"-x": 1, "+x": 2, "-y": 4, "+y": 8, "-z": 16, "+z": 32}
+
+
+def _box3(lo, hi, who):
+    lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError(f"{who}: lo and hi are (x, y, z)")
+    lim = np.iinfo(np.int32)
+    if any(not lim.min <= v <= lim.max for v in lo + hi):
+        raise ValueError(f"{who}: coordinates must fit 32 bits")
+    return (C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), tuple(h - l for l, h in zip(lo, hi))[::-1]
+
+
+def host_label_volume(volume):
+    """bm_host_label_volume (host only, no device): connected components by faces of a dense volume [z, y, x] (non-zero = solid) in plain
+    loops.  Returns (labels, count): int32 [z, y, x] with 0 for empty voxels and 1 + index of the component's first voxel for solid
+    ones, and the number of components."""
+    volume = np.asarray(volume)
+    if volume.ndim != 3 or volume.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise ValueError(f"host_label_volume: a uint8 or bool array [z, y, x] expected, got {volume.dtype} of shape {volume.shape}")
+    volume = np.ascontiguousarray(volume)
+    nz, ny, nx = volume.shape
+    labels = np.zeros(volume.shape, np.int32)
+    count = C.c_uint64(0)
+    check(_lib.load().bm_host_label_volume(volume.ctypes.data, nx, ny, nz, labels.ctypes.data, C.byref(count)))
+    return labels, int(count.value)
+
+
+class Components:
+    """Result of Scene.components: `labels` (int32 CUDA tensor [z, y, x]), `records` (numpy array of COMPONENT_DTYPE, ascending label),
+    and masks of chosen components as uint8 CUDA tensors [z, y, x] that write_region / read_region take as they are."""
+
+    def __init__(self, scene, lo, hi, labels, records, table):
+        self.scene, self.lo, self.hi, self.labels, self.records, self._table = scene, tuple(lo), tuple(hi), labels, records, table
+
+    def __len__(self):
+        return len(self.records)
+
+    def mask(self, chosen, stream=None):
+        """uint8 mask of the voxels whose component's entry in `chosen` (one value per record, non-zero = chosen) is set: that value."""
+        import torch
+        chosen = np.ascontiguousarray(np.asarray(chosen)).astype(np.uint8).reshape(-1)
+        if len(chosen) != len(self.records):
+            raise ValueError(f"mask: one value per record expected ({len(self.records)}), got {len(chosen)}")
+        dev = self.labels.device
+        mask = torch.empty(tuple(self.labels.shape), dtype=torch.uint8, device=dev)
+        if mask.numel() == 0:
+            return mask
+        d_chosen = torch.from_numpy(chosen).to(dev) if len(chosen) else torch.zeros(1, dtype=torch.uint8, device=dev)
+        self.scene.label_mask_raw(self.lo, self.hi, self.labels.data_ptr(), self._table.data_ptr() if len(chosen) else 0, len(chosen), d_chosen.data_ptr() if len(chosen) else 0,
+                                  mask.data_ptr(), stream)
+        return mask
+
+    def floating(self, anchor=("-x", "+x", "-y", "+y", "-z"), stream=None):
+        """uint8 mask (1) of the voxels whose component touches none of the anchor faces of (box and world)"""
+        return self.mask(self.loose(anchor), stream)
+
+    def loose(self, anchor=("-x", "+x", "-y", "+y", "-z")):
+        """per record: the component touches none of the anchor faces"""
+        bits = 0
+        for a in anchor:
+            if a not in FACE_BITS:
+                raise ValueError(f"anchor faces are {tuple(FACE_BITS)}, got {a!r}")
+            bits |= FACE_BITS[a]
+        return (self.records["faces"] & bits) == 0
+
+
 # ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmax", "<f4"), ("reserved", "<u4")])   # bm_ray
 RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("voxel", "<i4", 3), ("level", "<i4")])  # bm_ray_hit
@@ -797,6 +866,73 @@ class Scene:
         t = [C.c_float(0) for _ in range(4)]
         check(self._L.bm_scene_last_region_ms(self.gpuScene, *[C.byref(v) for v in t]))
         return tuple(float(v.value) for v in t)
+
+    # ---- connected components (bm_scene_label_region ...): label_region is issued like a query, asynchronous to the host
+    def label_region_raw(self, lo, hi, labels_ptr, count_ptr, flags=0, stream=None):
+        """bm_scene_label_region on device pointers (ints)"""
+        clo, chi, _ = _box3(lo, hi, "label_region")
+        check(self._L.bm_scene_label_region(self.gpuScene, C.byref(clo), C.byref(chi), int(flags), C.c_void_p(labels_ptr), C.c_void_p(count_ptr), self._stream(stream)))
+
+    def label_components_raw(self, lo, hi, labels_ptr, comps_ptr, capacity, stream=None):
+        clo, chi, _ = _box3(lo, hi, "label_components")
+        check(self._L.bm_scene_label_components(self.gpuScene, C.byref(clo), C.byref(chi), C.c_void_p(labels_ptr), C.c_void_p(comps_ptr), int(capacity), self._stream(stream)))
+
+    def label_mask_raw(self, lo, hi, labels_ptr, comps_ptr, n, chosen_ptr, mask_ptr, stream=None):
+        clo, chi, _ = _box3(lo, hi, "label_mask")
+        check(self._L.bm_scene_label_mask(self.gpuScene, C.byref(clo), C.byref(chi), C.c_void_p(labels_ptr), C.c_void_p(comps_ptr), int(n), C.c_void_p(chosen_ptr),
+                                          C.c_void_p(mask_ptr), self._stream(stream)))
+
+    def label_region(self, lo, hi, out=None, stream=None):
+        """Connected components (by faces) of the voxels lo <= v < hi (x, y, z; voxels outside the world are empty): (labels, count).
+        labels: an int32 tensor [z, y, x] on the scene's GPU, 0 for an empty voxel, else 1 + the index ((z * ny + y) * nx + x in the box)
+        of the first voxel of its component -- or `out`, a contiguous int32 CUDA tensor of that shape.  count: a one-element int64 tensor on
+        the GPU; reading it is the caller's synchronisation.  Issued like a query on `stream` (a raw HIP stream handle; None = torch's
+        current stream).  A wrong dtype, layout or device raises ValueError before the library is called."""
+        import torch
+        _, _, shape = _box3(lo, hi, "label_region")
+        if min(shape) < 0:
+            raise ValueError(f"label_region: hi < lo ({lo} ... {hi})")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=f"cuda:{self.device}")
+        elif not hasattr(out, "is_contiguous"):
+            raise ValueError(f"label_region: out must be a torch tensor on the scene's GPU, got {type(out).__name__}")
+        elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError(f"label_region: out must be a contiguous int32 CUDA tensor of shape {shape}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        current, target = self._volume_stream(out, stream)
+        with torch.cuda.stream(target):
+            count = torch.zeros(1, dtype=torch.int64, device=out.device)
+        self.label_region_raw(lo, hi, out.data_ptr(), count.data_ptr(), 0, target.cuda_stream)
+        if target.cuda_stream != current.cuda_stream:
+            current.wait_stream(target)
+        return out, count
+
+    def last_label_ms(self):
+        """(local_ms, merge_ms, flatten_ms) of the last label_region that launched its kernels (hipEvents on its stream)."""
+        t = [C.c_float(0) for _ in range(3)]
+        check(self._L.bm_scene_last_label_ms(self.gpuScene, *[C.byref(v) for v in t]))
+        return tuple(float(v.value) for v in t)
+
+    def components(self, lo, hi, stream=None):
+        """label_region, then the table of every component (waits for the count): a Components."""
+        import torch
+        labels, count = self.label_region(lo, hi, stream=stream)
+        n = int(count.item())
+        table = torch.zeros((max(n, 1), COMPONENT_DTYPE.itemsize // 8), dtype=torch.int64, device=labels.device)
+        if n:
+            _, target = self._volume_stream(labels, stream)
+            self.label_components_raw(lo, hi, labels.data_ptr(), table.data_ptr(), n, target.cuda_stream)
+            target.synchronize()
+        records = table[:n].cpu().numpy().view(COMPONENT_DTYPE).reshape(-1)
+        return Components(self, lo, hi, labels, records, table)
+
+    def remove_floating(self, lo, hi, anchor=("-x", "+x", "-y", "+y", "-z")):
+        """Clear every voxel of the box whose component (inside the box) touches none of the anchor faces: (pieces, voxels) removed."""
+        comps = self.components(lo, hi)
+        loose = comps.loose(anchor)
+        pieces, voxels = int(np.count_nonzero(loose)), int(comps.records["voxels"][loose].sum())
+        if voxels:
+            self.write_region(lo, comps.floating(anchor), op="clear")
+        return pieces, voxels
 
     # ---- ray queries (bm_scene_cast_rays): issued like a frame -- after every edit and upload issued before, asynchronous to the host
     def cast_rays_raw(self, n, rays_ptr, hits_ptr, flags=0, lod_origin=None, stream=None):

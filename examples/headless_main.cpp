@@ -1,12 +1,15 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
 // first voxel at (x, y, z) before the first frame, replacing what was there (Scene::write_region; clipped to the world).
 // --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
+// --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig: the pieces of that box that hang on nothing -- connected components by faces,
+// inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
+// and voxels went.
 // --dig-at picks the voxel under pixel (px, py) of the first frame's camera (Scene::pick) and carves a sphere of radius r there; the
 // world streams, so while the pick lands on a brick that is not resident yet (level 3) the load queue is serviced and the pick repeated
 // (at most 8 times).  Prints `picked voxel x,y,z level L`; after the carve, what the same pixel sees now.  A pick that stays
@@ -37,6 +40,8 @@ int main(int argc_in, char** argv_in) {
 	std::vector<char*> args;
 	int dig[4] = {0, 0, 0, -1};
 	int dig_at[3] = {0, 0, -1};
+	int drop_lo[3] = {0, 0, 0}, drop_hi[3] = {0, 0, 0};
+	bool drop = false;
 	int ground[2] = {-1, -1};
 	const char* voxels_path = nullptr;
 	bool denoise = false, temporal = false;
@@ -80,6 +85,14 @@ int main(int argc_in, char** argv_in) {
 			}
 			continue;
 		}
+		if (std::string(argv_in[i]) == "--drop-floating" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d,%d:%d,%d,%d", &drop_lo[0], &drop_lo[1], &drop_lo[2], &drop_hi[0], &drop_hi[1], &drop_hi[2]) != 6) {
+				std::cerr << "--drop-floating wants x0,y0,z0:x1,y1,z1\n";
+				return 2;
+			}
+			drop = true;
+			continue;
+		}
 		if (std::string(argv_in[i]) == "--dig" && i + 1 < argc_in) {
 			if (std::sscanf(argv_in[++i], "%d,%d,%d,%d", &dig[0], &dig[1], &dig[2], &dig[3]) != 4 || dig[3] < 0) {
 				std::cerr << "--dig wants x,y,z,r (r >= 0)\n";
@@ -121,6 +134,10 @@ int main(int argc_in, char** argv_in) {
 		scene.write_region(Scene::Region(paste_at, hi), volume.data());
 	}
 	if (dig[3] >= 0) scene.carve_sphere(dig, dig[3]);
+	if (drop) {
+		const Scene::Removed gone = scene.remove_floating(drop_lo, drop_hi);
+		std::printf("dropped %llu floating pieces, %llu voxels\n", static_cast<unsigned long long>(gone.pieces), static_cast<unsigned long long>(gone.voxels));
+	}
 	camera.position = {grid_size / 2.f, grid_size / 8.f, 0.8f * grid_height};
 	camera.horizontal_angle = 0.8;
 	camera.vertical_angle = -0.5;

@@ -485,6 +485,55 @@ typedef struct bm_volume_result { /* 40 bytes */
 BM_API int bm_scene_query_volumes(bm_scene* scene, int64_t n, const bm_volume* volumes_dev, bm_volume_result* results_dev, uint32_t flags,
                                   void* hip_stream);
 
+/* ---- connected components of a box of the live scene (no reference counterpart): which voxels hang together.  Carve a tunnel through a
+ * pillar and its top stays in the air; these calls say so, how big the piece is and which voxels belong to it.  All integers, all exact.
+ * For a half-open box lo <= v < hi with (nx, ny, nz) = hi - lo, bm_scene_label_region fills a tight int32 volume labels[z][y][x].
+ *  - Occupancy is exactly what bm_scene_read_region gives for the box: voxels outside the world are empty; in a streaming scene the
+ *    bricks the device does not hold are taken from the host world by the read route's staging; a preloaded scene stages nothing and the
+ *    call is asynchronous to the host.
+ *  - Connectivity is by faces (6 neighbours), inside the box only: voxels that touch along an edge or at a corner are not joined, and
+ *    voxels outside the box join nothing.
+ *  - The label of an empty voxel is 0; the label of a solid voxel is 1 + index(first voxel of its component), with
+ *    index(x, y, z) = ((z - lo.z) * ny + (y - lo.y)) * nx + (x - lo.x) and "first" the smallest index.  This does not depend on
+ *    scheduling: two runs give identical bytes.
+ *  - *count_dev (a uint64 in device memory) receives the number of components.
+ *  - Refused with BM_EINVAL, nothing launched: hi < lo on an axis; nx * ny * nz > 2^31 - 2 (computed in 64 bits); flags other than 0 (18- and
+ *    26-connectivity do not exist); a null buffer; labels_dev not 4-byte aligned, or its span not inside one allocation of the scene's
+ *    device; count_dev not 8-byte aligned (or not memory of that device).  A scene not on the device, or a failed one: BM_ESTATE.
+ *  - An empty box (hi == lo on some axis) writes count 0 and is otherwise a no-op.
+ *  - Ordering: issued like a query on hip_stream.  It sees every edit, region write and upload issued before it; later edits and
+ *    bm_scene_process_load_queue order themselves behind it.  It files no request and writes no index word.
+ *  - Temporary device memory is the scene's, kept and grown on demand: none per voxel -- the label volume is the parent array of the
+ *    union-find while the call runs (csrc/label.h) -- 8 bytes per 1024 voxels for bm_scene_label_components, and the list of non-resident
+ *    bricks of a streaming scene.  Label calls of one scene run one after another, also when issued on different streams.
+ * The component table: one record per component, in ascending label. */
+typedef struct bm_component {   /* 40 bytes */
+	int32_t  label;
+	uint32_t faces;             /* bit 0 ... 5: has a voxel on the -x, +x, -y, +y, -z, +z face of (box intersected with the world) */
+	uint64_t voxels;
+	int32_t  lo[3], hi[3];      /* tight half-open bounds, world voxel coordinates */
+} bm_component;
+BM_API int bm_scene_label_region(bm_scene* scene, const int32_t lo[3], const int32_t hi[3], uint32_t flags, int32_t* labels_dev, uint64_t* count_dev,
+                                 void* hip_stream);
+/* The table of a label volume made by bm_scene_label_region for the same box: the first min(capacity, count) records in ascending label;
+ * records past that are left untouched, and voxels of components beyond the capacity contribute nothing.  comps_dev: 8-byte aligned,
+ * min(capacity, nx * ny * nz) records inside one allocation.  It reads only the label volume, not the world, so it is ordered by
+ * hip_stream alone (and behind the scene's previous label call).  An empty box or capacity 0 is a no-op. */
+BM_API int bm_scene_label_components(bm_scene* scene, const int32_t lo[3], const int32_t hi[3], const int32_t* labels_dev, bm_component* comps_dev,
+                                     int64_t capacity, void* hip_stream);
+/* mask_dev[z][y][x] (tight, one byte per voxel: what bm_scene_write_region / bm_scene_read_region take) = chosen_dev[slot] where the voxel's
+ * label is that of record `slot` of the n records at comps_dev; 0 for empty voxels and for labels not in the table.  chosen is the
+ * caller's choice per record: by faces, by size, by anything computed on the small table. */
+BM_API int bm_scene_label_mask(bm_scene* scene, const int32_t lo[3], const int32_t hi[3], const int32_t* labels_dev, const bm_component* comps_dev,
+                               int64_t n, const uint8_t* chosen_dev, uint8_t* mask_dev, void* hip_stream);
+/* device times of the last bm_scene_label_region that launched its kernels, in ms (hipEvents on its stream; waits for it): the
+ * in-brick labelling, the merge across cell faces, and flatten + count.  BM_ESTATE when there was none. */
+BM_API int bm_scene_last_label_ms(bm_scene* scene, float* local_ms, float* merge_ms, float* flatten_ms);
+/* the same labelling of a dense host volume voxels[z][y][x] (non-zero = solid, tight) in plain loops, no device needed (csrc/label_host.cpp,
+ * by the rules of csrc/label.h): labels as above, *count = the number of components.  BM_EINVAL for a negative extent, more than 2^31 - 2
+ * voxels or a null pointer. */
+BM_API int bm_host_label_volume(const uint8_t* voxels, int64_t nx, int64_t ny, int64_t nz, int32_t* labels, uint64_t* count);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

@@ -241,6 +241,63 @@ public:
 		return result;
 	}
 
+	// connected components (no counterpart in the reference; bm_scene_label_region ...): which voxels of the box lo <= v < hi hang together
+	// by faces.  labels_dev: a tight int32 volume [z][y][x] of device memory, count_dev: a uint64 there; issued like a query on hip_stream
+	void label_region(const int lo[3], const int hi[3], int32_t* labels_dev, uint64_t* count_dev, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_label_region(gpuScene.handle, lo, hi, 0u, labels_dev, count_dev, hip_stream));
+	}
+	// the first min(capacity, count) records of the table of such a label volume, in ascending label
+	void label_components(const int lo[3], const int hi[3], const int32_t* labels_dev, bm_component* comps_dev, int64_t capacity, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_label_components(gpuScene.handle, lo, hi, labels_dev, comps_dev, capacity, hip_stream));
+	}
+	// mask_dev[z][y][x] = chosen_dev[record of the voxel's label], 0 for empty voxels and labels outside the n records: what write_region takes
+	void label_mask(const int lo[3], const int hi[3], const int32_t* labels_dev, const bm_component* comps_dev, int64_t n, const uint8_t* chosen_dev,
+					uint8_t* mask_dev, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_scene_label_mask(gpuScene.handle, lo, hi, labels_dev, comps_dev, n, chosen_dev, mask_dev, hip_stream));
+	}
+	// Clear every voxel of the box whose component (inside the box) has no voxel on one of the `anchor` faces of (box and world) -- bits as
+	// bm_component::faces; the default anchors to the four sides and the bottom.  Returns {pieces, voxels} removed.  The host waits.
+	struct Removed { uint64_t pieces, voxels; };
+	Removed remove_floating(const int lo[3], const int hi[3], uint32_t anchor = 0x1Fu) {
+		Removed out{0, 0};
+		const size_t voxels = Region(lo, hi).voxels();
+		if (voxels == 0) return out;
+		void* buf = nullptr; // the count, the labels, then the mask
+		BM_CHECKED(bm_buffer_alloc(device_, 8 + voxels * 5, &buf));
+		uint64_t* d_count = static_cast<uint64_t*>(buf);
+		int32_t* d_labels = reinterpret_cast<int32_t*>(static_cast<char*>(buf) + 8);
+		uint8_t* d_mask = reinterpret_cast<uint8_t*>(d_labels + voxels);
+		void* table = nullptr;
+		try {
+			label_region(lo, hi, d_labels, d_count);
+			uint64_t count = 0;
+			BM_CHECKED(bm_buffer_read(device_, &count, d_count, sizeof count)); // (waits for the device)
+			if (count > 0) {
+				BM_CHECKED(bm_buffer_alloc(device_, count * (sizeof(bm_component) + 1), &table));
+				bm_component* d_comps = static_cast<bm_component*>(table);
+				uint8_t* d_chosen = reinterpret_cast<uint8_t*>(d_comps + count);
+				label_components(lo, hi, d_labels, d_comps, static_cast<int64_t>(count));
+				std::vector<bm_component> comps(count);
+				BM_CHECKED(bm_buffer_read(device_, comps.data(), d_comps, count * sizeof(bm_component)));
+				std::vector<uint8_t> chosen(count);
+				for (uint64_t i = 0; i < count; ++i)
+					if ((comps[i].faces & anchor) == 0) { chosen[i] = 1; ++out.pieces; out.voxels += comps[i].voxels; }
+				if (out.pieces > 0) {
+					BM_CHECKED(bm_buffer_write(device_, d_chosen, chosen.data(), count));
+					label_mask(lo, hi, d_labels, d_comps, static_cast<int64_t>(count), d_chosen, d_mask);
+					write_region(Region(lo, hi), d_mask, BM_EDIT_CLEAR, BM_VOXELS_DEVICE);
+				}
+			}
+		} catch (...) {
+			if (table) (void)bm_buffer_free(device_, table);
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		if (table) BM_CHECKED(bm_buffer_free(device_, table));
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return out;
+	}
+
 private:
 	int device_;
 };
