@@ -88,6 +88,19 @@ class bm_denoise_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("sigma_l", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+BM_VOXELIZE_SURFACE = 1
+BM_VOXELIZE_SOLID = 2
+BM_VOXELIZE_KEEP = 1
+
+
+class bm_voxelize_params(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("row_pitch", C.c_int64), ("slice_pitch", C.c_int64), ("mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class bm_voxelize_result(C.Structure):
+    _fields_ = [("rejected", C.c_uint32), ("degenerate", C.c_uint32), ("open_columns", C.c_uint64)]
+
+
 class bm_volume(C.Structure):
     _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
 
@@ -171,6 +184,10 @@ SIGNATURES = {
     "bm_scene_label_mask": (_i, [_vp, C.POINTER(C.c_int32 * 3), C.POINTER(C.c_int32 * 3), _vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "bm_scene_last_label_ms": (_i, [_vp] + [C.POINTER(C.c_float)] * 3),
     "bm_host_label_volume": (_i, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.POINTER(C.c_uint64)]),
+    "bm_voxelize_workspace_bytes": (_i, [C.POINTER(bm_voxelize_params), C.c_int64, C.POINTER(C.c_size_t)]),
+    "bm_voxelize": (_i, [_vp, C.POINTER(bm_voxelize_params), C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bm_debug_voxelize_times": (_i, [_vp, C.POINTER(bm_voxelize_params), C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_float)]),
+    "bm_host_voxelize": (_i, [C.POINTER(bm_voxelize_params), C.c_int64, _vp, _vp, C.POINTER(bm_voxelize_result)]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "reproject.h"
 #include "scene.h"
+#include "voxelize.h"
 #include "wavefront.h"
 
 struct bm_scene {
@@ -223,6 +224,31 @@ int bm_debug_denoise_times(bm_scene* scene, const bm_denoise_params* params, con
 	BM_NEED(scene);
 	if (!kernel_ms) { set_error("bm_debug_denoise_times: null argument"); return BM_EINVAL; }
 	return scene->impl.denoise(params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+}
+
+// (bm_host_voxelize is csrc/voxelize_host.cpp: host code that needs nothing of the library)
+int bm_voxelize_workspace_bytes(const bm_voxelize_params* params, int64_t n, size_t* bytes) {
+	if (!params || !bytes) { set_error("bm_voxelize_workspace_bytes: null argument"); return BM_EINVAL; }
+	const bm::VxParamsView pv = bm::voxelize_params_view(*params);
+	if (const char* why = bm::voxelize_params_problem(pv, n)) { set_error(std::string("bm_voxelize_workspace_bytes: ") + why); return BM_EINVAL; }
+	bm::VoxelizeDims d = {};
+	for (int k = 0; k < 3; ++k) d.extent[k] = pv.extent[k];
+	d.words = bm::voxelize_row_words(pv.extent[0]);
+	*bytes = bm::voxelize_workspace_bytes(d, static_cast<uint32_t>(n));
+	return 0;
+}
+
+int bm_voxelize(bm_scene* scene, const bm_voxelize_params* params, int64_t n, const float* triangles_dev, uint8_t* volume_dev, bm_voxelize_result* result_dev,
+				void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.voxelize(params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_voxelize_times(bm_scene* scene, const bm_voxelize_params* params, int64_t n, const float* triangles_dev, uint8_t* volume_dev,
+							bm_voxelize_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms) {
+	BM_NEED(scene);
+	if (!kernel_ms) { set_error("bm_debug_voxelize_times: null argument"); return BM_EINVAL; }
+	return scene->impl.voxelize(params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)

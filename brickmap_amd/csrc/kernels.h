@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -142,6 +142,21 @@ void launch_label_region(const DeviceScene& sc, uint32_t* labels, uint64_t* coun
 size_t label_tmp_bytes(uint32_t voxels);
 void launch_label_components(const uint32_t* labels, void* comps, uint64_t capacity, const LabelDims& d, uint64_t* tmp, hipStream_t stream);
 void launch_label_mask(const uint32_t* labels, uint32_t voxels, const void* comps, uint64_t records, const uint8_t* chosen, uint8_t* mask, hipStream_t stream);
+
+// meshes -> voxels (voxelize.hip; voxelize.h has the rules): n triangles of 9 floats fill the volume V[z][y][x] of extent voxels at the
+// given pitches.  workspace: voxelize_workspace_bytes() bytes, 16-byte aligned, that no other launch uses until this one has finished
+// (zeroed here); result: null, or the 16 bytes of a bm_voxelize_result.  resident_blocks: the grids of the surface and the solid items.
+// marks: null, or 6 events around zeroing, plan + scan, surface, solid and the dense pass.
+struct VoxelizeDims {
+	int32_t lo[3], extent[3];
+	uint32_t words; // voxelize_row_words(extent[0])
+	uint32_t mode, keep;
+	int64_t row_pitch, slice_pitch; // resolved: never 0
+};
+size_t voxelize_workspace_bytes(const VoxelizeDims& d, uint32_t n);
+int voxelize_blocks_per_cu(bool solid);
+void launch_voxelize(const VoxelizeDims& d, const float* triangles, uint32_t n, uint8_t* volume, void* result, void* workspace, const int resident_blocks[2],
+					 hipStream_t stream, hipEvent_t* marks = nullptr);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

@@ -16,6 +16,7 @@
 
 #include "camera_rays.h"
 #include "denoise.h"
+#include "voxelize.h"
 #include "escape.h"
 #include "kernels.h"
 #include "label.h"
@@ -1843,6 +1844,61 @@ int Scene::denoise(const bm_denoise_params* params, const float* accum, const bm
 	BM_HIP(hipEventSynchronize(raw[kernels]));
 	for (int i = 0; i < 2 + params->iterations; ++i) kernel_ms[i] = 0.f;
 	for (int i = 0; i < kernels; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
+	return 0;
+}
+
+// ---- meshes -> voxels (bm_voxelize): kernels on the caller's stream over the caller's buffers; nothing of the world is read
+int Scene::voxelize(const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result, void* workspace,
+					size_t workspace_bytes, hipStream_t stream, float* kernel_ms) {
+	if (!params) { set_error("bm_voxelize: null params"); return BM_EINVAL; }
+	const VxParamsView pv = voxelize_params_view(*params);
+	if (const char* why = voxelize_params_problem(pv, n)) { set_error(std::string("bm_voxelize: ") + why); return BM_EINVAL; }
+	if (!volume || !workspace || (n > 0 && !triangles)) { set_error("bm_voxelize: null buffer"); return BM_EINVAL; }
+	VoxelizeDims d;
+	for (int k = 0; k < 3; ++k) { d.lo[k] = pv.lo[k]; d.extent[k] = pv.extent[k]; }
+	d.words = voxelize_row_words(pv.extent[0]);
+	d.mode = pv.mode;
+	d.keep = pv.flags & kVxKeep;
+	d.row_pitch = voxelize_row_pitch(pv);
+	d.slice_pitch = voxelize_slice_pitch(pv);
+	const size_t need = voxelize_workspace_bytes(d, static_cast<uint32_t>(n));
+	if (workspace_bytes < need) { set_error("bm_voxelize: the workspace is smaller than bm_voxelize_workspace_bytes"); return BM_EINVAL; }
+	const uintptr_t pt = reinterpret_cast<uintptr_t>(triangles), pv0 = reinterpret_cast<uintptr_t>(volume), pr = reinterpret_cast<uintptr_t>(result),
+					pw = reinterpret_cast<uintptr_t>(workspace);
+	if (pt % 4 != 0 || pr % 8 != 0 || pw % 16 != 0) { set_error("bm_voxelize: triangles must be 4-byte, the result 8-byte and the workspace 16-byte aligned"); return BM_EINVAL; }
+	const size_t span = static_cast<size_t>(pv.extent[2] - 1) * static_cast<size_t>(d.slice_pitch) + static_cast<size_t>(pv.extent[1] - 1) * static_cast<size_t>(d.row_pitch) +
+						static_cast<size_t>(pv.extent[0]);
+	const size_t tri_bytes = static_cast<size_t>(n) * 9 * sizeof(float);
+	auto overlaps_workspace = [&](uintptr_t p, size_t bytes) { return bytes > 0 && p < pw + need && pw < p + bytes; };
+	if (overlaps_workspace(pv0, span) || overlaps_workspace(pt, tri_bytes) || (result && overlaps_workspace(pr, sizeof(bm_voxelize_result)))) {
+		set_error("bm_voxelize: the workspace overlaps the volume, the triangles or the result");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(device_));
+	if (!device_span_ok(volume, span) || !device_span_ok(static_cast<const uint8_t*>(workspace), need) ||
+		(n > 0 && !device_span_ok(reinterpret_cast<const uint8_t*>(triangles), tri_bytes)) ||
+		(result && !device_span_ok(reinterpret_cast<const uint8_t*>(result), sizeof(bm_voxelize_result)))) {
+		set_error("bm_voxelize: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	static const int per_cu[2] = {voxelize_blocks_per_cu(false), voxelize_blocks_per_cu(true)};
+	const int resident[2] = {per_cu[0] * compute_units_, per_cu[1] * compute_units_};
+	if (!kernel_ms) {
+		launch_voxelize(d, triangles, static_cast<uint32_t>(n), volume, result, workspace, resident, stream);
+		BM_HIP(hipGetLastError());
+		return 0;
+	}
+	constexpr int kStages = 5;
+	Event marks[kStages + 1];
+	hipEvent_t raw[kStages + 1];
+	for (int i = 0; i <= kStages; ++i) {
+		if (int e = marks[i].create(hipEventDefault)) return e;
+		raw[i] = marks[i];
+	}
+	launch_voxelize(d, triangles, static_cast<uint32_t>(n), volume, result, workspace, resident, stream, raw);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventSynchronize(raw[kStages]));
+	for (int i = 0; i < kStages; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
 	return 0;
 }
 

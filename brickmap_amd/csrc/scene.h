@@ -73,6 +73,10 @@ public:
 	// kernel_ms: null, or 2 + iterations durations -- prepare, moments, every pass (the call then waits; bm_debug_denoise_times)
 	int denoise(const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream,
 				float* kernel_ms = nullptr);
+	// meshes -> voxels (voxelize.hip): like the filter, the buffers and the workspace are the caller's and the scene keeps no state
+	// kernel_ms: null, or 5 durations -- zeroing, plan + scan, surface, solid, the dense pass (the call then waits; bm_debug_voxelize_times)
+	int voxelize(const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result, void* workspace, size_t workspace_bytes,
+				 hipStream_t stream, float* kernel_ms = nullptr);
 	// pixel-centre rays of a frame, written on the device (denoise.hip)
 	int pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
 	// temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers; the scene keeps no state for it

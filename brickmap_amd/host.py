@@ -382,6 +382,81 @@ class Components:
         return (self.records["faces"] & bits) == 0
 
 
+# ---- meshes -> voxels (bm_voxelize / bm_host_voxelize)
+VOXELIZE_RESULT_DTYPE = np.dtype([("rejected", "<u4"), ("degenerate", "<u4"), ("open_columns", "<u8")])  # bm_voxelize_result, 16 bytes
+_VOXELIZE_MODES = {"surface": _lib.BM_VOXELIZE_SURFACE, "solid": _lib.BM_VOXELIZE_SOLID,
+                   "solid+surface": _lib.BM_VOXELIZE_SURFACE | _lib.BM_VOXELIZE_SOLID, "surface+solid": _lib.BM_VOXELIZE_SURFACE | _lib.BM_VOXELIZE_SOLID}
+
+
+def _voxelize_mode(mode):
+    if isinstance(mode, str):
+        if mode not in _VOXELIZE_MODES:
+            raise ValueError(f"voxelize: mode 'surface', 'solid' or 'solid+surface' expected, got {mode!r}")
+        return _VOXELIZE_MODES[mode]
+    return int(mode)
+
+
+def _voxelize_params(lo, volume, mode, keep, name="out"):
+    """(bm_voxelize_params, data pointer, is_cuda) of `volume` ([z, y, x], laid out as region_of takes it) with its voxel [0, 0, 0] at lo"""
+    r, ptr, cuda = region_of(lo, volume, name)
+    nz, ny, nx = volume.shape
+    par = _lib.bm_voxelize_params()
+    par.lo[:] = list(r.lo)
+    par.extent[:] = [nx, ny, nz]
+    par.row_pitch, par.slice_pitch = r.row_pitch, r.slice_pitch
+    par.mode = _voxelize_mode(mode)
+    par.flags = _lib.BM_VOXELIZE_KEEP if keep else 0
+    return par, ptr, cuda
+
+
+def voxelize_workspace_bytes(shape, n, mode="solid+surface"):
+    """bm_voxelize_workspace_bytes: device memory bm_voxelize needs beside its buffers for a volume of shape (nz, ny, nx) and n triangles."""
+    par = _lib.bm_voxelize_params()
+    par.extent[:] = [int(shape[2]), int(shape[1]), int(shape[0])]
+    par.mode = _voxelize_mode(mode)
+    out = C.c_size_t(0)
+    check(_lib.load().bm_voxelize_workspace_bytes(C.byref(par), int(n), C.byref(out)))
+    return int(out.value)
+
+
+def host_voxelize(triangles, lo, shape=None, mode="solid+surface", keep=False, out=None):
+    """bm_host_voxelize (host only, no device): the voxelization of Scene.voxelize as plain loops.  triangles: float32 [n, 3, 3] (xyz per
+    vertex, world voxel units); lo = (x, y, z), the world voxel of the volume's first voxel; shape = (nz, ny, nx), or `out`: a uint8 array
+    [z, y, x] to fill (a slice of a larger array works as long as x is contiguous).  keep: OR into what the volume holds.  Returns (volume, record): the uint8 volume and a VOXELIZE_RESULT_DTYPE record (rejected, degenerate,
+    open_columns)."""
+    tri = np.ascontiguousarray(triangles, dtype=np.float32)
+    if tri.size % 9:
+        raise ValueError(f"host_voxelize: triangles of shape [n, 3, 3] expected, got {tri.shape}")
+    if out is None:
+        out = np.zeros(tuple(int(v) for v in shape), np.uint8)
+    par, ptr, cuda = _voxelize_params(lo, out, mode, keep)
+    assert not cuda
+    res = _lib.bm_voxelize_result()
+    check(_lib.load().bm_host_voxelize(C.byref(par), tri.size // 9, C.c_void_p(tri.ctypes.data), C.c_void_p(ptr), C.byref(res)))
+    rec = np.zeros((), VOXELIZE_RESULT_DTYPE)
+    rec["rejected"], rec["degenerate"], rec["open_columns"] = res.rejected, res.degenerate, res.open_columns
+    return out, rec
+
+
+class VoxelizeResult:
+    """The bm_voxelize_result of a Scene.voxelize, read lazily: `packed` is the record on the device (two int64 words); rejected,
+    degenerate, open_columns and record (a VOXELIZE_RESULT_DTYPE scalar) copy it to the host, which waits for the call."""
+
+    def __init__(self, packed):
+        self.packed = packed
+        self._record = None
+
+    @property
+    def record(self):
+        if self._record is None:
+            self._record = self.packed.cpu().numpy().view(VOXELIZE_RESULT_DTYPE).reshape(())
+        return self._record
+
+    rejected = property(lambda self: int(self.record["rejected"]))
+    degenerate = property(lambda self: int(self.record["degenerate"]))
+    open_columns = property(lambda self: int(self.record["open_columns"]))
+
+
 # ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmax", "<f4"), ("reserved", "<u4")])   # bm_ray
 RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("voxel", "<i4", 3), ("level", "<i4")])  # bm_ray_hit
@@ -933,6 +1008,98 @@ class Scene:
         if voxels:
             self.write_region(lo, comps.floating(anchor), op="clear")
         return pieces, voxels
+
+    # ---- meshes -> voxels (bm_voxelize): the scene only names the GPU; nothing of the world is read
+    def _triangles(self, triangles):
+        """float32 [n, 3, 3] on the scene's GPU from such a tensor, or from (vertices [m, 3], faces [n, 3]) gathered with torch"""
+        import torch
+        if isinstance(triangles, (tuple, list)) and len(triangles) == 2:
+            vertices, faces = triangles
+            dev = torch.device("cuda", self.device)
+            vertices = torch.as_tensor(vertices, dtype=torch.float32, device=dev)
+            faces = torch.as_tensor(faces, device=dev).long()
+            if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3:
+                raise ValueError(f"voxelize: vertices [m, 3] and faces [n, 3] expected, got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+            return vertices[faces].contiguous()
+        if not hasattr(triangles, "is_cuda"):
+            raise ValueError(f"voxelize: a float32 tensor [n, 3, 3] on the scene's GPU, or (vertices, faces), expected, got {type(triangles).__name__}")
+        if not triangles.is_cuda or triangles.device.index != self.device or triangles.dtype != torch.float32 or triangles.ndim != 3 or tuple(triangles.shape[1:]) != (3, 3):
+            raise ValueError(f"voxelize: a float32 tensor [n, 3, 3] on cuda:{self.device} expected, got {triangles.dtype} {tuple(triangles.shape)} on {triangles.device}")
+        return triangles.contiguous()
+
+    def _voxelize(self, triangles, lo, shape, mode, keep, out, stream, times):
+        import torch
+        tri = self._triangles(triangles)
+        dev = tri.device
+        if out is None:
+            if shape is None or len(shape) != 3 or min(int(v) for v in shape) < 1:
+                raise ValueError(f"voxelize: shape (nz, ny, nx) with positive extents expected, got {shape}")
+            if keep:
+                raise ValueError("voxelize: keep needs the volume to keep (out)")
+        elif not hasattr(out, "is_cuda") or not out.is_cuda:
+            raise ValueError("voxelize: out must be a uint8 or bool tensor [z, y, x] on the scene's GPU")
+        current, target = self._volume_stream(tri, stream)
+        with torch.cuda.stream(target):
+            if out is None:
+                out = torch.empty(tuple(int(v) for v in shape), dtype=torch.uint8, device=dev)
+            par, ptr, _ = _voxelize_params(lo, out, mode, keep)
+            n = int(tri.shape[0])
+            ws = torch.empty(voxelize_workspace_bytes(out.shape, n, par.mode), dtype=torch.uint8, device=dev)
+            packed = torch.empty(2, dtype=torch.int64, device=dev)
+        if target.cuda_stream != current.cuda_stream:
+            for x in (tri, out):
+                x.record_stream(target)
+        args = (self.gpuScene, C.byref(par), n, C.c_void_p(tri.data_ptr()), C.c_void_p(ptr), C.c_void_p(packed.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                C.c_void_p(target.cuda_stream))
+        ms = None
+        if times:
+            ms = (C.c_float * 5)()
+            check(self._L.bm_debug_voxelize_times(*args, ms))
+        else:
+            check(self._L.bm_voxelize(*args))
+        if target.cuda_stream != current.cuda_stream:
+            current.wait_stream(target)
+        return out, VoxelizeResult(packed), ms
+
+    def voxelize(self, triangles, lo, shape=None, mode="solid+surface", keep=False, out=None, stream=None):
+        """bm_voxelize: fill a dense volume [z, y, x] of bytes 0 / 1 whose first voxel is world voxel lo = (x, y, z) from a
+        triangle mesh -- a float32 tensor [n, 3, 3] on the scene's GPU (xyz per vertex, world voxel units), or (vertices [m, 3], faces
+        [n, 3]), gathered with torch.  mode: "surface" (every voxel whose cube meets a triangle), "solid" (every voxel whose centre lies
+        inside the closed mesh) or "solid+surface".  shape = (nz, ny, nx) for a new uint8 tensor, or `out`: a uint8 / bool CUDA tensor to
+        fill (strides as in write_region); keep=True ORs into what `out` holds.  Returns (volume, VoxelizeResult); the result's
+        open_columns is 0 for a closed mesh.  Stream handling as in write_region; the workspace comes from torch's pool; the host does
+        not wait."""
+        out, res, _ = self._voxelize(triangles, lo, shape, mode, keep, out, stream, False)
+        return out, res
+
+    def voxelize_times(self, triangles, lo, shape=None, mode="solid+surface", keep=False, out=None, stream=None):
+        """bm_debug_voxelize_times: Scene.voxelize with a hipEvent between its stages; waits.  Returns (volume, VoxelizeResult, [ms of
+        zeroing the workspace, plan + scan, the surface items, the solid items, the dense pass])."""
+        out, res, ms = self._voxelize(triangles, lo, shape, mode, keep, out, stream, True)
+        return out, res, [float(v) for v in ms]
+
+    def write_mesh(self, triangles, op="set", mode="solid+surface", stream=None):
+        """Voxelize a mesh (as Scene.voxelize takes it) over its own bounds, clipped to the world, and write_region the result: op "set"
+        adds the mesh to the scene, "clear" carves it out.  The bounds are taken with torch and read by the host: one synchronisation, and
+        the one thing this call waits for.  Triangles with a non-finite coordinate do not count for the bounds.  Returns (lo, hi,
+        VoxelizeResult) -- the box written, (x, y, z), hi exclusive -- or (None, None, None) when nothing of the mesh lies in the world."""
+        import torch
+        tri = self._triangles(triangles)
+        if tri.shape[0] == 0:
+            return None, None, None
+        finite = torch.isfinite(tri).all(dim=2).all(dim=1)
+        pts = tri[finite].reshape(-1, 3).double()
+        if pts.shape[0] == 0:
+            return None, None, None
+        bounds = torch.stack((torch.floor(pts.amin(dim=0)) - 1, torch.floor(pts.amax(dim=0)) + 1)).cpu().numpy()  # the voxels a cube of which can touch
+        world = (self.grid_size, self.grid_size, self.grid_height)
+        lo = [int(max(bounds[0][k], 0)) for k in range(3)]
+        hi = [int(min(bounds[1][k], world[k])) for k in range(3)]
+        if any(h <= l for l, h in zip(lo, hi)):
+            return None, None, None
+        volume, res = self.voxelize(tri, lo, (hi[2] - lo[2], hi[1] - lo[1], hi[0] - lo[0]), mode=mode, stream=stream)
+        self.write_region(lo, volume, op=op, stream=stream)
+        return tuple(lo), tuple(hi), res
 
     # ---- ray queries (bm_scene_cast_rays): issued like a frame -- after every edit and upload issued before, asynchronous to the host
     def cast_rays_raw(self, n, rays_ptr, hits_ptr, flags=0, lod_origin=None, stream=None):

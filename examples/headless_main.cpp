@@ -1,11 +1,14 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--dig x,y,z,r] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--dig x,y,z,r] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
 // first voxel at (x, y, z) before the first frame, replacing what was there (Scene::write_region; clipped to the world).
+// --mesh FILE@x,y,z adds a triangle mesh to the world after --paste: FILE is raw, 9 floats per triangle (xyz per vertex, in voxels), moved
+// by (x, y, z); it is voxelized on the GPU over its own bounds -- every voxel a triangle touches and every voxel whose centre lies inside
+// the closed mesh -- and written with "set" (Scene::write_mesh).  Prints the triangle counts and `open columns`, 0 for a closed mesh.
 // --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
 // --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig: the pieces of that box that hang on nothing -- connected components by faces,
 // inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
@@ -47,6 +50,8 @@ int main(int argc_in, char** argv_in) {
 	bool denoise = false, temporal = false;
 	std::string paste_path;
 	int paste_size[3] = {0, 0, 0}, paste_at[3] = {0, 0, 0};
+	std::string mesh_path;
+	float mesh_at[3] = {0.f, 0.f, 0.f};
 	for (int i = 0; i < argc_in; ++i) {
 		if (std::string(argv_in[i]) == "--denoise") {
 			denoise = true;
@@ -69,6 +74,16 @@ int main(int argc_in, char** argv_in) {
 				return 2;
 			}
 			paste_path = spec.substr(0, colon);
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--mesh" && i + 1 < argc_in) {
+			const std::string spec = argv_in[++i];
+			const size_t at = spec.rfind('@');
+			if (at == std::string::npos || at == 0 || std::sscanf(spec.c_str() + at + 1, "%f,%f,%f", &mesh_at[0], &mesh_at[1], &mesh_at[2]) != 3) {
+				std::cerr << "--mesh wants FILE@x,y,z\n";
+				return 2;
+			}
+			mesh_path = spec.substr(0, at);
 			continue;
 		}
 		if (std::string(argv_in[i]) == "--dig-at" && i + 1 < argc_in) {
@@ -132,6 +147,25 @@ int main(int argc_in, char** argv_in) {
 		}
 		const int hi[3] = {paste_at[0] + paste_size[0], paste_at[1] + paste_size[1], paste_at[2] + paste_size[2]};
 		scene.write_region(Scene::Region(paste_at, hi), volume.data());
+	}
+	if (!mesh_path.empty()) {
+		std::ifstream in(mesh_path, std::ios::binary | std::ios::ate);
+		const std::streamoff bytes = in ? static_cast<std::streamoff>(in.tellg()) : -1;
+		if (bytes <= 0 || bytes % 36 != 0) {
+			std::cerr << "--mesh: " << mesh_path << " does not hold triangles of 9 floats\n";
+			return 2;
+		}
+		std::vector<float> triangles(static_cast<size_t>(bytes) / sizeof(float));
+		in.seekg(0);
+		if (!in.read(reinterpret_cast<char*>(triangles.data()), bytes)) {
+			std::cerr << "--mesh: cannot read " << mesh_path << "\n";
+			return 2;
+		}
+		for (size_t i = 0; i < triangles.size(); ++i) triangles[i] += mesh_at[i % 3];
+		size_t box = 0;
+		const bm_voxelize_result r = scene.write_mesh(triangles.data(), static_cast<int64_t>(triangles.size() / 9), BM_EDIT_SET, BM_VOXELIZE_SURFACE | BM_VOXELIZE_SOLID, &box);
+		std::printf("mesh: %zu triangles (%u rejected, %u degenerate) into a box of %zu voxels, open columns %llu\n", triangles.size() / 9, r.rejected, r.degenerate, box,
+					static_cast<unsigned long long>(r.open_columns));
 	}
 	if (dig[3] >= 0) scene.carve_sphere(dig, dig[3]);
 	if (drop) {

@@ -534,6 +534,67 @@ BM_API int bm_scene_last_label_ms(bm_scene* scene, float* local_ms, float* merge
  * voxels or a null pointer. */
 BM_API int bm_host_label_volume(const uint8_t* voxels, int64_t nx, int64_t ny, int64_t nz, int32_t* labels, uint64_t* count);
 
+/* ---- triangle meshes -> voxels (no reference counterpart): a triangle soup in device memory -- n x 9 floats, xyz per vertex, in world
+ * voxel units -- fills a dense byte volume V[z][y][x] with 0 / 1: the volume bm_scene_write_region takes (voxel [0][0][0] at world voxel
+ * lo, x contiguous, rows and slices at the given pitches).  Integers only after the snap, the same bytes on every run, and bm_voxelize ==
+ * bm_host_voxelize byte for byte (csrc/voxelize.h holds the rules once).  S = 256.
+ *  - Snap.  A triangle with a coordinate v whose fp32 product v * 256 is not finite or above 2^30 in magnitude is REJECTED.  Otherwise
+ *    q = rint(v * 256.0f) (an exact product, rounded half to even) as an integer, minus 256 * lo.  A triangle is also rejected when
+ *    any |q| > 2^22 or when max q - min q on an axis exceeds 2^19 (2048 voxels).  Within these bounds every expression below fits 64
+ *    bits: |n| < 2^40, |n . d| < 2^62.
+ *  - Normal.  n = (q1 - q0) x (q2 - q0); n == 0: the triangle is DEGENERATE and skipped.
+ *  - BM_VOXELIZE_SURFACE marks every voxel whose closed cube meets the triangle (conservative: nothing leaks through).  Voxel k stands
+ *    for the cube [k S, (k + 1) S]^3 and is set when all three hold:
+ *      1. per axis a: k_a S <= max q_a and (k_a + 1) S >= min q_a;
+ *      2. with d = n . (k S - q0): d + sum min(n_a S, 0) <= 0 <= d + sum max(n_a S, 0);
+ *      3. for each axis ax, with (u, v) the cyclic other two axes ((y, z), (z, x), (x, y)), sgn = (n_ax >= 0 ? 1 : -1), and for each edge
+ *         p0 -> p1 (q0 q1, q1 q2, q2 q0) with e = p1 - p0, a = -e_v sgn, b = e_u sgn:
+ *         a (k_u S - p0_u) + b (k_v S - p0_v) + max(a S, 0) + max(b S, 0) >= 0.
+ *  - BM_VOXELIZE_SOLID marks every voxel whose centre lies inside the closed mesh, by parity along x.  Only triangles with n_x != 0 take
+ *    part; sgn = sign(n_x), (u, v) = (y, z).  Column (y, z) has the centre (U, V) = (256 y + 128, 256 z + 128) and is COVERED by a triangle
+ *    when for every edge, with a = -(p1_v - p0_v) sgn, b = (p1_u - p0_u) sgn and E = a (U - p0_u) + b (V - p0_v): E > 0, or E == 0 and
+ *    (a > 0, or a == 0 and b > 0) -- so an edge or a vertex that two triangles share counts once.  A covered column has one crossing, at
+ *    k = the smallest x with |n_x| (256 x + 128 - q0_x) >= -sgn (n_y (U - q0_y) + n_z (V - q0_z)); k < 0 counts as 0, k >= nx as nx (outside
+ *    the volume).  Voxel x is solid when the number of crossings with k <= x is odd.
+ *  - Output.  byte = surface | solid as the mode asks (0 or 1); with BM_VOXELIZE_KEEP byte = old | that (non-zero stays non-zero).  Every
+ *    byte of the box's rows is written; the bytes between rows and slices are never touched.
+ *  - Result (optional, 16 bytes on the device): triangles rejected, degenerate, and open_columns = the columns whose total number of
+ *    crossings, those at nx included, is odd -- 0 for a closed mesh: the leak detector (0 without BM_VOXELIZE_SOLID).
+ *  - Refusals, BM_EINVAL with nothing launched and nothing written: an extent below 1 or above 16384; a pitch below the extent it spans
+ *    (0 = tight) or a volume spanning more than 2^46 bytes; a mode of 0, an unknown mode or flag bit; n < 0 or > 2^30; a null triangle
+ *    pointer with n > 0, a null volume or workspace; triangles or the result not 4-byte (8-byte) aligned, a workspace not 16-byte aligned;
+ *    a workspace below bm_voxelize_workspace_bytes; a workspace that overlaps the volume, the triangles or the result; a span (volume:
+ *    (nz - 1) slice_pitch + (ny - 1) row_pitch + nx bytes) that does not lie inside one allocation of the scene's device. */
+#define BM_VOXELIZE_SURFACE 1u
+#define BM_VOXELIZE_SOLID 2u
+#define BM_VOXELIZE_KEEP 1u /* flag: OR into what the volume holds */
+typedef struct bm_voxelize_params {
+	int32_t lo[3];       /* world voxel of V[0][0][0], (x, y, z) */
+	int32_t extent[3];   /* nx, ny, nz: 1 ... 16384 */
+	int64_t row_pitch;   /* bytes from one x-row to the next y; 0 = tight (nx) */
+	int64_t slice_pitch; /* bytes from one z-slice to the next; 0 = tight (row_pitch * ny) */
+	uint32_t mode;       /* BM_VOXELIZE_SURFACE | BM_VOXELIZE_SOLID, at least one */
+	uint32_t flags;      /* 0 or BM_VOXELIZE_KEEP */
+} bm_voxelize_params;
+typedef struct bm_voxelize_result {
+	uint32_t rejected, degenerate;
+	uint64_t open_columns;
+} bm_voxelize_result;
+/* bytes of device memory bm_voxelize needs beside its buffers: two bit planes of ny * nz rows of ceil((nx + 1) / 32) words, and two
+ * 64-bit words per triangle and per 256 triangles */
+BM_API int bm_voxelize_workspace_bytes(const bm_voxelize_params* params, int64_t n, size_t* bytes);
+/* the buffers and the workspace are the caller's and the scene keeps no state (the scene names the device): calls on different streams
+ * with workspaces of their own are independent.  Asynchronous on hip_stream; the workspace is zeroed by the call.  Nothing of the world
+ * is read. */
+BM_API int bm_voxelize(bm_scene* scene, const bm_voxelize_params* params, int64_t n, const float* triangles_dev, uint8_t* volume_dev,
+                       bm_voxelize_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+/* measuring door: bm_voxelize with a hipEvent between its stages; waits, then kernel_ms[0 ... 4] = the durations in ms of zeroing the
+ * workspace, plan + scan, the surface items, the solid items and the dense pass; a stage the mode does not ask for takes 0 */
+BM_API int bm_debug_voxelize_times(bm_scene* scene, const bm_voxelize_params* params, int64_t n, const float* triangles_dev, uint8_t* volume_dev,
+                                   bm_voxelize_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms);
+/* the same on host memory, as plain loops (csrc/voxelize_host.cpp; no device needed); the refusals that concern params and null pointers */
+BM_API int bm_host_voxelize(const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

@@ -298,6 +298,65 @@ public:
 		return out;
 	}
 
+	// triangle meshes -> voxels (no counterpart in the reference; bm_voxelize): n triangles of 9 floats in device memory fill the byte volume
+	// of `params` with 0 / 1; result_dev: null, or a bm_voxelize_result there; workspace_dev: voxelize_workspace_bytes() bytes of the caller's
+	static size_t voxelize_workspace_bytes(const bm_voxelize_params& params, int64_t n) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_voxelize_workspace_bytes(&params, n, &bytes));
+		return bytes;
+	}
+	void voxelize(const bm_voxelize_params& params, int64_t n, const float* triangles_dev, uint8_t* volume_dev, bm_voxelize_result* result_dev, void* workspace_dev,
+				  size_t workspace_bytes, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_voxelize(gpuScene.handle, &params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, hip_stream));
+	}
+	// Voxelize n triangles of HOST memory (9 floats each, world voxel units) over their own bounds, clipped to the world, and write the
+	// result into the scene with `op` (BM_EDIT_SET adds the mesh, BM_EDIT_CLEAR carves it out).  Returns the result record and the number of
+	// voxels of the box in `box_voxels`; a mesh wholly outside the world writes nothing.  The host waits.
+	bm_voxelize_result write_mesh(const float* triangles, int64_t n, int op = BM_EDIT_SET, uint32_t mode = BM_VOXELIZE_SURFACE | BM_VOXELIZE_SOLID,
+								  size_t* box_voxels = nullptr) {
+		bm_voxelize_result out{0, 0, 0};
+		if (box_voxels) *box_voxels = 0;
+		bm_scene_info info;
+		BM_CHECKED(bm_scene_get_info(gpuScene.handle, &info));
+		const int world[3] = {info.grid_size, info.grid_size, info.grid_height};
+		int lo[3], hi[3];
+		for (int a = 0; a < 3; ++a) {
+			double mn = 1e30, mx = -1e30;
+			for (int64_t i = 0; i < 3 * n; ++i) {
+				const double v = triangles[3 * i + a];
+				if (!(v - v == 0)) continue; // not finite
+				mn = v < mn ? v : mn;
+				mx = v > mx ? v : mx;
+			}
+			if (mn > mx) return out;
+			const double first = std::floor(mn) - 1, last = std::floor(mx) + 1; // the voxels a cube of which can touch the mesh
+			lo[a] = first < 0 ? 0 : (first > world[a] ? world[a] : static_cast<int>(first));
+			hi[a] = last < 0 ? 0 : (last > world[a] ? world[a] : static_cast<int>(last));
+			if (hi[a] <= lo[a]) return out;
+		}
+		bm_voxelize_params p{};
+		for (int a = 0; a < 3; ++a) { p.lo[a] = lo[a]; p.extent[a] = hi[a] - lo[a]; }
+		p.mode = mode;
+		const size_t voxels = Region(lo, hi).voxels(), tri_bytes = static_cast<size_t>(n) * 9 * sizeof(float), ws_bytes = voxelize_workspace_bytes(p, n);
+		const size_t at_tri = 16, at_vol = at_tri + (tri_bytes + 15) / 16 * 16, at_ws = at_vol + (voxels + 15) / 16 * 16;
+		void* buf = nullptr; // the result, the triangles, the volume, then the workspace
+		BM_CHECKED(bm_buffer_alloc(device_, at_ws + ws_bytes, &buf));
+		char* base = static_cast<char*>(buf);
+		try {
+			BM_CHECKED(bm_buffer_write(device_, base + at_tri, triangles, tri_bytes));
+			voxelize(p, n, reinterpret_cast<const float*>(base + at_tri), reinterpret_cast<uint8_t*>(base + at_vol), reinterpret_cast<bm_voxelize_result*>(base),
+					 base + at_ws, ws_bytes);
+			write_region(Region(lo, hi), reinterpret_cast<const uint8_t*>(base + at_vol), op, BM_VOXELS_DEVICE);
+			BM_CHECKED(bm_buffer_read(device_, &out, base, sizeof out)); // (waits for the device)
+		} catch (...) {
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		if (box_voxels) *box_voxels = voxels;
+		return out;
+	}
+
 private:
 	int device_;
 };
