@@ -101,6 +101,18 @@ class bm_voxelize_result(C.Structure):
     _fields_ = [("rejected", C.c_uint32), ("degenerate", C.c_uint32), ("open_columns", C.c_uint64)]
 
 
+BM_MESH_HALO = 1
+BM_MESH_UNIT_FACES = 2
+
+
+class bm_mesh_params(C.Structure):
+    _fields_ = [("lo", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("row_pitch", C.c_int64), ("slice_pitch", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class bm_mesh_result(C.Structure):
+    _fields_ = [("quads", C.c_uint64), ("faces", C.c_uint64)]
+
+
 class bm_volume(C.Structure):
     _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
 
@@ -188,6 +200,12 @@ SIGNATURES = {
     "bm_voxelize": (_i, [_vp, C.POINTER(bm_voxelize_params), C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bm_debug_voxelize_times": (_i, [_vp, C.POINTER(bm_voxelize_params), C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_float)]),
     "bm_host_voxelize": (_i, [C.POINTER(bm_voxelize_params), C.c_int64, _vp, _vp, C.POINTER(bm_voxelize_result)]),
+    "bm_mesh_workspace_bytes": (_i, [C.POINTER(bm_mesh_params), C.POINTER(C.c_size_t)]),
+    "bm_mesh_quads": (_i, [_vp, C.POINTER(bm_mesh_params), _vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t, _vp]),
+    "bm_debug_mesh_times": (_i, [_vp, C.POINTER(bm_mesh_params), _vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_float)]),
+    "bm_mesh_triangles": (_i, [_vp, _vp, C.c_int64, _vp, _vp]),
+    "bm_host_mesh_quads": (_i, [C.POINTER(bm_mesh_params), _vp, _vp, C.c_uint64, C.POINTER(bm_mesh_result)]),
+    "bm_host_mesh_triangles": (_i, [_vp, C.c_int64, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

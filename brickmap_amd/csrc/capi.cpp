@@ -10,6 +10,7 @@
 #include "camera_rays.h"
 #include "denoise.h"
 #include "kernels.h"
+#include "mesh.h"
 #include "reproject.h"
 #include "scene.h"
 #include "voxelize.h"
@@ -249,6 +250,33 @@ int bm_debug_voxelize_times(bm_scene* scene, const bm_voxelize_params* params, i
 	BM_NEED(scene);
 	if (!kernel_ms) { set_error("bm_debug_voxelize_times: null argument"); return BM_EINVAL; }
 	return scene->impl.voxelize(params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+}
+
+// (bm_host_mesh_quads and bm_host_mesh_triangles are csrc/mesh_host.cpp: host code that needs nothing of the library)
+int bm_mesh_workspace_bytes(const bm_mesh_params* params, size_t* bytes) {
+	if (!params || !bytes) { set_error("bm_mesh_workspace_bytes: null argument"); return BM_EINVAL; }
+	const bm::MeshParamsView pv = bm::mesh_params_view(*params);
+	if (const char* why = bm::mesh_params_problem(pv)) { set_error(std::string("bm_mesh_workspace_bytes: ") + why); return BM_EINVAL; }
+	*bytes = bm::mesh_workspace_bytes(bm::mesh_dims(pv));
+	return 0;
+}
+
+int bm_mesh_quads(bm_scene* scene, const bm_mesh_params* params, const uint8_t* volume_dev, bm_quad* quads_dev, uint64_t capacity, bm_mesh_result* result_dev,
+				  void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.mesh_quads(params, volume_dev, quads_dev, capacity, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_mesh_times(bm_scene* scene, const bm_mesh_params* params, const uint8_t* volume_dev, bm_quad* quads_dev, uint64_t capacity, bm_mesh_result* result_dev,
+						void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms) {
+	BM_NEED(scene);
+	if (!kernel_ms) { set_error("bm_debug_mesh_times: null argument"); return BM_EINVAL; }
+	return scene->impl.mesh_quads(params, volume_dev, quads_dev, capacity, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+}
+
+int bm_mesh_triangles(bm_scene* scene, const bm_quad* quads_dev, int64_t n, float* triangles_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return scene->impl.mesh_triangles(quads_dev, n, triangles_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -157,6 +157,19 @@ size_t voxelize_workspace_bytes(const VoxelizeDims& d, uint32_t n);
 int voxelize_blocks_per_cu(bool solid);
 void launch_voxelize(const VoxelizeDims& d, const float* triangles, uint32_t n, uint8_t* volume, void* result, void* workspace, const int resident_blocks[2],
 					 hipStream_t stream, hipEvent_t* marks = nullptr);
+
+// block_off[g * (nblocks + 1) + (0 ... nblocks)), g < groups: sums -> 64-bit exclusive offsets, entry nblocks = the total (voxelize.hip's
+// scan of workgroup sums, also the last step of mesh.hip's)
+void launch_offsets_scan(uint64_t* block_off, uint32_t nblocks, uint32_t groups, hipStream_t stream);
+
+// voxels -> quads (mesh.hip; mesh.h has the rules and MeshDims): the volume's surface as 16-byte quads, the first `capacity` of them
+// written (capacity 0: none), the totals in the 16 bytes of `result`.  workspace: mesh_workspace_bytes() bytes, 16-byte aligned, that no
+// other launch uses until this one has finished.  marks: null, or 4 events around count, scan and emit.
+struct MeshDims;
+void launch_mesh_quads(const MeshDims& d, const uint8_t* volume, void* quads, uint64_t capacity, void* result, void* workspace, hipStream_t stream,
+					   hipEvent_t* marks = nullptr);
+// n quads -> 2 n triangles of 9 floats
+void launch_mesh_triangles(const void* quads, uint64_t n, float* triangles, hipStream_t stream);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

@@ -20,6 +20,7 @@
 #include "escape.h"
 #include "kernels.h"
 #include "label.h"
+#include "mesh.h"
 
 namespace bm {
 
@@ -1899,6 +1900,72 @@ int Scene::voxelize(const bm_voxelize_params* params, int64_t n, const float* tr
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventSynchronize(raw[kStages]));
 	for (int i = 0; i < kStages; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
+	return 0;
+}
+
+// ---- voxels -> quads (bm_mesh_quads, bm_mesh_triangles): kernels on the caller's stream over the caller's buffers; nothing of the world is read
+int Scene::mesh_quads(const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result, void* workspace,
+					  size_t workspace_bytes, hipStream_t stream, float* kernel_ms) {
+	if (!params) { set_error("bm_mesh_quads: null params"); return BM_EINVAL; }
+	const MeshParamsView pv = mesh_params_view(*params);
+	if (const char* why = mesh_params_problem(pv)) { set_error(std::string("bm_mesh_quads: ") + why); return BM_EINVAL; }
+	if (!volume || !result || !workspace) { set_error("bm_mesh_quads: null volume, result or workspace"); return BM_EINVAL; }
+	if (!quads && capacity > 0) { set_error("bm_mesh_quads: null quads with a capacity above 0"); return BM_EINVAL; }
+	if (capacity > (uint64_t{1} << 40)) { set_error("bm_mesh_quads: a capacity above 2^40"); return BM_EINVAL; }
+	const MeshDims d = mesh_dims(pv);
+	const size_t need = mesh_workspace_bytes(d);
+	if (workspace_bytes < need) { set_error("bm_mesh_quads: the workspace is smaller than bm_mesh_workspace_bytes"); return BM_EINVAL; }
+	const uintptr_t pq = reinterpret_cast<uintptr_t>(quads), pv0 = reinterpret_cast<uintptr_t>(volume), pr = reinterpret_cast<uintptr_t>(result),
+					pw = reinterpret_cast<uintptr_t>(workspace);
+	if (pq % 4 != 0 || pr % 8 != 0 || pw % 16 != 0) { set_error("bm_mesh_quads: quads must be 4-byte, the result 8-byte and the workspace 16-byte aligned"); return BM_EINVAL; }
+	const size_t span = static_cast<size_t>(mesh_span(d));
+	const size_t quad_bytes = quads ? static_cast<size_t>(capacity) * sizeof(bm_quad) : 0;
+	auto overlaps_workspace = [&](uintptr_t p, size_t bytes) { return bytes > 0 && p < pw + need && pw < p + bytes; };
+	if (overlaps_workspace(pv0, span) || overlaps_workspace(pq, quad_bytes) || overlaps_workspace(pr, sizeof(bm_mesh_result))) {
+		set_error("bm_mesh_quads: the workspace overlaps the volume, the quads or the result");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(device_));
+	if (!device_span_ok(volume, span) || !device_span_ok(static_cast<const uint8_t*>(workspace), need) ||
+		(quad_bytes > 0 && !device_span_ok(reinterpret_cast<const uint8_t*>(quads), quad_bytes)) ||
+		!device_span_ok(reinterpret_cast<const uint8_t*>(result), sizeof(bm_mesh_result))) {
+		set_error("bm_mesh_quads: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (!kernel_ms) {
+		launch_mesh_quads(d, volume, quads, quads ? capacity : 0, result, workspace, stream);
+		BM_HIP(hipGetLastError());
+		return 0;
+	}
+	constexpr int kStages = 3;
+	Event marks[kStages + 1];
+	hipEvent_t raw[kStages + 1];
+	for (int i = 0; i <= kStages; ++i) {
+		if (int e = marks[i].create(hipEventDefault)) return e;
+		raw[i] = marks[i];
+	}
+	launch_mesh_quads(d, volume, quads, quads ? capacity : 0, result, workspace, stream, raw);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventSynchronize(raw[kStages]));
+	for (int i = 0; i < kStages; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
+	return 0;
+}
+
+int Scene::mesh_triangles(const bm_quad* quads, int64_t n, float* triangles, hipStream_t stream) {
+	if (n < 0 || n > (int64_t{1} << 32)) { set_error("bm_mesh_triangles: a quad count below 0 or above 2^32"); return BM_EINVAL; }
+	if (n == 0) return 0;
+	if (!quads || !triangles) { set_error("bm_mesh_triangles: null buffer"); return BM_EINVAL; }
+	if (reinterpret_cast<uintptr_t>(quads) % 4 != 0 || reinterpret_cast<uintptr_t>(triangles) % 4 != 0) { set_error("bm_mesh_triangles: quads and triangles must be 4-byte aligned"); return BM_EINVAL; }
+	const size_t quad_bytes = static_cast<size_t>(n) * sizeof(bm_quad), tri_bytes = static_cast<size_t>(n) * 18 * sizeof(float);
+	const uintptr_t pq = reinterpret_cast<uintptr_t>(quads), pt = reinterpret_cast<uintptr_t>(triangles);
+	if (pq < pt + tri_bytes && pt < pq + quad_bytes) { set_error("bm_mesh_triangles: the triangles overlap the quads"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	if (!device_span_ok(reinterpret_cast<const uint8_t*>(quads), quad_bytes) || !device_span_ok(reinterpret_cast<const uint8_t*>(triangles), tri_bytes)) {
+		set_error("bm_mesh_triangles: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	launch_mesh_triangles(quads, static_cast<uint64_t>(n), triangles, stream);
+	BM_HIP(hipGetLastError());
 	return 0;
 }
 

@@ -77,6 +77,11 @@ public:
 	// kernel_ms: null, or 5 durations -- zeroing, plan + scan, surface, solid, the dense pass (the call then waits; bm_debug_voxelize_times)
 	int voxelize(const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result, void* workspace, size_t workspace_bytes,
 				 hipStream_t stream, float* kernel_ms = nullptr);
+	// voxels -> quads (mesh.hip): like voxelize, the buffers and the workspace are the caller's and the scene keeps no state
+	// kernel_ms: null, or 3 durations -- count, scan, emit (the call then waits; bm_debug_mesh_times)
+	int mesh_quads(const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result, void* workspace, size_t workspace_bytes,
+				   hipStream_t stream, float* kernel_ms = nullptr);
+	int mesh_triangles(const bm_quad* quads, int64_t n, float* triangles, hipStream_t stream);
 	// pixel-centre rays of a frame, written on the device (denoise.hip)
 	int pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
 	// temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers; the scene keeps no state for it

@@ -20,6 +20,7 @@
 // (OR, XOR of one bit: any order, one result) and read by the dense pass after the kernel boundary; nothing waits for another workgroup.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "global_mem.h"
 #include "kernels.h"
 #include "voxelize.h"
@@ -30,25 +31,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kRowWordsMax = (kVxMaxExtent + 32) / 32; // 513
-
-// exclusive scan of one 64-bit value per thread of a 256-thread workgroup; *total = the sum (volume.hip's)
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* lds, uint64_t* total) {
-	const uint32_t t = threadIdx.x;
-	__syncthreads();
-	lds[t] = v;
-	__syncthreads();
-	uint64_t sum = v;
-#pragma unroll
-	for (uint32_t d = 1; d < 256; d <<= 1) {
-		const uint64_t other = t >= d ? lds[t - d] : 0;
-		__syncthreads();
-		sum += other;
-		lds[t] = sum;
-		__syncthreads();
-	}
-	*total = lds[255];
-	return sum - v;
-}
 
 __device__ __forceinline__ int load_tri(const float* __restrict__ triangles, uint32_t i, const VoxelizeDims& d, VxTri& t) {
 	float v[9];
@@ -294,6 +276,10 @@ __global__ __launch_bounds__(kThreads) void voxelize_dense(const uint32_t* __res
 }
 
 // ---- host-callable launchers (kernels.h)
+void launch_offsets_scan(uint64_t* block_off, uint32_t nblocks, uint32_t groups, hipStream_t stream) {
+	hipLaunchKernelGGL(voxelize_scan, dim3(groups), dim3(kThreads), 0, stream, block_off, nblocks);
+}
+
 size_t voxelize_plane_bytes(const VoxelizeDims& d) {
 	const size_t bytes = static_cast<size_t>(d.extent[1]) * static_cast<size_t>(d.extent[2]) * d.words * sizeof(uint32_t);
 	return (bytes + 15) & ~static_cast<size_t>(15);
@@ -323,7 +309,7 @@ void launch_voxelize(const VoxelizeDims& d, const float* triangles, uint32_t n, 
 	stamp();
 	if (n > 0) {
 		hipLaunchKernelGGL(voxelize_plan, dim3(nblocks), dim3(kThreads), 0, stream, triangles, local, block_off, static_cast<uint32_t*>(result), n, nblocks, d);
-		hipLaunchKernelGGL(voxelize_scan, dim3(2), dim3(kThreads), 0, stream, block_off, nblocks);
+		launch_offsets_scan(block_off, nblocks, 2, stream);
 	}
 	stamp();
 	if (n > 0 && surface)

@@ -457,6 +457,105 @@ class VoxelizeResult:
     open_columns = property(lambda self: int(self.record["open_columns"]))
 
 
+# ---- voxels -> quads (bm_mesh_quads / bm_host_mesh_quads)
+QUAD_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("shape", "<u4")])   # bm_quad, 16 bytes: shape = d | w << 4 | h << 8
+MESH_RESULT_DTYPE = np.dtype([("quads", "<u8"), ("faces", "<u8")])                     # bm_mesh_result, 16 bytes
+
+
+def _mesh_params(lo, volume, halo, unit, name="volume"):
+    """(bm_mesh_params, data pointer, is_cuda) of `volume` ([z, y, x], laid out as region_of takes it) with its voxel [0, 0, 0] at lo"""
+    r, ptr, cuda = region_of(lo, volume, name)
+    nz, ny, nx = volume.shape
+    par = _lib.bm_mesh_params()
+    par.lo[:] = list(r.lo)
+    par.extent[:] = [nx, ny, nz]
+    par.row_pitch, par.slice_pitch = r.row_pitch, r.slice_pitch
+    par.flags = (_lib.BM_MESH_HALO if halo else 0) | (_lib.BM_MESH_UNIT_FACES if unit else 0)
+    return par, ptr, cuda
+
+
+def mesh_workspace_bytes(shape, halo=False, lo=(0, 0, 0)):
+    """bm_mesh_workspace_bytes: device memory bm_mesh_quads needs beside its buffers for a volume of shape (nz, ny, nx) whose first voxel is
+    world voxel lo (the cells are the world's, so their number depends on lo modulo 8)."""
+    par = _lib.bm_mesh_params()
+    par.lo[:] = [int(v) for v in lo]
+    par.extent[:] = [int(shape[2]), int(shape[1]), int(shape[0])]
+    par.flags = _lib.BM_MESH_HALO if halo else 0
+    out = C.c_size_t(0)
+    check(_lib.load().bm_mesh_workspace_bytes(C.byref(par), C.byref(out)))
+    return int(out.value)
+
+
+def host_mesh_quads(volume, lo=(0, 0, 0), halo=False, unit=False):
+    """bm_host_mesh_quads (host only, no device): the surface of a dense volume [z, y, x] (uint8 or bool numpy array, non-zero = solid; a
+    slice of a larger array works as long as x is contiguous) whose first voxel is world voxel lo = (x, y, z), as plain loops.  halo: the
+    outermost shell of the volume is context only; unit: one quad per face.  Returns (quads, record): a QUAD_DTYPE array in the
+    contract's order and a MESH_RESULT_DTYPE record (quads, faces)."""
+    par, ptr, cuda = _mesh_params(lo, volume, halo, unit)
+    assert not cuda
+    L = _lib.load()
+    res = _lib.bm_mesh_result()
+    check(L.bm_host_mesh_quads(C.byref(par), C.c_void_p(ptr), None, 0, C.byref(res)))
+    quads = np.zeros(int(res.quads), QUAD_DTYPE)
+    if len(quads):
+        check(L.bm_host_mesh_quads(C.byref(par), C.c_void_p(ptr), C.c_void_p(quads.ctypes.data), len(quads), C.byref(res)))
+    rec = np.zeros((), MESH_RESULT_DTYPE)
+    rec["quads"], rec["faces"] = res.quads, res.faces
+    return quads, rec
+
+
+def host_mesh_triangles(quads):
+    """bm_host_mesh_triangles (host only): the two triangles of every quad (a QUAD_DTYPE array) as float32 [2 n, 3, 3], counter-clockwise
+    seen from outside: what host_voxelize and Scene.voxelize read."""
+    quads = np.ascontiguousarray(np.asarray(quads, dtype=QUAD_DTYPE).reshape(-1))
+    tri = np.zeros((2 * len(quads), 3, 3), np.float32)
+    check(_lib.load().bm_host_mesh_triangles(C.c_void_p(quads.ctypes.data), len(quads), C.c_void_p(tri.ctypes.data)))
+    return tri
+
+
+class Quads:
+    """The quads of a Scene.mesh_quads, read lazily: `packed` is the quad buffer on the device (an int32 tensor [capacity, 4]) and
+    `result` the bm_mesh_result there (two int64 words); count, faces, record (a MESH_RESULT_DTYPE scalar) and records (a QUAD_DTYPE array
+    of the min(count, capacity) quads written) copy to the host, which waits for the call.  triangles() stays on the device."""
+
+    def __init__(self, scene, packed, result, record=None):
+        self.scene, self.packed, self.result = scene, packed, result
+        self._record, self._records = record, None
+
+    @property
+    def record(self):
+        if self._record is None:
+            self._record = self.result.cpu().numpy().view(MESH_RESULT_DTYPE).reshape(())
+        return self._record
+
+    count = property(lambda self: int(self.record["quads"]))
+    faces = property(lambda self: int(self.record["faces"]))
+
+    def __len__(self):
+        return min(self.count, int(self.packed.shape[0]))
+
+    @property
+    def records(self):
+        if self._records is None:
+            self._records = np.ascontiguousarray(self.packed[:len(self)].cpu().numpy()).view(QUAD_DTYPE).reshape(-1)
+        return self._records
+
+    def triangles(self, stream=None):
+        """bm_mesh_triangles: a float32 tensor [2 n, 3, 3] on the scene's GPU for the n quads written, as Scene.voxelize takes it (reads
+        the count: waits for the call that made the quads)."""
+        import torch
+        n = len(self)
+        current, target = self.scene._volume_stream(self.packed, stream)
+        with torch.cuda.stream(target):
+            tri = torch.empty((2 * n, 3, 3), dtype=torch.float32, device=self.packed.device)
+        if n:
+            check(self.scene._L.bm_mesh_triangles(self.scene.gpuScene, C.c_void_p(self.packed.data_ptr()), n, C.c_void_p(tri.data_ptr()), C.c_void_p(target.cuda_stream)))
+            if target.cuda_stream != current.cuda_stream:
+                self.packed.record_stream(target)
+                current.wait_stream(target)
+        return tri
+
+
 # ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmax", "<f4"), ("reserved", "<u4")])   # bm_ray
 RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("voxel", "<i4", 3), ("level", "<i4")])  # bm_ray_hit
@@ -1100,6 +1199,70 @@ class Scene:
         volume, res = self.voxelize(tri, lo, (hi[2] - lo[2], hi[1] - lo[1], hi[0] - lo[0]), mode=mode, stream=stream)
         self.write_region(lo, volume, op=op, stream=stream)
         return tuple(lo), tuple(hi), res
+
+    # ---- voxels -> quads (bm_mesh_quads): the scene only names the GPU; nothing of the world is read
+    def _mesh_quads(self, volume, lo, halo, unit, capacity, stream, times):
+        import torch
+        if not hasattr(volume, "is_cuda") or not volume.is_cuda:
+            raise ValueError("mesh_quads: volume must be a uint8 or bool tensor [z, y, x] on the scene's GPU")
+        par, ptr, _ = _mesh_params(lo, volume, halo, unit)
+        if min(volume.shape) == 0:
+            raise ValueError(f"mesh_quads: a volume with positive extents expected, got shape {tuple(volume.shape)}")
+        dev = volume.device
+        current, target = self._volume_stream(volume, stream)
+        with torch.cuda.stream(target):
+            ws = torch.empty(mesh_workspace_bytes(volume.shape, halo, lo), dtype=torch.uint8, device=dev)
+            result = torch.empty(2, dtype=torch.int64, device=dev)
+        if target.cuda_stream != current.cuda_stream:
+            volume.record_stream(target)
+        ms = (C.c_float * 3)() if times else None
+
+        def call(packed, cap):
+            args = (self.gpuScene, C.byref(par), C.c_void_p(ptr), C.c_void_p(packed.data_ptr() if packed is not None else 0), cap, C.c_void_p(result.data_ptr()),
+                    C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(target.cuda_stream))
+            check(self._L.bm_debug_mesh_times(*args, ms) if times else self._L.bm_mesh_quads(*args))
+
+        record = None
+        if capacity is None:
+            call(None, 0)
+            with torch.cuda.stream(target):
+                record = result.cpu().numpy().view(MESH_RESULT_DTYPE).reshape(())   # waits for the counting call
+            capacity = int(record["quads"])
+        capacity = int(capacity)
+        with torch.cuda.stream(target):
+            packed = torch.empty((capacity, 4), dtype=torch.int32, device=dev)
+        if capacity > 0 or record is None:
+            call(packed if capacity > 0 else None, capacity)
+        if target.cuda_stream != current.cuda_stream:
+            current.wait_stream(target)
+        return Quads(self, packed, result, record), ([float(v) for v in ms] if times else None)
+
+    def mesh_quads(self, volume, lo=(0, 0, 0), halo=False, unit=False, capacity=None, stream=None):
+        """bm_mesh_quads: the surface of a dense volume [z, y, x] -- a uint8 or bool tensor on the scene's GPU, non-zero =
+        solid, strides as in write_region -- whose first voxel is world voxel lo = (x, y, z), as quads merged greedily inside the world's
+        8^3 cells.  halo=True: the volume's outermost shell is context only, so neighbouring tiles share no wall; unit=True: one quad per
+        face.  capacity=None makes the counting call, reads the total, allocates and emits: that read is one synchronisation, and the one
+        thing this call waits for.  With a capacity the first `capacity` quads are written and the host does not wait.  Returns a Quads.
+        Stream handling as in write_region; the workspace comes from torch's pool."""
+        return self._mesh_quads(volume, lo, halo, unit, capacity, stream, False)[0]
+
+    def mesh_quads_times(self, volume, lo=(0, 0, 0), halo=False, unit=False, capacity=None, stream=None):
+        """bm_debug_mesh_times: Scene.mesh_quads with a hipEvent between its stages; waits.  Returns (Quads, [ms of count, scan, emit]) of
+        the emitting call."""
+        return self._mesh_quads(volume, lo, halo, unit, capacity, stream, True)
+
+    def extract_mesh(self, lo, hi, closed=True, unit=False, stream=None):
+        """The surface of the voxels lo <= v < hi (x, y, z) of the live scene as a Quads.  closed=True: read_region(lo, hi, device=True),
+        meshed without flags -- everything outside the box is empty and the surface is closed.  closed=False: the box lo - 1 ... hi + 1 is
+        read and meshed with a halo -- faces only where a voxel of the box meets an empty voxel, inside the box or beside it, so
+        neighbouring boxes share no wall.  Waits once, for the quad count (see mesh_quads)."""
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if any(h <= l for l, h in zip(lo, hi)):
+            raise ValueError(f"extract_mesh: an empty box ({lo} ... {hi})")
+        if not closed:
+            lo, hi = [v - 1 for v in lo], [v + 1 for v in hi]
+        volume = self.read_region(lo, hi, device=True, stream=stream)
+        return self.mesh_quads(volume, lo, halo=not closed, unit=unit, stream=stream)
 
     # ---- ray queries (bm_scene_cast_rays): issued like a frame -- after every edit and upload issued before, asynchronous to the host
     def cast_rays_raw(self, n, rays_ptr, hits_ptr, flags=0, lod_origin=None, stream=None):

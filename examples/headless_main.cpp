@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--dig x,y,z,r] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -9,6 +9,9 @@
 // --mesh FILE@x,y,z adds a triangle mesh to the world after --paste: FILE is raw, 9 floats per triangle (xyz per vertex, in voxels), moved
 // by (x, y, z); it is voxelized on the GPU over its own bounds -- every voxel a triangle touches and every voxel whose centre lies inside
 // the closed mesh -- and written with "set" (Scene::write_mesh).  Prints the triangle counts and `open columns`, 0 for a closed mesh.
+// --mesh-out x0,y0,z0:x1,y1,z1=FILE, applied after every edit above and below (--dig, --drop-floating, --dig-at): the surface of that box
+// of the world, closed at the box's sides, is extracted on the GPU as quads merged inside the 8^3 cells (Scene::extract_mesh) and written
+// to FILE as triangles in the raw format --mesh reads; prints the counts of quads, faces and triangles.
 // --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
 // --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig: the pieces of that box that hang on nothing -- connected components by faces,
 // inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
@@ -52,6 +55,8 @@ int main(int argc_in, char** argv_in) {
 	int paste_size[3] = {0, 0, 0}, paste_at[3] = {0, 0, 0};
 	std::string mesh_path;
 	float mesh_at[3] = {0.f, 0.f, 0.f};
+	std::string mesh_out_path;
+	int mesh_out_lo[3] = {0, 0, 0}, mesh_out_hi[3] = {0, 0, 0};
 	for (int i = 0; i < argc_in; ++i) {
 		if (std::string(argv_in[i]) == "--denoise") {
 			denoise = true;
@@ -84,6 +89,20 @@ int main(int argc_in, char** argv_in) {
 				return 2;
 			}
 			mesh_path = spec.substr(0, at);
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--mesh-out" && i + 1 < argc_in) {
+			const std::string spec = argv_in[++i];
+			const size_t eq = spec.find('=');
+			int* lo = mesh_out_lo;
+			int* hi = mesh_out_hi;
+			if (eq == std::string::npos || eq + 1 == spec.size() ||
+				std::sscanf(spec.substr(0, eq).c_str(), "%d,%d,%d:%d,%d,%d", &lo[0], &lo[1], &lo[2], &hi[0], &hi[1], &hi[2]) != 6 || hi[0] <= lo[0] || hi[1] <= lo[1] ||
+				hi[2] <= lo[2]) {
+				std::cerr << "--mesh-out wants x0,y0,z0:x1,y1,z1=FILE (a box that is not empty)\n";
+				return 2;
+			}
+			mesh_out_path = spec.substr(eq + 1);
 			continue;
 		}
 		if (std::string(argv_in[i]) == "--dig-at" && i + 1 < argc_in) {
@@ -197,6 +216,18 @@ int main(int argc_in, char** argv_in) {
 			std::printf("carved radius %d at %d,%d,%d; the pixel now sees voxel %d,%d,%d level %d\n", dig_at[2], hit.voxel[0], hit.voxel[1],
 						hit.voxel[2], now.voxel[0], now.voxel[1], now.voxel[2], now.level);
 		}
+	}
+	if (!mesh_out_path.empty()) {
+		std::vector<float> triangles;
+		const Scene::Mesh mesh = scene.extract_mesh(Scene::Region(mesh_out_lo, mesh_out_hi), &triangles);
+		std::ofstream file(mesh_out_path, std::ios::binary);
+		file.write(reinterpret_cast<const char*>(triangles.data()), static_cast<std::streamsize>(triangles.size() * sizeof(float)));
+		if (!file) {
+			std::cerr << "--mesh-out: cannot write " << mesh_out_path << "\n";
+			return 2;
+		}
+		std::printf("mesh-out: %llu quads, %llu faces, %zu triangles\n", static_cast<unsigned long long>(mesh.result.quads),
+					static_cast<unsigned long long>(mesh.result.faces), triangles.size() / 9);
 	}
 	if (ground[0] >= 0) {
 		const int lo[3] = {ground[0], ground[1], 0}, hi[3] = {ground[0] + 1, ground[1] + 1, grid_height};

@@ -595,6 +595,72 @@ BM_API int bm_debug_voxelize_times(bm_scene* scene, const bm_voxelize_params* pa
 /* the same on host memory, as plain loops (csrc/voxelize_host.cpp; no device needed); the refusals that concern params and null pointers */
 BM_API int bm_host_voxelize(const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result);
 
+/* ---- voxels -> the quads of their surface (no reference counterpart): the counterpart of bm_voxelize.  A dense byte volume V[z][y][x] in
+ * device memory (any non-zero byte is solid; x contiguous, rows and slices at the given pitches, any base alignment; voxel [0][0][0] at
+ * world voxel lo) gives the quads of its surface as 16-byte records.  All integers, the same bytes on every run, and bm_mesh_quads ==
+ * bm_host_mesh_quads byte for byte (csrc/mesh.h holds the rules once).
+ *  - Faces.  A face is a pair (solid voxel p, direction d) whose neighbour p + d is empty; directions 0 ... 5 = -x, +x, -y, +y, -z, +z.
+ *    Without flags every voxel outside the volume is empty, so the surface is closed.  With BM_MESH_HALO the outermost one-voxel shell of
+ *    the volume is context only: faces are emitted for the voxels with index 1 ... n - 2 on every axis, their neighbours are read from the
+ *    shell, and every extent must be at least 3 -- tiles of a larger world meshed this way have no walls between them.
+ *  - Cells.  The meshed voxels are cut into the world's 8^3 brick cells: a boundary lies where lo + index is a multiple of 8 (floor
+ *    division: lo may be negative); the first and last cell of an axis may be ragged.  Cells are numbered in (z, y, x) order over the
+ *    cells the meshed box spans.
+ *  - Masks.  Inside a cell, direction d on axis a and slice s = 0 ... 7 (the solid voxel's cell-local coordinate along a) have an 8 x 8
+ *    mask: bit 8 v + u is the face at in-slice position (u, v), the other two axes in ascending order -- (y, z) for x, (x, z) for y,
+ *    (x, y) for z.
+ *  - Greedy cover, until the mask is empty: take the lowest set bit (u0, v0); w = the length of the run of set bits from u0 in row v0 (it
+ *    does not pass u = 7); h = 1 + the number of following rows that have all bits u0 ... u0 + w - 1 set; clear the rectangle; emit a
+ *    quad.  With BM_MESH_UNIT_FACES w = h = 1 always.  At most 64 rounds.
+ *  - Quad.  x, y, z = the world voxel of the quad's lowest solid voxel; shape = d | w << 4 | h << 8.
+ *  - Order: by cell, then direction, then slice, then the greedy order -- a total order without a sort.
+ *  - Capacity.  The first min(capacity, total) quads are written; records past that are never touched.  capacity == 0 with a null quad
+ *    pointer is the counting call.
+ *  - Result (16 bytes on the device), always the full totals: quads, and faces = the sum of w h.
+ *  - Triangles.  bm_mesh_triangles writes 2 n triangles of 9 floats, the format bm_voxelize reads.  The quad's plane is at coordinate c_a
+ *    for a negative direction and c_a + 1 for a positive one; its corners are c00, c10 = c00 + w e_u, c11 and c01 = c00 + h e_v.  If
+ *    e_u x e_v points along d the triangles are (c00, c10, c11) and (c00, c11, c01), otherwise (c00, c01, c11) and (c00, c11, c10):
+ *    counter-clockwise seen from outside.  A record whose direction is above 5 gives 18 zeros.  Voxelized again with BM_VOXELIZE_SOLID
+ *    the triangles of a volume give back the volume, with open_columns == 0.
+ *  - Refusals, BM_EINVAL with nothing launched and nothing written: an extent below 1 (below 3 with BM_MESH_HALO) or above 16384; more
+ *    than 2^31 - 2 voxels; a pitch below the extent it spans (0 = tight) or a volume spanning more than 2^46 bytes; a span ((nz - 1)
+ *    slice_pitch + (ny - 1) row_pitch + nx bytes) or any other buffer that does not lie inside one allocation of the scene's device; an
+ *    unknown flag bit or a non-zero `reserved`; a null volume, result or workspace; a null quad pointer with capacity > 0; quads not
+ *    4-byte, a result not 8-byte or a workspace not 16-byte aligned; a workspace below bm_mesh_workspace_bytes; a workspace that overlaps
+ *    the volume, the quads or the result; a box that does not lie within +-2^23 voxels (every corner is an exact fp32 integer). */
+#define BM_MESH_HALO 1u
+#define BM_MESH_UNIT_FACES 2u
+typedef struct bm_mesh_params {
+	int32_t lo[3];       /* world voxel of V[0][0][0], (x, y, z) */
+	int32_t extent[3];   /* nx, ny, nz: 1 ... 16384 */
+	int64_t row_pitch;   /* bytes from one x-row to the next y; 0 = tight (nx) */
+	int64_t slice_pitch; /* bytes from one z-slice to the next; 0 = tight (row_pitch * ny) */
+	uint32_t flags;      /* BM_MESH_HALO | BM_MESH_UNIT_FACES */
+	uint32_t reserved;   /* 0 */
+} bm_mesh_params;
+typedef struct bm_quad {
+	int32_t x, y, z;
+	uint32_t shape; /* d | w << 4 | h << 8 */
+} bm_quad;
+typedef struct bm_mesh_result {
+	uint64_t quads, faces;
+} bm_mesh_result;
+/* bytes of device memory bm_mesh_quads needs beside its buffers: 4 bytes per cell (rounded up to 16) and 8 per 256 cells, plus 8 */
+BM_API int bm_mesh_workspace_bytes(const bm_mesh_params* params, size_t* bytes);
+/* the buffers and the workspace are the caller's and the scene keeps no state (the scene names the device): calls on different streams
+ * with workspaces of their own are independent.  Asynchronous on hip_stream.  Nothing of the world is read. */
+BM_API int bm_mesh_quads(bm_scene* scene, const bm_mesh_params* params, const uint8_t* volume_dev, bm_quad* quads_dev, uint64_t capacity,
+                         bm_mesh_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+/* n quads (4-byte aligned) -> 2 n triangles of 9 floats (4-byte aligned), each inside one allocation of the scene's device; n <= 2^32 */
+BM_API int bm_mesh_triangles(bm_scene* scene, const bm_quad* quads_dev, int64_t n, float* triangles_dev, void* hip_stream);
+/* measuring door: bm_mesh_quads with a hipEvent between its stages; waits, then kernel_ms[0 ... 2] = the durations in ms of count, scan
+ * and emit (0 for the counting call's emit) */
+BM_API int bm_debug_mesh_times(bm_scene* scene, const bm_mesh_params* params, const uint8_t* volume_dev, bm_quad* quads_dev, uint64_t capacity,
+                               bm_mesh_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms);
+/* the same on host memory, as plain loops (csrc/mesh_host.cpp; no device needed); the refusals that concern params and null pointers */
+BM_API int bm_host_mesh_quads(const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result);
+BM_API int bm_host_mesh_triangles(const bm_quad* quads, int64_t n, float* triangles);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

@@ -357,6 +357,69 @@ public:
 		return out;
 	}
 
+	// voxels -> the quads of their surface (no counterpart in the reference; bm_mesh_quads): the byte volume of `params` in device memory
+	// gives its first `capacity` quads in quads_dev (null with capacity 0: the counting call) and the totals in result_dev;
+	// workspace_dev: mesh_workspace_bytes() bytes of the caller's
+	static size_t mesh_workspace_bytes(const bm_mesh_params& params) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_mesh_workspace_bytes(&params, &bytes));
+		return bytes;
+	}
+	void mesh_quads(const bm_mesh_params& params, const uint8_t* volume_dev, bm_quad* quads_dev, uint64_t capacity, bm_mesh_result* result_dev, void* workspace_dev,
+					size_t workspace_bytes, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_mesh_quads(gpuScene.handle, &params, volume_dev, quads_dev, capacity, result_dev, workspace_dev, workspace_bytes, hip_stream));
+	}
+	// n quads -> 2 n triangles of 9 floats, both in device memory: what voxelize reads
+	void mesh_triangles(const bm_quad* quads_dev, int64_t n, float* triangles_dev, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_mesh_triangles(gpuScene.handle, quads_dev, n, triangles_dev, hip_stream));
+	}
+	// The surface of the voxels of `region` (its lo and hi; the pitches are not used) of the live scene, closed at the box's sides, in HOST
+	// memory: the quads in the contract's order and, when `triangles` is given, their 2 n triangles of 9 floats.  The box is read on the
+	// device (read_region), counted, then emitted; the host waits.
+	struct Mesh {
+		bm_mesh_result result{0, 0};
+		std::vector<bm_quad> quads;
+	};
+	Mesh extract_mesh(const Region& region, std::vector<float>* triangles = nullptr, uint32_t flags = 0) {
+		Mesh out;
+		if (triangles) triangles->clear();
+		bm_mesh_params p{};
+		for (int a = 0; a < 3; ++a) { p.lo[a] = region.lo[a]; p.extent[a] = region.hi[a] - region.lo[a]; }
+		p.flags = flags;
+		const size_t voxels = Region(region.lo, region.hi).voxels(), ws_bytes = mesh_workspace_bytes(p);
+		const size_t at_ws = 16, at_vol = at_ws + (ws_bytes + 15) / 16 * 16;
+		void* buf = nullptr; // the result, the workspace, then the volume
+		void* out_buf = nullptr; // the quads, then the triangles
+		BM_CHECKED(bm_buffer_alloc(device_, at_vol + voxels, &buf));
+		char* base = static_cast<char*>(buf);
+		try {
+			read_region(Region(region.lo, region.hi), reinterpret_cast<uint8_t*>(base + at_vol), BM_VOXELS_DEVICE);
+			mesh_quads(p, reinterpret_cast<const uint8_t*>(base + at_vol), nullptr, 0, reinterpret_cast<bm_mesh_result*>(base), base + at_ws, ws_bytes);
+			BM_CHECKED(bm_buffer_read(device_, &out.result, base, sizeof out.result)); // (waits for the device)
+			const size_t n = static_cast<size_t>(out.result.quads);
+			if (n > 0) {
+				const size_t quad_bytes = n * sizeof(bm_quad), tri_bytes = triangles ? n * 18 * sizeof(float) : 0;
+				BM_CHECKED(bm_buffer_alloc(device_, quad_bytes + tri_bytes, &out_buf));
+				char* q = static_cast<char*>(out_buf);
+				mesh_quads(p, reinterpret_cast<const uint8_t*>(base + at_vol), reinterpret_cast<bm_quad*>(q), n, reinterpret_cast<bm_mesh_result*>(base), base + at_ws, ws_bytes);
+				out.quads.resize(n);
+				if (triangles) {
+					mesh_triangles(reinterpret_cast<const bm_quad*>(q), static_cast<int64_t>(n), reinterpret_cast<float*>(q + quad_bytes));
+					triangles->resize(n * 18);
+					BM_CHECKED(bm_buffer_read(device_, triangles->data(), q + quad_bytes, tri_bytes));
+				}
+				BM_CHECKED(bm_buffer_read(device_, out.quads.data(), q, quad_bytes));
+			}
+		} catch (...) {
+			(void)bm_buffer_free(device_, buf);
+			if (out_buf) (void)bm_buffer_free(device_, out_buf);
+			throw;
+		}
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		if (out_buf) BM_CHECKED(bm_buffer_free(device_, out_buf));
+		return out;
+	}
+
 private:
 	int device_;
 };
