@@ -3,9 +3,10 @@
 //
 // A shadow ray delivers one bit, occluded or not.  Below a column's shadow height that bit is decided by geometry alone: every ray of the
 // cone, from anywhere in the cell, enters a FULL cell (a resident brick with all 512 voxels set) before it can leave the world, and a ray
-// that enters a full brick is stopped by its first voxel at every level of detail.  Such a ray needs no walk.
+// that enters a full brick is stopped by its first voxel at every level of detail.  Such a ray needs no walk -- it is not even drawn
+// (shadow_origin below; trace.hip, shade block).
 //
-// A ray that ends at set-up makes no brick request.  In a scene that streams its bricks in, the requests of the shadow rays' walks are part
+// A ray that is never traced makes no brick request.  In a scene that streams its bricks in, the requests of the shadow rays' walks are part
 // of what makes them resident, so shadow heights are built only where EVERY brick is resident (a preloaded scene, scene.cpp
 // ensure_sun_plane); a streaming scene's slice is zero and its frames request what the parent's did.
 //
@@ -126,6 +127,36 @@ BM_JHD int shadow_dark_cells(const ShadowPlan& p, int w, int nz, Next next) {
 // the table's entry: the sun-plane byte offset of the first slice that is not dark (slice z of the grid is slice z + 1 of a plane)
 BM_JHD uint32_t shadow_entry(uint32_t sun_plane_offset, uint32_t cf_pxy, int dark_cells) {
 	return dark_cells > 0 ? sun_plane_offset + static_cast<uint32_t>(dark_cells + 1) * cf_pxy : 0u;
+}
+
+// WHERE A SHADOW RAY STARTS.  The rule is applied where the ray is drawn (trace.hip, shade block), before it is a ray at all: a ray whose
+// origin lies in a dark cell is never set up.  That needs the cell traverse.h ray_setup WOULD give it, bit for bit -- the origin is the
+// hit point pushed out along the normal and may lie in the cell next to the one the extend ray ended in -- so the cell is computed here,
+// once, for the kernel and for tests/shadow_origin_check.cpp: origin / 8.f truncated, then the bordered offset of cell_offset.
+// `entry` is the index of the column's entry in the escape table (slice 8), `cell` the ray's byte offset on the sun plane (plane 8 of the
+// cube field); the ray is dark iff cell < table[entry].  UNDECIDED where ray_setup would not take its short way -- an origin that is not
+// strictly inside the box (NaN included), a cell outside the grid: such a ray is traced like any other.  An undecided origin has
+// cell == kShadowUndecided, above every entry, and entry == 0, the table's first entry, whatever it holds: the caller may load and
+// compare without asking, and the answer is "not dark".  (Straight-line on purpose: the kernel runs it for every lane of a shade pass.)
+// grid_size, grid_height: the world's extents in voxels; cells, cells_height: in cells; cf_shift, cf_pxy: the field's row shift and slice
+// pitch (device_types.h); sun_plane: the sun plane's byte offset in the cube field, 8 * cf_plane (FrameConstants::shadow_field_off).
+constexpr uint32_t kShadowUndecided = 0xFFFFFFFFu;
+struct ShadowOrigin {
+	uint32_t entry, cell;
+};
+BM_JHD bool shadow_undecided(const ShadowOrigin& so) { return so.cell == kShadowUndecided; }
+BM_JHD ShadowOrigin shadow_origin(float grid_size, float grid_height, int cells, int cells_height, int cf_shift, uint32_t cf_pxy, uint32_t sun_plane, float ox, float oy,
+								  float oz) {
+	// (`&`, not `&&`: nothing here is worth a branch, and the device compiler makes one of every `&&`)
+	const bool inside = (ox > 0.f) & (ox < grid_size) & (oy > 0.f) & (oy < grid_size) & (oz > 0.f) & (oz < grid_height); // ray_setup's `inside`, the origin's part
+	const float qx = inside ? ox / 8.f : -1.f, qy = inside ? oy / 8.f : -1.f, qz = inside ? oz / 8.f : -1.f;          // (never the conversion of a NaN)
+	const int px = static_cast<int>(qx), py = static_cast<int>(qy), pz = static_cast<int>(qz);
+	const bool decided = inside & (px >= 0) & (px < cells) & (py >= 0) & (py < cells) & (pz >= 0) & (pz < cells_height);
+	const uint32_t column = (static_cast<uint32_t>(py + 1) << cf_shift) + static_cast<uint32_t>(px + 1);
+	ShadowOrigin so;
+	so.entry = jump_mul24(decided ? 8u : 0u, cf_pxy) + (decided ? column : 0u); // (the slice number as a lane's value: one multiply-add, and no constant for the compiler to carry round the caller's loop)
+	so.cell = decided ? sun_plane + jump_mul24(static_cast<uint32_t>(pz + 1), cf_pxy) + column : kShadowUndecided;
+	return so;
 }
 
 } // namespace bm

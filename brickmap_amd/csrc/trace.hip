@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 	RayState r;
 	constexpr bool kEscape = BM_ESCAPE != 0 && !DBG && (BM_ESCAPE_XCD != 0 || !XCD);
 	constexpr bool kSun = BM_SUNFIELD != 0 && kEscape && (BM_SUNFIELD_XCD != 0 || !XCD); // (the plane's stamps stand in for the escape test: only where that is compiled in)
-	// shadow heights (shadowheight.h, BM_SHADOWHEIGHT / BM_SHADOWHEIGHT_XCD): production shadow rays on the sun plane end at set-up where no ray of the cone reaches the sun
+	// shadow heights (shadowheight.h, BM_SHADOWHEIGHT / BM_SHADOWHEIGHT_XCD): in production frames with a sun plane, the shade block draws no shadow ray from a cell no ray of the cone reaches the sun from
 	constexpr bool kShade = BM_SHADOWHEIGHT != 0 && kSun && !DBG && (BM_SHADOWHEIGHT_XCD != 0 || !XCD);
 	uint32_t esc = 0; // kEscape: the escape threshold of the ray in flight (ray_setup)
 	r.hit = false;
@@ -456,6 +456,8 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 				if (n_conn) { runsD++; lanesD += n_conn; } // "connect" statistics: passes that held shadow-ray results, and how many
 			}
 			// ================= phase C: shade the finished extend ray / generate the next primary ray, then set the new ray up
+			// (kShade: the shade block draws no shadow ray from a dark cell -- shadow heights, shadowheight.h -- so such a ray costs no set-up,
+			// no hand-over, no ST_CONN wait and no second visit of this pass; the lane goes on as if the surface faced away from the sun)
 			unsigned long long t_sub = t_phase;
 			(void)t_sub;
 			BM_REGION("C.connect");
@@ -551,14 +553,26 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					f3 miss_color = mk(0.f, 0.f, 0.f);
 					float sunLight = 0.f;
 					bool cast = false;
+					uint32_t sh_cell = 0u, sh_entry = 0u; // kShade: the shadow ray's cell on the sun plane and its column's shadow height (dark: cell < entry)
 					if (is_hit && !primary_only) {
 						// ---- shade, hit branch (kernel.cu:255-302); frame = base_frame + bounce, queue slot = slot.
 						// throughput is identically (1,1,1) (kernel.cu:261,271) and is not carried.
+						hitp = hitp + r.d * r.distance;
+						hitp = hitp + pn * 2.f * kEpsilon;
+						if (kShade) {
+							// SHADOW HEIGHTS (shadowheight.h).  The shadow ray's origin is final; shadow_origin gives the very cell ray_setup would start
+							// it in and its column's entry of the table, whose load is on its way while the cone sample is drawn (issued where it is
+							// used, after the bounce direction, config 2 is 0.7 % slower; held across the sky block it costs the scalar registers the
+							// scheduler loop has none of to spare: profiles/r11_shadow_origin.txt 1).  No branch: an undecided origin, and every origin
+							// of a frame without a plane, loads entry 0 with a cell above every entry -- never dark.
+							const uint32_t plane = fc.shadow_field_off;
+							const ShadowOrigin so = shadow_origin(sc.grid_size_f, sc.grid_height_f, sc.cells, sc.cells_height, sc.cf_shift, sc.cf_pxy, plane, hitp.x, hitp.y, hitp.z);
+							sh_cell = plane != 0u ? so.cell : kShadowUndecided;
+							sh_entry = sc.escape[so.entry];
+						}
 						const uint32_t frame = fc.base_frame + static_cast<uint32_t>(bounces);
 						const uint32_t slot = p + static_cast<uint32_t>(fc.sample_base + s) * W * H;
 						uint32_t sseed = (frame * p * 147565741u) * 720898027u * slot;
-						hitp = hitp + r.d * r.distance;
-						hitp = hitp + pn * 2.f * kEpsilon;
 						view = cone_sample(fc, sseed);
 						sunLight = dot(pn, view);
 						cast = sunLight > 0.f;
@@ -570,6 +584,11 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 							// the direction is kept in `bdir` until the shadow ray (if any) has been traced.
 							bdir = bounce_direction(pn, sseed);
 						}
+						// a dark cell: no ray of the cone reaches the sun from it, the shadow ray is occluded without ever being a ray.  The lane takes
+						// the transition of a surface that faces away from the sun, one line down: no sky terms, no scolor, no hand-over, no ST_CONN
+						// -- what connect would do for it two passes from now happens in this one.  (The cone sample is drawn all the same: the
+						// bounce direction continues its stream.)
+						if (kShade) cast = cast && !(sh_cell < sh_entry);
 						if (!cast) {
 							if (terminated) { s++; pstate = P_GEN; }
 							else { bounces++; ro = hitp; rd = bdir; r.n = pn; shadow = false; need_setup = true; }
@@ -699,7 +718,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					ray_loads0 = tally.index_loads;
 				}
 				pstate = shadow ? ((HELP && pstate == P_HELPER) ? P_HELPER : P_SHD_DONE) : P_EXT_DONE;
-				const int st = ray_setup<DBG, kEscape, kShade>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u);
+				const int st = ray_setup<DBG, kEscape>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u);
 				state = (st == ST_NEED && shadow) ? ST_CONN : st;
 			}
 			BM_MARK(4, t_sub); // ray set-up

@@ -392,10 +392,9 @@ __device__ __forceinline__ int walk_round(const DeviceScene& sc, RayState& r, in
 // sun_plane: non-zero for a shadow ray whose frame has a sun plane (sunfield.h; FrameConstants::shadow_field_off) -- the ray walks that
 // plane instead of its octant's, by one select here; the plane's 255 stamps hold the escape rule, so the threshold becomes the plane's
 // end, which escape_reached never sees reached (such a ray moves up: the plan of a sun below the horizon is not valid).
-// SHADE (with ESC; production shadow rays only): a ray on the sun plane reads slice 8 of the escape table, its column's shadow height
-// (shadowheight.h), in the load slot of the octant's entry it has no use for -- one select of the slice number.  Below that height no ray of the
-// cone reaches the sun: the ray ends here, occluded, by the same select that ends an escaped one (r.hit is all a shadow ray delivers).
-template <bool DBG, bool ESC = false, bool SHADE = false>
+// (Shadow heights, shadowheight.h: a shadow ray that starts in a dark cell never gets here -- the shade block of trace.hip tests the
+// origin's cell with shadow_origin, which computes the very cell of this function, and does not draw the ray.)
+template <bool DBG, bool ESC = false>
 __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally, uint32_t* esc = nullptr, uint32_t sun_plane = 0u) {
 	r.hit = false;
 	r.d = dir;
@@ -437,8 +436,7 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 	const uint32_t oct = (dir.x < 0.f ? 1u : 0u) | (dir.y < 0.f ? 2u : 0u) | (dir.z < 0.f ? 4u : 0u);
 	r.field_off = sun_plane ? sun_plane : oct * sc.cf_plane;
 	r.p = cell_offset(sc, r.field_off, px, py, pz);
-	if (ESC) *esc = sc.escape[__umul24(SHADE && sun_plane ? 8u : oct, sc.cf_pxy) + (static_cast<uint32_t>(py + 1) << sc.cf_shift) + static_cast<uint32_t>(px + 1)]; // escape_index
-	const bool dark = ESC && SHADE && sun_plane != 0u && r.p < *esc; // (shadow_entry: the plane's offset of the column's first slice that is not dark, or 0)
+	if (ESC) *esc = sc.escape[__umul24(oct, sc.cf_pxy) + (static_cast<uint32_t>(py + 1) << sc.cf_shift) + static_cast<uint32_t>(px + 1)]; // escape_index
 	if (ESC) *esc = sun_plane ? sun_plane + sc.cf_plane : *esc;
 	const float cbx = dir.x > 0.f ? static_cast<float>(px + 1) : static_cast<float>(px);
 	const float cby = dir.y > 0.f ? static_cast<float>(py + 1) : static_cast<float>(py);
@@ -455,8 +453,7 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 	r.last_step = 0;
 	if (DBG) tally.index_loads++; // one per visited cell = the reference's index loads (algorithmic count)
 	const int st = field_lookup(sc, r); // inside the grid: never a border cell
-	if (SHADE) r.hit = dark;
-	return ESC && (escape_reached(r.p, *esc, r.stepz) || dark) ? ST_NEED : st;
+	return ESC && escape_reached(r.p, *esc, r.stepz) ? ST_NEED : st;
 }
 
 // voxel.cuh:200-247: the current cell holds a non-empty brick -- read its index word and resolve it.

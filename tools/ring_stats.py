@@ -1,3 +1,7 @@
+# scheduler statistics of config 2 per frame, as a single frame and as a uniform ring of 20 (passes and lanes per pass of J, S, B, C; connect lanes).
+# usage: python tools/ab_run.py <lib built with -DBM_PHASE_TIMING> tools/ring_stats.py [production]
+#   default: BM_FLAG_COUNTERS frames -- the INSTRUMENTED instantiation (no escape heights, no sun plane, no shadow heights), with its ray counts
+#   production: plain frames -- the production instantiation the benchmark times, which reports its statistics in a -DBM_PHASE_TIMING build only
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, brickmap_amd as bm
@@ -5,9 +9,10 @@ G, W, H = 1024, 1920, 1080
 scene = bm.Scene(G, G, device=0).generate().preload_all()
 cam = bm.Camera(position=(G/2, G/8, 0.8*G), horizontal_angle=0.8, vertical_angle=-0.5).update()
 acc = torch.zeros((H, W, 4), dtype=torch.float32, device='cuda')
+PRODUCTION = len(sys.argv) > 1 and sys.argv[1] == 'production'
 for K in (1, 20):
     scene.counters_reset()
-    ps = [bm.FrameParams(W, H, spp=1, sample_base=100 + i, max_bounces=3, flags=bm.BM_FLAG_COUNTERS) for i in range(K)]
+    ps = [bm.FrameParams(W, H, spp=1, sample_base=100 + i, max_bounces=3, flags=0 if PRODUCTION else bm.BM_FLAG_COUNTERS) for i in range(K)]
     if K == 1: scene.render(cam, ps[0], acc)
     else: scene.render_frames(cam, ps, acc)
     torch.cuda.synchronize()

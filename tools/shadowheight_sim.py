@@ -1,6 +1,7 @@
 """CPU estimate of what shadow heights (csrc/shadowheight.h) save the shadow rays of a scene, in the manner of tools/sunfield_sim.py: the
 oracle renders the frame and reports every ray, and every SHADOW ray is replayed stop by stop on the sun plane (what the kernel does
 today), once as it is and once with the rule: a ray whose start cell is below its column's dark height ends at set-up, with no stop at all.
+The last lines say, per path segment, how many shadow rays the rule ends: what the test in the shade block (shadow_origin) never draws.
 tools/sim/sunfield_plane.cpp and tools/sim/shadowheight_slice.cpp build the plane and the dark heights with the functions of the rule
 headers themselves.  Every ray the rule ends must be occluded in the reference's own trace, or the run fails.
 usage: python tools/shadowheight_sim.py [grid_size] [width] [height]   (default: bench config 2's world and camera at 160 x 90, 1 spp, 4 segments)
@@ -43,7 +44,16 @@ for sc in range(world.nsc):
 
 rays = []
 PROBE = C.CFUNCTYPE(None, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
-probe = PROBE(lambda pixel, sample, kind, o, d: rays.append((kind, o[0], o[1], o[2], d[0], d[1], d[2])))
+segment = {}  # (pixel, sample) -> extend rays of the path so far: a shadow ray belongs to segment count - 1
+
+
+def on_ray(pixel, sample, kind, o, d):
+    if kind == 0:
+        segment[(pixel, sample)] = segment.get((pixel, sample), 0) + 1
+    rays.append((kind, o[0], o[1], o[2], d[0], d[1], d[2], segment.get((pixel, sample), 1) - 1))
+
+
+probe = PROBE(on_ray)
 L.orc_set_ray_probe.argtypes, L.orc_set_ray_probe.restype = [PROBE], None
 L.orc_set_ray_probe(probe)
 world.render(oracle.make_camera((G / 2, G / 8, 0.8 * G), oracle.camera_direction(0.8, -0.5)), oracle.make_frame(W, H, spp=1, max_bounces=3), want_dbg=False)
@@ -109,6 +119,8 @@ def replay(o, d, loads):
 
 
 before, after = np.zeros(3), np.zeros(3)
+SEGMENTS = 4
+drawn_by_segment, ended_by_segment = np.zeros(SEGMENTS, int), np.zeros(SEGMENTS, int)
 n = skipped = hits = ended = ended_hits = 0
 campos = [int(v / 8) for v in (G / 2, G / 8, 0.8 * G)]
 for r in rays:
@@ -123,8 +135,11 @@ for r in rays:
     hits += hit
     before += kinds
     c = [int(v) for v in o]
+    seg = min(int(r[7]), SEGMENTS - 1)
+    drawn_by_segment[seg] += 1
     if c[2] < zd[c[1], c[0]]:
         ended += 1
+        ended_by_segment[seg] += 1
         ended_hits += hit
         assert hit, f"the rule ends a ray that reaches the sun: origin {r[1:4]}, direction {r[4:7]}"
     else:
@@ -134,3 +149,10 @@ print(f"ended at set-up: {ended} rays = {100 * ended / n:.1f} % of the shadow ra
 for k, v in (("sun plane", before), ("sun plane + shadow heights", after)):
     print(f"  {k:27s}: {v[0] / n:5.2f} single moves + {v[1] / n:5.2f} jumps + {v[2] / n:5.2f} candidates = {v.sum() / n:5.2f} stops per shadow ray")
 print(f"stops removed: {100 * (1 - after.sum() / before.sum()):.1f} %; candidates removed: {100 * (1 - after[2] / before[2]):.1f} %")
+# what ending these rays where they are DRAWN (the shade block, csrc/shadowheight.h shadow_origin) takes out of the scheduler: each is one ray set-up, one
+# ST_CONN wait and one visit of a second shade pass; a ray of the path's last segment lets its lane start the next path in the same pass, any other
+# lets it set up its bounce ray one pass earlier.  (Which of them an idle lane would have taken is the scheduler's business: tools/ring_stats.py counts
+# connect lanes on the GPU.)
+print(f"never drawn with the test in the shade block: {ended} of {n} shadow rays = {100 * ended / max(total, 1):.1f} % of all {total} rays")
+for k in range(SEGMENTS):
+    print(f"  segment {k}: {ended_by_segment[k]:6d} of {drawn_by_segment[k]:6d} shadow rays" + ("   (the path ends in the shade pass)" if k == SEGMENTS - 1 else "   (the bounce ray is set up one pass earlier)"))
