@@ -204,7 +204,7 @@ int bm_camera_pixel_rays(const bm_camera* camera, int width, int height, int64_t
 
 int bm_camera_pixel_rays_device(bm_scene* scene, const bm_camera* camera, int width, int height, bm_ray* rays_dev, void* hip_stream) {
 	BM_NEED(scene);
-	return scene->impl.pixel_rays(camera, width, height, rays_dev, static_cast<hipStream_t>(hip_stream));
+	return bm::pixel_rays(scene->impl.gpu(), camera, width, height, rays_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 // (bm_host_denoise is csrc/denoise_host.cpp: host code that needs nothing of the library)
@@ -217,14 +217,14 @@ int bm_denoise_workspace_bytes(int width, int height, size_t* bytes) {
 int bm_denoise(bm_scene* scene, const bm_denoise_params* params, const float* accum_dev, const bm_ray_hit* hits_dev, float* out_dev, void* workspace_dev,
 			   size_t workspace_bytes, void* hip_stream) {
 	BM_NEED(scene);
-	return scene->impl.denoise(params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+	return bm::denoise(scene->impl.gpu(), params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
 }
 
 int bm_debug_denoise_times(bm_scene* scene, const bm_denoise_params* params, const float* accum_dev, const bm_ray_hit* hits_dev, float* out_dev,
 						   void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms) {
 	BM_NEED(scene);
 	if (!kernel_ms) { set_error("bm_debug_denoise_times: null argument"); return BM_EINVAL; }
-	return scene->impl.denoise(params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+	return bm::denoise(scene->impl.gpu(), params, accum_dev, hits_dev, out_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
 }
 
 // (bm_host_voxelize is csrc/voxelize_host.cpp: host code that needs nothing of the library)
@@ -232,24 +232,21 @@ int bm_voxelize_workspace_bytes(const bm_voxelize_params* params, int64_t n, siz
 	if (!params || !bytes) { set_error("bm_voxelize_workspace_bytes: null argument"); return BM_EINVAL; }
 	const bm::VxParamsView pv = bm::voxelize_params_view(*params);
 	if (const char* why = bm::voxelize_params_problem(pv, n)) { set_error(std::string("bm_voxelize_workspace_bytes: ") + why); return BM_EINVAL; }
-	bm::VoxelizeDims d = {};
-	for (int k = 0; k < 3; ++k) d.extent[k] = pv.extent[k];
-	d.words = bm::voxelize_row_words(pv.extent[0]);
-	*bytes = bm::voxelize_workspace_bytes(d, static_cast<uint32_t>(n));
+	*bytes = bm::voxelize_workspace_bytes(bm::voxelize_dims(pv), static_cast<uint32_t>(n));
 	return 0;
 }
 
 int bm_voxelize(bm_scene* scene, const bm_voxelize_params* params, int64_t n, const float* triangles_dev, uint8_t* volume_dev, bm_voxelize_result* result_dev,
 				void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
 	BM_NEED(scene);
-	return scene->impl.voxelize(params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+	return bm::voxelize(scene->impl.gpu(), params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
 }
 
 int bm_debug_voxelize_times(bm_scene* scene, const bm_voxelize_params* params, int64_t n, const float* triangles_dev, uint8_t* volume_dev,
 							bm_voxelize_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms) {
 	BM_NEED(scene);
 	if (!kernel_ms) { set_error("bm_debug_voxelize_times: null argument"); return BM_EINVAL; }
-	return scene->impl.voxelize(params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+	return bm::voxelize(scene->impl.gpu(), params, n, triangles_dev, volume_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
 }
 
 // (bm_host_mesh_quads and bm_host_mesh_triangles are csrc/mesh_host.cpp: host code that needs nothing of the library)
@@ -264,19 +261,19 @@ int bm_mesh_workspace_bytes(const bm_mesh_params* params, size_t* bytes) {
 int bm_mesh_quads(bm_scene* scene, const bm_mesh_params* params, const uint8_t* volume_dev, bm_quad* quads_dev, uint64_t capacity, bm_mesh_result* result_dev,
 				  void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
 	BM_NEED(scene);
-	return scene->impl.mesh_quads(params, volume_dev, quads_dev, capacity, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+	return bm::mesh_quads(scene->impl.gpu(), params, volume_dev, quads_dev, capacity, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
 }
 
 int bm_debug_mesh_times(bm_scene* scene, const bm_mesh_params* params, const uint8_t* volume_dev, bm_quad* quads_dev, uint64_t capacity, bm_mesh_result* result_dev,
 						void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms) {
 	BM_NEED(scene);
 	if (!kernel_ms) { set_error("bm_debug_mesh_times: null argument"); return BM_EINVAL; }
-	return scene->impl.mesh_quads(params, volume_dev, quads_dev, capacity, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+	return bm::mesh_quads(scene->impl.gpu(), params, volume_dev, quads_dev, capacity, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
 }
 
 int bm_mesh_triangles(bm_scene* scene, const bm_quad* quads_dev, int64_t n, float* triangles_dev, void* hip_stream) {
 	BM_NEED(scene);
-	return scene->impl.mesh_triangles(quads_dev, n, triangles_dev, static_cast<hipStream_t>(hip_stream));
+	return bm::mesh_triangles(scene->impl.gpu(), quads_dev, n, triangles_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)
@@ -289,7 +286,7 @@ int bm_history_bytes(int width, int height, size_t* bytes) {
 int bm_reproject(bm_scene* scene, const bm_reproject_params* params, const bm_camera* camera, const bm_camera* camera_prev, const float* accum_dev,
 				 const bm_ray_hit* hits_dev, const void* history_prev_dev, void* history_out_dev, void* hip_stream) {
 	BM_NEED(scene);
-	return scene->impl.reproject(params, camera, camera_prev, accum_dev, hits_dev, history_prev_dev, history_out_dev, static_cast<hipStream_t>(hip_stream));
+	return bm::reproject(scene->impl.gpu(), params, camera, camera_prev, accum_dev, hits_dev, history_prev_dev, history_out_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 int bm_scene_column_heights(bm_scene* scene, int sx, int sy, float* heights) {
@@ -549,7 +546,7 @@ int bm_tuning_overrides(char* buf, size_t buflen) {
 }
 int bm_resolve(bm_scene* scene, const float* accum_dev, float* out_dev, int64_t n_pixels, void* hip_stream) {
 	BM_NEED(scene);
-	return scene->impl.resolve(accum_dev, out_dev, n_pixels, static_cast<hipStream_t>(hip_stream));
+	return bm::resolve(scene->impl.gpu(), accum_dev, out_dev, n_pixels, static_cast<hipStream_t>(hip_stream));
 }
 int bm_synchronize(bm_scene* scene) { BM_NEED(scene); return scene->impl.synchronize(); }
 int bm_last_render_ms(bm_scene* scene, float* ms) { BM_NEED(scene); return scene->impl.last_render_ms(ms); }

@@ -1,0 +1,193 @@
+// device_ops.cpp -- the stateless device operators (device_ops.h): what each refuses about its parameters and the caller's buffers, then its launch.
+#include "device_ops.h"
+
+#include <cstdlib>
+#include <string>
+
+#include "buffer_checks.h"
+#include "camera_rays.h"
+#include "denoise.h"
+#include "error.h"
+#include "hip_owned.h"
+#include "kernels.h"
+#include "mesh.h"
+#include "voxelize.h"
+
+namespace bm {
+
+bool device_span_ok(int device, const void* p, size_t bytes) {
+	hipPointerAttribute_t attr{};
+	void* base = nullptr;
+	size_t size = 0;
+	if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device ||
+		hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, const_cast<void*>(p)) != hipSuccess ||
+		static_cast<const uint8_t*>(base) + size < static_cast<const uint8_t*>(p) + bytes) {
+		(void)hipGetLastError();
+		return false;
+	}
+	return true;
+}
+
+int resolve(const Gpu& gpu, const float* accum, float* out, long long n, hipStream_t stream) {
+	if (!accum || !out || n < 0) { set_error("bad argument"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(gpu.device));
+	launch_resolve(accum, out, n, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- the a-trous filter (bm_denoise): image passes on the caller's stream over the caller's buffers; nothing of the world is read
+int denoise(const Gpu& gpu, const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out, void* workspace, size_t workspace_bytes,
+			hipStream_t stream, float* kernel_ms) {
+	if (!params || !accum || !hits || !out || !workspace) { set_error("bm_denoise: null argument"); return BM_EINVAL; }
+	const DenoiseParamsView pv = {params->width, params->height, params->iterations, params->sigma_l, params->flags, params->reserved};
+	if (const char* why = denoise_params_problem(pv)) { set_error(std::string("bm_denoise: ") + why); return BM_EINVAL; }
+	const size_t need = denoise_workspace_bytes(params->width, params->height);
+	if (workspace_bytes < need) { set_error("bm_denoise: the workspace is smaller than bm_denoise_workspace_bytes"); return BM_EINVAL; }
+	if (!all_aligned(16, accum, hits, out, workspace)) { set_error("bm_denoise: buffers must be 16-byte aligned"); return BM_EINVAL; }
+	const size_t image = need / 36 * 16;
+	const Span ws = span_of(workspace, need);
+	if (spans_overlap(span_of(accum, image), ws) || spans_overlap(span_of(out, image), ws) || spans_overlap(span_of(hits, 2 * image), ws)) {
+		set_error("bm_denoise: the workspace overlaps an image");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(gpu.device));
+	static const int tiled_max_step = [] { // experiment knob: the largest a-trous stride that stages its taps in LDS (0, 1, 2)
+		const char* e = std::getenv("BM_DENOISE_TILED_MAX");
+		return e && *e ? std::atoi(e) : kDenoiseTiledMaxStep;
+	}();
+	// without a pass there is one kernel; the 2 + iterations durations the caller reads are defined all the same
+	const int stages = params->iterations == 0 ? 1 : 2 + params->iterations;
+	if (kernel_ms)
+		for (int i = 0; i < 2 + params->iterations; ++i) kernel_ms[i] = 0.f;
+	return launch_staged<3 + kDenoiseMaxIterations>(stages, kernel_ms, [&](hipEvent_t* marks) {
+		launch_denoise(params->width, params->height, params->iterations, params->sigma_l, accum, hits, out, workspace, tiled_max_step, stream, marks);
+	});
+}
+
+// ---- meshes -> voxels (bm_voxelize): kernels on the caller's stream over the caller's buffers; nothing of the world is read
+int voxelize(const Gpu& gpu, const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result, void* workspace,
+			 size_t workspace_bytes, hipStream_t stream, float* kernel_ms) {
+	if (!params) { set_error("bm_voxelize: null params"); return BM_EINVAL; }
+	const VxParamsView pv = voxelize_params_view(*params);
+	if (const char* why = voxelize_params_problem(pv, n)) { set_error(std::string("bm_voxelize: ") + why); return BM_EINVAL; }
+	if (!volume || !workspace || (n > 0 && !triangles)) { set_error("bm_voxelize: null buffer"); return BM_EINVAL; }
+	const VoxelizeDims d = voxelize_dims(pv);
+	const size_t need = voxelize_workspace_bytes(d, static_cast<uint32_t>(n));
+	if (workspace_bytes < need) { set_error("bm_voxelize: the workspace is smaller than bm_voxelize_workspace_bytes"); return BM_EINVAL; }
+	if (!aligned(triangles, 4) || !aligned(result, 8) || !aligned(workspace, 16)) {
+		set_error("bm_voxelize: triangles must be 4-byte, the result 8-byte and the workspace 16-byte aligned");
+		return BM_EINVAL;
+	}
+	const size_t span = static_cast<size_t>(pv.extent[2] - 1) * static_cast<size_t>(d.slice_pitch) + static_cast<size_t>(pv.extent[1] - 1) * static_cast<size_t>(d.row_pitch) +
+						static_cast<size_t>(pv.extent[0]);
+	const size_t tri_bytes = static_cast<size_t>(n) * 9 * sizeof(float);
+	const Span ws = span_of(workspace, need);
+	if (spans_overlap(span_of(volume, span), ws) || spans_overlap(span_of(triangles, tri_bytes), ws) || (result && spans_overlap(span_of(result, sizeof(bm_voxelize_result)), ws))) {
+		set_error("bm_voxelize: the workspace overlaps the volume, the triangles or the result");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, volume, span) || !device_span_ok(gpu.device, workspace, need) || (n > 0 && !device_span_ok(gpu.device, triangles, tri_bytes)) ||
+		(result && !device_span_ok(gpu.device, result, sizeof(bm_voxelize_result)))) {
+		set_error("bm_voxelize: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	static const int per_cu[2] = {voxelize_blocks_per_cu(false), voxelize_blocks_per_cu(true)};
+	const int resident[2] = {per_cu[0] * gpu.compute_units, per_cu[1] * gpu.compute_units};
+	return launch_staged<6>(5, kernel_ms, [&](hipEvent_t* marks) {
+		launch_voxelize(d, triangles, static_cast<uint32_t>(n), volume, result, workspace, resident, stream, marks);
+	});
+}
+
+// ---- voxels -> quads (bm_mesh_quads, bm_mesh_triangles): kernels on the caller's stream over the caller's buffers; nothing of the world is read
+int mesh_quads(const Gpu& gpu, const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result, void* workspace,
+			   size_t workspace_bytes, hipStream_t stream, float* kernel_ms) {
+	if (!params) { set_error("bm_mesh_quads: null params"); return BM_EINVAL; }
+	const MeshParamsView pv = mesh_params_view(*params);
+	if (const char* why = mesh_params_problem(pv)) { set_error(std::string("bm_mesh_quads: ") + why); return BM_EINVAL; }
+	if (!volume || !result || !workspace) { set_error("bm_mesh_quads: null volume, result or workspace"); return BM_EINVAL; }
+	if (!quads && capacity > 0) { set_error("bm_mesh_quads: null quads with a capacity above 0"); return BM_EINVAL; }
+	if (capacity > (uint64_t{1} << 40)) { set_error("bm_mesh_quads: a capacity above 2^40"); return BM_EINVAL; }
+	const MeshDims d = mesh_dims(pv);
+	const size_t need = mesh_workspace_bytes(d);
+	if (workspace_bytes < need) { set_error("bm_mesh_quads: the workspace is smaller than bm_mesh_workspace_bytes"); return BM_EINVAL; }
+	if (!aligned(quads, 4) || !aligned(result, 8) || !aligned(workspace, 16)) {
+		set_error("bm_mesh_quads: quads must be 4-byte, the result 8-byte and the workspace 16-byte aligned");
+		return BM_EINVAL;
+	}
+	const size_t span = static_cast<size_t>(mesh_span(d));
+	const size_t quad_bytes = quads ? static_cast<size_t>(capacity) * sizeof(bm_quad) : 0;
+	const Span ws = span_of(workspace, need);
+	if (spans_overlap(span_of(volume, span), ws) || spans_overlap(span_of(quads, quad_bytes), ws) || spans_overlap(span_of(result, sizeof(bm_mesh_result)), ws)) {
+		set_error("bm_mesh_quads: the workspace overlaps the volume, the quads or the result");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, volume, span) || !device_span_ok(gpu.device, workspace, need) || (quad_bytes > 0 && !device_span_ok(gpu.device, quads, quad_bytes)) ||
+		!device_span_ok(gpu.device, result, sizeof(bm_mesh_result))) {
+		set_error("bm_mesh_quads: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	return launch_staged<4>(3, kernel_ms, [&](hipEvent_t* marks) { launch_mesh_quads(d, volume, quads, quads ? capacity : 0, result, workspace, stream, marks); });
+}
+
+int mesh_triangles(const Gpu& gpu, const bm_quad* quads, int64_t n, float* triangles, hipStream_t stream) {
+	if (n < 0 || n > (int64_t{1} << 32)) { set_error("bm_mesh_triangles: a quad count below 0 or above 2^32"); return BM_EINVAL; }
+	if (n == 0) return 0;
+	if (!quads || !triangles) { set_error("bm_mesh_triangles: null buffer"); return BM_EINVAL; }
+	if (!aligned(quads, 4) || !aligned(triangles, 4)) { set_error("bm_mesh_triangles: quads and triangles must be 4-byte aligned"); return BM_EINVAL; }
+	const size_t quad_bytes = static_cast<size_t>(n) * sizeof(bm_quad), tri_bytes = static_cast<size_t>(n) * 18 * sizeof(float);
+	if (spans_overlap(span_of(quads, quad_bytes), span_of(triangles, tri_bytes))) { set_error("bm_mesh_triangles: the triangles overlap the quads"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, quads, quad_bytes) || !device_span_ok(gpu.device, triangles, tri_bytes)) {
+		set_error("bm_mesh_triangles: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	launch_mesh_triangles(quads, static_cast<uint64_t>(n), triangles, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+int pixel_rays(const Gpu& gpu, const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream) {
+	if (!cam || !rays || width < 1 || height < 1 || width > 65535 || height > 65535 || !aligned(rays, 16)) {
+		set_error("bm_camera_pixel_rays_device: bad argument (null, a size outside 1 ... 65535, or rays not 16-byte aligned)");
+		return BM_EINVAL;
+	}
+	const CameraBasis basis = camera_basis(cam->position, cam->direction, cam->up, width, height); // the frames' basis, as bm_camera_pixel_rays takes it
+	PixelRayBasis b;
+	for (int k = 0; k < 3; ++k) { b.right[k] = basis.right[k]; b.up[k] = basis.up[k]; b.dir[k] = basis.dir[k]; b.origin[k] = basis.origin[k]; }
+	b.width = width; b.height = height;
+	BM_HIP(hipSetDevice(gpu.device));
+	launch_pixel_rays(b, rays, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- temporal accumulation (bm_reproject): like the filter, nothing of the world is read and nothing is kept
+int reproject(const Gpu& gpu, const bm_reproject_params* params, const bm_camera* cam, const bm_camera* cam_prev, const float* accum, const bm_ray_hit* hits,
+			  const void* history_prev, void* history_out, hipStream_t stream) {
+	if (!params || !cam || !accum || !hits || !history_out) { set_error("bm_reproject: null argument"); return BM_EINVAL; }
+	if (history_prev && !cam_prev) { set_error("bm_reproject: a previous history needs the camera it was made with"); return BM_EINVAL; }
+	const ReprojectParamsView pv = {params->width, params->height, params->max_history, params->flags, params->reserved};
+	if (const char* why = reproject_params_problem(pv)) { set_error(std::string("bm_reproject: ") + why); return BM_EINVAL; }
+	if (!all_aligned(16, accum, hits, history_prev, history_out)) { set_error("bm_reproject: buffers must be 16-byte aligned"); return BM_EINVAL; }
+	const size_t history = history_bytes(params->width, params->height), image = history / 20 * 16;
+	const Span written = span_of(history_out, history);
+	if ((history_prev && spans_overlap(span_of(history_prev, history), written)) || spans_overlap(span_of(accum, image), written) || spans_overlap(span_of(hits, 2 * image), written)) {
+		set_error("bm_reproject: history_out overlaps an input (taps read neighbours: ping-pong two histories)");
+		return BM_EINVAL;
+	}
+	ReprojectCameras cams;
+	cams.cur = camera_basis(cam->position, cam->direction, cam->up, params->width, params->height);
+	// (without a history the previous camera is not read; the current one stands in so that the argument holds defined values)
+	const bm_camera* before = history_prev ? cam_prev : cam;
+	cams.prev = reproject_prev_camera(camera_basis(before->position, before->direction, before->up, params->width, params->height));
+	cams.width = params->width; cams.height = params->height;
+	BM_HIP(hipSetDevice(gpu.device));
+	launch_reproject(cams, params->max_history, accum, hits, history_prev, history_out, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+} // namespace bm

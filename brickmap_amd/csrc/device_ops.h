@@ -1,0 +1,41 @@
+// device_ops.h -- the device operators that keep no state: kernels on the caller's stream over the caller's buffers, which read nothing
+// of a scene's world.  A scene only names the GPU they run on (Scene::gpu()); calls on different streams are independent.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/brickmap.h"
+
+namespace bm {
+
+struct Gpu {
+	int device;
+	int compute_units;
+};
+
+// [p, p + bytes) lies inside one allocation of `device` (which is current)
+bool device_span_ok(int device, const void* p, size_t bytes);
+
+int resolve(const Gpu& gpu, const float* accum, float* out, long long n, hipStream_t stream);
+// the a-trous filter (denoise.hip): the workspace is the caller's
+// kernel_ms: null, or 2 + iterations durations -- prepare, moments, every pass (the call then waits; bm_debug_denoise_times)
+int denoise(const Gpu& gpu, const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out, void* workspace, size_t workspace_bytes,
+			hipStream_t stream, float* kernel_ms = nullptr);
+// meshes -> voxels (voxelize.hip): like the filter, the buffers and the workspace are the caller's
+// kernel_ms: null, or 5 durations -- zeroing, plan + scan, surface, solid, the dense pass (the call then waits; bm_debug_voxelize_times)
+int voxelize(const Gpu& gpu, const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result, void* workspace,
+			 size_t workspace_bytes, hipStream_t stream, float* kernel_ms = nullptr);
+// voxels -> quads (mesh.hip): like voxelize, the buffers and the workspace are the caller's
+// kernel_ms: null, or 3 durations -- count, scan, emit (the call then waits; bm_debug_mesh_times)
+int mesh_quads(const Gpu& gpu, const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result, void* workspace,
+			   size_t workspace_bytes, hipStream_t stream, float* kernel_ms = nullptr);
+int mesh_triangles(const Gpu& gpu, const bm_quad* quads, int64_t n, float* triangles, hipStream_t stream);
+// pixel-centre rays of a frame, written on the device (denoise.hip)
+int pixel_rays(const Gpu& gpu, const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
+// temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers
+int reproject(const Gpu& gpu, const bm_reproject_params* params, const bm_camera* cam, const bm_camera* cam_prev, const float* accum, const bm_ray_hit* hits,
+			  const void* history_prev, void* history_out, hipStream_t stream);
+
+} // namespace bm

@@ -1,4 +1,4 @@
-// hip_owned.h -- move-only owners of HIP resources: device memory, pinned host memory, an event, a stream.  Each frees what it holds
+// hip_owned.h -- move-only owners of HIP resources: device memory, pinned host memory, an event, the events around a launch's stages, a stream.  Each frees what it holds
 // in its destructor (on whatever device is current: the owner's destructor body selects it) and allocates through a method that
 // returns the project's int error.  A default-constructed owner holds nothing, so an object whose init() failed halfway destructs cleanly.
 // None of them synchronises: a buffer that work in flight may still use is waited for by the caller before reserve() / alloc().
@@ -69,6 +69,47 @@ public:
 private:
 	hipEvent_t e_ = nullptr;
 };
+
+// N timing events around the stages of one launch: what the launch_* functions of kernels.h take as `marks` -- mark i is recorded before
+// stage i, mark `stages` behind the last one
+template <int N>
+class StageMarks {
+public:
+	int create(int count = N) { // the first `count` events, made on first use
+		for (int i = 0; i < count; ++i) {
+			if (int e = ev_[i].create(hipEventDefault)) return e;
+			raw_[i] = ev_[i];
+		}
+		return 0;
+	}
+	hipEvent_t* marks() { return raw_; }
+	// waits for mark `stages`, then ms[i] = the time from mark i to mark i + 1
+	int read(int stages, float* ms) const {
+		BM_HIP(hipEventSynchronize(raw_[stages]));
+		for (int i = 0; i < stages; ++i) BM_HIP(hipEventElapsedTime(&ms[i], raw_[i], raw_[i + 1]));
+		return 0;
+	}
+
+private:
+	Event ev_[N];
+	hipEvent_t raw_[N] = {};
+};
+
+// a launch of `stages` (< N) stages, as launch(marks) issues it.  kernel_ms null: launched without marks.  Otherwise the call waits for
+// the launch and kernel_ms[0 ... stages) are the stages' durations
+template <int N, class Launch>
+int launch_staged(int stages, float* kernel_ms, Launch&& launch) {
+	if (!kernel_ms) {
+		launch(nullptr);
+		BM_HIP(hipGetLastError());
+		return 0;
+	}
+	StageMarks<N> marks;
+	if (int e = marks.create(stages + 1)) return e;
+	launch(marks.marks());
+	BM_HIP(hipGetLastError());
+	return marks.read(stages, kernel_ms);
+}
 
 class Stream {
 public:

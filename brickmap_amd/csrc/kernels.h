@@ -143,16 +143,11 @@ size_t label_tmp_bytes(uint32_t voxels);
 void launch_label_components(const uint32_t* labels, void* comps, uint64_t capacity, const LabelDims& d, uint64_t* tmp, hipStream_t stream);
 void launch_label_mask(const uint32_t* labels, uint32_t voxels, const void* comps, uint64_t records, const uint8_t* chosen, uint8_t* mask, hipStream_t stream);
 
-// meshes -> voxels (voxelize.hip; voxelize.h has the rules): n triangles of 9 floats fill the volume V[z][y][x] of extent voxels at the
+// meshes -> voxels (voxelize.hip; voxelize.h has the rules and VoxelizeDims): n triangles of 9 floats fill the volume V[z][y][x] of extent voxels at the
 // given pitches.  workspace: voxelize_workspace_bytes() bytes, 16-byte aligned, that no other launch uses until this one has finished
 // (zeroed here); result: null, or the 16 bytes of a bm_voxelize_result.  resident_blocks: the grids of the surface and the solid items.
 // marks: null, or 6 events around zeroing, plan + scan, surface, solid and the dense pass.
-struct VoxelizeDims {
-	int32_t lo[3], extent[3];
-	uint32_t words; // voxelize_row_words(extent[0])
-	uint32_t mode, keep;
-	int64_t row_pitch, slice_pitch; // resolved: never 0
-};
+struct VoxelizeDims;
 size_t voxelize_workspace_bytes(const VoxelizeDims& d, uint32_t n);
 int voxelize_blocks_per_cu(bool solid);
 void launch_voxelize(const VoxelizeDims& d, const float* triangles, uint32_t n, uint8_t* volume, void* result, void* workspace, const int resident_blocks[2],

@@ -14,13 +14,10 @@
 #include <thread>
 #include <unordered_map>
 
-#include "camera_rays.h"
-#include "denoise.h"
-#include "voxelize.h"
+#include "buffer_checks.h"
 #include "escape.h"
 #include "kernels.h"
 #include "label.h"
-#include "mesh.h"
 
 namespace bm {
 
@@ -455,7 +452,7 @@ int Scene::load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream
 	if (static_cast<uint64_t>(d.supercells) * kCellsPerSupercell >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
 	if (where == BM_VOXELS_DEVICE) { // the kernels read [voxels, voxels + bytes): it has to be memory of this device, all of it
-		if (!device_span_ok(voxels, bytes)) {
+		if (!device_span_ok(device_, voxels, bytes)) {
 			set_error("bm_scene_load_voxels: BM_VOXELS_DEVICE needs `bytes` bytes of memory of the scene's device");
 			return BM_EINVAL;
 		}
@@ -475,20 +472,6 @@ int Scene::load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream
 		world.generated = false;
 	}
 	return e;
-}
-
-// [p, p + bytes) lies inside one allocation of this scene's device
-bool Scene::device_span_ok(const uint8_t* p, size_t bytes) const {
-	hipPointerAttribute_t attr{};
-	void* base = nullptr;
-	size_t size = 0;
-	if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device_ ||
-		hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, const_cast<uint8_t*>(p)) != hipSuccess ||
-		static_cast<const uint8_t*>(base) + size < p + bytes) {
-		(void)hipGetLastError();
-		return false;
-	}
-	return true;
 }
 
 int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
@@ -1112,7 +1095,7 @@ int Scene::check_region(const char* who, const bm_region* region, const void* vo
 	if (!on_device_) { set_error(at + "scene not generated"); return BM_ESTATE; }
 	if (int e = require_not_failed()) return e;
 	BM_HIP(hipSetDevice(device_));
-	if (where == BM_VOXELS_DEVICE && *span > 0 && !device_span_ok(static_cast<const uint8_t*>(voxels), *span)) {
+	if (where == BM_VOXELS_DEVICE && *span > 0 && !device_span_ok(device_, voxels, *span)) {
 		set_error(at + "BM_VOXELS_DEVICE needs the volume's whole span inside one allocation of the scene's device");
 		return BM_EINVAL;
 	}
@@ -1343,7 +1326,7 @@ int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags
 	if (flags != 0) { set_error("bm_scene_label_region: unknown flags (must be 0)"); return BM_EINVAL; }
 	if (int e = check_label_box(who, lo, hi, &ld, &empty)) return e;
 	if (!count || (!empty && !labels)) { set_error("bm_scene_label_region: null label volume or count"); return BM_EINVAL; }
-	if (reinterpret_cast<uintptr_t>(count) % 8 != 0 || (!empty && reinterpret_cast<uintptr_t>(labels) % 4 != 0)) {
+	if (!aligned(count, 8) || (!empty && !aligned(labels, 4))) {
 		set_error("bm_scene_label_region: labels must be 4-byte aligned, count 8-byte aligned");
 		return BM_EINVAL;
 	}
@@ -1351,15 +1334,15 @@ int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags
 	if (int e = require_not_failed()) return e;
 	BM_HIP(hipSetDevice(device_));
 	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
-	if (!device_span_ok(reinterpret_cast<const uint8_t*>(count), sizeof(uint64_t)) ||
-		(!empty && !device_span_ok(reinterpret_cast<const uint8_t*>(labels), voxels * sizeof(int32_t)))) {
+	if (!device_span_ok(device_, count, sizeof(uint64_t)) ||
+		(!empty && !device_span_ok(device_, labels, voxels * sizeof(int32_t)))) {
 		set_error("bm_scene_label_region: the label volume's whole span and the count must lie inside one allocation each of the scene's device");
 		return BM_EINVAL;
 	}
 	const bool inside = !empty && label_clip(world.dims, lo, hi, &ld);
 	size_t n = 0, o_bricks = 0, bytes = 0;
 	if (int e = stage_absent_bricks(inside, ld.lo, ld.hi, &n, &o_bricks, &bytes)) return e;
-	for (Event& ev : ev_label_time_) if (int e = ev.create()) return e;
+	if (int e = label_marks_.create()) return e;
 	DeviceScene view;
 	if (int e = begin_frame(stream, &view, nullptr)) return e;
 	if (int e = label_turn(stream)) return e;
@@ -1373,9 +1356,8 @@ int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags
 		});
 		if (inside) {
 			if (n > 0) BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));
-			hipEvent_t marks[4] = {ev_label_time_[0], ev_label_time_[1], ev_label_time_[2], ev_label_time_[3]};
 			launch_label_region(view, reinterpret_cast<uint32_t*>(labels), count, ld, reinterpret_cast<const int*>(d_patch_.get()),
-								reinterpret_cast<const uint32_t*>(d_patch_.get() + o_bricks), static_cast<uint32_t>(n), stream, marks);
+								reinterpret_cast<const uint32_t*>(d_patch_.get() + o_bricks), static_cast<uint32_t>(n), stream, label_marks_.marks());
 			label_timed_ = true;
 			if (n > 0) {
 				BM_HIP(hipEventRecord(ev_region_read_, stream));
@@ -1394,10 +1376,9 @@ int Scene::last_label_ms(float* local_ms, float* merge_ms, float* flatten_ms) {
 	if (!local_ms || !merge_ms || !flatten_ms) { set_error("null argument"); return BM_EINVAL; }
 	if (!label_timed_) { set_error("the last bm_scene_label_region launched nothing, or there was none"); return BM_ESTATE; }
 	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipEventSynchronize(ev_label_time_[3]));
-	BM_HIP(hipEventElapsedTime(local_ms, ev_label_time_[0], ev_label_time_[1]));
-	BM_HIP(hipEventElapsedTime(merge_ms, ev_label_time_[1], ev_label_time_[2]));
-	BM_HIP(hipEventElapsedTime(flatten_ms, ev_label_time_[2], ev_label_time_[3]));
+	float ms[3];
+	if (int e = label_marks_.read(3, ms)) return e;
+	*local_ms = ms[0]; *merge_ms = ms[1]; *flatten_ms = ms[2];
 	return 0;
 }
 
@@ -1411,7 +1392,7 @@ int Scene::label_components(const int32_t lo[3], const int32_t hi[3], const int3
 	if (capacity < 0) { set_error("bm_scene_label_components: negative capacity"); return BM_EINVAL; }
 	if (empty || capacity == 0) return 0;
 	if (!labels || !comps) { set_error("bm_scene_label_components: null label volume or table"); return BM_EINVAL; }
-	if (reinterpret_cast<uintptr_t>(labels) % 4 != 0 || reinterpret_cast<uintptr_t>(comps) % 8 != 0) {
+	if (!aligned(labels, 4) || !aligned(comps, 8)) {
 		set_error("bm_scene_label_components: labels must be 4-byte aligned, the table 8-byte aligned");
 		return BM_EINVAL;
 	}
@@ -1420,8 +1401,8 @@ int Scene::label_components(const int32_t lo[3], const int32_t hi[3], const int3
 	BM_HIP(hipSetDevice(device_));
 	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
 	const size_t records = static_cast<size_t>(std::min<int64_t>(capacity, static_cast<int64_t>(voxels))); // (no more components than voxels)
-	if (!device_span_ok(reinterpret_cast<const uint8_t*>(labels), voxels * sizeof(int32_t)) ||
-		!device_span_ok(reinterpret_cast<const uint8_t*>(comps), records * sizeof(bm_component))) {
+	if (!device_span_ok(device_, labels, voxels * sizeof(int32_t)) ||
+		!device_span_ok(device_, comps, records * sizeof(bm_component))) {
 		set_error("bm_scene_label_components: the label volume and min(capacity, voxels) records must lie inside one allocation each of the scene's device");
 		return BM_EINVAL;
 	}
@@ -1448,7 +1429,7 @@ int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* l
 	if (n < 0) { set_error("bm_scene_label_mask: negative record count"); return BM_EINVAL; }
 	if (empty) return 0;
 	if (!labels || !mask || (n > 0 && (!comps || !chosen))) { set_error("bm_scene_label_mask: null buffer"); return BM_EINVAL; }
-	if (reinterpret_cast<uintptr_t>(labels) % 4 != 0 || reinterpret_cast<uintptr_t>(comps) % 8 != 0) {
+	if (!aligned(labels, 4) || !aligned(comps, 8)) {
 		set_error("bm_scene_label_mask: labels must be 4-byte aligned, the table 8-byte aligned");
 		return BM_EINVAL;
 	}
@@ -1456,8 +1437,8 @@ int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* l
 	if (int e = require_not_failed()) return e;
 	BM_HIP(hipSetDevice(device_));
 	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
-	if (!device_span_ok(reinterpret_cast<const uint8_t*>(labels), voxels * sizeof(int32_t)) || !device_span_ok(mask, voxels) ||
-		(n > 0 && (!device_span_ok(reinterpret_cast<const uint8_t*>(comps), static_cast<size_t>(n) * sizeof(bm_component)) || !device_span_ok(chosen, static_cast<size_t>(n))))) {
+	if (!device_span_ok(device_, labels, voxels * sizeof(int32_t)) || !device_span_ok(device_, mask, voxels) ||
+		(n > 0 && (!device_span_ok(device_, comps, static_cast<size_t>(n) * sizeof(bm_component)) || !device_span_ok(device_, chosen, static_cast<size_t>(n))))) {
 		set_error("bm_scene_label_mask: every buffer's whole span must lie inside one allocation of the scene's device");
 		return BM_EINVAL;
 	}
@@ -1759,7 +1740,7 @@ int Scene::query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* 
 	if (n < 0 || n > (int64_t{1} << 24)) { set_error("bm_scene_query_volumes: n must be 0 ... 2^24"); return BM_EINVAL; }
 	if (n == 0) return 0;
 	if (!volumes || !results) { set_error("bm_scene_query_volumes: null volume or result buffer"); return BM_EINVAL; }
-	if (reinterpret_cast<uintptr_t>(volumes) % 4 != 0 || reinterpret_cast<uintptr_t>(results) % 8 != 0) {
+	if (!aligned(volumes, 4) || !aligned(results, 8)) {
 		set_error("bm_scene_query_volumes: volumes must be 4-byte aligned, results 8-byte aligned");
 		return BM_EINVAL;
 	}
@@ -1800,216 +1781,6 @@ int Scene::begin_frame(hipStream_t stream, DeviceScene* view, DeviceCounters** c
 void Scene::end_frame(hipStream_t stream) {
 	other_frames_++;
 	(void)frame_end(stream);
-}
-
-int Scene::resolve(const float* accum, float* out, long long n, hipStream_t stream) {
-	if (!accum || !out || n < 0) { set_error("bad argument"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	launch_resolve(accum, out, n, stream);
-	BM_HIP(hipGetLastError());
-	return 0;
-}
-
-// ---- the a-trous filter (bm_denoise): image passes on the caller's stream over the caller's buffers; nothing of the world is read
-int Scene::denoise(const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream,
-				   float* kernel_ms) {
-	if (!params || !accum || !hits || !out || !workspace) { set_error("bm_denoise: null argument"); return BM_EINVAL; }
-	const DenoiseParamsView pv = {params->width, params->height, params->iterations, params->sigma_l, params->flags, params->reserved};
-	if (const char* why = denoise_params_problem(pv)) { set_error(std::string("bm_denoise: ") + why); return BM_EINVAL; }
-	const size_t need = denoise_workspace_bytes(params->width, params->height);
-	if (workspace_bytes < need) { set_error("bm_denoise: the workspace is smaller than bm_denoise_workspace_bytes"); return BM_EINVAL; }
-	const uintptr_t pa = reinterpret_cast<uintptr_t>(accum), ph = reinterpret_cast<uintptr_t>(hits), po = reinterpret_cast<uintptr_t>(out), pw = reinterpret_cast<uintptr_t>(workspace);
-	if ((pa | ph | po | pw) % 16 != 0) { set_error("bm_denoise: buffers must be 16-byte aligned"); return BM_EINVAL; }
-	const size_t image = need / 36 * 16;
-	auto overlaps_workspace = [&](uintptr_t p, size_t bytes) { return p < pw + need && pw < p + bytes; };
-	if (overlaps_workspace(pa, image) || overlaps_workspace(po, image) || overlaps_workspace(ph, 2 * image)) { set_error("bm_denoise: the workspace overlaps an image"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	static const int tiled_max_step = [] { // experiment knob: the largest a-trous stride that stages its taps in LDS (0, 1, 2)
-		const char* e = std::getenv("BM_DENOISE_TILED_MAX");
-		return e && *e ? std::atoi(e) : kDenoiseTiledMaxStep;
-	}();
-	if (!kernel_ms) {
-		launch_denoise(params->width, params->height, params->iterations, params->sigma_l, accum, hits, out, workspace, tiled_max_step, stream);
-		BM_HIP(hipGetLastError());
-		return 0;
-	}
-	const int kernels = params->iterations == 0 ? 1 : 2 + params->iterations;
-	Event marks[3 + kDenoiseMaxIterations];
-	hipEvent_t raw[3 + kDenoiseMaxIterations];
-	for (int i = 0; i <= kernels; ++i) {
-		if (int e = marks[i].create(hipEventDefault)) return e;
-		raw[i] = marks[i];
-	}
-	launch_denoise(params->width, params->height, params->iterations, params->sigma_l, accum, hits, out, workspace, tiled_max_step, stream, raw);
-	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventSynchronize(raw[kernels]));
-	for (int i = 0; i < 2 + params->iterations; ++i) kernel_ms[i] = 0.f;
-	for (int i = 0; i < kernels; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
-	return 0;
-}
-
-// ---- meshes -> voxels (bm_voxelize): kernels on the caller's stream over the caller's buffers; nothing of the world is read
-int Scene::voxelize(const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result, void* workspace,
-					size_t workspace_bytes, hipStream_t stream, float* kernel_ms) {
-	if (!params) { set_error("bm_voxelize: null params"); return BM_EINVAL; }
-	const VxParamsView pv = voxelize_params_view(*params);
-	if (const char* why = voxelize_params_problem(pv, n)) { set_error(std::string("bm_voxelize: ") + why); return BM_EINVAL; }
-	if (!volume || !workspace || (n > 0 && !triangles)) { set_error("bm_voxelize: null buffer"); return BM_EINVAL; }
-	VoxelizeDims d;
-	for (int k = 0; k < 3; ++k) { d.lo[k] = pv.lo[k]; d.extent[k] = pv.extent[k]; }
-	d.words = voxelize_row_words(pv.extent[0]);
-	d.mode = pv.mode;
-	d.keep = pv.flags & kVxKeep;
-	d.row_pitch = voxelize_row_pitch(pv);
-	d.slice_pitch = voxelize_slice_pitch(pv);
-	const size_t need = voxelize_workspace_bytes(d, static_cast<uint32_t>(n));
-	if (workspace_bytes < need) { set_error("bm_voxelize: the workspace is smaller than bm_voxelize_workspace_bytes"); return BM_EINVAL; }
-	const uintptr_t pt = reinterpret_cast<uintptr_t>(triangles), pv0 = reinterpret_cast<uintptr_t>(volume), pr = reinterpret_cast<uintptr_t>(result),
-					pw = reinterpret_cast<uintptr_t>(workspace);
-	if (pt % 4 != 0 || pr % 8 != 0 || pw % 16 != 0) { set_error("bm_voxelize: triangles must be 4-byte, the result 8-byte and the workspace 16-byte aligned"); return BM_EINVAL; }
-	const size_t span = static_cast<size_t>(pv.extent[2] - 1) * static_cast<size_t>(d.slice_pitch) + static_cast<size_t>(pv.extent[1] - 1) * static_cast<size_t>(d.row_pitch) +
-						static_cast<size_t>(pv.extent[0]);
-	const size_t tri_bytes = static_cast<size_t>(n) * 9 * sizeof(float);
-	auto overlaps_workspace = [&](uintptr_t p, size_t bytes) { return bytes > 0 && p < pw + need && pw < p + bytes; };
-	if (overlaps_workspace(pv0, span) || overlaps_workspace(pt, tri_bytes) || (result && overlaps_workspace(pr, sizeof(bm_voxelize_result)))) {
-		set_error("bm_voxelize: the workspace overlaps the volume, the triangles or the result");
-		return BM_EINVAL;
-	}
-	BM_HIP(hipSetDevice(device_));
-	if (!device_span_ok(volume, span) || !device_span_ok(static_cast<const uint8_t*>(workspace), need) ||
-		(n > 0 && !device_span_ok(reinterpret_cast<const uint8_t*>(triangles), tri_bytes)) ||
-		(result && !device_span_ok(reinterpret_cast<const uint8_t*>(result), sizeof(bm_voxelize_result)))) {
-		set_error("bm_voxelize: a buffer does not lie inside one allocation of the scene's device");
-		return BM_EINVAL;
-	}
-	static const int per_cu[2] = {voxelize_blocks_per_cu(false), voxelize_blocks_per_cu(true)};
-	const int resident[2] = {per_cu[0] * compute_units_, per_cu[1] * compute_units_};
-	if (!kernel_ms) {
-		launch_voxelize(d, triangles, static_cast<uint32_t>(n), volume, result, workspace, resident, stream);
-		BM_HIP(hipGetLastError());
-		return 0;
-	}
-	constexpr int kStages = 5;
-	Event marks[kStages + 1];
-	hipEvent_t raw[kStages + 1];
-	for (int i = 0; i <= kStages; ++i) {
-		if (int e = marks[i].create(hipEventDefault)) return e;
-		raw[i] = marks[i];
-	}
-	launch_voxelize(d, triangles, static_cast<uint32_t>(n), volume, result, workspace, resident, stream, raw);
-	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventSynchronize(raw[kStages]));
-	for (int i = 0; i < kStages; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
-	return 0;
-}
-
-// ---- voxels -> quads (bm_mesh_quads, bm_mesh_triangles): kernels on the caller's stream over the caller's buffers; nothing of the world is read
-int Scene::mesh_quads(const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result, void* workspace,
-					  size_t workspace_bytes, hipStream_t stream, float* kernel_ms) {
-	if (!params) { set_error("bm_mesh_quads: null params"); return BM_EINVAL; }
-	const MeshParamsView pv = mesh_params_view(*params);
-	if (const char* why = mesh_params_problem(pv)) { set_error(std::string("bm_mesh_quads: ") + why); return BM_EINVAL; }
-	if (!volume || !result || !workspace) { set_error("bm_mesh_quads: null volume, result or workspace"); return BM_EINVAL; }
-	if (!quads && capacity > 0) { set_error("bm_mesh_quads: null quads with a capacity above 0"); return BM_EINVAL; }
-	if (capacity > (uint64_t{1} << 40)) { set_error("bm_mesh_quads: a capacity above 2^40"); return BM_EINVAL; }
-	const MeshDims d = mesh_dims(pv);
-	const size_t need = mesh_workspace_bytes(d);
-	if (workspace_bytes < need) { set_error("bm_mesh_quads: the workspace is smaller than bm_mesh_workspace_bytes"); return BM_EINVAL; }
-	const uintptr_t pq = reinterpret_cast<uintptr_t>(quads), pv0 = reinterpret_cast<uintptr_t>(volume), pr = reinterpret_cast<uintptr_t>(result),
-					pw = reinterpret_cast<uintptr_t>(workspace);
-	if (pq % 4 != 0 || pr % 8 != 0 || pw % 16 != 0) { set_error("bm_mesh_quads: quads must be 4-byte, the result 8-byte and the workspace 16-byte aligned"); return BM_EINVAL; }
-	const size_t span = static_cast<size_t>(mesh_span(d));
-	const size_t quad_bytes = quads ? static_cast<size_t>(capacity) * sizeof(bm_quad) : 0;
-	auto overlaps_workspace = [&](uintptr_t p, size_t bytes) { return bytes > 0 && p < pw + need && pw < p + bytes; };
-	if (overlaps_workspace(pv0, span) || overlaps_workspace(pq, quad_bytes) || overlaps_workspace(pr, sizeof(bm_mesh_result))) {
-		set_error("bm_mesh_quads: the workspace overlaps the volume, the quads or the result");
-		return BM_EINVAL;
-	}
-	BM_HIP(hipSetDevice(device_));
-	if (!device_span_ok(volume, span) || !device_span_ok(static_cast<const uint8_t*>(workspace), need) ||
-		(quad_bytes > 0 && !device_span_ok(reinterpret_cast<const uint8_t*>(quads), quad_bytes)) ||
-		!device_span_ok(reinterpret_cast<const uint8_t*>(result), sizeof(bm_mesh_result))) {
-		set_error("bm_mesh_quads: a buffer does not lie inside one allocation of the scene's device");
-		return BM_EINVAL;
-	}
-	if (!kernel_ms) {
-		launch_mesh_quads(d, volume, quads, quads ? capacity : 0, result, workspace, stream);
-		BM_HIP(hipGetLastError());
-		return 0;
-	}
-	constexpr int kStages = 3;
-	Event marks[kStages + 1];
-	hipEvent_t raw[kStages + 1];
-	for (int i = 0; i <= kStages; ++i) {
-		if (int e = marks[i].create(hipEventDefault)) return e;
-		raw[i] = marks[i];
-	}
-	launch_mesh_quads(d, volume, quads, quads ? capacity : 0, result, workspace, stream, raw);
-	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventSynchronize(raw[kStages]));
-	for (int i = 0; i < kStages; ++i) BM_HIP(hipEventElapsedTime(&kernel_ms[i], raw[i], raw[i + 1]));
-	return 0;
-}
-
-int Scene::mesh_triangles(const bm_quad* quads, int64_t n, float* triangles, hipStream_t stream) {
-	if (n < 0 || n > (int64_t{1} << 32)) { set_error("bm_mesh_triangles: a quad count below 0 or above 2^32"); return BM_EINVAL; }
-	if (n == 0) return 0;
-	if (!quads || !triangles) { set_error("bm_mesh_triangles: null buffer"); return BM_EINVAL; }
-	if (reinterpret_cast<uintptr_t>(quads) % 4 != 0 || reinterpret_cast<uintptr_t>(triangles) % 4 != 0) { set_error("bm_mesh_triangles: quads and triangles must be 4-byte aligned"); return BM_EINVAL; }
-	const size_t quad_bytes = static_cast<size_t>(n) * sizeof(bm_quad), tri_bytes = static_cast<size_t>(n) * 18 * sizeof(float);
-	const uintptr_t pq = reinterpret_cast<uintptr_t>(quads), pt = reinterpret_cast<uintptr_t>(triangles);
-	if (pq < pt + tri_bytes && pt < pq + quad_bytes) { set_error("bm_mesh_triangles: the triangles overlap the quads"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	if (!device_span_ok(reinterpret_cast<const uint8_t*>(quads), quad_bytes) || !device_span_ok(reinterpret_cast<const uint8_t*>(triangles), tri_bytes)) {
-		set_error("bm_mesh_triangles: a buffer does not lie inside one allocation of the scene's device");
-		return BM_EINVAL;
-	}
-	launch_mesh_triangles(quads, static_cast<uint64_t>(n), triangles, stream);
-	BM_HIP(hipGetLastError());
-	return 0;
-}
-
-int Scene::pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream) {
-	if (!cam || !rays || width < 1 || height < 1 || width > 65535 || height > 65535 || reinterpret_cast<uintptr_t>(rays) % 16 != 0) {
-		set_error("bm_camera_pixel_rays_device: bad argument (null, a size outside 1 ... 65535, or rays not 16-byte aligned)");
-		return BM_EINVAL;
-	}
-	const CameraBasis basis = camera_basis(cam->position, cam->direction, cam->up, width, height); // the frames' basis, as bm_camera_pixel_rays takes it
-	PixelRayBasis b;
-	for (int k = 0; k < 3; ++k) { b.right[k] = basis.right[k]; b.up[k] = basis.up[k]; b.dir[k] = basis.dir[k]; b.origin[k] = basis.origin[k]; }
-	b.width = width; b.height = height;
-	BM_HIP(hipSetDevice(device_));
-	launch_pixel_rays(b, rays, stream);
-	BM_HIP(hipGetLastError());
-	return 0;
-}
-
-// ---- temporal accumulation (bm_reproject): like the filter, nothing of the world is read and nothing is kept
-int Scene::reproject(const bm_reproject_params* params, const bm_camera* cam, const bm_camera* cam_prev, const float* accum, const bm_ray_hit* hits,
-					 const void* history_prev, void* history_out, hipStream_t stream) {
-	if (!params || !cam || !accum || !hits || !history_out) { set_error("bm_reproject: null argument"); return BM_EINVAL; }
-	if (history_prev && !cam_prev) { set_error("bm_reproject: a previous history needs the camera it was made with"); return BM_EINVAL; }
-	const ReprojectParamsView pv = {params->width, params->height, params->max_history, params->flags, params->reserved};
-	if (const char* why = reproject_params_problem(pv)) { set_error(std::string("bm_reproject: ") + why); return BM_EINVAL; }
-	const uintptr_t pa = reinterpret_cast<uintptr_t>(accum), ph = reinterpret_cast<uintptr_t>(hits), pp = reinterpret_cast<uintptr_t>(history_prev),
-					po = reinterpret_cast<uintptr_t>(history_out);
-	if ((pa | ph | pp | po) % 16 != 0) { set_error("bm_reproject: buffers must be 16-byte aligned"); return BM_EINVAL; }
-	const size_t history = history_bytes(params->width, params->height), image = history / 20 * 16;
-	auto overlaps_out = [&](uintptr_t p, size_t bytes) { return p < po + history && po < p + bytes; };
-	if ((history_prev && overlaps_out(pp, history)) || overlaps_out(pa, image) || overlaps_out(ph, 2 * image)) {
-		set_error("bm_reproject: history_out overlaps an input (taps read neighbours: ping-pong two histories)");
-		return BM_EINVAL;
-	}
-	ReprojectCameras cams;
-	cams.cur = camera_basis(cam->position, cam->direction, cam->up, params->width, params->height);
-	// (without a history the previous camera is not read; the current one stands in so that the argument holds defined values)
-	const bm_camera* before = history_prev ? cam_prev : cam;
-	cams.prev = reproject_prev_camera(camera_basis(before->position, before->direction, before->up, params->width, params->height));
-	cams.width = params->width; cams.height = params->height;
-	BM_HIP(hipSetDevice(device_));
-	launch_reproject(cams, params->max_history, accum, hits, history_prev, history_out, stream);
-	BM_HIP(hipGetLastError());
-	return 0;
 }
 
 int Scene::synchronize() {

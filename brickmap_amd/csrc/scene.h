@@ -9,6 +9,7 @@
 
 #include "../../include/brickmap.h"
 #include "arena.h"
+#include "device_ops.h"
 #include "device_types.h"
 #include "error.h"
 #include "frame_plan.h"
@@ -68,25 +69,6 @@ public:
 	int render(const bm_camera* cam, const bm_frame_params* fp, float* accum, uint32_t* dbg, hipStream_t stream);
 	// `count` consecutive frames as one launch (the frame ring, trace.hip); dbgs may be null, and so may any of its entries
 	int render_frames(int count, const bm_camera* cams, const bm_frame_params* fps, float* const* accums, uint32_t* const* dbgs, hipStream_t stream);
-	int resolve(const float* accum, float* out, long long n, hipStream_t stream);
-	// the a-trous filter (denoise.hip): the workspace is the caller's, the scene keeps no state for it -- calls on different streams are independent
-	// kernel_ms: null, or 2 + iterations durations -- prepare, moments, every pass (the call then waits; bm_debug_denoise_times)
-	int denoise(const bm_denoise_params* params, const float* accum, const bm_ray_hit* hits, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream,
-				float* kernel_ms = nullptr);
-	// meshes -> voxels (voxelize.hip): like the filter, the buffers and the workspace are the caller's and the scene keeps no state
-	// kernel_ms: null, or 5 durations -- zeroing, plan + scan, surface, solid, the dense pass (the call then waits; bm_debug_voxelize_times)
-	int voxelize(const bm_voxelize_params* params, int64_t n, const float* triangles, uint8_t* volume, bm_voxelize_result* result, void* workspace, size_t workspace_bytes,
-				 hipStream_t stream, float* kernel_ms = nullptr);
-	// voxels -> quads (mesh.hip): like voxelize, the buffers and the workspace are the caller's and the scene keeps no state
-	// kernel_ms: null, or 3 durations -- count, scan, emit (the call then waits; bm_debug_mesh_times)
-	int mesh_quads(const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result, void* workspace, size_t workspace_bytes,
-				   hipStream_t stream, float* kernel_ms = nullptr);
-	int mesh_triangles(const bm_quad* quads, int64_t n, float* triangles, hipStream_t stream);
-	// pixel-centre rays of a frame, written on the device (denoise.hip)
-	int pixel_rays(const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
-	// temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers; the scene keeps no state for it
-	int reproject(const bm_reproject_params* params, const bm_camera* cam, const bm_camera* cam_prev, const float* accum, const bm_ray_hit* hits, const void* history_prev,
-				  void* history_out, hipStream_t stream);
 	int synchronize();
 	int last_render_ms(float* ms);
 	int render_times(float* ms, int capacity, int* count); // durations of the most recent launches, oldest first
@@ -100,6 +82,7 @@ public:
 	int begin_frame(hipStream_t stream, DeviceScene* view, DeviceCounters** counters);
 	void end_frame(hipStream_t stream);
 	int compute_units() const { return compute_units_; }
+	Gpu gpu() const { return {device_, compute_units_}; } // what the stateless operators (device_ops.h) need of a scene
 
 	World world;
 	int device() const { return device_; }
@@ -112,7 +95,6 @@ private:
 	EscapeUpdate escape_update_box(int x0, int x1, int y0, int y1) const; // the columns [x0, x1) x [y0, y1) of the escape-height table (escape.hip)
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
-	bool device_span_ok(const uint8_t* p, size_t bytes) const;
 	// the device half of a change of the host world (scene.cpp "voxel edits"): the touched cells of every changed supercell are staged, then submitted
 	struct DeviceBatch {
 		std::vector<uint32_t> cells, words, slots;
@@ -255,9 +237,10 @@ private:
 	bool volume_busy_ = false;
 	int volume_blocks_per_cu_[2] = {0, 0};
 	// connected components: the root counts of one bm_scene_label_components (label_tmp_bytes, grown on demand); label calls of a scene run
-	// one after another, each waits for the one before it.  ev_label_time_: around local, merge and flatten of the last label_region
+	// one after another, each waits for the one before it.  label_marks_: around local, merge and flatten of the last label_region
 	DeviceBuffer<uint64_t> d_label_tmp_;
-	Event ev_label_, ev_label_time_[4];
+	Event ev_label_;
+	StageMarks<4> label_marks_;
 	bool label_busy_ = false, label_timed_ = false;
 	int queue_cap_ = 1024;                       // variables.h:35
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27

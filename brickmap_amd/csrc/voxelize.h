@@ -53,6 +53,24 @@ inline int64_t voxelize_slice_pitch(const VxParamsView& p) { return p.slice_pitc
 // words of one row of a bit plane: bit x of the row for voxel x, and bit nx for the crossings beyond the volume
 inline uint32_t voxelize_row_words(int nx) { return static_cast<uint32_t>(nx + 1 + 31) / 32u; }
 
+// accepted parameters as the kernels and voxelize_workspace_bytes take them (kernels.h): a kernel argument, passed by value
+struct VoxelizeDims {
+	int32_t lo[3], extent[3];
+	uint32_t words; // voxelize_row_words(extent[0])
+	uint32_t mode, keep;
+	int64_t row_pitch, slice_pitch; // resolved: never 0
+};
+inline VoxelizeDims voxelize_dims(const VxParamsView& p) {
+	VoxelizeDims d;
+	for (int k = 0; k < 3; ++k) { d.lo[k] = p.lo[k]; d.extent[k] = p.extent[k]; }
+	d.words = voxelize_row_words(p.extent[0]);
+	d.mode = p.mode;
+	d.keep = p.flags & kVxKeep;
+	d.row_pitch = voxelize_row_pitch(p);
+	d.slice_pitch = voxelize_slice_pitch(p);
+	return d;
+}
+
 // a snapped triangle: q[vertex][axis], its normal, and its bounds per axis
 struct VxTri {
 	int32_t q[3][3];

@@ -136,12 +136,16 @@ def test_refusals_launch_nothing(bm, scene256, torch_cuda):
         p = bm_denoise_params(ww, hh, it, sigma, flags, reserved)
         return L.bm_denoise(scene256.gpuScene, C.byref(p) if par else None, C.c_void_p(a), C.c_void_p(hp), C.c_void_p(o), C.c_void_p(wsp), wsb, stream)
 
-    for kw in (dict(it=-1), dict(it=9), dict(sigma=0.0), dict(sigma=-4.0), dict(sigma=float("inf")), dict(sigma=float("nan")),
-               dict(ww=0), dict(hh=0), dict(ww=65536), dict(hh=65536), dict(flags=1), dict(reserved=7),
-               dict(a=None), dict(hp=None), dict(o=None), dict(wsp=None), dict(wsb=need - 1), dict(wsb=0), dict(par=False),
-               dict(wsp=ws.data_ptr() + 4), dict(o=ws.data_ptr())):
+    its, sigma, size, zero, null, small = (b"iterations must be 0 ... 8", b"sigma_l must be finite and positive", b"width and height must be 1 ... 65535",
+                                          b"flags and reserved must be 0", b"null", b"smaller than")
+    for kw, fragment in ((dict(it=-1), its), (dict(it=9), its), (dict(sigma=0.0), sigma), (dict(sigma=-4.0), sigma), (dict(sigma=float("inf")), sigma),
+                         (dict(sigma=float("nan")), sigma), (dict(ww=0), size), (dict(hh=0), size), (dict(ww=65536), size), (dict(hh=65536), size),
+                         (dict(flags=1), zero), (dict(reserved=7), zero),
+                         (dict(a=None), null), (dict(hp=None), null), (dict(o=None), null), (dict(wsp=None), null), (dict(wsb=need - 1), small), (dict(wsb=0), small),
+                         (dict(par=False), null), (dict(wsp=ws.data_ptr() + 4), b"aligned"), (dict(o=ws.data_ptr()), b"overlaps")):
         assert call(**kw) == EINVAL, kw
-        assert b"denoise" in L.bm_last_error_string()
+        msg = L.bm_last_error_string()
+        assert msg.startswith(b"bm_denoise: ") and fragment in msg, (kw, msg)  # which refusal fired
     torch.cuda.synchronize()
     assert bool((out == -7.0).all()), "a refused call wrote its output"
     assert call() == 0

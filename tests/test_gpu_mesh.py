@@ -204,25 +204,41 @@ def test_refusals_that_need_a_device(bm, torch_cuda, scene):
         par.row_pitch, par.slice_pitch, par.flags, par.reserved = row, sl, flags, reserved
         return L.bm_mesh_quads(scene.gpuScene, C.byref(par), C.c_void_p(v), C.c_void_p(q), cap, C.c_void_p(r), C.c_void_p(w), wb, None)
 
-    bad = [dict(extent=(0, 8, 8)), dict(extent=(8, 8, 16385)), dict(extent=(2, 8, 8), flags=1), dict(row=7), dict(sl=63), dict(flags=4), dict(reserved=1),
-           dict(v=0), dict(r=0), dict(w=0), dict(q=0), dict(q=quads.data_ptr() + 2), dict(r=res.data_ptr() + 4), dict(w=ws.data_ptr() + 8), dict(wb=need - 1),
-           dict(w=vol.data_ptr(), wb=need), dict(v=ws.data_ptr() + 16), dict(q=ws.data_ptr()), dict(r=ws.data_ptr()), dict(lo=((1 << 23) - 7, 0, 0)), dict(lo=(0, -(1 << 23) - 1, 0))]
-    for kw in bad:
+    def fired(entry, fragment):
+        """the refusal that fired: the message names the entry point and holds the fragment of its class"""
+        msg = L.bm_last_error_string()
+        return msg.startswith(entry + b": ") and fragment in msg
+
+    def refused(kw, fragment):
         assert call(**kw) == EINVAL, kw
+        assert fired(b"bm_mesh_quads", fragment), (kw, L.bm_last_error_string())
+
+    extent, null, aligned, overlaps, outside = b"an extent below 1 (below 3 with BM_MESH_HALO) or above 16384", b"null", b"aligned", b"overlaps", b"a box outside +-2^23 voxels"
+    bad = [(dict(extent=(0, 8, 8)), extent), (dict(extent=(8, 8, 16385)), extent), (dict(extent=(2, 8, 8), flags=1), extent), (dict(row=7), b"row_pitch below the extent along x"),
+           (dict(sl=63), b"slice_pitch below row_pitch * the extent along y"), (dict(flags=4), b"unknown flag"), (dict(reserved=1), b"reserved is not 0"),
+           (dict(v=0), null), (dict(r=0), null), (dict(w=0), null), (dict(q=0), null), (dict(q=quads.data_ptr() + 2), aligned), (dict(r=res.data_ptr() + 4), aligned),
+           (dict(w=ws.data_ptr() + 8), aligned), (dict(wb=need - 1), b"smaller than"),
+           (dict(w=vol.data_ptr(), wb=need), overlaps), (dict(v=ws.data_ptr() + 16), overlaps), (dict(q=ws.data_ptr()), overlaps), (dict(r=ws.data_ptr()), overlaps),
+           (dict(lo=((1 << 23) - 7, 0, 0)), outside), (dict(lo=(0, -(1 << 23) - 1, 0)), outside)]
+    for kw, fragment in bad:
+        refused(kw, fragment)
     # a volume whose pitches carry it 56 MiB past an allocation of 512 bytes (one of its own: torch's tensors share theirs)
     own = C.c_void_p()
     assert L.bm_buffer_alloc(scene.device, 512, C.byref(own)) == 0
-    assert call(row=1 << 20, sl=8 << 20, v=own.value) == EINVAL
+    refused(dict(row=1 << 20, sl=8 << 20, v=own.value), b"does not lie inside")
     torch.cuda.synchronize()
     assert (quads == -1).all().item() and not res.any().item() and not ws.any().item()
     assert call(v=own.value, q=0, cap=0) == 0
     assert L.bm_mesh_triangles(scene.gpuScene, C.c_void_p(quads.data_ptr()), 8, own, None) == EINVAL, "8 x 72 bytes do not fit an allocation of 512"
+    assert fired(b"bm_mesh_triangles", b"does not lie inside"), L.bm_last_error_string()
     assert L.bm_synchronize(scene.gpuScene) == 0 and L.bm_buffer_free(scene.device, own) == 0
     assert call(q=0, cap=0) == 0 and call() == 0
     torch.cuda.synchronize()
     assert quads.cpu().numpy()[:6].tobytes() == bm.host_mesh_quads(np.ones((8, 8, 8), np.uint8))[0].tobytes() and (quads[6:] == -1).all().item()
     assert L.bm_mesh_triangles(scene.gpuScene, C.c_void_p(quads.data_ptr() + 2), 1, C.c_void_p(ws.data_ptr()), None) == EINVAL
+    assert fired(b"bm_mesh_triangles", b"aligned"), L.bm_last_error_string()
     assert L.bm_mesh_triangles(scene.gpuScene, C.c_void_p(quads.data_ptr()), -1, C.c_void_p(ws.data_ptr()), None) == EINVAL
+    assert fired(b"bm_mesh_triangles", b"a quad count below 0 or above 2^32"), L.bm_last_error_string()
 
 
 # ---------------------------------------------------------------- the scene level

@@ -112,14 +112,19 @@ def test_refusals_launch_nothing(bm, scene256, torch_cuda):
         return L.bm_reproject(scene256.gpuScene, C.byref(pp) if par else None, C.byref(c) if c is not None else None, C.byref(cp) if cp is not None else None,
                               C.c_void_p(a), C.c_void_p(hp), C.c_void_p(p), C.c_void_p(o), stream)
 
-    for kw in (dict(ww=0), dict(hh=0), dict(ww=65536), dict(hh=65536), dict(mh=0.5), dict(mh=-2.0), dict(mh=float("inf")), dict(mh=float("nan")),
-               dict(flags=1), dict(reserved=7), dict(c=None), dict(a=None), dict(hp=None), dict(o=None), dict(par=False), dict(cp=None),
-               dict(o=out.data_ptr() + 4), dict(a=accum.data_ptr() + 8), dict(hp=hits.data_ptr() + 4), dict(p=prev.data_ptr() + 4),
-               # history_out overlapping the previous history (the same, and its last 16 bytes), accum and hits
-               dict(p=out.data_ptr()), dict(p=out.data_ptr() + 20 * n - 16), dict(p=out.data_ptr() - 20 * n + 16), dict(a=out.data_ptr() + 16 * n),
-               dict(hp=out.data_ptr() + 16)):
+    size, cap, zero, null, aligned, overlaps = (b"width and height must be 1 ... 65535", b"max_history must be finite and at least 1", b"flags and reserved must be 0",
+                                                b"null", b"aligned", b"overlaps")
+    for kw, fragment in ((dict(ww=0), size), (dict(hh=0), size), (dict(ww=65536), size), (dict(hh=65536), size), (dict(mh=0.5), cap), (dict(mh=-2.0), cap),
+                         (dict(mh=float("inf")), cap), (dict(mh=float("nan")), cap), (dict(flags=1), zero), (dict(reserved=7), zero),
+                         (dict(c=None), null), (dict(a=None), null), (dict(hp=None), null), (dict(o=None), null), (dict(par=False), null),
+                         (dict(cp=None), b"a previous history needs the camera it was made with"),
+                         (dict(o=out.data_ptr() + 4), aligned), (dict(a=accum.data_ptr() + 8), aligned), (dict(hp=hits.data_ptr() + 4), aligned), (dict(p=prev.data_ptr() + 4), aligned),
+                         # history_out overlapping the previous history (the same, and its last 16 bytes), accum and hits
+                         (dict(p=out.data_ptr()), overlaps), (dict(p=out.data_ptr() + 20 * n - 16), overlaps), (dict(p=out.data_ptr() - 20 * n + 16), overlaps),
+                         (dict(a=out.data_ptr() + 16 * n), overlaps), (dict(hp=out.data_ptr() + 16), overlaps)):
         assert call(**kw) == EINVAL, kw
-        assert b"bm_reproject" in L.bm_last_error_string()
+        msg = L.bm_last_error_string()
+        assert msg.startswith(b"bm_reproject: ") and fragment in msg, (kw, msg)  # which refusal fired
     torch.cuda.synchronize()
     assert bool((out == -7.0).all()), "a refused call wrote its output"
     assert call() == 0 and call(p=None, cp=None) == 0

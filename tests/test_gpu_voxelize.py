@@ -168,15 +168,25 @@ def test_refusals_leave_the_volume_untouched(bm, torch_cuda, scene):
         par.row_pitch, par.slice_pitch, par.mode, par.flags = row, sl, mode, flags
         return L.bm_voxelize(scene.gpuScene, C.byref(par), count, C.c_void_p(t), C.c_void_p(v), C.c_void_p(r), C.c_void_p(w), wb, None)
 
-    bad = [dict(extent=(0, 8, 8)), dict(extent=(8, 8, 16385)), dict(row=7), dict(sl=63), dict(mode=0), dict(mode=4), dict(flags=2), dict(count=-1),
-           dict(t=0), dict(v=0), dict(w=0), dict(t=tri.data_ptr() + 2), dict(r=res.data_ptr() + 4), dict(w=ws.data_ptr() + 8), dict(wb=need - 1),
-           dict(w=vol.data_ptr(), wb=need), dict(v=ws.data_ptr() + 16), dict(t=ws.data_ptr())]
-    for kw in bad:
+    def refused(kw, fragment):
+        """BM_EINVAL, and the refusal that fired: the message names the entry point and holds the fragment of its class"""
         assert call(**kw) == EINVAL, kw
+        msg = L.bm_last_error_string()
+        assert msg.startswith(b"bm_voxelize: ") and fragment in msg, (kw, msg)
+
+    extent, null, aligned, overlaps = b"an extent below 1 or above 16384", b"null", b"aligned", b"overlaps"
+    bad = [(dict(extent=(0, 8, 8)), extent), (dict(extent=(8, 8, 16385)), extent), (dict(row=7), b"row_pitch below the extent along x"),
+           (dict(sl=63), b"slice_pitch below row_pitch * the extent along y"), (dict(mode=0), b"unknown mode"), (dict(mode=4), b"unknown mode"),
+           (dict(flags=2), b"unknown flag"), (dict(count=-1), b"a triangle count below 0 or above 2^30"),
+           (dict(t=0), null), (dict(v=0), null), (dict(w=0), null), (dict(t=tri.data_ptr() + 2), aligned), (dict(r=res.data_ptr() + 4), aligned),
+           (dict(w=ws.data_ptr() + 8), aligned), (dict(wb=need - 1), b"smaller than"),
+           (dict(w=vol.data_ptr(), wb=need), overlaps), (dict(v=ws.data_ptr() + 16), overlaps), (dict(t=ws.data_ptr()), overlaps)]
+    for kw, fragment in bad:
+        refused(kw, fragment)
     # a volume whose pitches carry it 56 MiB past an allocation of 512 bytes (one of its own: torch's tensors share theirs)
     own = C.c_void_p()
     assert L.bm_buffer_alloc(scene.device, 512, C.byref(own)) == 0
-    assert call(row=1 << 20, sl=8 << 20, v=own.value) == EINVAL
+    refused(dict(row=1 << 20, sl=8 << 20, v=own.value), b"does not lie inside")
     torch.cuda.synchronize()
     assert (vol == 7).all().item() and not res.any().item() and not ws.any().item()
     assert call(v=own.value) == 0
