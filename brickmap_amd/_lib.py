@@ -182,6 +182,8 @@ SIGNATURES = {
     "bm_scene_sun_plane": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
     "bm_scene_shadow_heights": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), _vp]),
     "bm_scene_sun_plane_stats": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    "bm_scene_view_plane": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t), _vp]),
+    "bm_scene_view_plane_stats": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "bm_scene_last_edit_ms": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bm_scene_load_voxels": (_i, [_vp, _vp, C.c_size_t, _i, _vp]),
     "bm_scene_host_voxels": (_i, [_vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -83,11 +83,13 @@ int voxelize(const Gpu& gpu, const bm_voxelize_params* params, int64_t n, const 
 						static_cast<size_t>(pv.extent[0]);
 	const size_t tri_bytes = static_cast<size_t>(n) * 9 * sizeof(float);
 	const Span ws = span_of(workspace, need);
-	if (spans_overlap(span_of(volume, span), ws) || spans_overlap(span_of(triangles, tri_bytes), ws) || (result && spans_overlap(span_of(result, sizeof(bm_voxelize_result)), ws))) {
+	BM_HIP(hipSetDevice(gpu.device));
+	// (a volume whose pitches carry it past its allocation has no extent to overlap anything with, see mesh_quads)
+	if ((spans_overlap(span_of(volume, span), ws) && device_span_ok(gpu.device, volume, span)) || spans_overlap(span_of(triangles, tri_bytes), ws) ||
+		(result && spans_overlap(span_of(result, sizeof(bm_voxelize_result)), ws))) {
 		set_error("bm_voxelize: the workspace overlaps the volume, the triangles or the result");
 		return BM_EINVAL;
 	}
-	BM_HIP(hipSetDevice(gpu.device));
 	if (!device_span_ok(gpu.device, volume, span) || !device_span_ok(gpu.device, workspace, need) || (n > 0 && !device_span_ok(gpu.device, triangles, tri_bytes)) ||
 		(result && !device_span_ok(gpu.device, result, sizeof(bm_voxelize_result)))) {
 		set_error("bm_voxelize: a buffer does not lie inside one allocation of the scene's device");
@@ -119,11 +121,14 @@ int mesh_quads(const Gpu& gpu, const bm_mesh_params* params, const uint8_t* volu
 	const size_t span = static_cast<size_t>(mesh_span(d));
 	const size_t quad_bytes = quads ? static_cast<size_t>(capacity) * sizeof(bm_quad) : 0;
 	const Span ws = span_of(workspace, need);
-	if (spans_overlap(span_of(volume, span), ws) || spans_overlap(span_of(quads, quad_bytes), ws) || spans_overlap(span_of(result, sizeof(bm_mesh_result)), ws)) {
+	BM_HIP(hipSetDevice(gpu.device));
+	// (a volume whose pitches carry it past its allocation has no extent to overlap anything with: whether that phantom extent crosses the
+	// workspace depends on where the allocator put the two, and the refusal must not)
+	if ((spans_overlap(span_of(volume, span), ws) && device_span_ok(gpu.device, volume, span)) || spans_overlap(span_of(quads, quad_bytes), ws) ||
+		spans_overlap(span_of(result, sizeof(bm_mesh_result)), ws)) {
 		set_error("bm_mesh_quads: the workspace overlaps the volume, the quads or the result");
 		return BM_EINVAL;
 	}
-	BM_HIP(hipSetDevice(gpu.device));
 	if (!device_span_ok(gpu.device, volume, span) || !device_span_ok(gpu.device, workspace, need) || (quad_bytes > 0 && !device_span_ok(gpu.device, quads, quad_bytes)) ||
 		!device_span_ok(gpu.device, result, sizeof(bm_mesh_result))) {
 		set_error("bm_mesh_quads: a buffer does not lie inside one allocation of the scene's device");

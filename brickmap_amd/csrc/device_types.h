@@ -43,7 +43,8 @@ BM_VHD size_t brick_first_word(uint32_t pool_base_value, uint32_t index_word) {
 //                                         a new region of the arena and its entry here is rewritten.
 //   brick_arena 64 B * arena capacity    one allocation that all pools live in (power-of-two regions, free lists per
 //                                         size; grows by residency, not by world size)
-//   cube_field  8 planes, 1 B per cell   octant cube field (below): what the walk reads while it crosses empty space
+//   cube_field  8 planes, 1 B per cell   octant cube field (below): what the walk reads while it crosses empty space; plane 8: the sun plane
+//                                         (sunfield.h), plane 9: the view plane (viewfield.h) -- ten planes in one allocation, every offset below 2^32
 //   escape      u32[9 * cf_pxy]          escape heights of the walk (below, escape.h); slice 8: the shadow heights of the sun plane's cone (shadowheight.h)
 //   load_queue  int3[queue_cap] + count  brick-request ring (voxel.cuh:228-245)
 struct DeviceScene {
@@ -118,6 +119,9 @@ struct FrameConstants {
 	// the sun plane (sunfield.h): byte offset of the cube-field plane this frame's shadow rays read, 8 * cf_plane, or 0 -- they keep their octant
 	// plane -- when the scene's sun plane was not built for this frame's cone (scene.cpp render_frames)
 	uint32_t shadow_field_off;
+	// the view plane (viewfield.h): byte offset of the cube-field plane this frame's primary rays read, 9 * cf_plane, or 0 -- they keep their
+	// octant plane -- when the scene's view plane does not stand for this frame's origin (scene.cpp render_frames)
+	uint32_t view_field_off;
 	// the frame ring (trace.hip): where this frame's results go, and how many frames of the launch follow it (the queue kernels of
 	// wavefront.hip take their buffers as arguments)
 	float* accum;          // float4 per pixel of the shard

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -8,6 +8,7 @@
 #include "reproject.h"
 #include "shadowheight.h"
 #include "sunfield.h"
+#include "viewfield.h"
 
 namespace bm {
 // resident workgroups of `threads` threads per compute unit of a kernel, at least 1 (host code of the file that defines the kernel)
@@ -81,6 +82,16 @@ size_t sun_build_tmp_bytes(const SunBuild& u);
 size_t shadow_build_tmp_bytes(const SunBuild& u); // tmp_shadow: the scratch of the shadow heights, under the same condition
 void launch_sun_build(const uint32_t* index_grid, const uint32_t* pool_base, const uint32_t* arena, const int32_t* cols, uint32_t* escape, uint8_t* field, uint8_t* tmp,
 					  uint8_t* tmp_shadow, const SunBuild& u, bool with_field, hipStream_t stream);
+
+// the view plane (viewfield.hip; viewfield.h has the rule): plane 9 of `field`, every interior byte, rebuilt for the camera position of
+// `plan` from the octant planes of `field` and the escape table (both as the field and escape updates leave them on the stream)
+struct ViewBuild {
+	ViewPlan plan; // valid
+	int cells, cells_height;
+	int cf_shift;
+	uint32_t cf_pxy, cf_plane;
+};
+void launch_view_build(const uint32_t* escape, uint8_t* field, const ViewBuild& u, hipStream_t stream);
 
 // dense voxels -> scene (load.hip): the volume is V[z][y][x], one byte per voxel, in device memory.  classify leaves lod << 12 in every
 // cell's index word; number turns the words into slot | loaded | lod << 12 (slots in local cell order), fills counts[supercells] and

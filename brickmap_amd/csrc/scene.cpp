@@ -45,7 +45,7 @@ namespace {
 struct CubeFieldLayout {
 	int shift;
 	uint64_t pxy, plane;
-	bool fits, ninth;
+	bool fits, ninth, tenth;
 };
 CubeFieldLayout cube_field_layout(const WorldDims& d) {
 	int shift = 2;
@@ -56,6 +56,7 @@ CubeFieldLayout cube_field_layout(const WorldDims& d) {
 	l.plane = l.pxy * static_cast<uint64_t>(d.cells_height + 2);
 	l.fits = l.pxy < (1ull << 23) && l.plane * 8 < (1ull << 32);
 	l.ninth = BM_SUNFIELD != 0 && l.fits && l.plane * 9 < (1ull << 32); // the sun plane's offsets fit 32 bits as well
+	l.tenth = BM_VIEWFIELD != 0 && l.ninth && l.plane * 10 < (1ull << 32); // ... and the view plane's, behind it
 	return l;
 }
 
@@ -223,6 +224,7 @@ void Scene::free_device() {
 	arena_.close();
 	(void)d_cube_field_.release();
 	sun_plane_ = sun_built_ = false;
+	view_plane_ = view_built_ = false;
 	(void)d_escape_.release();
 	(void)d_escape_cols_.release();
 	on_device_ = false;
@@ -298,8 +300,13 @@ int Scene::alloc_cube_field() {
 	const CubeFieldLayout l = cube_field_layout(world.dims);
 	if (!l.fits) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
 	// a ninth plane behind the eight is the sun plane of shadow rays (sunfield.h), where it can be had: a scene without it renders as before
-	sun_plane_ = false;
-	if (l.ninth) {
+	sun_plane_ = view_plane_ = false;
+	// ... and a tenth the view plane of primary rays (viewfield.h), on the same terms
+	if (l.tenth) {
+		if (d_cube_field_.alloc(l.plane * 10) == 0) sun_plane_ = view_plane_ = true;
+		else { (void)hipGetLastError(); set_error(""); }
+	}
+	if (!sun_plane_ && l.ninth) {
 		if (d_cube_field_.alloc(l.plane * 9) == 0) sun_plane_ = true;
 		else { (void)hipGetLastError(); set_error(""); } // (doing without the plane is no error: neither HIP's slot nor ours keeps it)
 	}
@@ -308,6 +315,8 @@ int Scene::alloc_cube_field() {
 	shadow_full_valid_ = false;
 	shadow_zero_ = true; // (the memset of the escape allocation below)
 	sun_dirty_ = true;
+	view_built_ = false;
+	view_dirty_ = true;
 	BM_HIP(hipMemset(d_cube_field_, 255, d_cube_field_.bytes())); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
 	view_.cf_shift = l.shift;
 	view_.cf_pxy = static_cast<uint32_t>(l.pxy);
@@ -1044,6 +1053,7 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 			launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(b.box_lo[0], b.box_hi[0] + 1, b.box_lo[1], b.box_hi[1] + 1), load_stream_);
 			BM_HIP(hipGetLastError());
 			sun_dirty_ = true; // the sun plane is rebuilt before the next frame that reads it (ensure_sun_plane): a run of batches pays once
+			view_dirty_ = true; // ... and so is the view plane (ensure_view_plane)
 		}
 		BM_HIP(hipEventRecord(times[2], load_stream_));
 		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
@@ -1607,6 +1617,72 @@ int Scene::sun_plane_stats(uint64_t* builds, float* last_build_ms) {
 	return 0;
 }
 
+// ---- the view plane (viewfield.h, viewfield.hip): plane 9 of the cube field, for ONE camera position.  Keyed on the bits of the origin of
+// the launch's first frame and built only for a camera that rests: the launch holds at least two frames from this origin, or the
+// production launch before it started from it.  A camera that moves every frame never builds and pays nothing; a plane of another
+// position simply goes unused.  Residency and LoD never change the plane ("occupied" is "index word non-zero").
+int Scene::ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usable) {
+	*usable = false;
+	const FrameConstants& fc = fcs[0];
+	const bool rested = std::memcmp(fc.origin, view_last_origin_, sizeof view_last_origin_) == 0 && view_last_valid_;
+	std::memcpy(view_last_origin_, fc.origin, sizeof view_last_origin_);
+	view_last_valid_ = true;
+	if (!view_plane_) return 0;
+	const WorldDims& d = world.dims;
+	const ViewPlan plan = view_plan(fc.origin, fc.lens_radius, view_.grid_size_f, view_.grid_height_f, d.cells, d.cells_height);
+	if (!plan.valid) return 0;
+	if (view_built_ && !view_dirty_ && std::memcmp(fc.origin, view_key_, sizeof view_key_) == 0) { *usable = true; return 0; }
+	int same = 0;
+	for (const FrameConstants& f : fcs) same += std::memcmp(f.origin, fc.origin, sizeof fc.origin) == 0 && f.lens_radius == 0.0f ? 1 : 0;
+	if (!(same >= 2 || rested)) return 0;
+	ViewBuild u{};
+	u.plan = plan;
+	u.cells = d.cells; u.cells_height = d.cells_height;
+	u.cf_shift = view_.cf_shift; u.cf_pxy = view_.cf_pxy; u.cf_plane = view_.cf_plane;
+	for (Event& ev : ev_view_time_) if (int e = ev.create()) return e;
+	// behind every frame in flight (their primary rays read the plane) and, on the load stream, behind the field and escape updates it reads
+	if (int e = order_load_stream_behind_frames()) return e;
+	BM_HIP(hipEventRecord(ev_view_time_[0], load_stream_));
+	launch_view_build(d_escape_, d_cube_field_, u, load_stream_);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipEventRecord(ev_view_time_[1], load_stream_));
+	BM_HIP(hipEventRecord(ev_upload_, load_stream_)); // frames wait for it like for an upload batch (frame_begin)
+	upload_seq_++;
+	std::memcpy(view_key_, fc.origin, sizeof view_key_);
+	view_built_ = true;
+	view_dirty_ = false;
+	view_builds_++;
+	*usable = true;
+	return 0;
+}
+
+// the plane as last built, [z][y][x] with its border, and the origin it was built for; *bytes = 0 while there is none (or it is stale)
+int Scene::view_plane(uint8_t* dst, size_t capacity, size_t* bytes, float* origin3) {
+	if (int e = require_on_device()) return e;
+	const WorldDims& d = world.dims;
+	const bool have = view_plane_ && view_built_ && !view_dirty_;
+	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = have ? X * X * Z : 0;
+	if (bytes) *bytes = need;
+	if (origin3) for (int k = 0; k < 3; ++k) origin3[k] = have ? view_key_[k] : 0.0f;
+	if (!dst || !have) return 0;
+	if (capacity < need) { set_error("view plane buffer too small"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipDeviceSynchronize());
+	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_ + 9 * static_cast<size_t>(view_.cf_plane), static_cast<size_t>(1) << view_.cf_shift, X, X * Z, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int Scene::view_plane_stats(uint64_t* builds, float* last_build_ms) {
+	if (!builds || !last_build_ms) { set_error("null argument"); return BM_EINVAL; }
+	*builds = view_builds_;
+	*last_build_ms = 0.0f;
+	if (view_builds_ == 0) return 0;
+	BM_HIP(hipSetDevice(device_));
+	BM_HIP(hipEventSynchronize(ev_view_time_[1]));
+	BM_HIP(hipEventElapsedTime(last_build_ms, ev_view_time_[0], ev_view_time_[1]));
+	return 0;
+}
+
 int Scene::host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
 	const WorldDims& d = world.dims;
 	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = 8 * X * X * Z;
@@ -1642,6 +1718,14 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 		if (usable)
 			for (FrameConstants& f : fcs)
 				if (std::memcmp(f.cone_dir, sun_key_, 3 * sizeof(float)) == 0 && f.cone_extent == sun_key_[3]) f.shadow_field_off = 8u * view_.cf_plane;
+	}
+	// the view plane, for the first frame's origin: built now if the camera rests there; frames of the launch from another origin keep their octant planes
+	if (BM_VIEWFIELD != 0 && !plan.instrumented) {
+		bool usable = false;
+		if (int e = ensure_view_plane(fcs, &usable)) return e;
+		if (usable)
+			for (FrameConstants& f : fcs)
+				if (std::memcmp(f.origin, view_key_, sizeof view_key_) == 0 && f.lens_radius == 0.0f) f.view_field_off = 9u * view_.cf_plane;
 	}
 	// `stream` is used as given: nullptr is HIP's default stream (what the reference's <<<>>> launches use), which is
 	// ordered with the caller's other default-stream work (e.g. torch's fill kernels on the accumulation buffer).

@@ -48,6 +48,9 @@ public:
 	int sun_plane(uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12);
 	int sun_plane_stats(uint64_t* builds, float* last_build_ms);
 	int shadow_heights(uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4);
+	// the view plane (viewfield.h): likewise, with the origin it was built for
+	int view_plane(uint8_t* dst, size_t capacity, size_t* bytes, float* origin3);
+	int view_plane_stats(uint64_t* builds, float* last_build_ms);
 	// dense regions (region.hip / scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
 	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
 	int read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream);
@@ -92,6 +95,7 @@ private:
 	int alloc_index_grid();   // the pieces of allocate_device that the device route of load_voxels shares with it
 	int alloc_cube_field();
 	int ensure_sun_plane(const FrameConstants& fc, bool* usable); // builds the sun plane for the frame's cone unless it stands; *usable: shadow rays of that cone may read it
+	int ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usable); // builds the view plane for the first frame's origin if the camera rests there; *usable: the plane stands for that origin
 	EscapeUpdate escape_update_box(int x0, int x1, int y0, int y1) const; // the columns [x0, x1) x [y0, y1) of the escape-height table (escape.hip)
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
@@ -176,6 +180,14 @@ private:
 	uint64_t sun_builds_ = 0;
 	DeviceBuffer<uint8_t> d_sun_tmp_, d_shadow_tmp_;
 	Event ev_sun_time_[2];
+	// the view plane (viewfield.h): plane 9 of d_cube_field_ where alloc_cube_field got ten planes; built for the origin in view_key_, stale once
+	// the field has changed (view_dirty_, set wherever sun_dirty_ is), rebuilt by the next production launch of a resting camera
+	bool view_plane_ = false, view_built_ = false, view_dirty_ = true;
+	float view_key_[3] = {0.f, 0.f, 0.f};
+	float view_last_origin_[3] = {0.f, 0.f, 0.f}; // origin of the first frame of the production launch before this one
+	bool view_last_valid_ = false;
+	uint64_t view_builds_ = 0;
+	Event ev_view_time_[2];
 	// two request rings: the blocking (reference-order) mode only uses ring 0; the overlapped mode alternates them so
 	// that a frame can raise requests while the previous frame's ring is being copied out and serviced
 	DeviceBuffer<int> d_load_queue_[2];

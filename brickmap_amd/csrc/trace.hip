@@ -231,6 +231,8 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 	constexpr bool kSun = BM_SUNFIELD != 0 && kEscape && (BM_SUNFIELD_XCD != 0 || !XCD); // (the plane's stamps stand in for the escape test: only where that is compiled in)
 	// shadow heights (shadowheight.h, BM_SHADOWHEIGHT / BM_SHADOWHEIGHT_XCD): in production frames with a sun plane, the shade block draws no shadow ray from a cell no ray of the cone reaches the sun from
 	constexpr bool kShade = BM_SHADOWHEIGHT != 0 && kSun && !DBG && (BM_SHADOWHEIGHT_XCD != 0 || !XCD);
+	// the view plane (viewfield.h, BM_VIEWFIELD / BM_VIEWFIELD_XCD): in production frames whose camera rests, a primary ray walks the plane built for the camera's position
+	constexpr bool kView = BM_VIEWFIELD != 0 && kEscape && !DBG && (BM_VIEWFIELD_XCD != 0 || !XCD);
 	uint32_t esc = 0; // kEscape: the escape threshold of the ray in flight (ray_setup)
 	r.hit = false;
 	r.n = mk(0.f, 0.f, 0.f);
@@ -718,7 +720,9 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					ray_loads0 = tally.index_loads;
 				}
 				pstate = shadow ? ((HELP && pstate == P_HELPER) ? P_HELPER : P_SHD_DONE) : P_EXT_DONE;
-				const int st = ray_setup<DBG, kEscape>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u);
+				// the plane this ray walks instead of its octant's: the sun plane for a shadow ray, the view plane for a primary ray, 0 = none
+				const int st = ray_setup<DBG, kEscape, kView>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u,
+															  kView && !shadow && bounces == 0 ? fc.view_field_off : 0u);
 				state = (st == ST_NEED && shadow) ? ST_CONN : st;
 			}
 			BM_MARK(4, t_sub); // ray set-up

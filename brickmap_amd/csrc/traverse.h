@@ -392,10 +392,13 @@ __device__ __forceinline__ int walk_round(const DeviceScene& sc, RayState& r, in
 // sun_plane: non-zero for a shadow ray whose frame has a sun plane (sunfield.h; FrameConstants::shadow_field_off) -- the ray walks that
 // plane instead of its octant's, by one select here; the plane's 255 stamps hold the escape rule, so the threshold becomes the plane's
 // end, which escape_reached never sees reached (such a ray moves up: the plan of a sun below the horizon is not valid).
+// VIEW: view_plane is non-zero for a primary ray whose frame has a view plane (viewfield.h; FrameConstants::view_field_off).  Such a ray
+// keeps the escape threshold of its own octant -- the rule holds for the ray whatever plane's bytes it walks -- moved by the distance
+// between the two planes, so that escape_reached compares offsets of one plane; the plane's own 255 stamps come on top.
 // (Shadow heights, shadowheight.h: a shadow ray that starts in a dark cell never gets here -- the shade block of trace.hip tests the
 // origin's cell with shadow_origin, which computes the very cell of this function, and does not draw the ray.)
-template <bool DBG, bool ESC = false>
-__device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally, uint32_t* esc = nullptr, uint32_t sun_plane = 0u) {
+template <bool DBG, bool ESC = false, bool VIEW = false>
+__device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally, uint32_t* esc = nullptr, uint32_t sun_plane = 0u, uint32_t view_plane = 0u) {
 	r.hit = false;
 	r.d = dir;
 	// intersect_aabb_branchless2 (voxel.cuh:13-24).  For an origin strictly inside the box every slab entry time is
@@ -435,8 +438,10 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 	// octant of the direction: a zero component never moves, either plane is valid for it
 	const uint32_t oct = (dir.x < 0.f ? 1u : 0u) | (dir.y < 0.f ? 2u : 0u) | (dir.z < 0.f ? 4u : 0u);
 	r.field_off = sun_plane ? sun_plane : oct * sc.cf_plane;
+	if (VIEW) r.field_off = view_plane ? view_plane : r.field_off;
 	r.p = cell_offset(sc, r.field_off, px, py, pz);
 	if (ESC) *esc = sc.escape[__umul24(oct, sc.cf_pxy) + (static_cast<uint32_t>(py + 1) << sc.cf_shift) + static_cast<uint32_t>(px + 1)]; // escape_index
+	if (ESC && VIEW) *esc += r.field_off - oct * sc.cf_plane; // (0 for a ray on its octant plane; overwritten below for one on the sun plane)
 	if (ESC) *esc = sun_plane ? sun_plane + sc.cf_plane : *esc;
 	const float cbx = dir.x > 0.f ? static_cast<float>(px + 1) : static_cast<float>(px);
 	const float cby = dir.y > 0.f ? static_cast<float>(py + 1) : static_cast<float>(py);

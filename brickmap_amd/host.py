@@ -962,6 +962,25 @@ class Scene:
         check(self._L.bm_scene_sun_plane_stats(self.gpuScene, C.byref(builds), C.byref(ms)))
         return int(builds.value), float(ms.value)
 
+    def view_plane(self):
+        """bm_scene_view_plane: (plane, origin) -- the view plane as last built, uint8 [cells_z + 2, cells + 2, cells + 2] with its border, and
+        the origin it was built for as float32 [3]; (None, None) while no plane stands."""
+        n = C.c_size_t(0)
+        origin = np.zeros(3, np.float32)
+        check(self._L.bm_scene_view_plane(self.gpuScene, None, 0, C.byref(n), origin.ctypes.data))
+        if n.value == 0:
+            return None, None
+        out = np.zeros(n.value, np.uint8)
+        check(self._L.bm_scene_view_plane(self.gpuScene, out.ctypes.data, out.size, C.byref(n), None))
+        c = self.grid_size // 8 + 2
+        return out.reshape(-1, c, c), origin
+
+    def view_plane_stats(self):
+        """bm_scene_view_plane_stats: (builds so far, device ms of the last build)."""
+        builds, ms = C.c_uint64(0), C.c_float(0)
+        check(self._L.bm_scene_view_plane_stats(self.gpuScene, C.byref(builds), C.byref(ms)))
+        return int(builds.value), float(ms.value)
+
     def escape_table(self):
         """bm_scene_escape_table: the device's escape heights as thresholds, int32 [8, cells, cells] (octant, y, x)."""
         n = C.c_size_t(0)

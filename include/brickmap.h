@@ -245,6 +245,17 @@ BM_API int bm_scene_shadow_heights(bm_scene* scene, uint32_t* dst, size_t capaci
 /* how often the sun plane has been built since the scene was created, and the device time of the last build in ms (0 before the first;
  * waits for that build).  A rebuild of the shadow heights alone (above) is not counted as a build, but last_build_ms is then its time. */
 BM_API int bm_scene_sun_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms);
+/* ---- the view plane: a tenth plane of the cube field that only primary rays read, built for ONE camera position (the origin of the first
+ * frame of a production launch) once the camera rests there: the launch holds at least two frames from that origin, or the production
+ * launch before it started from it.  Rebuilt on the same terms after the world has changed; positions outside the world box, cameras
+ * with a lens and scenes whose tenth plane could not be allocated do without, and a camera that moves every frame never builds one.
+ * bm_scene_view_plane copies the plane as it was last built (waits for the device), in the sun plane's layout: 0: the cell holds a brick;
+ * 255: no ray from the origin that visits the cell can hit anything from here on; n: no such ray enters an occupied cell before one of
+ * its axes has moved n cells.  *bytes = the size needed, 0 when no plane stands (also when dst is null); origin3 (may be null) gets the
+ * origin it was built for.  The plane takes one more plane of the cube field's size (cube_field_bytes / 8), counted nowhere else.
+ * bm_scene_view_plane_stats: how often it has been built, and the device time of the last build in ms (0 before the first; waits for it). */
+BM_API int bm_scene_view_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, float* origin3);
+BM_API int bm_scene_view_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms);
 /* device time of the last batch that changed the scene (hipEvents on the load stream): the scatter (pool moves, bricks, words)
  * and the cube-field update with the escape-height update behind it (0 when no cell's occupancy changed); waits for that batch */
 BM_API int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms);
