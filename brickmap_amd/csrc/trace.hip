@@ -29,7 +29,9 @@ namespace bm {
 // sample of a pixel, shadow rays may run on helper lanes (HELP below), every event is added to the pixel with float atomics.
 //
 // Path state machine per lane:
-//   GEN -> [extend ray] -> EXT_DONE (shade) -> [shadow ray] -> SHD_DONE (connect) -> BOUNCE -> [extend ray] ...
+//   GEN -> SETUP_EXT -> [extend ray] -> EXT_DONE (shade) -> SETUP_SHD -> [shadow ray] -> SHD_DONE (connect) -> SETUP_EXT -> [extend ray] ...
+//   (SHD_LAST for SHD_DONE where the path ends after the shadow ray: connect -> GEN; a SETUP_* state lasts from the block of a shade
+//   pass that decides on the ray to the set-up block of the same pass)
 // A wave interleaves three kinds of work, each run only when enough lanes want it (or nothing else can
 // run), so that the expensive, rarely-needed code never executes for a handful of lanes:
 //   phase A  the brick-grid walk: exact jumps over empty cubes (ST_JUMP) / single moves near the surface (ST_OUTER),
@@ -61,7 +63,16 @@ __device__ __forceinline__ void pixel_atomic_add(float* p, float v) {
 	[[clang::atomic(ignore_denormal_mode)]] { (void)__hip_atomic_fetch_add((float_in_global_memory*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 }
 
-enum : int { P_GEN = 0, P_EXT_DONE = 1, P_SHD_DONE = 2, P_BOUNCE = 3, P_HELPER = 6 };
+// A lane whose next ray is decided in a shade pass says so in its path state alone: P_SETUP | <the state the ray will be in flight in>.
+// The set-up block at the end of the pass is the only reader -- "is there a ray to set up", "is it a shadow ray" and the state that
+// follows are all that one word, so no block before it carries a flag of its own or copies a ray into temporaries (see phase C).
+// The same word says what the ray in flight is -- an extend ray is P_EXT_DONE, every other value a shadow ray -- and whether the path
+// ends after its pending shadow ray (P_SHD_LAST: the bounce limit was reached when it was drawn): no lane carries a flag for either.
+enum : int { P_GEN = 0, P_EXT_DONE = 1, P_SHD_DONE = 2, P_SHD_LAST = 3, P_HELPER = 6, P_SETUP = 8,
+             P_SETUP_EXT = P_SETUP | P_EXT_DONE,        // an extend ray from hitp along bdir with normal pn: a bounce, or a primary ray
+             P_SETUP_SHD = P_SETUP | P_SHD_DONE,        // the lane's own shadow ray, drawn in this pass, from hitp along the cone sample in r.d
+             P_SETUP_SHD_LAST = P_SETUP | P_SHD_LAST,   //   ... of a path that ends after it
+             P_SETUP_HELP = P_SETUP | P_HELPER };       // a shadow ray taken from another lane in this pass (origin and direction read into hitp and r.d)
 enum : int { ST_IDLE = 4, ST_CONN = 5 };
 
 // Resident waves per SIMD of the production instantiations (the register budget follows: 512 / waves, in steps of 8).  Round 5:
@@ -237,13 +248,11 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 	r.hit = false;
 	r.n = mk(0.f, 0.f, 0.f);
 	int state = ST_IDLE;
-	int pstate = P_GEN;
+	int pstate = P_GEN;      // where the path is -- and with it the kind of the ray in flight, and whether the path ends after its pending shadow ray
 	int s = 0;               // sample being traced
 	int s_end = 0;           // first sample that is no longer this lane's
 	int bounces = 0;
-	bool shadow = false;     // kind of the ray in flight
-	bool terminated = false; // path ends after its pending shadow ray
-	f3 hitp = mk(0.f, 0.f, 0.f);   // surface point: shadow-ray origin and next extend origin
+	f3 hitp = mk(0.f, 0.f, 0.f);   // surface point: shadow-ray origin and next extend origin (between paths: the next primary ray's origin)
 	f3 pn = mk(0.f, 0.f, 0.f);     // surface normal of the path (RayQueue::normal)
 	f3 scolor = mk(0.f, 0.f, 0.f); // ShadowQueue::color
 	f3 bdir = mk(0.f, 0.f, 0.f);   // next bounce direction, drawn in shade, used once the shadow ray is done
@@ -462,10 +471,15 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 			// no hand-over, no ST_CONN wait and no second visit of this pass; the lane goes on as if the surface faced away from the sun)
 			unsigned long long t_sub = t_phase;
 			(void)t_sub;
+			// THE NEXT RAY'S INPUTS HAVE ONE HOME EACH, and no block copies them anywhere: the origin is `hitp` (the surface point of a
+			// bounce or a shadow ray; primary_ray writes the camera's there; a helper reads the giver's there -- an idle lane's is dead), the
+			// direction is `bdir` for an extend ray (the bounce direction; primary_ray writes the camera ray's there -- dead between
+			// paths) and `r.d` for a shadow ray (the cone sample is drawn into the finished ray's direction, which the sky block reads
+			// either way; a helper reads the giver's there), the normal is `pn` (zero for a primary ray) or zero for a shadow ray.  A block
+			// that decides which ray comes next only sets `pstate`; the set-up block selects among the homes, once per component.
+			// (One variable assigned in six divergent branches is what this replaces: the compiler makes copies of that in every branch
+			// -- and of every constant such a branch sets.)
 			BM_REGION("C.connect");
-			bool need_setup = false;
-			bool hand = false; // HELP: this lane has just drawn a shadow ray that an idle lane may take
-			f3 ro = mk(0.f, 0.f, 0.f), rd = mk(0.f, 0.f, 0.f);
 			if (state == ST_NEED || state == ST_CONN) {
 				if (state == ST_CONN) {
 					// ---- connect (kernel.cu:328-346) -- runs after shade within the same reference frame -- then the stored bounce
@@ -501,13 +515,12 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 							add_rgb(scolor);
 						}
 						state = ST_NEED;
-						if (terminated) {
+						if (pstate == P_SHD_LAST) {
 							s++;
 							pstate = P_GEN; // the next primary ray (or the pixel hand-back) follows below
 						} else {
 							bounces++;
-							pstate = P_BOUNCE; // neither shaded nor generated below: only set up
-							ro = hitp; rd = bdir; r.n = pn; shadow = false; need_setup = true;
+							pstate = P_SETUP_EXT; // the stored bounce ray: neither shaded nor generated below, only set up
 						}
 					}
 				}
@@ -550,17 +563,16 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 						}
 					}
 					const bool primary_only = fg.flags & 1u; // BM_FLAG_PRIMARY_ONLY
-					// direction whose sky terms are needed: the ray itself on a miss, the sun sample on a hit
-					f3 view = r.d; // RayQueue::direction of the extend ray that just finished
-					f3 miss_color = mk(0.f, 0.f, 0.f);
-					float sunLight = 0.f;
+					// direction whose sky terms are needed: the ray itself on a miss, the sun sample on a hit -- both in r.d, RayQueue::direction
+					// of the extend ray that just finished, which the hit branch overwrites with the cone sample once the surface point is known
+					float sunLight = 0.f; // (written by the hit branch, read where `cast` says so: no value of its own on the other ways here)
 					bool cast = false;
-					uint32_t sh_cell = 0u, sh_entry = 0u; // kShade: the shadow ray's cell on the sun plane and its column's shadow height (dark: cell < entry)
 					if (is_hit && !primary_only) {
 						// ---- shade, hit branch (kernel.cu:255-302); frame = base_frame + bounce, queue slot = slot.
 						// throughput is identically (1,1,1) (kernel.cu:261,271) and is not carried.
 						hitp = hitp + r.d * r.distance;
 						hitp = hitp + pn * 2.f * kEpsilon;
+						uint32_t sh_cell = 0u, sh_entry = 0u; // kShade: the shadow ray's cell on the sun plane and its column's shadow height (dark: cell < entry)
 						if (kShade) {
 							// SHADOW HEIGHTS (shadowheight.h).  The shadow ray's origin is final; shadow_origin gives the very cell ray_setup would start
 							// it in and its column's entry of the table, whose load is on its way while the cone sample is drawn (issued where it is
@@ -575,10 +587,10 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 						const uint32_t frame = fc.base_frame + static_cast<uint32_t>(bounces);
 						const uint32_t slot = p + static_cast<uint32_t>(fc.sample_base + s) * W * H;
 						uint32_t sseed = (frame * p * 147565741u) * 720898027u * slot;
-						view = cone_sample(fc, sseed);
-						sunLight = dot(pn, view);
+						r.d = cone_sample(fc, sseed);
+						sunLight = dot(pn, r.d);
 						cast = sunLight > 0.f;
-						terminated = !(bounces < fg.max_bounces);
+						const bool terminated = !(bounces < fg.max_bounces); // the path ends here, after this surface's shadow ray if it draws one
 						if (terminated) {
 							add_terminated(); // kernel.cu:301
 						} else {
@@ -591,31 +603,25 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 						// -- what connect would do for it two passes from now happens in this one.  (The cone sample is drawn all the same: the
 						// bounce direction continues its stream.)
 						if (kShade) cast = cast && !(sh_cell < sh_entry);
-						if (!cast) {
-							if (terminated) { s++; pstate = P_GEN; }
-							else { bounces++; ro = hitp; rd = bdir; r.n = pn; shadow = false; need_setup = true; }
-						}
+						if (cast) pstate = terminated ? P_SETUP_SHD_LAST : P_SETUP_SHD; // a shadow ray (its colour: the sky block; HELP: an idle lane may take it, below)
+						else if (terminated) { s++; pstate = P_GEN; }
+						else { bounces++; pstate = P_SETUP_EXT; }
 					}
 					BM_MARK(1, t_sub); // shade, hit branch (cone sample, bounce direction)
 					BM_REGION("C.sky");
 					if (!is_hit || cast) {
-						const SkyView sv = sky_view(fc, view);
+						const SkyView sv = sky_view(fc, r.d);
 						if (cast) {
 							scolor = (sun_from_view(fc, sv) * sunLight) * 1E-5f; // kernel.cu:278
-							ro = hitp; rd = view;
-							shadow = true;
-							need_setup = true;
-							hand = HELP;
 						} else {
 							// ---- shade, miss branch (kernel.cu:316-323)
 							f3 c;
 							if (bounces == 0) c = fc.sun_angular_cos == 1.0f ? mk(1.0f, 0.0f, 0.0f) : sunsky_from_view(fc, sv);
 							else c = sky_from_view(fc, sv);
-							miss_color = c;
+							add_rgb(c);
 						}
 					}
-					if (!is_hit || primary_only) { // the path ends here
-						if (!(is_hit && primary_only)) add_rgb(miss_color); // (nothing to add for a primary-only hit)
+					if (!is_hit || primary_only) { // the path ends here (a miss has added its sky colour above; nothing to add for a primary-only hit)
 						add_terminated();
 						s++;
 						pstate = P_GEN;
@@ -627,6 +633,8 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 			if (HELP) {
 				// ---- hand shadow rays to idle lanes: the k-th lane that has one writes (origin, direction, colour, pixel) to slot k of the
 				// wave's part of the LDS staging area, the k-th idle lane reads slot k and becomes its helper
+				static_assert((P_SETUP_SHD | 1) == P_SETUP_SHD_LAST, "the two states of a shadow ray drawn in this pass differ in bit 0");
+				const bool hand = (pstate | 1) == P_SETUP_SHD_LAST; // this lane has just drawn a shadow ray (the set-up, below, ends that state in the same pass)
 				const unsigned long long hand_m = __ballot(hand), free_m = __ballot(state == ST_IDLE);
 				if (hand_m != 0ull && free_m != 0ull) {
 					const int n_pairs = min(__popcll(hand_m), __popcll(free_m));
@@ -635,32 +643,30 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					const bool gives = hand && hrank < n_pairs, takes = state == ST_IDLE && frank < n_pairs;
 					if (gives) {
 						const uint32_t k = static_cast<uint32_t>(hrank);
-						staging_word(lds_brick, k, 0) = ro.x; staging_word(lds_brick, k, 1) = ro.y; staging_word(lds_brick, k, 2) = ro.z;
-						staging_word(lds_brick, k, 3) = rd.x; staging_word(lds_brick, k, 4) = rd.y; staging_word(lds_brick, k, 5) = rd.z;
+						staging_word(lds_brick, k, 0) = hitp.x; staging_word(lds_brick, k, 1) = hitp.y; staging_word(lds_brick, k, 2) = hitp.z;
+						staging_word(lds_brick, k, 3) = r.d.x; staging_word(lds_brick, k, 4) = r.d.y; staging_word(lds_brick, k, 5) = r.d.z;
 						staging_word(lds_brick, k, 6) = scolor.x; staging_word(lds_brick, k, 7) = scolor.y; staging_word(lds_brick, k, 8) = scolor.z;
 						staging_word(lds_brick, k, 9) = __uint_as_float(local_pixel);
 						if (DBG) staging_word(lds_brick, k, 10) = __uint_as_float((static_cast<uint32_t>(s) << 8) | static_cast<uint32_t>(bounces)); // the shadow ray's digest key
 						// the owner is done with this shadow ray: what connect would have done next happens now.  (Invariants: the hand-over runs
 						// BEFORE the generate block of the same pass, which either starts the owner's next primary ray or idles the lane; the owner
-						// no longer has a shadow ray in flight either way -- say so; and a lane that TAKES a ray keeps pstate == P_HELPER through
-						// the set-up below and through connect, so it never reaches the shade / generate / write-back code with the owner's pixel)
-						shadow = false;
-						if (terminated) { s++; pstate = P_GEN; need_setup = false; }
-						else { bounces++; ro = hitp; rd = bdir; r.n = pn; }
+						// no longer has a shadow ray to set up either way -- its path state says so; and a lane that TAKES a ray is P_SETUP_HELP, then
+						// P_HELPER through connect, so it never reaches the shade / generate / write-back code with the owner's pixel)
+						if (pstate == P_SETUP_SHD_LAST) { s++; pstate = P_GEN; }
+						else { bounces++; pstate = P_SETUP_EXT; }
 					}
 					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 					__builtin_amdgcn_wave_barrier();
 					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 					if (takes) {
 						const uint32_t k = static_cast<uint32_t>(frank);
-						ro = mk(staging_word(lds_brick, k, 0), staging_word(lds_brick, k, 1), staging_word(lds_brick, k, 2));
-						rd = mk(staging_word(lds_brick, k, 3), staging_word(lds_brick, k, 4), staging_word(lds_brick, k, 5));
+						// (an idle lane's surface point and ray direction are dead: the ray is read straight into the homes the set-up reads)
+						hitp = mk(staging_word(lds_brick, k, 0), staging_word(lds_brick, k, 1), staging_word(lds_brick, k, 2));
+						r.d = mk(staging_word(lds_brick, k, 3), staging_word(lds_brick, k, 4), staging_word(lds_brick, k, 5));
 						scolor = mk(staging_word(lds_brick, k, 6), staging_word(lds_brick, k, 7), staging_word(lds_brick, k, 8));
 						local_pixel = __float_as_uint(staging_word(lds_brick, k, 9));
 						if (DBG) ray_key = __float_as_uint(staging_word(lds_brick, k, 10));
-						shadow = true;
-						pstate = P_HELPER;
-						need_setup = true;
+						pstate = P_SETUP_HELP;
 					}
 				}
 			}
@@ -696,22 +702,20 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 						// ---- primary_rays (kernel.cu:157-200) for queue slot `slot`, start_position 0
 						const uint32_t slot = p + static_cast<uint32_t>(fc.sample_base + s) * W * H;
 						uint32_t seed = (fc.base_frame * 147565741u) * 720898027u * slot;
-						primary_ray(fc, seed, xy & 0xFFFFu, xy >> 16, hitp, rd);
+						primary_ray(fc, seed, xy & 0xFFFFu, xy >> 16, hitp, bdir); // (no bounce direction is pending between two paths)
 						pn = mk(0.f, 0.f, 0.f);
 						bounces = 0;
-						terminated = false;
 						if (DBG) tally.paths++;
-						ro = hitp;
-						r.n = pn;
-						shadow = false;
-						need_setup = true;
+						pstate = P_SETUP_EXT;
 					}
 				}
 				BM_MARK(3, t_sub); // pixel hand-back + primary ray
 			}
 			BM_REGION("C.set-up");
-			if (need_setup) {
-				if (shadow) r.n = mk(0.f, 0.f, 0.f); // connect passes a zeroed normal (kernel.cu:338)
+			if (pstate >= P_SETUP) {
+				pstate &= P_SETUP - 1; // the state the ray is in flight in: P_EXT_DONE, P_SHD_DONE / P_SHD_LAST or P_HELPER
+				const bool shadow = pstate != P_EXT_DONE; // kind of the ray
+				r.n = shadow ? mk(0.f, 0.f, 0.f) : pn; // connect passes a zeroed normal (kernel.cu:338)
 				if (DBG) {
 					// digest key of the ray about to start: its path's sample and segment.  An extend ray is segment `bounces` (already counted up
 					// for a bounce ray), a shadow ray belongs to the segment that drew it (`bounces` is counted up after connect -- or was, by the
@@ -719,9 +723,9 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					if (!(HELP && pstate == P_HELPER)) ray_key = (static_cast<uint32_t>(s) << 8) | static_cast<uint32_t>(bounces);
 					ray_loads0 = tally.index_loads;
 				}
-				pstate = shadow ? ((HELP && pstate == P_HELPER) ? P_HELPER : P_SHD_DONE) : P_EXT_DONE;
+				const f3 dir = shadow ? r.d : bdir;
 				// the plane this ray walks instead of its octant's: the sun plane for a shadow ray, the view plane for a primary ray, 0 = none
-				const int st = ray_setup<DBG, kEscape, kView>(sc, ro, rd, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u,
+				const int st = ray_setup<DBG, kEscape, kView>(sc, hitp, dir, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u,
 															  kView && !shadow && bounces == 0 ? fc.view_field_off : 0u);
 				state = (st == ST_NEED && shadow) ? ST_CONN : st;
 			}
@@ -757,7 +761,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 			if (state == ST_CAND) {
 				int st = process_candidate<DBG>(sc, fc.campos, r, info, tally, lds_brick);
 #endif
-				state = (st == ST_NEED && shadow) ? ST_CONN : st;
+				state = (st == ST_NEED && pstate != P_EXT_DONE) ? ST_CONN : st;
 			}
 #if defined(BM_PHASE_TIMING) && !defined(BM_SHARE_PROBE)
 			{ // longest 8^3 walk of this pass (= its loop length) and the lanes' own walk lengths
@@ -785,7 +789,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 						int st;
 						if (!(r.cube & kCubeNoJump)) st = field_jump<DBG, true, kEscape>(sc, r, tally, esc);
 						else st = field_step<DBG>(sc, r, tally); // tmax outside the range jump.h handles (first move of a ray that starts on a cell face)
-						state = (st == ST_NEED && shadow) ? ST_CONN : st;
+						state = (st == ST_NEED && pstate != P_EXT_DONE) ? ST_CONN : st;
 					}
 					if (BM_JUMP_PASSES > 1) { // another pass right away while most of the walkers are still walking (saves a scheduler round)
 						const int still = __popcll(__ballot(state == ST_JUMP) | __ballot(state == ST_OUTER));
@@ -800,7 +804,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					if (BM_TIMED) { runsA++; lanesA += __popcll(__ballot(state == ST_OUTER)); }
 					if (state == ST_OUTER) {
 						const int st = field_step<DBG>(sc, r, tally);
-						state = (st == ST_NEED && shadow) ? ST_CONN : st;
+						state = (st == ST_NEED && pstate != P_EXT_DONE) ? ST_CONN : st;
 					}
 				}
 			}

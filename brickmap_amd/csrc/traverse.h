@@ -221,12 +221,14 @@ struct RayState {
 	uint32_t p;         // current brick cell AS THE BYTE OFFSET OF ITS CUBE-FIELD ENTRY (octant plane included, see cell_offset): the
 	                    // walk's lookup is a load at this offset, no address arithmetic; coordinates are recovered at candidates only
 	int sx, stepy, stepz; // increment of that offset for a move along x / y / z: sign(d) * (1, row pitch, slice pitch)
-	float tminn;
 	f3 n;               // normal carried in/out of the traversal (voxel.cuh:135 `normal`)
 	int last_step;      // offset increment of the last move (0 before the first): which axis it was, see move_axis
 	uint32_t field_off;      // byte offset in DeviceScene::cube_field of the plane the ray walks: its octant's, or the sun plane for a shadow ray that has one (ray_setup)
 	uint32_t cube;           // edge of the empty cube ahead of the current cell (its cube_field byte)
-	float distance;     // result
+	// ONE register for two values that are never alive together: `tminn`, the distance to the world box that ray_setup found (0 for a ray
+	// that starts inside), is read exactly once more, by the candidate that ends the ray -- in the very sum that becomes `distance`, the
+	// result, which nothing reads before that.  (A lane carries every field of this record round the scheduler loop.)
+	union { float tminn; float distance; };
 	bool hit;
 };
 
