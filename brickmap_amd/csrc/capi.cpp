@@ -126,14 +126,19 @@ int bm_scene_set_voxels(bm_scene* scene, int n, const int32_t* xyz, const uint8_
 	return scene->impl.edit(static_cast<int>(edits.size()), edits.data(), static_cast<hipStream_t>(hip_stream));
 }
 
-int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.device_cube_field(dst, capacity, bytes); }
+// the readbacks of the walk fields (walk_fields.h) need the world on the device; the build statistics do not
+#define BM_FIELDS(scene, f)                                         \
+	BM_NEED(scene);                                                 \
+	bm::WalkFields* const f = (scene)->impl.fields_on_device();     \
+	if (!f) return BM_ESTATE
+int bm_scene_device_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_FIELDS(scene, f); return f->device_cube_field(dst, capacity, bytes); }
 int bm_scene_host_cube_field(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes) { BM_NEED(scene); return scene->impl.host_cube_field(dst, capacity, bytes); }
-int bm_scene_escape_table(bm_scene* scene, int32_t* dst, size_t capacity, size_t* count) { BM_NEED(scene); return scene->impl.escape_table(dst, capacity, count); }
-int bm_scene_sun_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12) { BM_NEED(scene); return scene->impl.sun_plane(dst, capacity, bytes, plan12); }
-int bm_scene_shadow_heights(bm_scene* scene, uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4) { BM_NEED(scene); return scene->impl.shadow_heights(dst, capacity, count, bytes, plan4); }
-int bm_scene_sun_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms) { BM_NEED(scene); return scene->impl.sun_plane_stats(builds, last_build_ms); }
-int bm_scene_view_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, float* origin3) { BM_NEED(scene); return scene->impl.view_plane(dst, capacity, bytes, origin3); }
-int bm_scene_view_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms) { BM_NEED(scene); return scene->impl.view_plane_stats(builds, last_build_ms); }
+int bm_scene_escape_table(bm_scene* scene, int32_t* dst, size_t capacity, size_t* count) { BM_FIELDS(scene, f); return f->escape_table(dst, capacity, count); }
+int bm_scene_sun_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12) { BM_FIELDS(scene, f); return f->sun_plane(dst, capacity, bytes, plan12); }
+int bm_scene_shadow_heights(bm_scene* scene, uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4) { BM_FIELDS(scene, f); return f->shadow_heights(dst, capacity, count, bytes, plan4); }
+int bm_scene_sun_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms) { BM_NEED(scene); return scene->impl.fields().sun_plane_stats(builds, last_build_ms); }
+int bm_scene_view_plane(bm_scene* scene, uint8_t* dst, size_t capacity, size_t* bytes, float* origin3) { BM_FIELDS(scene, f); return f->view_plane(dst, capacity, bytes, origin3); }
+int bm_scene_view_plane_stats(bm_scene* scene, uint64_t* builds, float* last_build_ms) { BM_NEED(scene); return scene->impl.fields().view_plane_stats(builds, last_build_ms); }
 int bm_scene_last_edit_ms(bm_scene* scene, float* scatter_ms, float* field_ms) { BM_NEED(scene); return scene->impl.last_edit_ms(scatter_ms, field_ms); }
 
 int bm_scene_load_voxels(bm_scene* scene, const uint8_t* voxels, size_t bytes, int where, void* hip_stream) {

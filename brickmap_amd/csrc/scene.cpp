@@ -15,8 +15,6 @@
 #include <unordered_map>
 
 #include "buffer_checks.h"
-#include "escape.h"
-#include "kernels.h"
 #include "label.h"
 
 namespace bm {
@@ -39,48 +37,6 @@ Scene::~Scene() {
 	hipSetDevice(device_); // the members free themselves on it (scene.h: the arena synchronises before it unmaps, the streams go last)
 }
 
-// octant cube field, device layout: rows padded to a power of two (1 << shift bytes), pxy = bytes of a slice, plane = bytes of one of the 8
-// planes.  The walk keeps a ray's cell as ONE 32-bit byte offset into the 8 planes and steps slices with 23-bit immediates (traverse.h cell_offset).
-namespace {
-struct CubeFieldLayout {
-	int shift;
-	uint64_t pxy, plane;
-	bool fits, ninth, tenth;
-};
-CubeFieldLayout cube_field_layout(const WorldDims& d) {
-	int shift = 2;
-	while ((1 << shift) < d.cells + 2) ++shift;
-	CubeFieldLayout l{};
-	l.shift = shift;
-	l.pxy = static_cast<uint64_t>(d.cells + 2) << shift;
-	l.plane = l.pxy * static_cast<uint64_t>(d.cells_height + 2);
-	l.fits = l.pxy < (1ull << 23) && l.plane * 8 < (1ull << 32);
-	l.ninth = BM_SUNFIELD != 0 && l.fits && l.plane * 9 < (1ull << 32); // the sun plane's offsets fit 32 bits as well
-	l.tenth = BM_VIEWFIELD != 0 && l.ninth && l.plane * 10 < (1ull << 32); // ... and the view plane's, behind it
-	return l;
-}
-
-// The box of the cube field that has to be recomputed when the occupancy of the cells in [lo, hi] (unbordered, inclusive) has changed:
-// an entry can change up to 254 cells away from a changed cell (kernels.h FieldUpdate)
-FieldUpdate field_update_box(const WorldDims& d, const int lo[3], const int hi[3]) {
-	FieldUpdate fu{};
-	const int lim[3] = {d.cells, d.cells, d.cells_height};
-	int r0[3], r1[3];
-	for (int k = 0; k < 3; ++k) { // bordered coordinates: interior cells are 1 ... lim
-		r0[k] = std::max(1, lo[k] + 1 - 254);
-		r1[k] = std::min(lim[k] + 1, hi[k] + 1 + 254 + 1);
-	}
-	fu.rx0 = r0[0]; fu.rx1 = r1[0]; fu.ry0 = r0[1]; fu.ry1 = r1[1]; fu.rz0 = r0[2]; fu.rz1 = r1[2];
-	fu.ay0 = std::max(1, fu.ry0 - 254); fu.ay1 = std::min(d.cells + 1, fu.ry1 + 254);
-	fu.bz0 = std::max(1, fu.rz0 - 254); fu.bz1 = std::min(d.cells_height + 1, fu.rz1 + 254);
-	fu.cells = d.cells; fu.cells_height = d.cells_height;
-	fu.sg_xy = d.supergrid_xy; fu.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
-	const CubeFieldLayout l = cube_field_layout(d);
-	fu.cf_shift = l.shift; fu.cf_pxy = static_cast<uint32_t>(l.pxy); fu.cf_plane = static_cast<uint32_t>(l.plane);
-	return fu;
-}
-} // namespace
-
 int Scene::require_on_device() const {
 	if (!on_device_) { set_error("scene not generated"); return BM_ESTATE; }
 	return 0;
@@ -101,8 +57,8 @@ int Scene::init(int grid_size, int grid_height) {
 		return BM_EINVAL;
 	}
 	// the walk keeps a ray's cell as ONE 32-bit byte offset into the 8 planes of the octant cube field, whose rows are padded to a
-	// power of two (traverse.h cell_offset; allocate_device lays it out): 8 x (cells_h + 2) x (cells + 2) x 2^shift bytes < 4 GiB
-	if (!cube_field_layout(world.dims).fits) { // (the slice-pitch limit cannot be what fails here: cells <= 1024 above)
+	// power of two (traverse.h cell_offset; walk_fields.h lays it out): 8 x (cells_h + 2) x (cells + 2) x 2^shift bytes < 4 GiB
+	if (!WalkFields::layout(world.dims).fits) { // (the slice-pitch limit cannot be what fails here: cells <= 1024 above)
 		set_error("world too large: the octant cube field (8 planes of (cells_h + 2) x (cells + 2) rows padded to a power of two) must stay below 4 GiB -- cubic worlds up to 5760 voxels a side");
 		return BM_EINVAL;
 	}
@@ -168,8 +124,7 @@ void Scene::residency_rebuilt(bool preloaded) {
 	use_ring(0);
 	snapshot_pending_ = false;
 	preloaded_ = preloaded;
-	shadow_dirty_ = true; // the shadow heights count resident bricks, and only where all of them are (ensure_sun_plane)
-	shadow_full_valid_ = false;
+	fields_.book().residency_rebuilt();
 	staging_busy_ = false;
 	failed_ = false;
 	stream_batches_ = stream_host_ns_ = 0;
@@ -222,11 +177,7 @@ void Scene::free_device() {
 	(void)d_index_grid_.release();
 	(void)d_pool_base_.release();
 	arena_.close();
-	(void)d_cube_field_.release();
-	sun_plane_ = sun_built_ = false;
-	view_plane_ = view_built_ = false;
-	(void)d_escape_.release();
-	(void)d_escape_cols_.release();
+	fields_.release();
 	on_device_ = false;
 }
 
@@ -259,22 +210,17 @@ int Scene::allocate_device() {
 	if (int e = alloc_index_grid()) return e;
 	if (int e = arena_.open(device_, 4 * run + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
 	view_.brick_arena = arena_.base();
-	if (int e = alloc_cube_field()) return e;
+	if (int e = fields_.allocate(d, &view_)) return e;
 	{ // the host builds the field with tight rows (world.cpp) and every slice is copied row by row
 		std::vector<uint8_t> field;
 		world.build_cube_field(field, 8);
-		const int X = d.cells + 2, Z = d.cells_height + 2;
-		// 8 planes x Z slices, each X rows of X bytes -> rows of 2^shift bytes (the padding is never read)
-		for (int o = 0; o < 8; ++o)
-			BM_HIP(hipMemcpy2D(d_cube_field_ + static_cast<size_t>(o) * view_.cf_plane, static_cast<size_t>(1) << view_.cf_shift, field.data() + static_cast<size_t>(o) * X * X * Z, X, X,
-							   static_cast<size_t>(X) * Z, hipMemcpyHostToDevice));
+		if (int e = fields_.upload(field.data())) return e;
 	}
 	set_view_dims();
 	on_device_ = true;
 	if (int e = reset_residency()) return e;
-	// the escape heights, from the index words reset_residency has just written: which words are non-zero never changes with residency
-	launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(0, d.cells, 0, d.cells), load_stream_);
-	BM_HIP(hipGetLastError());
+	// the escape heights alone (the field is the host's), from the index words reset_residency has just written: which words are non-zero never changes with residency
+	if (int e = fields_.update(d_index_grid_, FieldChange::whole(d), false, load_stream_)) return e;
 	BM_HIP(hipStreamSynchronize(load_stream_));
 	return 0;
 }
@@ -290,58 +236,6 @@ int Scene::alloc_index_grid() {
 	view_.pool_base = d_pool_base_;
 	view_.brick_arena = nullptr;
 	return 0;
-}
-
-// octant cube field: what the walk reads instead of index words while it crosses empty space.  Device layout: rows padded to a
-// power of two, so that a cell's entry offset -- which is what a ray carries as its position (traverse.h cell_offset) -- moves by
-// +-1 / +- 2^shift / +- slice pitch.  Allocated and set to 255 everywhere; the interior is the caller's (a host build copied up, or
-// the GPU passes of edit.hip).
-int Scene::alloc_cube_field() {
-	const CubeFieldLayout l = cube_field_layout(world.dims);
-	if (!l.fits) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
-	// a ninth plane behind the eight is the sun plane of shadow rays (sunfield.h), where it can be had: a scene without it renders as before
-	sun_plane_ = view_plane_ = false;
-	// ... and a tenth the view plane of primary rays (viewfield.h), on the same terms
-	if (l.tenth) {
-		if (d_cube_field_.alloc(l.plane * 10) == 0) sun_plane_ = view_plane_ = true;
-		else { (void)hipGetLastError(); set_error(""); }
-	}
-	if (!sun_plane_ && l.ninth) {
-		if (d_cube_field_.alloc(l.plane * 9) == 0) sun_plane_ = true;
-		else { (void)hipGetLastError(); set_error(""); } // (doing without the plane is no error: neither HIP's slot nor ours keeps it)
-	}
-	if (!sun_plane_) { if (int e = d_cube_field_.alloc(l.plane * 8)) return e; }
-	sun_built_ = false; // (whoever fills the field afterwards has a new world)
-	shadow_full_valid_ = false;
-	shadow_zero_ = true; // (the memset of the escape allocation below)
-	sun_dirty_ = true;
-	view_built_ = false;
-	view_dirty_ = true;
-	BM_HIP(hipMemset(d_cube_field_, 255, d_cube_field_.bytes())); // the row padding reads as border cells: a stray offset ends a walk instead of reading whatever was there
-	view_.cf_shift = l.shift;
-	view_.cf_pxy = static_cast<uint32_t>(l.pxy);
-	view_.cf_plane = static_cast<uint32_t>(l.plane);
-	division_magic(view_.cf_pxy, &view_.cf_magic, &view_.cf_magic_shift);
-	view_.cube_field = d_cube_field_;
-	// ... and the escape heights that go with it (escape.h)
-	// (a ninth slice behind the octants' eight holds the shadow heights of the sun plane's cone, shadowheight.h: zero = no dark cell)
-	if (int e = d_escape_.alloc((escape_entries(view_.cf_pxy) + (BM_SHADOWHEIGHT != 0 ? view_.cf_pxy : 0u)) * sizeof(uint32_t))) return e;
-	BM_HIP(hipMemset(d_escape_, 0, d_escape_.bytes())); // (border and padding entries: never read, never written)
-	if (int e = d_escape_cols_.alloc(escape_columns_bytes(world.dims.cells))) return e;
-	view_.escape = d_escape_;
-	return 0;
-}
-
-EscapeUpdate Scene::escape_update_box(int x0, int x1, int y0, int y1) const {
-	const WorldDims& d = world.dims;
-	EscapeUpdate u{};
-	u.x0 = std::max(0, x0); u.x1 = std::min(d.cells, x1); u.y0 = std::max(0, y0); u.y1 = std::min(d.cells, y1);
-	if (u.x1 < u.x0) u.x1 = u.x0;
-	if (u.y1 < u.y0) u.y1 = u.y0;
-	u.cells = d.cells; u.cells_height = d.cells_height;
-	u.sg_xy = d.supergrid_xy; u.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
-	u.cf_shift = view_.cf_shift; u.cf_pxy = view_.cf_pxy; u.cf_plane = view_.cf_plane;
-	return u;
 }
 
 void Scene::set_view_dims() {
@@ -489,7 +383,7 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	world.generated = false;
 	for (Event& ev : ev_load_time_) if (int e = ev.create()) return e;
 	if (int e = alloc_index_grid()) return e;
-	if (int e = alloc_cube_field()) return e;
+	if (int e = fields_.allocate(d, &view_)) return e;
 	set_view_dims();
 	LoadDims ld{static_cast<uint32_t>(d.grid_size), static_cast<uint32_t>(d.supergrid_xy), static_cast<uint32_t>(d.supergrid_xy * d.supergrid_xy),
 				static_cast<uint32_t>(d.supercells)};
@@ -497,10 +391,9 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	DeviceBuffer<uint32_t> counts;
 	if (int e = counts.alloc((static_cast<size_t>(d.supercells) + 2) * sizeof(uint32_t))) return e;
 	uint32_t* d_total = counts + d.supercells;
-	// the field comes from the update of edit.hip with the box = every cell, into the field alloc_cube_field set to 255
-	const int box_lo[3] = {0, 0, 0}, box_hi[3] = {d.cells - 1, d.cells - 1, d.cells_height - 1};
-	const FieldUpdate fu = field_update_box(d, box_lo, box_hi);
-	if (int e = d_cf_tmp_.reserve(field_update_tmp_bytes(fu))) return e; // (load_voxels has synchronised the device)
+	// the field comes from the update of edit.hip with the box = every cell, into the field the allocation set to 255
+	const FieldChange all = FieldChange::whole(d);
+	if (int e = fields_.prepare_update(all, nullptr)) return e; // (load_voxels has synchronised the device: no stream to wait for, unlike submit_batch)
 	BM_HIP(hipEventRecord(ev_edit_caller_, stream)); // the volume is whatever the caller's stream has written by now
 	BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
 	// ---- classify + number
@@ -523,10 +416,7 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(ev_load_time_[3], load_stream_));
 	// ---- field
-	launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
-	BM_HIP(hipGetLastError());
-	launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(0, d.cells, 0, d.cells), load_stream_);
-	BM_HIP(hipGetLastError());
+	if (int e = fields_.update(d_index_grid_, all, true, load_stream_)) return e;
 	BM_HIP(hipEventRecord(ev_load_time_[4], load_stream_));
 	// ---- mirror: the host world becomes what World::load_voxels builds, in the state preload_all leaves it in
 	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell), bases(d.supercells);
@@ -833,9 +723,9 @@ int Scene::info(bm_scene_info* out) {
 	out->index_bytes = on_device_ ? static_cast<uint64_t>(d.supercells) * kCellsPerSupercell * 4 : 0;
 	out->brick_bytes = on_device_ ? arena_.capacity() * 64 : 0;
 	out->pool_bytes = on_device_ ? arena_.pool_bricks() * 64 : 0;
-	out->cube_field_bytes = on_device_ ? 8 * static_cast<uint64_t>(view_.cf_plane) : 0; // (the octant planes; the sun plane, where there is one, is one more plane)
-	out->escape_bytes = on_device_ ? escape_entries(view_.cf_pxy) * sizeof(uint32_t) : 0; // (the octants' slices; the shadow heights' slice: bm_scene_shadow_heights)
-	out->sun_plane_bytes = on_device_ && sun_plane_ ? static_cast<uint64_t>(view_.cf_plane) + d_sun_tmp_.bytes() : 0;
+	out->cube_field_bytes = on_device_ ? fields_.cube_field_bytes() : 0;
+	out->escape_bytes = on_device_ ? fields_.escape_bytes() : 0;
+	out->sun_plane_bytes = on_device_ ? fields_.sun_plane_bytes() : 0;
 	out->arena_growths = arena_.growths();
 	out->arena_copy_growths = arena_.copy_growths();
 	out->arena_virtual = arena_.is_virtual() ? 1 : 0;
@@ -942,8 +832,9 @@ int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const 
 		const uint32_t ow = old_words[j], nw = c.indices[j];
 		{
 			const int gx = sx * kSupercell + (j & 15), gy = sy * kSupercell + ((j >> 4) & 15);
-			b.touch_lo[0] = std::min(b.touch_lo[0], gx); b.touch_hi[0] = std::max(b.touch_hi[0], gx);
-			b.touch_lo[1] = std::min(b.touch_lo[1], gy); b.touch_hi[1] = std::max(b.touch_hi[1], gy);
+			FieldChange& ch = b.change;
+			ch.touch_lo[0] = std::min(ch.touch_lo[0], gx); ch.touch_hi[0] = std::max(ch.touch_hi[0], gx);
+			ch.touch_lo[1] = std::min(ch.touch_lo[1], gy); ch.touch_hi[1] = std::max(ch.touch_hi[1], gy);
 		}
 		const uint16_t ods = ow ? old_dev[ow & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
 		if (ods != kNoDeviceSlot) {
@@ -954,7 +845,7 @@ int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const 
 		}
 		if ((ow != 0) != (nw != 0)) {
 			const int g[3] = {sx * kSupercell + (j & 15), sy * kSupercell + ((j >> 4) & 15), sz * kSupercell + (j >> 8)};
-			for (int k = 0; k < 3; ++k) { b.box_lo[k] = std::min(b.box_lo[k], g[k]); b.box_hi[k] = std::max(b.box_hi[k], g[k]); }
+			for (int k = 0; k < 3; ++k) { b.change.box_lo[k] = std::min(b.change.box_lo[k], g[k]); b.change.box_hi[k] = std::max(b.change.box_hi[k], g[k]); }
 		}
 	}
 	if (!fresh_cells.empty()) { // preloaded scene: new bricks get pool slots now, freed ones first
@@ -996,7 +887,6 @@ int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const 
 // submit_batch: the staged cells go to the device on the load stream -- one copy, the pool moves, the scatter and, when some cell's
 // occupancy changed, the cube-field update -- as an upload batch.  times[0 ... 2] are recorded around the scatter and the field update.
 int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* scattered, bool* field_updated) {
-	const WorldDims& d = world.dims;
 	*scattered = *field_updated = false;
 	const uint32_t n = static_cast<uint32_t>(b.cells.size());
 	if (n == 0) { // nothing inside the world changed a brick (e.g. clearing empty space)
@@ -1008,26 +898,23 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 	auto up = [](size_t v) { return (v + 63) / 64 * 64; };
 	const size_t o_cells = up(b.moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
 				 o_bricks = o_slots + up(n * 4ull), bytes = o_bricks + n * sizeof(Brick);
-	const bool field = b.box_hi[0] >= 0;
-	const FieldUpdate fu = field ? field_update_box(d, b.box_lo, b.box_hi) : FieldUpdate{};
-	auto queue = [&]() -> int {
+	auto stage = [&]() -> int {
 		if (bytes > d_edit_.bytes()) { // (the two grow together: h_edit_ is as large as d_edit_)
 			BM_HIP(hipStreamSynchronize(load_stream_)); // the previous batch's kernels may still read the device staging
 			const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
 			if (int e = h_edit_.reserve(cap)) return e;
 			if (int e = d_edit_.reserve(cap)) return e;
 		}
-		if (field && field_update_tmp_bytes(fu) > d_cf_tmp_.bytes()) {
-			BM_HIP(hipStreamSynchronize(load_stream_));
-			if (int e = d_cf_tmp_.reserve(field_update_tmp_bytes(fu))) return e;
-		}
+		if (int e = fields_.prepare_update(b.change, load_stream_)) return e;
 		if (!b.moves.empty()) std::memcpy(h_edit_, b.moves.data(), b.moves.size() * sizeof(PoolMove));
 		std::memcpy(h_edit_ + o_cells, b.cells.data(), n * 4ull);
 		std::memcpy(h_edit_ + o_words, b.words.data(), n * 4ull);
 		std::memcpy(h_edit_ + o_slots, b.slots.data(), n * 4ull);
 		std::memcpy(h_edit_ + o_bricks, b.bricks.data(), n * sizeof(Brick));
-		// behind every frame in flight (they read the words, pool bases, bricks and field this rewrites) and the caller's queued work
-		if (int e = order_load_stream_behind_frames()) return e;
+		return 0;
+	};
+	// behind every frame in flight (they read the words, pool bases, bricks and field this rewrites) and the caller's queued work
+	auto queue = [&]() -> int {
 		BM_HIP(hipEventRecord(ev_edit_caller_, stream));
 		BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
 		BM_HIP(hipMemcpyAsync(d_edit_, h_edit_, bytes, hipMemcpyHostToDevice, load_stream_));
@@ -1042,29 +929,18 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 							load_stream_);
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipEventRecord(times[1], load_stream_));
-		// a brick's bits changed: the shadow heights count full bricks (shadowheight.h); rebuilt like the plane, before the next frame that reads
-		// them, from a scan of the touched columns alone
-		shadow_dirty_ = true;
-		for (int k = 0; k < 2; ++k) { shadow_box_[k] = std::min(shadow_box_[k], b.touch_lo[k]); shadow_box_[2 + k] = std::max(shadow_box_[2 + k], b.touch_hi[k]); }
-		if (field) {
-			launch_field_update(d_index_grid_, d_cube_field_, d_cf_tmp_, fu, load_stream_);
-			BM_HIP(hipGetLastError());
-			// the escape heights: the columns of the cells whose occupancy changed, then the quadrant passes over the whole table
-			launch_escape_update(d_index_grid_, d_escape_cols_, d_escape_, escape_update_box(b.box_lo[0], b.box_hi[0] + 1, b.box_lo[1], b.box_hi[1] + 1), load_stream_);
-			BM_HIP(hipGetLastError());
-			sun_dirty_ = true; // the sun plane is rebuilt before the next frame that reads it (ensure_sun_plane): a run of batches pays once
-			view_dirty_ = true; // ... and so is the view plane (ensure_view_plane)
-		}
+		// the field and the escape heights where some cell's occupancy changed; what that makes stale is rebuilt before the next frame that reads it
+		if (int e = fields_.update(d_index_grid_, b.change, true, load_stream_)) return e;
 		BM_HIP(hipEventRecord(times[2], load_stream_));
-		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
 		return 0;
 	};
-	if (int e = queue()) { failed_ = true; return e; } // the host world is ahead of the device: refuse to go on
+	int e = stage();
+	if (!e) e = publish_behind_frames(queue);
+	if (e) { failed_ = true; return e; } // the host world is ahead of the device: refuse to go on
 	arena_.commit_freed_regions();
 	edit_busy_ = true;
-	upload_seq_++;
 	*scattered = true;
-	*field_updated = field;
+	*field_updated = b.change.occupancy();
 	return 0;
 }
 
@@ -1460,232 +1336,33 @@ int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* l
 	return 0;
 }
 
-int Scene::device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
-	if (int e = require_on_device()) return e;
-	const WorldDims& d = world.dims;
-	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = 8 * X * X * Z;
-	if (bytes) *bytes = need;
-	if (!dst) return 0;
-	if (capacity < need) { set_error("cube field buffer too small"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	// every plane is Z slices of X rows padded to 2^cf_shift bytes, and the planes follow each other: 8 X Z rows in all
-	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_, static_cast<size_t>(1) << view_.cf_shift, X, 8 * X * Z, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-int Scene::escape_table(int32_t* dst, size_t capacity, size_t* count) {
-	if (int e = require_on_device()) return e;
-	const WorldDims& d = world.dims;
-	const size_t plane = static_cast<size_t>(d.cells) * d.cells, need = 8 * plane;
-	if (count) *count = need;
-	if (!dst) return 0;
-	if (capacity < need) { set_error("escape table buffer too small"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	std::vector<uint32_t> entries(escape_entries(view_.cf_pxy));
-	BM_HIP(hipMemcpy(entries.data(), d_escape_, entries.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	for (int o = 0; o < 8; ++o)
-		for (int y = 0; y < d.cells; ++y)
-			for (int x = 0; x < d.cells; ++x)
-				dst[o * plane + static_cast<size_t>(y) * d.cells + x] = escape_height_of(o, entries[escape_index(o, view_.cf_shift, view_.cf_pxy, x, y)], view_.cf_pxy, view_.cf_plane);
-	return 0;
-}
-
-// ---- the sun plane (sunfield.h, sunfield.hip): plane 8 of the cube field, for the cone of ONE sun.  The sun is a scene setting that stays
-// put from frame to frame (the reference sets it from a slider), so the plane is keyed on the cone and rebuilt only when a production
-// frame is about to read it and the cone or the field has changed since it was built.
+// ---- the sun plane and the view plane (walk_fields.h; field_book.h decides): each is built on the load stream by the production launch that is
+// about to read it, unless it stands.  *usable: the launch's frames with the book's key may read the plane.
 int Scene::ensure_sun_plane(const FrameConstants& fc, bool* usable) {
-	*usable = false;
-	if (!sun_plane_) return 0;
-	const SunPlan plan = sun_plan(fc.cone_dir, fc.cone_extent);
-	if (!plan.valid) return 0; // (the plane of another sun, if any, stays: the frames of this one keep their octant planes)
-	const float key[4] = {fc.cone_dir[0], fc.cone_dir[1], fc.cone_dir[2], fc.cone_extent};
-	*usable = true;
-	const bool stands = sun_built_ && !sun_dirty_ && std::memcmp(key, sun_key_, sizeof key) == 0; // the plane does; the shadow heights may still be stale
-	if (stands && !(BM_SHADOWHEIGHT != 0 && shadow_dirty_)) return 0;
-	const WorldDims& d = world.dims;
-	const int n[3] = {d.cells, d.cells, d.cells_height};
-	SunBuild u{};
-	u.plan = plan;
-	// shadow heights only where every brick is resident: a ray that ends at set-up requests nothing, and in a streaming scene the requests of
-	// the shadow rays' walks are part of what brings the bricks in (the steady state must be the resident scene's) -- there the slice is zeroed
-	u.shadow = BM_SHADOWHEIGHT != 0 && preloaded_ ? shadow_plan(fc.cone_dir, fc.cone_extent) : ShadowPlan{};
-	if (stands && !u.shadow.valid && shadow_zero_) { // (an edit batch of a streaming scene, or under a sun without shadow heights: the slice is zero and stays so, nothing to launch)
-		shadow_dirty_ = false;
-		shadow_plan_ = u.shadow;
-		return 0;
-	}
-	u.cells = d.cells; u.cells_height = d.cells_height;
-	u.sg_xy = d.supergrid_xy; u.sg_xy2 = d.supergrid_xy * d.supergrid_xy;
-	u.nd = n[plan.dom]; u.n1 = n[plan.m1]; u.n2 = n[plan.m2];
-	u.cf_shift = view_.cf_shift; u.cf_pxy = view_.cf_pxy; u.cf_plane = view_.cf_plane;
-	*usable = false;
-	for (Event& ev : ev_sun_time_) if (int e = ev.create()) return e;
-	if (sun_build_tmp_bytes(u) > d_sun_tmp_.bytes()) {
-		BM_HIP(hipStreamSynchronize(load_stream_)); // an earlier build may still use the scratch
-		if (d_sun_tmp_.reserve(sun_build_tmp_bytes(u)) != 0) { (void)hipGetLastError(); set_error(""); return 0; } // no scratch, no plane: not an error
-	}
-	if (u.shadow.valid && shadow_build_tmp_bytes(u) > d_shadow_tmp_.bytes()) {
-		BM_HIP(hipStreamSynchronize(load_stream_));
-		shadow_full_valid_ = false;
-		if (d_shadow_tmp_.reserve(shadow_build_tmp_bytes(u)) != 0) { (void)hipGetLastError(); set_error(""); return 0; }
-	}
-	// the full tops do not depend on the sun: a scan of the whole world once, afterwards of the columns that batches have touched since
-	if (!shadow_full_valid_) { u.fx0 = u.fy0 = 0; u.fx1 = u.fy1 = d.cells; }
-	else {
-		u.fx0 = std::max(0, shadow_box_[0]); u.fy0 = std::max(0, shadow_box_[1]);
-		u.fx1 = std::min(d.cells, shadow_box_[2] + 1); u.fy1 = std::min(d.cells, shadow_box_[3] + 1);
-		if (u.fx1 <= u.fx0 || u.fy1 <= u.fy0) u.fx0 = u.fx1 = u.fy0 = u.fy1 = 0;
-	}
+	FieldBook::SunStep s = fields_.book().sun_launch(fc.cone_dir, fc.cone_extent, preloaded_);
+	*usable = s.step == FieldBook::kStands;
+	if (s.step != FieldBook::kBuildSlice && s.step != FieldBook::kBuildPlane) return 0;
+	bool ready = false;
+	if (int e = fields_.prepare(&s, load_stream_, &ready)) return e;
+	if (!ready) return 0;
 	// behind every frame in flight (their shadow rays read the plane) and, on the load stream, behind the field and escape updates it reads
-	if (int e = order_load_stream_behind_frames()) return e;
-	BM_HIP(hipEventRecord(ev_sun_time_[0], load_stream_));
-	launch_sun_build(d_index_grid_, d_pool_base_, arena_.base(), d_escape_cols_, d_escape_, d_cube_field_, d_sun_tmp_, d_shadow_tmp_, u, !stands, load_stream_);
-	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_sun_time_[1], load_stream_));
-	BM_HIP(hipEventRecord(ev_upload_, load_stream_)); // frames wait for it like for an upload batch (frame_begin)
-	upload_seq_++;
-	std::memcpy(sun_key_, key, sizeof key);
-	sun_plan_ = plan;
-	sun_built_ = true;
-	sun_dirty_ = false;
-	shadow_dirty_ = false;
-	shadow_plan_ = u.shadow;
-	shadow_zero_ = !u.shadow.valid;
-	if (u.shadow.valid) { // the scan has run
-		shadow_full_valid_ = true;
-		shadow_box_[0] = shadow_box_[1] = 1 << 30; shadow_box_[2] = shadow_box_[3] = -1;
-	}
-	if (!stands) sun_builds_++;
+	if (int e = publish_behind_frames([&] { return fields_.build(s, d_index_grid_, d_pool_base_, arena_.base(), load_stream_); })) return e;
 	*usable = true;
 	return 0;
 }
 
-int Scene::sun_plane(uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12) {
-	if (int e = require_on_device()) return e;
-	const WorldDims& d = world.dims;
-	const bool have = sun_plane_ && sun_built_;
-	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = have ? X * X * Z : 0;
-	if (bytes) *bytes = need;
-	if (plan12) {
-		const SunPlan p = have ? sun_plan_ : SunPlan{};
-		const int32_t v[12] = {p.valid, p.octant, p.dom, p.m1, p.m2, p.lo1, p.hi1, p.lo2, p.hi2, p.clear, p.rise, kSunBins};
-		std::memcpy(plan12, v, sizeof v);
-	}
-	if (!dst || !have) return 0;
-	if (capacity < need) { set_error("sun plane buffer too small"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_ + 8 * static_cast<size_t>(view_.cf_plane), static_cast<size_t>(1) << view_.cf_shift, X, X * Z, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-// the shadow heights as last built: the table's entries per (y, x) -- the sun plane's offset of the column's first slice that is not dark, or 0; *bytes = what they take on the device (the slice and the build's scratch)
-int Scene::shadow_heights(uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4) {
-	if (int e = require_on_device()) return e;
-	const WorldDims& d = world.dims;
-	const bool have = BM_SHADOWHEIGHT != 0 && sun_plane_ && sun_built_;
-	const size_t need = have ? static_cast<size_t>(d.cells) * d.cells : 0;
-	if (count) *count = need;
-	if (bytes) *bytes = BM_SHADOWHEIGHT != 0 && on_device_ ? static_cast<uint64_t>(view_.cf_pxy) * sizeof(uint32_t) + d_shadow_tmp_.bytes() : 0;
-	if (plan4) {
-		const ShadowPlan p = have ? shadow_plan_ : ShadowPlan{};
-		const int32_t v[4] = {p.valid, p.sun.rise, p.rise_hi, kSunHeightUnit};
-		std::memcpy(plan4, v, sizeof v);
-	}
-	if (!dst || !have) return 0;
-	if (capacity < need) { set_error("shadow heights buffer too small"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	std::vector<uint32_t> slice(view_.cf_pxy);
-	BM_HIP(hipMemcpy(slice.data(), d_escape_ + escape_entries(view_.cf_pxy), slice.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	for (int y = 0; y < d.cells; ++y)
-		for (int x = 0; x < d.cells; ++x)
-			dst[static_cast<size_t>(y) * d.cells + x] = slice[escape_index(0, view_.cf_shift, view_.cf_pxy, x, y)];
-	return 0;
-}
-
-int Scene::sun_plane_stats(uint64_t* builds, float* last_build_ms) {
-	if (!builds || !last_build_ms) { set_error("null argument"); return BM_EINVAL; }
-	*builds = sun_builds_;
-	*last_build_ms = 0.0f;
-	if (sun_builds_ == 0) return 0;
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipEventSynchronize(ev_sun_time_[1]));
-	BM_HIP(hipEventElapsedTime(last_build_ms, ev_sun_time_[0], ev_sun_time_[1]));
-	return 0;
-}
-
-// ---- the view plane (viewfield.h, viewfield.hip): plane 9 of the cube field, for ONE camera position.  Keyed on the bits of the origin of
-// the launch's first frame and built only for a camera that rests: the launch holds at least two frames from this origin, or the
-// production launch before it started from it.  A camera that moves every frame never builds and pays nothing; a plane of another
-// position simply goes unused.  Residency and LoD never change the plane ("occupied" is "index word non-zero").
 int Scene::ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usable) {
-	*usable = false;
-	const FrameConstants& fc = fcs[0];
-	const bool rested = std::memcmp(fc.origin, view_last_origin_, sizeof view_last_origin_) == 0 && view_last_valid_;
-	std::memcpy(view_last_origin_, fc.origin, sizeof view_last_origin_);
-	view_last_valid_ = true;
-	if (!view_plane_) return 0;
-	const WorldDims& d = world.dims;
-	const ViewPlan plan = view_plan(fc.origin, fc.lens_radius, view_.grid_size_f, view_.grid_height_f, d.cells, d.cells_height);
-	if (!plan.valid) return 0;
-	if (view_built_ && !view_dirty_ && std::memcmp(fc.origin, view_key_, sizeof view_key_) == 0) { *usable = true; return 0; }
-	int same = 0;
-	for (const FrameConstants& f : fcs) same += std::memcmp(f.origin, fc.origin, sizeof fc.origin) == 0 && f.lens_radius == 0.0f ? 1 : 0;
-	if (!(same >= 2 || rested)) return 0;
-	ViewBuild u{};
-	u.plan = plan;
-	u.cells = d.cells; u.cells_height = d.cells_height;
-	u.cf_shift = view_.cf_shift; u.cf_pxy = view_.cf_pxy; u.cf_plane = view_.cf_plane;
-	for (Event& ev : ev_view_time_) if (int e = ev.create()) return e;
-	// behind every frame in flight (their primary rays read the plane) and, on the load stream, behind the field and escape updates it reads
-	if (int e = order_load_stream_behind_frames()) return e;
-	BM_HIP(hipEventRecord(ev_view_time_[0], load_stream_));
-	launch_view_build(d_escape_, d_cube_field_, u, load_stream_);
-	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_view_time_[1], load_stream_));
-	BM_HIP(hipEventRecord(ev_upload_, load_stream_)); // frames wait for it like for an upload batch (frame_begin)
-	upload_seq_++;
-	std::memcpy(view_key_, fc.origin, sizeof view_key_);
-	view_built_ = true;
-	view_dirty_ = false;
-	view_builds_++;
+	const FieldBook::ViewStep v = fields_.book().view_launch(fcs, static_cast<int>(fcs.size()));
+	*usable = v.step == FieldBook::kStands;
+	if (v.step != FieldBook::kBuildPlane) return 0;
+	if (int e = publish_behind_frames([&] { return fields_.build(v, load_stream_); })) return e; // (their primary rays read the plane)
 	*usable = true;
-	return 0;
-}
-
-// the plane as last built, [z][y][x] with its border, and the origin it was built for; *bytes = 0 while there is none (or it is stale)
-int Scene::view_plane(uint8_t* dst, size_t capacity, size_t* bytes, float* origin3) {
-	if (int e = require_on_device()) return e;
-	const WorldDims& d = world.dims;
-	const bool have = view_plane_ && view_built_ && !view_dirty_;
-	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = have ? X * X * Z : 0;
-	if (bytes) *bytes = need;
-	if (origin3) for (int k = 0; k < 3; ++k) origin3[k] = have ? view_key_[k] : 0.0f;
-	if (!dst || !have) return 0;
-	if (capacity < need) { set_error("view plane buffer too small"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_ + 9 * static_cast<size_t>(view_.cf_plane), static_cast<size_t>(1) << view_.cf_shift, X, X * Z, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-int Scene::view_plane_stats(uint64_t* builds, float* last_build_ms) {
-	if (!builds || !last_build_ms) { set_error("null argument"); return BM_EINVAL; }
-	*builds = view_builds_;
-	*last_build_ms = 0.0f;
-	if (view_builds_ == 0) return 0;
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipEventSynchronize(ev_view_time_[1]));
-	BM_HIP(hipEventElapsedTime(last_build_ms, ev_view_time_[0], ev_view_time_[1]));
 	return 0;
 }
 
 int Scene::host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes) {
 	const WorldDims& d = world.dims;
-	const size_t X = static_cast<size_t>(d.cells) + 2, Z = static_cast<size_t>(d.cells_height) + 2, need = 8 * X * X * Z;
+	const size_t need = 8 * WalkFields::tight_plane_bytes(d);
 	if (bytes) *bytes = need;
 	if (!dst) return 0;
 	if (!world.generated) { set_error("world not generated"); return BM_ESTATE; }
@@ -1717,7 +1394,7 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 		if (int e = ensure_sun_plane(fc, &usable)) return e;
 		if (usable)
 			for (FrameConstants& f : fcs)
-				if (std::memcmp(f.cone_dir, sun_key_, 3 * sizeof(float)) == 0 && f.cone_extent == sun_key_[3]) f.shadow_field_off = 8u * view_.cf_plane;
+				if (std::memcmp(f.cone_dir, fields_.book().sun_key(), 3 * sizeof(float)) == 0 && f.cone_extent == fields_.book().sun_key()[3]) f.shadow_field_off = 8u * view_.cf_plane;
 	}
 	// the view plane, for the first frame's origin: built now if the camera rests there; frames of the launch from another origin keep their octant planes
 	if (BM_VIEWFIELD != 0 && !plan.instrumented) {
@@ -1725,7 +1402,7 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 		if (int e = ensure_view_plane(fcs, &usable)) return e;
 		if (usable)
 			for (FrameConstants& f : fcs)
-				if (std::memcmp(f.origin, view_key_, sizeof view_key_) == 0 && f.lens_radius == 0.0f) f.view_field_off = 9u * view_.cf_plane;
+				if (std::memcmp(f.origin, fields_.book().view_key(), sizeof f.origin) == 0 && f.lens_radius == 0.0f) f.view_field_off = 9u * view_.cf_plane;
 	}
 	// `stream` is used as given: nullptr is HIP's default stream (what the reference's <<<>>> launches use), which is
 	// ordered with the caller's other default-stream work (e.g. torch's fill kernels on the accumulation buffer).

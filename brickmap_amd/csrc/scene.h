@@ -15,13 +15,14 @@
 #include "frame_plan.h"
 #include "hip_owned.h"
 #include "kernels.h"
+#include "walk_fields.h"
 #include "world.h"
 
 namespace bm {
 
 class Scene {
 public:
-	explicit Scene(int device) : device_(device) {}
+	explicit Scene(int device) : device_(device), fields_(device) {}
 	~Scene();
 
 	int init(int grid_size, int grid_height); // Scene::Scene: streams + pinned staging
@@ -39,18 +40,11 @@ public:
 	int device_brick(int supercell, uint32_t device_slot, uint32_t* out16);
 	// voxel edits (edit.hip / scene.cpp "voxel edits"): host world first, then one scatter + the cube-field update on the load stream
 	int edit(int count, const bm_edit* edits, hipStream_t stream);
-	int device_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
-	int escape_table(int32_t* dst, size_t capacity, size_t* count); // the device's escape heights (escape.h), as thresholds [8][cells][cells]
 	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
-	// the sun plane (sunfield.h): the device's plane as it was last built, [z][y][x] with its border, and the plan it was built for; how often it
-	// has been built and what the last build took
-	int sun_plane(uint8_t* dst, size_t capacity, size_t* bytes, int32_t* plan12);
-	int sun_plane_stats(uint64_t* builds, float* last_build_ms);
-	int shadow_heights(uint32_t* dst, size_t capacity, size_t* count, uint64_t* bytes, int32_t* plan4);
-	// the view plane (viewfield.h): likewise, with the origin it was built for
-	int view_plane(uint8_t* dst, size_t capacity, size_t* bytes, float* origin3);
-	int view_plane_stats(uint64_t* builds, float* last_build_ms);
+	// the cube field, the escape table and the planes derived from them: walk_fields.h has their readbacks and build statistics
+	WalkFields& fields() { return fields_; }
+	WalkFields* fields_on_device() { return require_on_device() ? nullptr : &fields_; } // null + message unless the world is on the device
 	// dense regions (region.hip / scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
 	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
 	int read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream);
@@ -93,10 +87,8 @@ public:
 private:
 	int allocate_device();
 	int alloc_index_grid();   // the pieces of allocate_device that the device route of load_voxels shares with it
-	int alloc_cube_field();
 	int ensure_sun_plane(const FrameConstants& fc, bool* usable); // builds the sun plane for the frame's cone unless it stands; *usable: shadow rays of that cone may read it
 	int ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usable); // builds the view plane for the first frame's origin if the camera rests there; *usable: the plane stands for that origin
-	EscapeUpdate escape_update_box(int x0, int x1, int y0, int y1) const; // the columns [x0, x1) x [y0, y1) of the escape-height table (escape.hip)
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
 	// the device half of a change of the host world (scene.cpp "voxel edits"): the touched cells of every changed supercell are staged, then submitted
@@ -104,8 +96,7 @@ private:
 		std::vector<uint32_t> cells, words, slots;
 		std::vector<Brick> bricks;
 		std::vector<PoolMove> moves;
-		int box_lo[3] = {1 << 30, 1 << 30, 1 << 30}, box_hi[3] = {-1, -1, -1}; // cells whose occupancy changed (unbordered, inclusive)
-		int touch_lo[2] = {1 << 30, 1 << 30}, touch_hi[2] = {-1, -1};          // columns of every touched cell (x, y): what the shadow heights scan again
+		FieldChange change;
 	};
 	int wait_edit_staging();
 	int stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b);
@@ -157,37 +148,20 @@ private:
 	int frame_end(hipStream_t stream);        // record the stream's "frame done" event
 	int wait_frames_on_host();                // host waits for every frame in flight
 	int order_load_stream_behind_frames();    // load stream waits for every frame in flight
+	// work that rewrites what frames read: queue() issues it on the load stream behind every frame in flight, and it is published as an upload batch -- every frame issued later waits for it
+	template <class Queue> int publish_behind_frames(Queue&& queue) {
+		if (int e = order_load_stream_behind_frames()) return e;
+		if (int e = queue()) return e;
+		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
+		upload_seq_++;
+		return 0;
+	}
 
 	// device memory (DeviceScene view)
 	DeviceBuffer<uint32_t> d_index_grid_, d_pool_base_;
-	DeviceBuffer<uint8_t> d_cube_field_;
-	// escape heights (escape.h): the table the walk reads, and every column's top and bottom, kept for the updates after edits.  Valid and
-	// rebuilt wherever the cube field is, on the same stream right behind it.
-	DeviceBuffer<uint32_t> d_escape_;
-	DeviceBuffer<int32_t> d_escape_cols_;
-	// the sun plane (sunfield.h): plane 8 of d_cube_field_ where alloc_cube_field got nine planes; built for the cone in sun_key_ (cone_dir,
-	// cone_extent), stale once the field has changed (every field change sets sun_dirty_), rebuilt by the next production frame that reads it
-	bool sun_plane_ = false, sun_built_ = false, sun_dirty_ = true;
-	float sun_key_[4] = {0.f, 0.f, 0.f, 0.f};
-	SunPlan sun_plan_{};
-	// the shadow heights (shadowheight.h): slice 8 of d_escape_, built with the plane and for its cone; stale once a brick's bits have changed
-	// (shadow_dirty_), also where no cell's occupancy did and the plane stands -- then ensure_sun_plane rebuilds the slice alone
-	bool shadow_dirty_ = true;
-	bool shadow_zero_ = true;        // the slice holds zeros only (as allocated, or built for a sun or a scene without shadow heights)
-	bool shadow_full_valid_ = false; // d_shadow_tmp_ holds every column's full top of the world as it was at the last scan; the full tops do not depend on the sun
-	int shadow_box_[4] = {1 << 30, 1 << 30, -1, -1}; // ... and the columns touched since (x0, y0, x1, y1; unbordered, inclusive): the next build scans these alone
-	ShadowPlan shadow_plan_{};
-	uint64_t sun_builds_ = 0;
-	DeviceBuffer<uint8_t> d_sun_tmp_, d_shadow_tmp_;
-	Event ev_sun_time_[2];
-	// the view plane (viewfield.h): plane 9 of d_cube_field_ where alloc_cube_field got ten planes; built for the origin in view_key_, stale once
-	// the field has changed (view_dirty_, set wherever sun_dirty_ is), rebuilt by the next production launch of a resting camera
-	bool view_plane_ = false, view_built_ = false, view_dirty_ = true;
-	float view_key_[3] = {0.f, 0.f, 0.f};
-	float view_last_origin_[3] = {0.f, 0.f, 0.f}; // origin of the first frame of the production launch before this one
-	bool view_last_valid_ = false;
-	uint64_t view_builds_ = 0;
-	Event ev_view_time_[2];
+	// what the walk reads instead of index words: the cube field with the sun and the view plane, the escape table with the shadow heights, their
+	// scratch and the book of which derived plane stands and what makes it stale (walk_fields.h; every flag is explained in field_book.h)
+	WalkFields fields_;
 	// two request rings: the blocking (reference-order) mode only uses ring 0; the overlapped mode alternates them so
 	// that a frame can raise requests while the previous frame's ring is being copied out and serviced
 	DeviceBuffer<int> d_load_queue_[2];
@@ -219,14 +193,13 @@ private:
 	bool preloaded_ = false;                     // bm_scene_preload_all: an edit uploads new bricks at once (no requests are serviced)
 	DeviceBuffer<int> d_positions_;              // a ring's entries without the stale ones, when service_ring skips some
 	// edits: pinned + device staging of one batch (pool moves, dirty cells, their words, arena slots and bricks), grown on demand;
-	// the staging is free again once ev_edit_ has passed.  d_cf_tmp_: the intermediate planes of the cube-field update.
+	// the staging is free again once ev_edit_ has passed
 	PinnedBuffer<char> h_edit_;
 	DeviceBuffer<char> d_edit_;
 	Event ev_edit_, ev_edit_caller_;
 	Event ev_edit_time_[3]; // around the scatter and the field update of the last batch
 	bool edit_timed_ = false, edit_field_timed_ = false;
 	bool edit_busy_ = false;
-	DeviceBuffer<uint8_t> d_cf_tmp_;
 	// region writes: the packed bricks of a device volume (64 bytes per covered cell, device + pinned, grown on demand) and the events
 	// around pack, copy, scatter and field; region reads: the list of non-resident bricks (pinned + device), free once ev_region_read_ has passed
 	DeviceBuffer<char> d_region_, d_patch_;
