@@ -1,4 +1,4 @@
-// hip_owned.h -- move-only owners of HIP resources: device memory, pinned host memory, an event, the events around a launch's stages, a stream.  Each frees what it holds
+// hip_owned.h -- move-only owners of HIP resources: device memory, pinned host memory, an event, a turn, the events around a launch's stages, a stream.  Each frees what it holds
 // in its destructor (on whatever device is current: the owner's destructor body selects it) and allocates through a method that
 // returns the project's int error.  A default-constructed owner holds nothing, so an object whose init() failed halfway destructs cleanly.
 // None of them synchronises: a buffer that work in flight may still use is waited for by the caller before reserve() / alloc().
@@ -70,6 +70,33 @@ private:
 	hipEvent_t e_ = nullptr;
 };
 
+// Whose turn it is with something one call at a time may use (a scratch buffer, a staging area): the call that uses it passes the turn on its
+// stream behind its work, and the next one orders its stream behind that -- or, before it rewrites or grows the thing from the host, waits.
+class Turn {
+public:
+	bool pending() const { return pending_; }
+	int order(hipStream_t stream) const { // `stream` goes on once the call before has finished
+		if (pending_) BM_HIP(hipStreamWaitEvent(stream, ev_, 0));
+		return 0;
+	}
+	int wait() { // the host does
+		if (pending_) BM_HIP(hipEventSynchronize(ev_));
+		pending_ = false;
+		return 0;
+	}
+	int pass(hipStream_t stream) { // behind what this call has queued on `stream`
+		if (int e = ev_.create(hipEventDisableTiming)) return e;
+		BM_HIP(hipEventRecord(ev_, stream));
+		pending_ = true;
+		return 0;
+	}
+	void clear() { pending_ = false; } // the device has just been waited for
+
+private:
+	Event ev_; // made on first use
+	bool pending_ = false;
+};
+
 // N timing events around the stages of one launch: what the launch_* functions of kernels.h take as `marks` -- mark i is recorded before
 // stage i, mark `stages` behind the last one
 template <int N>
@@ -83,10 +110,10 @@ public:
 		return 0;
 	}
 	hipEvent_t* marks() { return raw_; }
-	// waits for mark `stages`, then ms[i] = the time from mark i to mark i + 1
-	int read(int stages, float* ms) const {
-		BM_HIP(hipEventSynchronize(raw_[stages]));
-		for (int i = 0; i < stages; ++i) BM_HIP(hipEventElapsedTime(&ms[i], raw_[i], raw_[i + 1]));
+	// waits for mark first + stages, then ms[i] = the time from mark first + i to the mark after it
+	int read(int stages, float* ms, int first = 0) const {
+		BM_HIP(hipEventSynchronize(raw_[first + stages]));
+		for (int i = 0; i < stages; ++i) BM_HIP(hipEventElapsedTime(&ms[i], raw_[first + i], raw_[first + i + 1]));
 		return 0;
 	}
 

@@ -64,13 +64,12 @@ int Scene::init(int grid_size, int grid_height) {
 	}
 	BM_HIP(hipSetDevice(device_));
 	if (int e = load_stream_.create(hipStreamNonBlocking)) return e;
-	if (int e = kernel_stream_.create(hipStreamNonBlocking)) return e;
 	for (int i = 0; i < kTimingRing; ++i) {
 		if (int e = ev_start_[i].create()) return e;
 		if (int e = ev_stop_[i].create()) return e;
 	}
-	for (Event* ev : {&ev_upload_, &ev_snapshot_, &ev_edit_, &ev_edit_caller_}) if (int e = ev->create(hipEventDisableTiming)) return e;
-	for (Event& ev : ev_edit_time_) if (int e = ev.create()) return e;
+	if (int e = order_.init(load_stream_)) return e;
+	if (int e = edit_marks_.create()) return e;
 	for (int r = 0; r < 2; ++r) {
 		if (int e = h_count_[r].alloc(sizeof(uint32_t))) return e;
 		if (int e = d_load_count_[r].alloc(sizeof(uint32_t))) return e;
@@ -81,7 +80,6 @@ int Scene::init(int grid_size, int grid_height) {
 	if (int e = d_work_counter_.alloc(kWorkCounterBytes * kFrameRing)) return e; // one block of counters per frame in flight
 	if (int e = d_frame_constants_.alloc(kFrameRing * sizeof(FrameConstants))) return e;
 	if (int e = h_frame_constants_.alloc(kFrameRing * sizeof(FrameConstants))) return e;
-	std::fill(ring_owner_, ring_owner_ + kFrameRing, -1ll);
 	hipDeviceProp_t prop;
 	BM_HIP(hipGetDeviceProperties(&prop, device_));
 	compute_units_ = prop.multiProcessorCount; // main.cpp:97 sm_cores
@@ -109,7 +107,7 @@ int Scene::alloc_queue() {
 	if (int e = h_moves_.alloc(n * sizeof(PoolMove))) return e;
 	if (int e = d_moves_.alloc(n * sizeof(PoolMove))) return e;
 	use_ring(0);
-	snapshot_pending_ = false;
+	snapshot_.clear();
 	view_.queue_cap = static_cast<uint32_t>(queue_cap_);
 	return 0;
 }
@@ -122,21 +120,19 @@ void Scene::use_ring(int ring) {
 
 void Scene::residency_rebuilt(bool preloaded) {
 	use_ring(0);
-	snapshot_pending_ = false;
+	snapshot_.clear();
 	preloaded_ = preloaded;
 	fields_.book().residency_rebuilt();
-	staging_busy_ = false;
+	order_.residency_rebuilt();
 	failed_ = false;
 	stream_batches_ = stream_host_ns_ = 0;
-	upload_seq_ = 0;
-	for (FrameStream& f : frame_streams_) f.upload_seen = 0;
 }
 
 int Scene::set_streaming_mode(int overlapped) {
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
-	if (snapshot_pending_) { // drain: the copied-out ring is serviced now, so no request is lost by switching modes
-		snapshot_pending_ = false;
+	if (snapshot_.pending()) { // drain: the copied-out ring is serviced now, so no request is lost by switching modes
+		snapshot_.clear();
 		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[ring_snapshot_]);
 		if (count > 0) {
 			if (int e = service_ring(ring_snapshot_, count, nullptr)) return e;
@@ -361,7 +357,7 @@ int Scene::load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream
 		}
 	}
 	BM_HIP(hipDeviceSynchronize()); // no frame, edit or upload in flight from here on: the old world (if any) can go
-	load_timed_ = false;
+	load_clocked_ = 0;
 	if (where == BM_VOXELS_HOST) {
 		world.load_voxels(voxels, 16);
 		if (int e = allocate_device()) return e;
@@ -381,7 +377,8 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	const WorldDims& d = world.dims;
 	free_device();
 	world.generated = false;
-	for (Event& ev : ev_load_time_) if (int e = ev.create()) return e;
+	if (int e = load_marks_.create()) return e;
+	hipEvent_t* const marks = load_marks_.marks();
 	if (int e = alloc_index_grid()) return e;
 	if (int e = fields_.allocate(d, &view_)) return e;
 	set_view_dims();
@@ -394,15 +391,14 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	// the field comes from the update of edit.hip with the box = every cell, into the field the allocation set to 255
 	const FieldChange all = FieldChange::whole(d);
 	if (int e = fields_.prepare_update(all, nullptr)) return e; // (load_voxels has synchronised the device: no stream to wait for, unlike submit_batch)
-	BM_HIP(hipEventRecord(ev_edit_caller_, stream)); // the volume is whatever the caller's stream has written by now
-	BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
+	if (int e = order_.load_behind_caller(stream)) return e; // the volume is whatever the caller's stream has written by now
 	// ---- classify + number
-	BM_HIP(hipEventRecord(ev_load_time_[0], load_stream_));
+	BM_HIP(hipEventRecord(marks[0], load_stream_));
 	launch_load_classify(voxels, d_index_grid_, ld, load_stream_);
 	BM_HIP(hipGetLastError());
 	launch_load_number(d_index_grid_, counts, d_pool_base_, d_total, ld, load_stream_);
 	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_load_time_[1], load_stream_));
+	BM_HIP(hipEventRecord(marks[1], load_stream_));
 	uint32_t total_words[2] = {0, 0};
 	BM_HIP(hipMemcpyAsync(total_words, d_total, sizeof total_words, hipMemcpyDeviceToHost, load_stream_));
 	BM_HIP(hipStreamSynchronize(load_stream_)); // the one host round trip: the arena is sized by what the volume holds
@@ -411,13 +407,13 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	if (int e = arena_.open(device_, 4 * total + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
 	if (int e = arena_fit(total)) return e;
 	// ---- pack
-	BM_HIP(hipEventRecord(ev_load_time_[2], load_stream_));
+	BM_HIP(hipEventRecord(marks[2], load_stream_));
 	launch_load_pack(voxels, d_index_grid_, d_pool_base_, arena_.base(), ld, load_stream_);
 	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_load_time_[3], load_stream_));
+	BM_HIP(hipEventRecord(marks[3], load_stream_));
 	// ---- field
 	if (int e = fields_.update(d_index_grid_, all, true, load_stream_)) return e;
-	BM_HIP(hipEventRecord(ev_load_time_[4], load_stream_));
+	BM_HIP(hipEventRecord(marks[4], load_stream_));
 	// ---- mirror: the host world becomes what World::load_voxels builds, in the state preload_all leaves it in
 	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell), bases(d.supercells);
 	std::vector<Brick> bricks(total);
@@ -425,7 +421,7 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	BM_HIP(hipMemcpyAsync(bases.data(), d_pool_base_, bases.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
 	if (total) BM_HIP(hipMemcpyAsync(bricks.data(), arena_.base(), total * sizeof(Brick), hipMemcpyDeviceToHost, load_stream_));
 	for (int r = 0; r < 2; ++r) BM_HIP(hipMemsetAsync(d_load_count_[r], 0, sizeof(uint32_t), load_stream_));
-	BM_HIP(hipEventRecord(ev_load_time_[5], load_stream_));
+	BM_HIP(hipEventRecord(marks[5], load_stream_));
 	BM_HIP(hipStreamSynchronize(load_stream_));
 	world.supercells.clear();
 	world.supercells.resize(d.supercells);
@@ -454,20 +450,20 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	resident_bricks_ = total;
 	on_device_ = true;
 	residency_rebuilt(true);
-	load_timed_ = true;
+	load_clocked_ = kClockedCall;
 	return 0;
 }
 
 int Scene::last_load_ms(float* pack_ms, float* field_ms, float* mirror_ms) {
 	if (!pack_ms || !field_ms || !mirror_ms) { set_error("null argument"); return BM_EINVAL; }
-	if (!load_timed_) { set_error("no volume has been loaded from device memory yet"); return BM_ESTATE; }
+	if (!load_clocked_) { set_error("no volume has been loaded from device memory yet"); return BM_ESTATE; }
 	BM_HIP(hipSetDevice(device_));
-	float classify = 0.f, pack = 0.f;
-	BM_HIP(hipEventElapsedTime(&classify, ev_load_time_[0], ev_load_time_[1]));
-	BM_HIP(hipEventElapsedTime(&pack, ev_load_time_[2], ev_load_time_[3]));
-	*pack_ms = classify + pack; // without the host's round trip between them (the arena is mapped there)
-	BM_HIP(hipEventElapsedTime(field_ms, ev_load_time_[3], ev_load_time_[4]));
-	BM_HIP(hipEventElapsedTime(mirror_ms, ev_load_time_[4], ev_load_time_[5]));
+	float classify = 0.f, rest[3];
+	if (int e = load_marks_.read(1, &classify)) return e;
+	if (int e = load_marks_.read(3, rest, 2)) return e;
+	*pack_ms = classify + rest[0]; // without the host's round trip between them (the arena is mapped there)
+	*field_ms = rest[1];
+	*mirror_ms = rest[2];
 	return 0;
 }
 
@@ -479,65 +475,6 @@ int Scene::host_voxels(uint8_t* dst, size_t capacity, size_t* bytes) {
 	if (!world.generated) { set_error("world not generated"); return BM_ESTATE; }
 	if (capacity < need) { set_error("voxel buffer too small"); return BM_EINVAL; }
 	world.store_voxels(dst, 16);
-	return 0;
-}
-
-// ---------------------------------------------------------------- frames vs. uploads
-// A frame on `stream` must see every brick batch queued so far: wait for the latest upload event unless this stream
-// already has.  (Per stream, not per scene: with frames on several streams each of them has to be ordered.)
-int Scene::frame_begin(hipStream_t stream) {
-	if (int e = require_not_failed()) return e;
-	FrameStream* fs = nullptr;
-	bool created = false;
-	for (FrameStream& f : frame_streams_) if (f.stream == stream) { fs = &f; break; }
-	if (!fs) {
-		created = true;
-		if (frame_streams_.size() >= kMaxFrameStreams) {
-			// retire the entry that has been idle longest (a caller that keeps creating streams): its last frame must have
-			// finished before the entry -- and with it the ordering of the load stream behind that frame -- can go
-			size_t lru = 0;
-			for (size_t i = 1; i < frame_streams_.size(); ++i) if (frame_streams_[i].last_use < frame_streams_[lru].last_use) lru = i;
-			BM_HIP(hipEventSynchronize(frame_streams_[lru].done));
-			frame_streams_.erase(frame_streams_.begin() + static_cast<long>(lru));
-		}
-		FrameStream f;
-		f.stream = stream;
-		if (int e = f.done.create(hipEventDisableTiming)) return e;
-		frame_streams_.push_back(std::move(f));
-		fs = &frame_streams_.back();
-	}
-	// (a stream handle can be recycled by the runtime after its owner destroyed it: an entry that claims to have seen the
-	// latest batch is only trusted once that batch has actually completed)
-	// (the event is only queried for an entry that claims to be up to date and was not made by this call; a stream that has
-	// waited is not asked to wait again, and only the query's own "not ready" status is cleared -- never a sticky error of the
-	// caller's that happens to be pending on this thread)
-	bool must_wait = fs->upload_seen < upload_seq_;
-	if (!must_wait && upload_seq_ > 0 && !created) {
-		const hipError_t q = hipEventQuery(ev_upload_);
-		if (q == hipErrorNotReady) { (void)hipGetLastError(); must_wait = true; }
-	}
-	if (must_wait) {
-		BM_HIP(hipStreamWaitEvent(stream, ev_upload_, 0)); // ev_upload_ is re-recorded behind every batch: waiting for it covers all earlier ones
-		fs->upload_seen = upload_seq_;
-	}
-	fs->last_use = ++frame_seq_;
-	return 0;
-}
-
-int Scene::frame_end(hipStream_t stream) {
-	for (FrameStream& f : frame_streams_)
-		if (f.stream == stream) { BM_HIP(hipEventRecord(f.done, stream)); return 0; }
-	set_error("frame_end without frame_begin");
-	return BM_ESTATE;
-}
-
-int Scene::wait_frames_on_host() {
-	for (FrameStream& f : frame_streams_) BM_HIP(hipEventSynchronize(f.done));
-	return 0;
-}
-
-int Scene::order_load_stream_behind_frames() {
-	for (FrameStream& f : frame_streams_) BM_HIP(hipStreamWaitEvent(load_stream_, f.done, 0));
 	return 0;
 }
 
@@ -569,10 +506,7 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 			return BM_ESTATE;
 		}
 	}
-	if (staging_busy_) { // the staging buffers of the previous upload are free again once its copies have run
-		BM_HIP(hipEventSynchronize(ev_upload_));
-		staging_busy_ = false;
-	}
+	if (int e = order_.wait_upload_on_host()) return e; // the staging buffers of the previous upload are free again once its copies have run
 	// ---- pass 2: hand out slots, grow pools.  From here on host state changes entry by entry; the only thing that can
 	// still go wrong is running out of device memory while the arena grows, and that leaves the scene marked as failed
 	// (every later frame / batch is refused until the residency is reset) instead of half-updated and in use.
@@ -628,7 +562,7 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 		// (plain load + atomicOr): a word flipping to "loaded" between the two would be requested a second time; the move
 		// kernel rewrites pool bases such a frame addresses bricks with.  In overlapped mode both therefore run behind every
 		// frame in flight, whatever stream it is on; the copies above already overlap them.
-		if (overlapped_) { if (int e = order_load_stream_behind_frames()) return e; }
+		if (overlapped_) { if (int e = order_.load_behind_frames()) return e; }
 		DeviceScene ring_view = view_;
 		ring_view.load_queue = compacted ? d_positions_.get() : d_load_queue_[ring].get();
 		ring_view.load_queue_count = d_load_count_[ring];
@@ -640,13 +574,10 @@ int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
 		launch_upload(ring_view, d_bricks_queue_, d_indices_queue_, arena_.base(), kept, load_stream_); // kernel.cu:412
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipMemsetAsync(d_load_count_[ring], 0, sizeof(uint32_t), load_stream_));             // kernel.cu:413
-		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
-		return 0;
+		return order_.published(true);
 	};
 	if (int e = queue()) { failed_ = true; return e; } // the host bookkeeping is ahead of the device: refuse to go on
 	arena_.commit_freed_regions();
-	staging_busy_ = true;
-	upload_seq_++;
 	resident_bricks_ += kept;
 	if (serviced) *serviced = kept;
 	stream_batches_++;
@@ -662,7 +593,7 @@ int Scene::process_load_queue(uint32_t* serviced) {
 	if (!overlapped_) {
 		// ---- reference order (main.cpp:142-144): the frames that raised the requests have finished (kernel.cu:431), the host
 		// reads the ring, stages, uploads; the next frame sees the bricks
-		if (int e = wait_frames_on_host()) return e; // every stream a frame was issued on
+		if (int e = order_.wait_frames_on_host()) return e; // every stream a frame was issued on
 		BM_HIP(hipMemcpyAsync(h_count_[0], d_load_count_[0], sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_)); // Scene.cpp:202
 		BM_HIP(hipStreamSynchronize(load_stream_));
 		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[0]);                   // Scene.cpp:203
@@ -674,15 +605,14 @@ int Scene::process_load_queue(uint32_t* serviced) {
 	// ---- overlapped mode: never wait for the GPU.  (1) service the ring that was copied out by the previous call,
 	// (2) start copying out the ring the last frame wrote, behind that frame, on the load stream, (3) hand the other
 	// ring to the next frame.  A brick requested in frame k is resident from frame k+2 on (reference order: from k+1 on).
-	if (snapshot_pending_) {
-		BM_HIP(hipEventSynchronize(ev_snapshot_));
-		snapshot_pending_ = false;
+	if (snapshot_.pending()) {
+		if (int e = snapshot_.wait()) return e;
 		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[ring_snapshot_]);
 		if (count > 0) {
 			if (int e = service_ring(ring_snapshot_, count, serviced)) return e;
 		}
 	}
-	if (int e = order_load_stream_behind_frames()) return e; // the ring is complete once every frame that may append to it has ended
+	if (int e = order_.load_behind_frames()) return e; // the ring is complete once every frame that may append to it has ended
 	const int ring = ring_cur_;
 	// the count is not known on the host without waiting for the frame: a small kernel copies count + the entries that exist into
 	// the pinned (device-mapped) mirrors -- min(count, capacity) x 12 bytes over PCIe instead of the ring's whole capacity
@@ -694,8 +624,7 @@ int Scene::process_load_queue(uint32_t* serviced) {
 		launch_snapshot_ring(d_load_queue_[ring], d_load_count_[ring], dev_positions, dev_count, static_cast<uint32_t>(queue_cap_), load_stream_);
 		BM_HIP(hipGetLastError());
 	}
-	BM_HIP(hipEventRecord(ev_snapshot_, load_stream_));
-	snapshot_pending_ = true;
+	if (int e = snapshot_.pass(load_stream_)) return e;
 	ring_snapshot_ = ring;
 	use_ring(ring ^ 1);
 	return 0;
@@ -787,7 +716,7 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 	if (reached.empty()) return 0;
 	std::sort(reached.begin(), reached.end());
 	BM_HIP(hipSetDevice(device_));
-	if (int e = wait_edit_staging()) return e;
+	if (int e = edit_staging_.wait()) return e; // the staging of the previous batch has been copied
 
 	// ---- host world, supercell by supercell (voxels of different supercells are independent: batch order is kept within each)
 	DeviceBatch batch;
@@ -801,17 +730,8 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 		World::edit_supercell(d, c, sx, sy, sz, edits, count, touched.data());
 		if (int e = stage_touched(sci, old_words, touched.data(), batch)) return e;
 	}
-	bool scattered = false, field = false;
-	if (int e = submit_batch(batch, stream, ev_edit_time_, &scattered, &field)) return e;
-	if (scattered) {
-		edit_timed_ = true;
-		edit_field_timed_ = field;
-	}
-	return 0;
-}
-
-int Scene::wait_edit_staging() {
-	if (edit_busy_) { BM_HIP(hipEventSynchronize(ev_edit_)); edit_busy_ = false; } // the staging of the previous batch has been copied
+	if (int e = submit_batch(batch, stream, edit_marks_.marks())) return e;
+	if (batch.clocked()) edit_clocked_ = batch.clocked(); // (a batch that scatters nothing leaves the last one's times readable)
 	return 0;
 }
 
@@ -885,9 +805,9 @@ int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const 
 }
 
 // submit_batch: the staged cells go to the device on the load stream -- one copy, the pool moves, the scatter and, when some cell's
-// occupancy changed, the cube-field update -- as an upload batch.  times[0 ... 2] are recorded around the scatter and the field update.
-int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* scattered, bool* field_updated) {
-	*scattered = *field_updated = false;
+// occupancy changed, the cube-field update -- as an upload batch.  marks[0 ... 2] are recorded around the scatter and the field update
+// (DeviceBatch::clocked says which of the two a batch has).
+int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, hipEvent_t* marks) {
 	const uint32_t n = static_cast<uint32_t>(b.cells.size());
 	if (n == 0) { // nothing inside the world changed a brick (e.g. clearing empty space)
 		arena_.commit_freed_regions();
@@ -915,11 +835,10 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 	};
 	// behind every frame in flight (they read the words, pool bases, bricks and field this rewrites) and the caller's queued work
 	auto queue = [&]() -> int {
-		BM_HIP(hipEventRecord(ev_edit_caller_, stream));
-		BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
+		if (int e = order_.load_behind_caller(stream)) return e;
 		BM_HIP(hipMemcpyAsync(d_edit_, h_edit_, bytes, hipMemcpyHostToDevice, load_stream_));
-		BM_HIP(hipEventRecord(ev_edit_, load_stream_)); // the pinned staging is free again from here on
-		BM_HIP(hipEventRecord(times[0], load_stream_));
+		if (int e = edit_staging_.pass(load_stream_)) return e; // the pinned staging is free again from here on
+		BM_HIP(hipEventRecord(marks[0], load_stream_));
 		if (!b.moves.empty()) {
 			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_.get()), static_cast<uint32_t>(b.moves.size()), arena_.base(), d_pool_base_, load_stream_);
 			BM_HIP(hipGetLastError());
@@ -928,30 +847,27 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* 
 							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, d_index_grid_, arena_.base(),
 							load_stream_);
 		BM_HIP(hipGetLastError());
-		BM_HIP(hipEventRecord(times[1], load_stream_));
+		BM_HIP(hipEventRecord(marks[1], load_stream_));
 		// the field and the escape heights where some cell's occupancy changed; what that makes stale is rebuilt before the next frame that reads it
 		if (int e = fields_.update(d_index_grid_, b.change, true, load_stream_)) return e;
-		BM_HIP(hipEventRecord(times[2], load_stream_));
+		BM_HIP(hipEventRecord(marks[2], load_stream_));
 		return 0;
 	};
 	int e = stage();
-	if (!e) e = publish_behind_frames(queue);
+	if (!e) e = order_.publish_behind_frames(queue);
 	if (e) { failed_ = true; return e; } // the host world is ahead of the device: refuse to go on
 	arena_.commit_freed_regions();
-	edit_busy_ = true;
-	*scattered = true;
-	*field_updated = b.change.occupancy();
 	return 0;
 }
 
 int Scene::last_edit_ms(float* scatter_ms, float* field_ms) {
 	if (!scatter_ms || !field_ms) { set_error("null argument"); return BM_EINVAL; }
-	if (!edit_timed_) { set_error("no edit has changed the scene yet"); return BM_ESTATE; }
+	if (!edit_clocked_) { set_error("no edit has changed the scene yet"); return BM_ESTATE; }
 	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipEventSynchronize(ev_edit_time_[2]));
-	BM_HIP(hipEventElapsedTime(scatter_ms, ev_edit_time_[0], ev_edit_time_[1]));
-	BM_HIP(hipEventElapsedTime(field_ms, ev_edit_time_[1], ev_edit_time_[2]));
-	if (!edit_field_timed_) *field_ms = 0.0f;
+	float ms[2];
+	if (int e = edit_marks_.read(2, ms)) return e;
+	*scatter_ms = ms[0];
+	*field_ms = (edit_clocked_ & kClockedField) ? ms[1] : 0.0f;
 	return 0;
 }
 
@@ -1015,8 +931,9 @@ int Scene::write_region(const bm_region* region, int op, const uint8_t* voxels, 
 	const WorldDims& d = world.dims;
 	int lo[3], hi[3];
 	if (!World::region_bounds(d, r, lo, hi)) return 0;
-	if (int e = wait_edit_staging()) return e;
-	for (Event& ev : ev_region_time_) if (int e = ev.create()) return e;
+	if (int e = edit_staging_.wait()) return e;
+	if (int e = region_marks_.create()) return e;
+	hipEvent_t* const marks = region_marks_.marks();
 	const RegionDims rd = region_dims(r, lo, hi);
 	World::RegionSource src;
 	for (int k = 0; k < 3; ++k) { src.c0[k] = rd.c0[k]; src.nc[k] = rd.nc[k]; src.origin[k] = r.lo[k]; }
@@ -1026,14 +943,13 @@ int Scene::write_region(const bm_region* region, int op, const uint8_t* voxels, 
 			if (int e = d_region_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
 			if (int e = h_region_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
 		}
-		BM_HIP(hipEventRecord(ev_edit_caller_, stream)); // the volume is whatever the caller's stream has written by now
-		BM_HIP(hipStreamWaitEvent(load_stream_, ev_edit_caller_, 0));
-		BM_HIP(hipEventRecord(ev_region_time_[0], load_stream_));
+		if (int e = order_.load_behind_caller(stream)) return e; // the volume is whatever the caller's stream has written by now
+		BM_HIP(hipEventRecord(marks[0], load_stream_));
 		launch_region_pack(voxels, reinterpret_cast<uint32_t*>(d_region_.get()), rd, load_stream_);
 		BM_HIP(hipGetLastError());
-		BM_HIP(hipEventRecord(ev_region_time_[1], load_stream_));
+		BM_HIP(hipEventRecord(marks[1], load_stream_));
 		BM_HIP(hipMemcpyAsync(h_region_, d_region_, bytes, hipMemcpyDeviceToHost, load_stream_));
-		BM_HIP(hipEventRecord(ev_region_time_[2], load_stream_));
+		BM_HIP(hipEventRecord(marks[2], load_stream_));
 		BM_HIP(hipStreamSynchronize(load_stream_));
 		src.packed = h_region_;
 	} else {
@@ -1068,27 +984,23 @@ int Scene::write_region(const bm_region* region, int op, const uint8_t* voxels, 
 	DeviceBatch batch;
 	for (size_t i = 0; i < reached.size(); ++i)
 		if (int e = stage_touched(reached[i], old_words[i], touched[i].data(), batch)) return e;
-	region_timed_ = true;
-	region_packed_ = where == BM_VOXELS_DEVICE;
-	region_scattered_ = region_field_ = false;
-	return submit_batch(batch, stream, ev_region_time_ + 3, &region_scattered_, &region_field_);
+	region_clocked_ = kClockedCall | (where == BM_VOXELS_DEVICE ? kClockedPack : 0u);
+	if (int e = submit_batch(batch, stream, marks + 3)) return e;
+	region_clocked_ |= batch.clocked();
+	return 0;
 }
 
 int Scene::last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms) {
 	if (!pack_ms || !copy_ms || !scatter_ms || !field_ms) { set_error("null argument"); return BM_EINVAL; }
-	if (!region_timed_) { set_error("no region has been written yet"); return BM_ESTATE; }
+	if (!region_clocked_) { set_error("no region has been written yet"); return BM_ESTATE; }
 	BM_HIP(hipSetDevice(device_));
-	*pack_ms = *copy_ms = *scatter_ms = *field_ms = 0.0f;
-	if (region_packed_) {
-		BM_HIP(hipEventSynchronize(ev_region_time_[2]));
-		BM_HIP(hipEventElapsedTime(pack_ms, ev_region_time_[0], ev_region_time_[1]));
-		BM_HIP(hipEventElapsedTime(copy_ms, ev_region_time_[1], ev_region_time_[2]));
-	}
-	if (region_scattered_) {
-		BM_HIP(hipEventSynchronize(ev_region_time_[5]));
-		BM_HIP(hipEventElapsedTime(scatter_ms, ev_region_time_[3], ev_region_time_[4]));
-		if (region_field_) BM_HIP(hipEventElapsedTime(field_ms, ev_region_time_[4], ev_region_time_[5]));
-	}
+	float ms[4] = {0.f, 0.f, 0.f, 0.f};
+	if (region_clocked_ & kClockedPack) { if (int e = region_marks_.read(2, ms)) return e; }
+	if (region_clocked_ & kClockedScatter) { if (int e = region_marks_.read(2, ms + 2, 3)) return e; }
+	*pack_ms = ms[0];
+	*copy_ms = ms[1];
+	*scatter_ms = ms[2];
+	*field_ms = (region_clocked_ & kClockedField) ? ms[3] : 0.0f;
 	return 0;
 }
 
@@ -1108,8 +1020,7 @@ int Scene::stage_absent_bricks(bool inside, const int lo[3], const int hi[3], si
 				}
 	const size_t n = bricks.size(), o_bricks = (n * 3 * sizeof(int) + 63) / 64 * 64, bytes = o_bricks + n * sizeof(Brick);
 	if (n > 0) {
-		if (int e = ev_region_read_.create(hipEventDisableTiming)) return e;
-		if (region_read_busy_) { BM_HIP(hipEventSynchronize(ev_region_read_)); region_read_busy_ = false; } // the previous read's list has been used
+		if (int e = region_read_.wait()) return e; // the previous read's list has been used
 		if (int e = h_patch_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
 		if (int e = d_patch_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
 		std::memcpy(h_patch_, cells.data(), n * 3 * sizeof(int));
@@ -1142,6 +1053,7 @@ int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipS
 	if (int e = stage_absent_bricks(inside, lo, hi, &n, &o_bricks, &bytes)) return e;
 	DeviceScene view;
 	if (int e = begin_frame(stream, &view, nullptr)) return e;
+	FrameOrder::Ending frame(order_, stream);
 	for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
 		launch_region_zero(voxels + region_offset(r, x0, y0, z0), r.row_pitch, r.slice_pitch, x1 - x0, y1 - y0, z1 - z0, stream);
 	});
@@ -1151,12 +1063,11 @@ int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipS
 		if (n > 0) {
 			BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));
 			launch_region_patch(voxels, reinterpret_cast<const int*>(d_patch_.get()), reinterpret_cast<const uint32_t*>(d_patch_ + o_bricks), static_cast<uint32_t>(n), rd, stream);
-			BM_HIP(hipEventRecord(ev_region_read_, stream));
-			region_read_busy_ = true;
+			if (int e = region_read_.pass(stream)) return e;
 		}
 	}
 	BM_HIP(hipGetLastError());
-	end_frame(stream);
+	(void)frame.end();
 	return 0;
 }
 
@@ -1177,12 +1088,6 @@ int Scene::check_label_box(const char* who, const int32_t lo[3], const int32_t h
 	d->nx = static_cast<uint32_t>(n[0]); d->ny = static_cast<uint32_t>(n[1]); d->nz = static_cast<uint32_t>(n[2]);
 	d->sg_xy = static_cast<uint32_t>(world.dims.supergrid_xy);
 	d->sg_xy2 = d->sg_xy * d->sg_xy;
-	return 0;
-}
-
-int Scene::label_turn(hipStream_t stream) {
-	if (int e = ev_label_.create(hipEventDisableTiming)) return e;
-	if (label_busy_) BM_HIP(hipStreamWaitEvent(stream, ev_label_, 0));
 	return 0;
 }
 
@@ -1231,9 +1136,10 @@ int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags
 	if (int e = label_marks_.create()) return e;
 	DeviceScene view;
 	if (int e = begin_frame(stream, &view, nullptr)) return e;
-	if (int e = label_turn(stream)) return e;
+	FrameOrder::Ending frame(order_, stream);
+	if (int e = label_.order(stream)) return e;
 	BM_HIP(hipMemsetAsync(count, 0, sizeof(uint64_t), stream));
-	label_timed_ = false;
+	label_clocked_ = 0;
 	if (!empty) {
 		uint8_t* bytes_out = reinterpret_cast<uint8_t*>(labels);
 		const int64_t row = static_cast<int64_t>(ld.nx) * 4, slice = row * ld.ny;
@@ -1244,23 +1150,19 @@ int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags
 			if (n > 0) BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));
 			launch_label_region(view, reinterpret_cast<uint32_t*>(labels), count, ld, reinterpret_cast<const int*>(d_patch_.get()),
 								reinterpret_cast<const uint32_t*>(d_patch_.get() + o_bricks), static_cast<uint32_t>(n), stream, label_marks_.marks());
-			label_timed_ = true;
-			if (n > 0) {
-				BM_HIP(hipEventRecord(ev_region_read_, stream));
-				region_read_busy_ = true;
-			}
+			label_clocked_ = kClockedCall;
+			if (n > 0) { if (int e = region_read_.pass(stream)) return e; }
 		}
 	}
 	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_label_, stream));
-	label_busy_ = true;
-	end_frame(stream);
+	if (int e = label_.pass(stream)) return e;
+	(void)frame.end();
 	return 0;
 }
 
 int Scene::last_label_ms(float* local_ms, float* merge_ms, float* flatten_ms) {
 	if (!local_ms || !merge_ms || !flatten_ms) { set_error("null argument"); return BM_EINVAL; }
-	if (!label_timed_) { set_error("the last bm_scene_label_region launched nothing, or there was none"); return BM_ESTATE; }
+	if (!label_clocked_) { set_error("the last bm_scene_label_region launched nothing, or there was none"); return BM_ESTATE; }
 	BM_HIP(hipSetDevice(device_));
 	float ms[3];
 	if (int e = label_marks_.read(3, ms)) return e;
@@ -1295,15 +1197,13 @@ int Scene::label_components(const int32_t lo[3], const int32_t hi[3], const int3
 	label_clip(world.dims, lo, hi, &ld);
 	const size_t need = label_tmp_bytes(static_cast<uint32_t>(voxels));
 	if (d_label_tmp_.bytes() < need) {
-		if (label_busy_) { BM_HIP(hipEventSynchronize(ev_label_)); label_busy_ = false; }
+		if (int e = label_.wait()) return e;
 		if (int e = d_label_tmp_.reserve(std::max<size_t>(need, 1 << 16))) return e;
 	}
-	if (int e = label_turn(stream)) return e;
+	if (int e = label_.order(stream)) return e;
 	launch_label_components(reinterpret_cast<const uint32_t*>(labels), comps, static_cast<uint64_t>(capacity), ld, d_label_tmp_, stream);
 	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_label_, stream));
-	label_busy_ = true;
-	return 0;
+	return label_.pass(stream);
 }
 
 int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* mask,
@@ -1328,12 +1228,10 @@ int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* l
 		set_error("bm_scene_label_mask: every buffer's whole span must lie inside one allocation of the scene's device");
 		return BM_EINVAL;
 	}
-	if (int e = label_turn(stream)) return e;
+	if (int e = label_.order(stream)) return e;
 	launch_label_mask(reinterpret_cast<const uint32_t*>(labels), static_cast<uint32_t>(voxels), comps, static_cast<uint64_t>(n), chosen, mask, stream);
 	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_label_, stream));
-	label_busy_ = true;
-	return 0;
+	return label_.pass(stream);
 }
 
 // ---- the sun plane and the view plane (walk_fields.h; field_book.h decides): each is built on the load stream by the production launch that is
@@ -1346,7 +1244,7 @@ int Scene::ensure_sun_plane(const FrameConstants& fc, bool* usable) {
 	if (int e = fields_.prepare(&s, load_stream_, &ready)) return e;
 	if (!ready) return 0;
 	// behind every frame in flight (their shadow rays read the plane) and, on the load stream, behind the field and escape updates it reads
-	if (int e = publish_behind_frames([&] { return fields_.build(s, d_index_grid_, d_pool_base_, arena_.base(), load_stream_); })) return e;
+	if (int e = order_.publish_behind_frames([&] { return fields_.build(s, d_index_grid_, d_pool_base_, arena_.base(), load_stream_); })) return e;
 	*usable = true;
 	return 0;
 }
@@ -1355,7 +1253,7 @@ int Scene::ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usabl
 	const FieldBook::ViewStep v = fields_.book().view_launch(fcs, static_cast<int>(fcs.size()));
 	*usable = v.step == FieldBook::kStands;
 	if (v.step != FieldBook::kBuildPlane) return 0;
-	if (int e = publish_behind_frames([&] { return fields_.build(v, load_stream_); })) return e; // (their primary rays read the plane)
+	if (int e = order_.publish_behind_frames([&] { return fields_.build(v, load_stream_); })) return e; // (their primary rays read the plane)
 	*usable = true;
 	return 0;
 }
@@ -1406,24 +1304,14 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 	}
 	// `stream` is used as given: nullptr is HIP's default stream (what the reference's <<<>>> launches use), which is
 	// ordered with the caller's other default-stream work (e.g. torch's fill kernels on the accumulation buffer).
-	if (int e = frame_begin(stream)) return e; // bricks uploaded on the load stream must be visible to these frames
-	const int slot = static_cast<int>(launches_ % kTimingRing);
-	// the event pair of this slot is reused every kTimingRing launches: wait for the launch that used it last (almost always done)
-	if (launches_ >= kTimingRing) BM_HIP(hipEventSynchronize(ev_stop_[slot]));
-	// ---- `count` consecutive entries of the frame ring (constants + ticket counters).  An entry is free once the launch that used
-	// it last has finished: launches older than the timing ring have been waited for when their event pair was recycled (above, in
-	// their turn); a younger one is waited for here -- a caller that queues thousands of frames without a synchronisation would
-	// otherwise overwrite constants whose copy has not run yet.
-	int first = ring_next_;
-	if (first + count > kFrameRing) first = 0;
-	long long waited = -1;
-	for (int e = first; e < first + count; ++e) {
-		const long long owner = ring_owner_[e];
-		if (owner >= 0 && owner != waited && launches_ - owner < kTimingRing) {
-			BM_HIP(hipEventSynchronize(ev_stop_[owner % kTimingRing]));
-			waited = owner;
-		}
-	}
+	if (int e = require_not_failed()) return e;
+	if (int e = order_.begin(stream)) return e; // bricks uploaded on the load stream must be visible to these frames
+	FrameOrder::Ending frame(order_, stream);
+	// ---- `count` consecutive entries of the frame ring (constants + ticket counters) and a clock slot, once the launches that used them
+	// last have finished (launch_book.h FrameRing: the slot's previous user, then the younger owners of the entries)
+	const auto ring = frame_ring_.plan(count);
+	for (int w = 0; w < ring.waits; ++w) BM_HIP(hipEventSynchronize(ev_stop_[ring.wait_slot[w]]));
+	const int first = ring.first, slot = ring.slot;
 	uint32_t* const work_counter = d_work_counter_ + static_cast<size_t>(first) * (kWorkCounterBytes / sizeof(uint32_t));
 #ifdef BM_PHASE_TIMING
 	DeviceCounters* const counters = d_counters_; // profiling build: the plain kernel reports its phase timers too
@@ -1439,7 +1327,7 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 					 compute_units_, blocks_per_cu_[plan.instrumented ? 1 : 0], stream);
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipEventRecord(ev_stop_[slot], stream));
-		return frame_end(stream); // what process_load_queue orders itself behind
+		return frame.end(); // what process_load_queue orders itself behind
 	};
 	if (int e = enqueue()) {
 		// part of the launch may be queued, and nothing records that it uses the ring entries and the pinned constants: wait for it
@@ -1447,9 +1335,7 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 		(void)hipStreamSynchronize(stream);
 		return e;
 	}
-	for (int e = first; e < first + count; ++e) ring_owner_[e] = launches_;
-	ring_next_ = first + count;
-	launches_++;
+	frame_ring_.issued(ring);
 	return 0;
 }
 
@@ -1481,16 +1367,17 @@ int Scene::cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t f
 	const bool request = !(flags & BM_QUERY_NO_REQUESTS);
 	DeviceScene view;
 	if (int e = begin_frame(stream, &view, nullptr)) return e;
+	FrameOrder::Ending frame(order_, stream);
 	if (!(flags & BM_QUERY_LOD)) view.lod_distance_8x8x8 = view.lod_distance_2x2x2 = INT_MAX; // exact: every brick at voxel level
-	const int slot = static_cast<int>(queries_ % kQueryRing);
+	const int slot = query_ring_.slot();
 	uint32_t* ticket = d_query_tickets_ + slot * 32;
-	if (queries_ >= static_cast<uint64_t>(kQueryRing)) BM_HIP(hipStreamWaitEvent(stream, ev_query_[slot], 0));
+	if (query_ring_.reused()) BM_HIP(hipStreamWaitEvent(stream, ev_query_[slot], 0));
 	BM_HIP(hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream));
 	launch_query(view, campos, rays, hits, static_cast<uint32_t>(n), ticket, query_blocks_per_cu_[request ? 1 : 0] * compute_units_, request, stream);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(ev_query_[slot], stream));
-	queries_++;
-	end_frame(stream);
+	query_ring_.issued();
+	(void)frame.end();
 	return 0;
 }
 
@@ -1509,40 +1396,37 @@ int Scene::query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* 
 	if (int e = require_not_failed()) return e;
 	BM_HIP(hipSetDevice(device_));
 	if (!volume_blocks_per_cu_[0]) {
-		if (int e = ev_volume_.create(hipEventDisableTiming)) return e;
 		volume_blocks_per_cu_[0] = volume_blocks_per_cu(false);
 		volume_blocks_per_cu_[1] = volume_blocks_per_cu(true);
 	}
 	const size_t need = volume_tmp_bytes(static_cast<uint32_t>(n));
 	if (d_volume_tmp_.bytes() < need) {
-		if (volume_busy_) { BM_HIP(hipEventSynchronize(ev_volume_)); volume_busy_ = false; }
+		if (int e = volume_.wait()) return e;
 		if (int e = d_volume_tmp_.reserve(std::max<size_t>(need, 1 << 16))) return e;
 	}
 	const bool any = (flags & BM_VOLUME_ANY) != 0;
 	DeviceScene view;
 	if (int e = begin_frame(stream, &view, nullptr)) return e;
-	if (volume_busy_) BM_HIP(hipStreamWaitEvent(stream, ev_volume_, 0));
+	FrameOrder::Ending frame(order_, stream);
+	if (int e = volume_.order(stream)) return e;
 	launch_volume_query(view, volumes, results, static_cast<uint32_t>(n), any, d_volume_tmp_, volume_blocks_per_cu_[any ? 1 : 0] * compute_units_, stream);
 	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_volume_, stream));
-	volume_busy_ = true;
-	end_frame(stream);
+	if (int e = volume_.pass(stream)) return e;
+	(void)frame.end();
 	return 0;
 }
 
 int Scene::begin_frame(hipStream_t stream, DeviceScene* view, DeviceCounters** counters) {
 	if (int e = require_on_device()) return e;
 	BM_HIP(hipSetDevice(device_));
-	if (int e = frame_begin(stream)) return e; // bricks uploaded on the load stream must be visible to this frame
+	if (int e = require_not_failed()) return e;
+	if (int e = order_.begin(stream)) return e; // bricks uploaded on the load stream must be visible to this frame
 	if (view) *view = view_;
 	if (counters) *counters = d_counters_;
 	return 0;
 }
 
-void Scene::end_frame(hipStream_t stream) {
-	other_frames_++;
-	(void)frame_end(stream);
-}
+void Scene::end_frame(hipStream_t stream) { (void)order_.end(stream); }
 
 int Scene::synchronize() {
 	BM_HIP(hipSetDevice(device_));
@@ -1552,9 +1436,9 @@ int Scene::synchronize() {
 
 int Scene::last_render_ms(float* ms) {
 	if (!ms) { set_error("null argument"); return BM_EINVAL; }
-	if (launches_ == 0) { set_error("no frame rendered yet"); return BM_ESTATE; }
+	if (frame_ring_.clock().launches() == 0) { set_error("no frame rendered yet"); return BM_ESTATE; }
 	BM_HIP(hipSetDevice(device_));
-	const int slot = static_cast<int>((launches_ - 1) % kTimingRing);
+	const int slot = frame_ring_.clock().last_slot();
 	BM_HIP(hipEventSynchronize(ev_stop_[slot]));
 	BM_HIP(hipEventElapsedTime(ms, ev_start_[slot], ev_stop_[slot]));
 	return 0;
@@ -1563,14 +1447,13 @@ int Scene::last_render_ms(float* ms) {
 int Scene::render_times(float* ms, int capacity, int* count) {
 	if (!ms || !count || capacity <= 0) { set_error("bad argument"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
-	const long long have = std::min<long long>(launches_, kTimingRing);
-	const long long n = std::min<long long>(have, capacity);
-	for (long long k = 0; k < n; ++k) {
-		const int slot = static_cast<int>((launches_ - n + k) % kTimingRing);
+	const int n = frame_ring_.clock().recent(capacity);
+	for (int k = 0; k < n; ++k) {
+		const int slot = frame_ring_.clock().recent_slot(n, k);
 		BM_HIP(hipEventSynchronize(ev_stop_[slot]));
 		BM_HIP(hipEventElapsedTime(&ms[k], ev_start_[slot], ev_stop_[slot]));
 	}
-	*count = static_cast<int>(n);
+	*count = n;
 	return 0;
 }
 

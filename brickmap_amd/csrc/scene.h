@@ -12,9 +12,11 @@
 #include "device_ops.h"
 #include "device_types.h"
 #include "error.h"
+#include "frame_order.h"
 #include "frame_plan.h"
 #include "hip_owned.h"
 #include "kernels.h"
+#include "launch_book.h"
 #include "walk_fields.h"
 #include "world.h"
 
@@ -75,7 +77,7 @@ public:
 	int sched_detail_read(uint64_t* out8);
 
 	// Hooks for a frame issued by other code on this scene (the wavefront mode): begin_frame orders `stream` behind
-	// pending brick uploads and hands out the current device view; end_frame records the "frame done" event process_load_queue waits for.
+	// pending brick uploads (frame_order.h) and hands out the current device view; end_frame records the "frame done" event process_load_queue waits for.
 	int begin_frame(hipStream_t stream, DeviceScene* view, DeviceCounters** counters);
 	void end_frame(hipStream_t stream);
 	int compute_units() const { return compute_units_; }
@@ -97,10 +99,10 @@ private:
 		std::vector<Brick> bricks;
 		std::vector<PoolMove> moves;
 		FieldChange change;
+		unsigned clocked() const { return cells.empty() ? 0u : change.occupancy() ? kClockedScatter | kClockedField : kClockedScatter; } // the stages submit_batch records for it
 	};
-	int wait_edit_staging();
 	int stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b);
-	int submit_batch(DeviceBatch& b, hipStream_t stream, Event* times, bool* scattered, bool* field_updated);
+	int submit_batch(DeviceBatch& b, hipStream_t stream, hipEvent_t* marks); // marks[0 ... 2]: around the scatter and the field update
 	int check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span);
 	RegionDims region_dims(const bm_region& r, const int lo[3], const int hi[3]) const;
 	// the bricks of the clipped box [lo, hi) that the device does not hold, from the host world into h_patch_ / d_patch_'s layout: *n of them,
@@ -108,7 +110,6 @@ private:
 	int stage_absent_bricks(bool inside, const int lo[3], const int hi[3], size_t* n, size_t* o_bricks, size_t* bytes);
 	// what the three label calls refuse about their box, before anything is launched; *d gets the box's dimensions
 	int check_label_box(const char* who, const int32_t lo[3], const int32_t hi[3], LabelDims* d, bool* empty);
-	int label_turn(hipStream_t stream);  // a label call waits for the one before it
 	void free_device();
 	int alloc_queue();
 	int service_ring(int ring, uint32_t count, uint32_t* serviced);
@@ -122,40 +123,15 @@ private:
 	int device_;
 	bool on_device_ = false;
 	// the owners below free what they hold when the scene goes, in reverse order of declaration: the streams last
-	Stream load_stream_, kernel_stream_; // Scene.cpp:34-35
+	Stream load_stream_; // Scene.cpp:34 (the reference's kernel stream, :35, has no counterpart: frames run on the caller's streams)
+	// Who waits for whom.  Frames and the queries issued like them, on any stream, against what rewrites the world on the load stream: order_
+	// (frame_order.h) owns those events and every decision about them.  The entries of the frame ring and the clocks of the launches:
+	// frame_ring_ (launch_book.h) says which entries a launch takes and which earlier launches it waits for; the events stand here, indexed by
+	// its clock slots.  A scratch or staging buffer that one call at a time may use: a Turn (hip_owned.h) beside the buffer.
+	FrameOrder order_;
 	static constexpr int kTimingRing = 256; // hipEvent pairs around the most recent render launches
 	Event ev_start_[kTimingRing], ev_stop_[kTimingRing];
-	Event ev_upload_;
-	long long launches_ = 0;       // render() launches (index into the timing ring)
-	long long other_frames_ = 0;   // frames issued through begin_frame / end_frame
-	// Ordering between frames and brick uploads.  Frames may be issued on any number of streams (bench.py --pipeline, the
-	// multi-stream tests); uploads run on the load stream.  Every stream a frame was issued on has an entry here:
-	// `done` is recorded behind its most recent frame (process_load_queue orders the ring copy-out and the scatter kernel
-	// behind ALL of them, not only behind the last frame launched), `upload_seen` is the upload batch the stream has
-	// already been ordered behind (a frame waits for ev_upload_ when its stream has not seen the latest batch).
-	struct FrameStream {
-		hipStream_t stream = nullptr;
-		Event done;
-		uint64_t upload_seen = 0;
-		uint64_t last_use = 0;
-	};
-	static constexpr size_t kMaxFrameStreams = 16;
-	std::vector<FrameStream> frame_streams_;
-	uint64_t upload_seq_ = 0, frame_seq_ = 0; // upload batches queued on the load stream / frames issued
-	bool staging_busy_ = false;               // the pinned staging buffers belong to an upload that may still be copying
-	bool failed_ = false;                     // a streaming batch could not be completed (allocation failure): residency state is undefined until reset
-	int frame_begin(hipStream_t stream);      // order `stream` behind pending uploads
-	int frame_end(hipStream_t stream);        // record the stream's "frame done" event
-	int wait_frames_on_host();                // host waits for every frame in flight
-	int order_load_stream_behind_frames();    // load stream waits for every frame in flight
-	// work that rewrites what frames read: queue() issues it on the load stream behind every frame in flight, and it is published as an upload batch -- every frame issued later waits for it
-	template <class Queue> int publish_behind_frames(Queue&& queue) {
-		if (int e = order_load_stream_behind_frames()) return e;
-		if (int e = queue()) return e;
-		BM_HIP(hipEventRecord(ev_upload_, load_stream_));
-		upload_seq_++;
-		return 0;
-	}
+	bool failed_ = false; // a streaming batch could not be completed (allocation failure): residency state is undefined until reset
 
 	// device memory (DeviceScene view)
 	DeviceBuffer<uint32_t> d_index_grid_, d_pool_base_;
@@ -173,16 +149,15 @@ private:
 	DeviceBuffer<FrameConstants> d_frame_constants_; // kFrameRing device copies
 	PinnedBuffer<FrameConstants> h_frame_constants_; // pinned source of the copies
 	DeviceBuffer<uint32_t> d_work_counter_; // chunk counters of the persistent trace kernel: kFrameRing blocks of kWorkCounterBytes, zeroed before the launch that uses them
-	long long ring_owner_[kFrameRing];   // the launch (value of launches_) that used the entry last, -1 = none
-	int ring_next_ = 0;
+	FrameRing<kFrameRing, kTimingRing, kMaxFramesPerLaunch> frame_ring_;
 	int compute_units_ = 0, blocks_per_cu_[2] = {0, 0};
 	// pinned staging (Scene.cpp:30-32)
 	PinnedBuffer<int> h_positions_[2];
 	PinnedBuffer<uint32_t> h_bricks_, h_indices_;
 	PinnedBuffer<uint32_t> h_count_[2];
-	bool overlapped_ = false, snapshot_pending_ = false;
+	bool overlapped_ = false;
 	int ring_cur_ = 0, ring_snapshot_ = 0;
-	Event ev_snapshot_;
+	Turn snapshot_; // pending: ring_snapshot_ is being copied out on the load stream
 
 	BrickArena arena_; // every supercell's pool (arena.h); view_.brick_arena follows its base
 	static constexpr uint32_t kStartingPool = BrickArena::kStartingPool;
@@ -193,40 +168,39 @@ private:
 	bool preloaded_ = false;                     // bm_scene_preload_all: an edit uploads new bricks at once (no requests are serviced)
 	DeviceBuffer<int> d_positions_;              // a ring's entries without the stale ones, when service_ring skips some
 	// edits: pinned + device staging of one batch (pool moves, dirty cells, their words, arena slots and bricks), grown on demand;
-	// the staging is free again once ev_edit_ has passed
+	// the pinned staging is the batch's until its copy has run (edit_staging_)
 	PinnedBuffer<char> h_edit_;
 	DeviceBuffer<char> d_edit_;
-	Event ev_edit_, ev_edit_caller_;
-	Event ev_edit_time_[3]; // around the scatter and the field update of the last batch
-	bool edit_timed_ = false, edit_field_timed_ = false;
-	bool edit_busy_ = false;
-	// region writes: the packed bricks of a device volume (64 bytes per covered cell, device + pinned, grown on demand) and the events
-	// around pack, copy, scatter and field; region reads: the list of non-resident bricks (pinned + device), free once ev_region_read_ has passed
+	Turn edit_staging_;
+	// region writes: the packed bricks of a device volume (64 bytes per covered cell, device + pinned, grown on demand);
+	// region reads: the list of non-resident bricks (pinned + device), the read's until its launch has used it (region_read_)
 	DeviceBuffer<char> d_region_, d_patch_;
 	PinnedBuffer<Brick> h_region_;
 	PinnedBuffer<char> h_patch_;
-	Event ev_region_time_[6], ev_region_read_;
-	bool region_timed_ = false, region_packed_ = false, region_scattered_ = false, region_field_ = false, region_read_busy_ = false;
-	// loads from device memory: events around classify + number, pack, field and mirror (created by the first such load)
-	Event ev_load_time_[6];
-	bool load_timed_ = false;
+	Turn region_read_;
+	// Stage clocks of the calls that report device times (StageMarks, made on first use), each with the stages its last call recorded.
+	// Edits: marks 0 ... 2 around scatter and field, of the last batch that scattered something.  Region writes: 0 ... 2 around pack and copy
+	// (a device volume), 3 ... 5 around scatter and field.  Loads from device memory: 0, 1 around classify + number, 2 ... 5 around pack,
+	// field and mirror (the host's round trip lies between 1 and 2).  label_region: 0 ... 3 around local, merge and flatten.
+	enum : unsigned { kClockedCall = 1, kClockedPack = 2, kClockedScatter = 4, kClockedField = 8 };
+	StageMarks<3> edit_marks_;
+	StageMarks<6> region_marks_, load_marks_;
+	StageMarks<4> label_marks_;
+	unsigned edit_clocked_ = 0, region_clocked_ = 0, load_clocked_ = 0, label_clocked_ = 0; // kClocked*: 0 = the call has nothing to report
 	// ray queries: a ring of slot counters (one 128-byte line each); a query that reuses an entry waits for the one that used it last
 	static constexpr int kQueryRing = 64;
 	DeviceBuffer<uint32_t> d_query_tickets_;
 	Event ev_query_[kQueryRing];
-	uint64_t queries_ = 0;
+	ClockRing<kQueryRing> query_ring_;
 	int query_blocks_per_cu_[2] = {0, 0};
 	// volume queries: the item offsets of one launch (volume_tmp_bytes, grown on demand); a query waits for the one before it, which used them
 	DeviceBuffer<uint64_t> d_volume_tmp_;
-	Event ev_volume_;
-	bool volume_busy_ = false;
+	Turn volume_;
 	int volume_blocks_per_cu_[2] = {0, 0};
 	// connected components: the root counts of one bm_scene_label_components (label_tmp_bytes, grown on demand); label calls of a scene run
-	// one after another, each waits for the one before it.  label_marks_: around local, merge and flatten of the last label_region
+	// one after another, each waits for the one before it
 	DeviceBuffer<uint64_t> d_label_tmp_;
-	Event ev_label_;
-	StageMarks<4> label_marks_;
-	bool label_busy_ = false, label_timed_ = false;
+	Turn label_;
 	int queue_cap_ = 1024;                       // variables.h:35
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27
 	DeviceScene view_{};
