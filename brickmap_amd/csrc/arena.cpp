@@ -9,13 +9,6 @@
 
 namespace bm {
 
-void BrickArena::reset() {
-	top_ = 0;
-	pool_bricks_ = 0;
-	for (auto& f : free_regions_) f.clear();
-	freed_this_batch_.clear();
-}
-
 // ---- the arena's address range.  Reserved once per world for the worst case -- every pool is a power of two >= its
 // supercell's brick count, and a pool that doubles its way up leaves regions of every smaller size behind (reused only by
 // pools of that size) -- i.e. below 4 x the world's bricks + 32 per supercell; address space costs nothing.
@@ -74,7 +67,8 @@ void BrickArena::close() {
 	base_ = nullptr;
 	virtual_ = false;
 	va_bytes_ = 0;
-	capacity_ = top_ = pool_bricks_ = 0;
+	capacity_ = 0;
+	regions_.reset();
 	chunks_.clear();
 }
 
@@ -83,7 +77,8 @@ void BrickArena::close() {
 // batches already queued are not disturbed (the reference grows one pool at a time with a blocking cudaMemcpy,
 // Scene.cpp:242-247).  exact: (re)size an EMPTY arena to fit a known residency (callers have synchronised the device).
 int BrickArena::reserve(uint64_t bricks, bool exact, bool* left_unmapped) {
-	if (bricks <= capacity_ && !(exact && top_ == 0 && capacity_ > 2 * std::max<uint64_t>(bricks, 1ull << 16))) return 0;
+	const uint64_t top = regions_.top();
+	if (bricks <= capacity_ && !(exact && top == 0 && capacity_ > 2 * std::max<uint64_t>(bricks, 1ull << 16))) return 0;
 	if (bricks >= (1ull << 32)) { set_error("brick arena would exceed 2^32 bricks"); return BM_EINVAL; }
 	if (virtual_) {
 		const size_t gran = granularity_;
@@ -93,7 +88,7 @@ int BrickArena::reserve(uint64_t bricks, bool exact, bool* left_unmapped) {
 		// (when the arena was unmapped for an exact re-size, any failure below is reported as *left_unmapped: the owner refuses frames
 		// until the residency has been rebuilt -- the device index words may still carry loaded bits)
 		auto fail = [&](int code) { if (remapping_empty_arena && left_unmapped) *left_unmapped = true; return code; };
-		if (exact && top_ == 0) {
+		if (exact && top == 0) {
 			if (!chunks_.empty()) BM_HIP(hipDeviceSynchronize()); // (callers have synchronised already; unmapping itself does not wait)
 			remapping_empty_arena = true; // from here on a failure leaves base() pointing at an unmapped range
 			if (int e = unmap_all()) return fail(e);
@@ -138,15 +133,15 @@ int BrickArena::reserve(uint64_t bricks, bool exact, bool* left_unmapped) {
 	if (!exact) { // growth by residency: double
 		cap = std::max<uint64_t>(capacity_, 1ull << 16); // 4 MiB to start with
 		while (cap < bricks) cap *= 2;
-	} else if (top_ == 0) {
+	} else if (top == 0) {
 		cap = std::max<uint64_t>(bricks, 1ull << 16); // (re)sized for a known residency: exact fit, shrinking an oversized arena
 	}
 	if (cap >= (1ull << 32)) { set_error("brick arena would exceed 2^32 bricks"); return BM_EINVAL; }
 	BM_HIP(hipDeviceSynchronize());
 	uint32_t* fresh = nullptr;
 	BM_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), cap * sizeof(Brick)));
-	if (base_ && top_ > 0) {
-		BM_HIP(hipMemcpy(fresh, base_, top_ * sizeof(Brick), hipMemcpyDeviceToDevice));
+	if (base_ && top > 0) {
+		BM_HIP(hipMemcpy(fresh, base_, top * sizeof(Brick), hipMemcpyDeviceToDevice));
 		growths_++; copy_growths_++;
 	}
 	if (base_) BM_HIP(hipFree(base_));
@@ -155,43 +150,11 @@ int BrickArena::reserve(uint64_t bricks, bool exact, bool* left_unmapped) {
 	return 0;
 }
 
-// A region of `bricks` (a power of two >= kStartingPool) for one pool: from the free list of that size, else from the top.
 int BrickArena::region_alloc(uint32_t bricks, uint32_t* offset) {
-	int cls = 0;
-	while ((1u << cls) < bricks) ++cls;
-	if (!free_regions_[cls].empty()) {
-		*offset = free_regions_[cls].back();
-		free_regions_[cls].pop_back();
-	} else {
-		if (int e = reserve(top_ + bricks)) return e;
-		*offset = static_cast<uint32_t>(top_);
-		top_ += bricks;
-	}
-	pool_bricks_ += bricks;
+	if (regions_.take_free(bricks, offset)) return 0;
+	if (int e = reserve(regions_.top() + bricks)) return e;
+	*offset = regions_.claim_top(bricks);
 	return 0;
-}
-
-uint32_t BrickArena::claim_top(uint64_t bricks) {
-	const uint32_t offset = static_cast<uint32_t>(top_);
-	top_ += bricks;
-	pool_bricks_ += bricks;
-	return offset;
-}
-
-// A vacated region becomes reusable once the batch that vacates it has been queued: its move kernel still reads it, and
-// a pool growing in the SAME batch must not be given it (later batches are ordered behind this one on the load stream).
-// The region is filed under the largest power of two it holds: a grown pool is one, and of a preloaded pool -- an exact fit --
-// only that much is handed out again.
-void BrickArena::region_free_deferred(uint32_t bricks, uint32_t offset) {
-	int cls = 0;
-	while ((2u << cls) <= bricks) ++cls;
-	freed_this_batch_.emplace_back(cls, offset);
-	pool_bricks_ -= bricks;
-}
-
-void BrickArena::commit_freed_regions() {
-	for (const auto& f : freed_this_batch_) free_regions_[f.first].push_back(f.second);
-	freed_this_batch_.clear();
 }
 
 } // namespace bm

@@ -1,6 +1,6 @@
 // arena.h -- the brick arena: one device address range that every supercell's pool lives in (Scene.cpp:152-175,231-251 made one
-// allocator).  Regions are powers of two of at least kStartingPool bricks, handed out from per-size free lists or
-// from the top of the arena.  The arena is a RESERVED VIRTUAL RANGE sized for the world's worst case into which
+// allocator).  Which region is whose is arithmetic without HIP, RegionLists (pool_book.h), held here as a member; this class keeps the
+// address range and maps memory before the top of the regions moves.  The arena is a RESERVED VIRTUAL RANGE sized for the world's worst case into which
 // physical chunks are mapped as residency grows (hipMemAddressReserve / hipMemCreate / hipMemMap): growing it
 // neither copies a brick nor synchronises the device, and every pointer into it stays valid for frames in flight.
 // (Devices without virtual memory management fall back to reallocate + copy behind a device synchronisation.)
@@ -8,15 +8,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <utility>
 #include <vector>
+
+#include "pool_book.h"
 
 namespace bm {
 
 class BrickArena {
 public:
-	static constexpr uint32_t kStartingPool = 16; // supergrid_starting_size, variables.h:15
-
 	BrickArena() = default;
 	BrickArena(const BrickArena&) = delete;
 	BrickArena& operator=(const BrickArena&) = delete;
@@ -24,19 +23,18 @@ public:
 
 	int open(int device, uint64_t max_bricks); // reserve the address range (once per world); base() may change
 	void close();
-	void reset();                              // nothing handed out, nothing free-listed; what is mapped stays mapped
+	void reset() { regions_.reset(); }         // nothing handed out, nothing free-listed; what is mapped stays mapped
 	// make the arena at least this large (contents kept); exact: (re)size an EMPTY arena to fit.  *left_unmapped: the emptied arena
 	// was unmapped and could not be mapped again.  base() may change (reallocate + copy devices only).
 	int reserve(uint64_t bricks, bool exact = false, bool* left_unmapped = nullptr);
-	int region_alloc(uint32_t bricks, uint32_t* offset);
-	void region_free_deferred(uint32_t bricks, uint32_t offset);
-	void commit_freed_regions();               // regions vacated by the batch just queued become reusable by the next
-	uint32_t claim_top(uint64_t bricks);       // an exact-fit pool (preloaded residency) from the top of a reserve()d arena: its offset
+	int region_alloc(uint32_t bricks, uint32_t* offset); // a region for one pool: a free one of that size, else the arena grows to hold it at the top
+	uint32_t claim_top(uint64_t bricks) { return regions_.claim_top(bricks); } // an exact-fit pool from the top of a reserve()d arena: its offset
+	RegionLists& regions() { return regions_; } // where vacated regions go back to (pool_book.h)
 
 	uint32_t* base() const { return base_; }
 	bool is_virtual() const { return virtual_; }
 	uint64_t capacity() const { return capacity_; }       // bricks mapped
-	uint64_t pool_bricks() const { return pool_bricks_; } // bricks of capacity currently handed to pools
+	uint64_t pool_bricks() const { return regions_.pool_bricks(); } // bricks of capacity currently handed to pools
 	uint64_t growths() const { return growths_; }         // times the arena grew / grew by synchronise + copy
 	uint64_t copy_growths() const { return copy_growths_; }
 
@@ -50,10 +48,8 @@ private:
 	size_t va_bytes_ = 0, granularity_ = 0;
 	std::vector<Chunk> chunks_;
 	uint64_t growths_ = 0, copy_growths_ = 0;
-	uint64_t capacity_ = 0, top_ = 0; // bricks
-	uint64_t pool_bricks_ = 0;
-	std::vector<uint32_t> free_regions_[32];                 // [log2 size]: arena offsets of free regions
-	std::vector<std::pair<int, uint32_t>> freed_this_batch_; // (log2 size, offset) of regions vacated by the batch being built
+	uint64_t capacity_ = 0; // bricks mapped
+	RegionLists regions_;
 };
 
 } // namespace bm

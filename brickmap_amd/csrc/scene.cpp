@@ -1,18 +1,15 @@
-// scene.cpp -- device residency, brick streaming and frame launch for one GPU.
+// scene.cpp -- one GPU's scene: the world on the device, edits, regions, labels, queries and frame launch (residency and streaming: residency.cpp).
 #include "scene.h"
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <thread>
-#include <unordered_map>
 
 #include "buffer_checks.h"
 #include "label.h"
@@ -43,7 +40,7 @@ int Scene::require_on_device() const {
 }
 
 int Scene::require_not_failed() const {
-	if (failed_) { set_error("a streaming batch failed on this scene: call bm_scene_reset_residency / bm_scene_preload_all"); return BM_ESTATE; }
+	if (residency_.book().failed()) { set_error(PoolBook::kFailedWhy); return BM_ESTATE; }
 	return 0;
 }
 
@@ -70,11 +67,7 @@ int Scene::init(int grid_size, int grid_height) {
 	}
 	if (int e = order_.init(load_stream_)) return e;
 	if (int e = edit_marks_.create()) return e;
-	for (int r = 0; r < 2; ++r) {
-		if (int e = h_count_[r].alloc(sizeof(uint32_t))) return e;
-		if (int e = d_load_count_[r].alloc(sizeof(uint32_t))) return e;
-		BM_HIP(hipMemset(d_load_count_[r], 0, sizeof(uint32_t)));
-	}
+	if (int e = residency_.init(&view_)) return e;
 	if (int e = d_counters_.alloc(sizeof(DeviceCounters))) return e;
 	BM_HIP(hipMemset(d_counters_, 0, sizeof(DeviceCounters)));
 	if (int e = d_work_counter_.alloc(kWorkCounterBytes * kFrameRing)) return e; // one block of counters per frame in flight
@@ -86,69 +79,15 @@ int Scene::init(int grid_size, int grid_height) {
 	blocks_per_cu_[0] = blocks_per_cu_[1] = 0; // no cap: every instantiation of the fused kernel runs at its own occupancy (trace.hip launch_trace)
 	if (tuning().blocks_per_cu > 0) blocks_per_cu_[0] = tuning().blocks_per_cu; // experiment knob: fewer resident waves per SIMD (1 block = 1 wave per SIMD)
 
-	return alloc_queue();
+	return residency_.alloc_queue();
 }
 
-int Scene::alloc_queue() {
-	BM_HIP(hipSetDevice(device_));
-	const size_t n = static_cast<size_t>(queue_cap_);
-	for (int r = 0; r < 2; ++r) {
-		if (int e = h_positions_[r].alloc(n * 3 * sizeof(int))) return e; // Scene.cpp:30
-		if (int e = d_load_queue_[r].alloc(n * 3 * sizeof(int))) return e; // Scene.cpp:186
-		BM_HIP(hipMemset(d_load_queue_[r], 0, n * 3 * sizeof(int)));
-		BM_HIP(hipMemset(d_load_count_[r], 0, sizeof(uint32_t)));
-	}
-	if (int e = h_bricks_.alloc(n * sizeof(Brick))) return e;             // Scene.cpp:31
-	if (int e = h_indices_.alloc(n * sizeof(uint32_t))) return e;         // Scene.cpp:32
-	if (int e = d_bricks_queue_.alloc(n * sizeof(Brick))) return e;       // Scene.cpp:189
-	if (int e = d_indices_queue_.alloc(n * sizeof(uint32_t))) return e;   // Scene.cpp:190
-	if (int e = d_positions_.alloc(n * 3 * sizeof(int))) return e;
-	// a batch of n requests can make at most n pools grow
-	if (int e = h_moves_.alloc(n * sizeof(PoolMove))) return e;
-	if (int e = d_moves_.alloc(n * sizeof(PoolMove))) return e;
-	use_ring(0);
-	snapshot_.clear();
-	view_.queue_cap = static_cast<uint32_t>(queue_cap_);
-	return 0;
-}
-
-void Scene::use_ring(int ring) {
-	ring_cur_ = ring;
-	view_.load_queue = d_load_queue_[ring];
-	view_.load_queue_count = d_load_count_[ring];
-}
-
-void Scene::residency_rebuilt(bool preloaded) {
-	use_ring(0);
-	snapshot_.clear();
-	preloaded_ = preloaded;
+void Scene::residency_rebuilt() {
 	fields_.book().residency_rebuilt();
 	order_.residency_rebuilt();
-	failed_ = false;
-	stream_batches_ = stream_host_ns_ = 0;
 }
 
-int Scene::set_streaming_mode(int overlapped) {
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	if (snapshot_.pending()) { // drain: the copied-out ring is serviced now, so no request is lost by switching modes
-		snapshot_.clear();
-		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[ring_snapshot_]);
-		if (count > 0) {
-			if (int e = service_ring(ring_snapshot_, count, nullptr)) return e;
-		}
-		BM_HIP(hipDeviceSynchronize());
-	}
-	if (overlapped_ && !overlapped && ring_cur_ != 0) {
-		// the blocking mode always works on ring 0: carry over whatever the last frame queued in ring 1
-		BM_HIP(hipMemcpy(d_load_queue_[0], d_load_queue_[1], static_cast<size_t>(queue_cap_) * 3 * sizeof(int), hipMemcpyDeviceToDevice));
-		BM_HIP(hipMemcpy(d_load_count_[0], d_load_count_[1], sizeof(uint32_t), hipMemcpyDeviceToDevice));
-		BM_HIP(hipMemset(d_load_count_[1], 0, sizeof(uint32_t)));
-		use_ring(0);
-	}
-	overlapped_ = overlapped != 0;
-	return 0;
-}
+int Scene::set_streaming_mode(int overlapped) { return residency_.set_streaming_mode(overlapped, order_, load_stream_); }
 
 int Scene::set_lod(int lod8, int lod2) {
 	lod8_ = lod8;
@@ -163,35 +102,13 @@ int Scene::set_queue_capacity(int cap) {
 	// resizing the ring drops what it holds while the REQUESTED bits of those bricks stay set (they would never be asked
 	// for again): the capacity belongs to the scene's construction, like the reference's constexpr (variables.h:35)
 	if (on_device_) { set_error("set the queue capacity before bm_scene_generate"); return BM_ESTATE; }
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	queue_cap_ = cap;
-	return alloc_queue();
+	return residency_.set_queue_capacity(cap);
 }
 
 void Scene::free_device() {
-	(void)d_index_grid_.release();
-	(void)d_pool_base_.release();
-	arena_.close();
+	residency_.release();
 	fields_.release();
 	on_device_ = false;
-}
-
-// ---------------------------------------------------------------- brick arena (arena.h): the device view follows its base
-int Scene::arena_fit(uint64_t bricks) {
-	arena_.reset();
-	bool left_unmapped = false;
-	const int e = arena_.reserve(std::max<uint64_t>(bricks, 1), true, &left_unmapped);
-	// (frames are refused until bm_scene_reset_residency / bm_scene_preload_all succeeds: view_.brick_arena points at an unmapped range)
-	if (left_unmapped) failed_ = true;
-	view_.brick_arena = arena_.base();
-	return e;
-}
-
-int Scene::pool_region(uint32_t bricks, uint32_t* offset) {
-	const int e = arena_.region_alloc(bricks, offset);
-	view_.brick_arena = arena_.base();
-	return e;
 }
 
 // device half of Scene::generate (Scene.cpp:152-190): one flat index grid, one pool-base word per supercell and one
@@ -203,9 +120,8 @@ int Scene::allocate_device() {
 	uint64_t run = 0;
 	for (int i = 0; i < d.supercells; ++i) run += world.supercells[i].bricks.size();
 	if (run >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
-	if (int e = alloc_index_grid()) return e;
-	if (int e = arena_.open(device_, 4 * run + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
-	view_.brick_arena = arena_.base();
+	if (int e = residency_.alloc_index_grid()) return e;
+	if (int e = residency_.open_arena(run)) return e;
 	if (int e = fields_.allocate(d, &view_)) return e;
 	{ // the host builds the field with tight rows (world.cpp) and every slice is copied row by row
 		std::vector<uint8_t> field;
@@ -216,21 +132,8 @@ int Scene::allocate_device() {
 	on_device_ = true;
 	if (int e = reset_residency()) return e;
 	// the escape heights alone (the field is the host's), from the index words reset_residency has just written: which words are non-zero never changes with residency
-	if (int e = fields_.update(d_index_grid_, FieldChange::whole(d), false, load_stream_)) return e;
+	if (int e = fields_.update(residency_.index_grid(), FieldChange::whole(d), false, load_stream_)) return e;
 	BM_HIP(hipStreamSynchronize(load_stream_));
-	return 0;
-}
-
-// the flat index grid and one pool-base word per supercell
-int Scene::alloc_index_grid() {
-	const WorldDims& d = world.dims;
-	const size_t index_bytes = static_cast<size_t>(d.supercells) * kCellsPerSupercell * sizeof(uint32_t);
-	if (int e = d_index_grid_.alloc(index_bytes)) return e;
-	if (int e = d_pool_base_.alloc(static_cast<size_t>(d.supercells) * sizeof(uint32_t))) return e;
-	BM_HIP(hipMemset(d_pool_base_, 0, static_cast<size_t>(d.supercells) * sizeof(uint32_t)));
-	view_.index_grid = d_index_grid_;
-	view_.pool_base = d_pool_base_;
-	view_.brick_arena = nullptr;
 	return 0;
 }
 
@@ -265,74 +168,17 @@ int Scene::generate_supercell(int sx, int sy, int sz) {
 	return 0;
 }
 
-// reference initial state: every non-empty brick is "unloaded | lod", nothing resident (Scene.cpp:157-175)
 int Scene::reset_residency() {
 	if (int e = require_on_device()) return e;
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	const WorldDims& d = world.dims;
-	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell);
-	std::vector<uint32_t> bases(d.supercells, 0u);
-	// every supercell that holds bricks starts with a pool of kStartingPool bricks (Scene.cpp:157-175, variables.h:15)
-	uint64_t initial = 0;
-	for (int i = 0; i < d.supercells; ++i) initial += world.supercells[i].bricks.empty() ? 0u : kStartingPool;
-	if (int e = arena_fit(initial)) return e;
-	for (int i = 0; i < d.supercells; ++i) {
-		HostSupercell& c = world.supercells[i];
-		c.resident = 0;
-		c.pool_capacity = 0;
-		c.pool_base = 0;
-		c.dev_slot.assign(c.bricks.size(), kNoDeviceSlot);
-		c.pool_free.clear();
-		if (!c.bricks.empty()) {
-			if (int e = pool_region(kStartingPool, &c.pool_base)) return e;
-			c.pool_capacity = kStartingPool;
-		}
-		bases[i] = c.pool_base;
-		uint32_t* dst = &words[static_cast<size_t>(i) * kCellsPerSupercell];
-		for (int j = 0; j < kCellsPerSupercell; ++j)
-			dst[j] = (c.indices[j] & BM_BRICK_LOADED_BIT) ? (BM_BRICK_UNLOADED_BIT | (c.indices[j] & BM_BRICK_LOD_BITS)) : 0u;
-	}
-	BM_HIP(hipMemcpy(d_index_grid_, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	BM_HIP(hipMemcpy(d_pool_base_, bases.data(), bases.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	for (int r = 0; r < 2; ++r) BM_HIP(hipMemset(d_load_count_[r], 0, sizeof(uint32_t)));
-	resident_bricks_ = 0;
-	residency_rebuilt(false);
+	if (int e = residency_.reset()) return e;
+	residency_rebuilt();
 	return 0;
 }
 
 int Scene::preload_all() {
 	if (int e = require_on_device()) return e;
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	const WorldDims& d = world.dims;
-	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell);
-	std::vector<uint32_t> bases(d.supercells, 0u);
-	// "all bricks pre-loaded" (BASELINE configs 1-2): every pool is its supercell's full host brick vector, exact fit, and
-	// the device words are the host words (slot | loaded | lod, Scene.cpp:104).  Host slots that edits freed keep their place in the
-	// pool and are the pool's free slots.
-	uint64_t total_bricks = 0;
-	for (int i = 0; i < d.supercells; ++i) total_bricks += world.supercells[i].bricks.size();
-	if (int e = arena_fit(total_bricks)) return e;
-	for (int i = 0; i < d.supercells; ++i) {
-		HostSupercell& c = world.supercells[i];
-		c.pool_base = arena_.claim_top(c.bricks.size());
-		c.pool_capacity = static_cast<uint32_t>(c.bricks.size());
-		bases[i] = c.pool_base;
-		std::memcpy(&words[static_cast<size_t>(i) * kCellsPerSupercell], c.indices.data(), kCellsPerSupercell * sizeof(uint32_t));
-		c.resident = static_cast<uint32_t>(c.bricks.size());
-		c.dev_slot.resize(c.bricks.size());
-		for (size_t s = 0; s < c.bricks.size(); ++s) c.dev_slot[s] = static_cast<uint16_t>(s);
-		c.pool_free = c.free_slots;
-		if (!c.bricks.empty())
-			BM_HIP(hipMemcpy(arena_.base() + static_cast<size_t>(c.pool_base) * kBrickWords, c.bricks.data(), c.bricks.size() * sizeof(Brick), hipMemcpyHostToDevice));
-	}
-	BM_HIP(hipMemcpy(d_pool_base_, bases.data(), bases.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	BM_HIP(hipMemcpyAsync(d_index_grid_, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, load_stream_));
-	for (int r = 0; r < 2; ++r) BM_HIP(hipMemsetAsync(d_load_count_[r], 0, sizeof(uint32_t), load_stream_));
-	BM_HIP(hipStreamSynchronize(load_stream_));
-	resident_bricks_ = world.total_bricks();
-	residency_rebuilt(true);
+	if (int e = residency_.preload_all(load_stream_)) return e;
+	residency_rebuilt();
 	return 0;
 }
 
@@ -379,7 +225,7 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	world.generated = false;
 	if (int e = load_marks_.create()) return e;
 	hipEvent_t* const marks = load_marks_.marks();
-	if (int e = alloc_index_grid()) return e;
+	if (int e = residency_.alloc_index_grid()) return e;
 	if (int e = fields_.allocate(d, &view_)) return e;
 	set_view_dims();
 	LoadDims ld{static_cast<uint32_t>(d.grid_size), static_cast<uint32_t>(d.supergrid_xy), static_cast<uint32_t>(d.supergrid_xy * d.supergrid_xy),
@@ -393,10 +239,12 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	if (int e = fields_.prepare_update(all, nullptr)) return e; // (load_voxels has synchronised the device: no stream to wait for, unlike submit_batch)
 	if (int e = order_.load_behind_caller(stream)) return e; // the volume is whatever the caller's stream has written by now
 	// ---- classify + number
+	uint32_t* const index_grid = residency_.index_grid();
+	uint32_t* const pool_base = residency_.pool_base();
 	BM_HIP(hipEventRecord(marks[0], load_stream_));
-	launch_load_classify(voxels, d_index_grid_, ld, load_stream_);
+	launch_load_classify(voxels, index_grid, ld, load_stream_);
 	BM_HIP(hipGetLastError());
-	launch_load_number(d_index_grid_, counts, d_pool_base_, d_total, ld, load_stream_);
+	launch_load_number(index_grid, counts, pool_base, d_total, ld, load_stream_);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(marks[1], load_stream_));
 	uint32_t total_words[2] = {0, 0};
@@ -404,27 +252,28 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	BM_HIP(hipStreamSynchronize(load_stream_)); // the one host round trip: the arena is sized by what the volume holds
 	const uint64_t total = total_words[0] | (static_cast<uint64_t>(total_words[1]) << 32);
 	if (total >= (1ull << 32)) { set_error("world has more than 2^32 bricks"); return BM_EINVAL; }
-	if (int e = arena_.open(device_, 4 * total + 32ull * static_cast<uint64_t>(d.supercells) + (1ull << 16))) return e;
-	if (int e = arena_fit(total)) return e;
+	if (int e = residency_.open_arena(total)) return e;
+	if (int e = residency_.arena_fit(total)) return e;
 	// ---- pack
 	BM_HIP(hipEventRecord(marks[2], load_stream_));
-	launch_load_pack(voxels, d_index_grid_, d_pool_base_, arena_.base(), ld, load_stream_);
+	launch_load_pack(voxels, index_grid, pool_base, residency_.arena_base(), ld, load_stream_);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(marks[3], load_stream_));
 	// ---- field
-	if (int e = fields_.update(d_index_grid_, all, true, load_stream_)) return e;
+	if (int e = fields_.update(index_grid, all, true, load_stream_)) return e;
 	BM_HIP(hipEventRecord(marks[4], load_stream_));
 	// ---- mirror: the host world becomes what World::load_voxels builds, in the state preload_all leaves it in
 	std::vector<uint32_t> words(static_cast<size_t>(d.supercells) * kCellsPerSupercell), bases(d.supercells);
 	std::vector<Brick> bricks(total);
-	BM_HIP(hipMemcpyAsync(words.data(), d_index_grid_, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
-	BM_HIP(hipMemcpyAsync(bases.data(), d_pool_base_, bases.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
-	if (total) BM_HIP(hipMemcpyAsync(bricks.data(), arena_.base(), total * sizeof(Brick), hipMemcpyDeviceToHost, load_stream_));
-	for (int r = 0; r < 2; ++r) BM_HIP(hipMemsetAsync(d_load_count_[r], 0, sizeof(uint32_t), load_stream_));
+	BM_HIP(hipMemcpyAsync(words.data(), index_grid, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
+	BM_HIP(hipMemcpyAsync(bases.data(), pool_base, bases.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_));
+	if (total) BM_HIP(hipMemcpyAsync(bricks.data(), residency_.arena_base(), total * sizeof(Brick), hipMemcpyDeviceToHost, load_stream_));
+	if (int e = residency_.clear_ring_counts(load_stream_)) return e;
 	BM_HIP(hipEventRecord(marks[5], load_stream_));
 	BM_HIP(hipStreamSynchronize(load_stream_));
 	world.supercells.clear();
 	world.supercells.resize(d.supercells);
+	residency_.begin_adopt();
 	std::atomic<int> next{0};
 	auto fill = [&]() {
 		for (int i = next.fetch_add(1); i < d.supercells; i = next.fetch_add(1)) {
@@ -433,10 +282,7 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 			const uint64_t end = i + 1 < d.supercells ? bases[i + 1] : total;
 			c.indices.assign(w, w + kCellsPerSupercell);
 			c.bricks.assign(bricks.begin() + bases[i], bricks.begin() + static_cast<ptrdiff_t>(end));
-			c.pool_base = bases[i];
-			c.pool_capacity = c.resident = static_cast<uint32_t>(c.bricks.size());
-			c.dev_slot.resize(c.bricks.size());
-			for (size_t s = 0; s < c.bricks.size(); ++s) c.dev_slot[s] = static_cast<uint16_t>(s);
+			residency_.adopt(i, bases[i]);
 		}
 	};
 	{
@@ -446,10 +292,9 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 		for (auto& t : pool) t.join();
 	}
 	world.generated = true;
-	arena_.claim_top(total);
-	resident_bricks_ = total;
+	residency_.adopted(total);
 	on_device_ = true;
-	residency_rebuilt(true);
+	residency_rebuilt();
 	load_clocked_ = kClockedCall;
 	return 0;
 }
@@ -478,164 +323,16 @@ int Scene::host_voxels(uint8_t* dst, size_t capacity, size_t* bytes) {
 	return 0;
 }
 
-// ---------------------------------------------------------------- streaming
-// Stage the first `count` requests of a ring (positions already in its pinned mirror), copy them up and scatter
-// them into the arena / index grid on the load stream (Scene.cpp:215-229 + the upload kernel, kernel.cu:141-151,412-413).
-// An entry is stale when an edit has emptied its brick since it was requested, or when its brick is resident already (a brick an
-// edit changed is asked for again, and may then stand in the ring twice): it is skipped and not counted in *serviced.
-int Scene::service_ring(int ring, uint32_t count, uint32_t* serviced) {
-	const auto t_host0 = std::chrono::steady_clock::now();
-	const WorldDims& d = world.dims;
-	int* pos = h_positions_[ring];
-	// ---- pass 1: nothing is mutated before every entry has been checked (the positions come back from device memory:
-	// never index host arrays with an entry that cannot be a request)
-	for (uint32_t i = 0; i < count; ++i) {
-		const int px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
-		if (px < 0 || py < 0 || pz < 0 || px >= d.cells || py >= d.cells || pz >= d.cells_height) {
-			// (the ring's counter is still set and the requested bits still stand: every later call would fail the same way while
-			// frames went on as if nothing had happened -- mark the scene failed, recovery is a residency reset)
-			set_error("brick request ring holds a position outside the world");
-			failed_ = true;
-			return BM_ESTATE;
-		}
-		const HostSupercell& c = world.supercells[d.supercell_id(px / kSupercell, py / kSupercell, pz / kSupercell)];
-		const uint32_t word = c.indices[cell_local_index(px, py, pz)];
-		if (word != 0 && (!(word & BM_BRICK_LOADED_BIT) || (word & BM_BRICK_INDEX_BITS) >= c.bricks.size() || (word & BM_BRICK_INDEX_BITS) >= c.dev_slot.size())) {
-			set_error("brick request ring names a brick that does not exist");
-			failed_ = true;
-			return BM_ESTATE;
-		}
-	}
-	if (int e = order_.wait_upload_on_host()) return e; // the staging buffers of the previous upload are free again once its copies have run
-	// ---- pass 2: hand out slots, grow pools.  From here on host state changes entry by entry; the only thing that can
-	// still go wrong is running out of device memory while the arena grows, and that leaves the scene marked as failed
-	// (every later frame / batch is refused until the residency is reset) instead of half-updated and in use.
-	uint32_t n_moves = 0, kept = 0;
-	std::unordered_map<int, uint32_t> batch_first_resident, batch_move; // per supercell: bricks resident before this batch / its entry in h_moves_
-	for (uint32_t i = 0; i < count; ++i) {
-		const int px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
-		const int sci = d.supercell_id(px / kSupercell, py / kSupercell, pz / kSupercell);
-		HostSupercell& c = world.supercells[sci];
-		const uint32_t word = c.indices[cell_local_index(px, py, pz)];
-		if (word == 0 || c.dev_slot[word & BM_BRICK_INDEX_BITS] != kNoDeviceSlot) continue; // stale (above)
-		const uint32_t i_out = kept++;
-		if (i_out != i) { pos[3 * i_out] = px; pos[3 * i_out + 1] = py; pos[3 * i_out + 2] = pz; }
-		std::memcpy(h_bricks_ + static_cast<size_t>(i_out) * kBrickWords, c.bricks[word & BM_BRICK_INDEX_BITS].data, sizeof(Brick));
-		// slots are handed out in request order (gpu_index_highest++, Scene.cpp:224); a full pool doubles first
-		// (Scene.cpp:231-251: 2^ceil(log2(highest + 1))) -- here it moves to a larger region of the arena.  A slot an edit freed is reused first.
-		const uint32_t resident_before_batch = batch_first_resident.emplace(sci, c.resident).first->second;
-		if (!c.pool_free.empty()) {
-			const uint32_t slot = c.pool_free.back();
-			c.pool_free.pop_back();
-			c.dev_slot[word & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(slot);
-			h_indices_[i_out] = slot | BM_BRICK_LOADED_BIT | (word & BM_BRICK_LOD_BITS);
-			continue;
-		}
-		if (c.resident >= c.pool_capacity) {
-			const uint32_t grown = std::max<uint32_t>(kStartingPool, c.pool_capacity * 2u);
-			uint32_t fresh = 0;
-			if (int e = pool_region(grown, &fresh)) { failed_ = true; return e; }
-			// Only the bricks that were resident BEFORE this batch have to be copied (the batch's own bricks are scattered to
-			// base + slot after the bases are published), and only once: a pool that grows twice in one batch moves from
-			// the region it had when the batch began straight to the last one.
-			auto mv = batch_move.find(sci);
-			if (mv == batch_move.end()) {
-				batch_move.emplace(sci, n_moves);
-				h_moves_[n_moves++] = PoolMove{c.pool_base, fresh, resident_before_batch, static_cast<uint32_t>(sci)};
-			} else {
-				h_moves_[mv->second].dst = fresh;
-			}
-			if (c.pool_capacity > 0) arena_.region_free_deferred(c.pool_capacity, c.pool_base);
-			c.pool_base = fresh;
-			c.pool_capacity = grown;
-		}
-		c.dev_slot[word & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(c.resident);
-		h_indices_[i_out] = c.resident | BM_BRICK_LOADED_BIT | (word & BM_BRICK_LOD_BITS);
-		c.resident++;
-	}
-	const bool compacted = kept != count; // stale entries were dropped: the scatter reads the kept positions from d_positions_
-	auto queue = [&]() -> int {
-		BM_HIP(hipMemcpyAsync(d_bricks_queue_, h_bricks_, static_cast<size_t>(kept) * sizeof(Brick), hipMemcpyHostToDevice, load_stream_));    // :228
-		BM_HIP(hipMemcpyAsync(d_indices_queue_, h_indices_, static_cast<size_t>(kept) * sizeof(uint32_t), hipMemcpyHostToDevice, load_stream_)); // :229
-		if (compacted) BM_HIP(hipMemcpyAsync(d_positions_, pos, static_cast<size_t>(kept) * 3 * sizeof(int), hipMemcpyHostToDevice, load_stream_));
-		// The scatter kernel rewrites index words that a frame still in flight may be reading and requesting through
-		// (plain load + atomicOr): a word flipping to "loaded" between the two would be requested a second time; the move
-		// kernel rewrites pool bases such a frame addresses bricks with.  In overlapped mode both therefore run behind every
-		// frame in flight, whatever stream it is on; the copies above already overlap them.
-		if (overlapped_) { if (int e = order_.load_behind_frames()) return e; }
-		DeviceScene ring_view = view_;
-		ring_view.load_queue = compacted ? d_positions_.get() : d_load_queue_[ring].get();
-		ring_view.load_queue_count = d_load_count_[ring];
-		if (n_moves > 0) { // grown pools: copy their bricks to the new regions and publish the new bases, ahead of the scatter
-			BM_HIP(hipMemcpyAsync(d_moves_, h_moves_, static_cast<size_t>(n_moves) * sizeof(PoolMove), hipMemcpyHostToDevice, load_stream_));
-			launch_pool_moves(d_moves_, n_moves, arena_.base(), d_pool_base_, load_stream_);
-			BM_HIP(hipGetLastError());
-		}
-		launch_upload(ring_view, d_bricks_queue_, d_indices_queue_, arena_.base(), kept, load_stream_); // kernel.cu:412
-		BM_HIP(hipGetLastError());
-		BM_HIP(hipMemsetAsync(d_load_count_[ring], 0, sizeof(uint32_t), load_stream_));             // kernel.cu:413
-		return order_.published(true);
-	};
-	if (int e = queue()) { failed_ = true; return e; } // the host bookkeeping is ahead of the device: refuse to go on
-	arena_.commit_freed_regions();
-	resident_bricks_ += kept;
-	if (serviced) *serviced = kept;
-	stream_batches_++;
-	stream_host_ns_ += static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_host0).count());
-	return 0;
-}
-
+// ---------------------------------------------------------------- streaming and readbacks: residency.cpp
 int Scene::process_load_queue(uint32_t* serviced) {
 	if (serviced) *serviced = 0;
 	if (int e = require_on_device()) return e;
 	if (int e = require_not_failed()) return e;
 	BM_HIP(hipSetDevice(device_));
-	if (!overlapped_) {
-		// ---- reference order (main.cpp:142-144): the frames that raised the requests have finished (kernel.cu:431), the host
-		// reads the ring, stages, uploads; the next frame sees the bricks
-		if (int e = order_.wait_frames_on_host()) return e; // every stream a frame was issued on
-		BM_HIP(hipMemcpyAsync(h_count_[0], d_load_count_[0], sizeof(uint32_t), hipMemcpyDeviceToHost, load_stream_)); // Scene.cpp:202
-		BM_HIP(hipStreamSynchronize(load_stream_));
-		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[0]);                   // Scene.cpp:203
-		if (count == 0) return 0;
-		BM_HIP(hipMemcpyAsync(h_positions_[0], d_load_queue_[0], static_cast<size_t>(count) * 3 * sizeof(int), hipMemcpyDeviceToHost, load_stream_)); // :209
-		BM_HIP(hipStreamSynchronize(load_stream_));
-		return service_ring(0, count, serviced);
-	}
-	// ---- overlapped mode: never wait for the GPU.  (1) service the ring that was copied out by the previous call,
-	// (2) start copying out the ring the last frame wrote, behind that frame, on the load stream, (3) hand the other
-	// ring to the next frame.  A brick requested in frame k is resident from frame k+2 on (reference order: from k+1 on).
-	if (snapshot_.pending()) {
-		if (int e = snapshot_.wait()) return e;
-		const uint32_t count = std::min<uint32_t>(static_cast<uint32_t>(queue_cap_), *h_count_[ring_snapshot_]);
-		if (count > 0) {
-			if (int e = service_ring(ring_snapshot_, count, serviced)) return e;
-		}
-	}
-	if (int e = order_.load_behind_frames()) return e; // the ring is complete once every frame that may append to it has ended
-	const int ring = ring_cur_;
-	// the count is not known on the host without waiting for the frame: a small kernel copies count + the entries that exist into
-	// the pinned (device-mapped) mirrors -- min(count, capacity) x 12 bytes over PCIe instead of the ring's whole capacity
-	{
-		int* dev_positions = nullptr;
-		uint32_t* dev_count = nullptr;
-		BM_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev_positions), h_positions_[ring], 0));
-		BM_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev_count), h_count_[ring], 0));
-		launch_snapshot_ring(d_load_queue_[ring], d_load_count_[ring], dev_positions, dev_count, static_cast<uint32_t>(queue_cap_), load_stream_);
-		BM_HIP(hipGetLastError());
-	}
-	if (int e = snapshot_.pass(load_stream_)) return e;
-	ring_snapshot_ = ring;
-	use_ring(ring ^ 1);
-	return 0;
+	return residency_.process_load_queue(order_, load_stream_, serviced);
 }
 
-int Scene::dump(const char* path) { // Scene.cpp:254-258
-	std::ofstream file(path ? path : "dump.txt");
-	if (!file) { set_error("cannot open dump file"); return BM_EINVAL; }
-	for (const auto& c : world.supercells) file << c.resident << "\n";
-	return 0;
-}
+int Scene::dump(const char* path) { return residency_.dump(path); }
 
 int Scene::info(bm_scene_info* out) {
 	if (!out) { set_error("null argument"); return BM_EINVAL; }
@@ -643,46 +340,25 @@ int Scene::info(bm_scene_info* out) {
 	std::memset(out, 0, sizeof *out);
 	out->grid_size = d.grid_size; out->grid_height = d.grid_height;
 	out->supergrid_xy = d.supergrid_xy; out->supergrid_z = d.supergrid_z; out->supercells = d.supercells;
-	out->queue_capacity = queue_cap_;
 	out->lod_distance_8x8x8 = lod8_; out->lod_distance_2x2x2 = lod2_;
 	out->generated = world.generated ? 1 : 0;
 	out->on_device = on_device_ ? 1 : 0;
 	out->total_bricks = world.generated ? world.total_bricks() : 0;
-	out->resident_bricks = resident_bricks_;
-	out->index_bytes = on_device_ ? static_cast<uint64_t>(d.supercells) * kCellsPerSupercell * 4 : 0;
-	out->brick_bytes = on_device_ ? arena_.capacity() * 64 : 0;
-	out->pool_bytes = on_device_ ? arena_.pool_bricks() * 64 : 0;
 	out->cube_field_bytes = on_device_ ? fields_.cube_field_bytes() : 0;
 	out->escape_bytes = on_device_ ? fields_.escape_bytes() : 0;
 	out->sun_plane_bytes = on_device_ ? fields_.sun_plane_bytes() : 0;
-	out->arena_growths = arena_.growths();
-	out->arena_copy_growths = arena_.copy_growths();
-	out->arena_virtual = arena_.is_virtual() ? 1 : 0;
-	out->failed = failed_ ? 1 : 0;
-	out->stream_batches = stream_batches_;
-	out->stream_host_ns = stream_host_ns_;
+	residency_.info(on_device_, out);
 	return 0;
 }
 
 int Scene::device_indices(int supercell, uint32_t* out4096) {
 	if (int e = require_on_device()) return e;
-	if (supercell < 0 || supercell >= world.dims.supercells || !out4096) { set_error("bad supercell"); return BM_EINVAL; }
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	BM_HIP(hipMemcpy(out4096, d_index_grid_ + static_cast<size_t>(supercell) * kCellsPerSupercell, kCellsPerSupercell * 4, hipMemcpyDeviceToHost));
-	return 0;
+	return residency_.device_indices(supercell, out4096);
 }
 
 int Scene::device_brick(int supercell, uint32_t device_slot, uint32_t* out16) {
 	if (int e = require_on_device()) return e;
-	if (supercell < 0 || supercell >= world.dims.supercells || !out16 || device_slot >= world.supercells[supercell].resident) {
-		set_error("bad supercell or slot");
-		return BM_EINVAL;
-	}
-	BM_HIP(hipSetDevice(device_));
-	BM_HIP(hipDeviceSynchronize());
-	BM_HIP(hipMemcpy(out16, arena_.base() + (static_cast<size_t>(world.supercells[supercell].pool_base) + device_slot) * kBrickWords, sizeof(Brick), hipMemcpyDeviceToHost));
-	return 0;
+	return residency_.device_brick(supercell, device_slot, out16);
 }
 
 // ---------------------------------------------------------------- voxel edits
@@ -720,6 +396,7 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 
 	// ---- host world, supercell by supercell (voxels of different supercells are independent: batch order is kept within each)
 	DeviceBatch batch;
+	residency_.begin_batch();
 	std::vector<uint32_t> old_words;
 	std::vector<uint8_t> touched;
 	for (const int sci : reached) {
@@ -736,69 +413,26 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 }
 
 // The device half of a change of the host world, shared by edits and region writes.  stage_touched: the touched cells of one supercell
-// whose host world has just changed (old_words = its index words before) get their device slots by the residency rule above and join the batch.
+// whose host world has just changed (old_words = its index words before) get their device slots by the residency rule above
+// (PoolBook::rebind) and join the batch.
 int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b) {
 	const WorldDims& d = world.dims;
-	HostSupercell& c = world.supercells[sci];
+	const HostSupercell& c = world.supercells[sci];
 	const int sx = sci % d.supergrid_xy, sy = (sci / d.supergrid_xy) % d.supergrid_xy, sz = sci / (d.supergrid_xy * d.supergrid_xy);
-	const std::vector<uint16_t>& old_dev = c.dev_slot; // (the host half does not know about device slots)
-	// device slots of the host slots after the batch: untouched cells keep theirs (their host slots did not move)
-	std::vector<uint16_t> dev(c.bricks.size(), kNoDeviceSlot);
-	for (int j = 0; j < kCellsPerSupercell; ++j)
-		if (c.indices[j] && !touched[j]) dev[c.indices[j] & BM_BRICK_INDEX_BITS] = old_dev[c.indices[j] & BM_BRICK_INDEX_BITS];
-	std::vector<int> fresh_cells;
+	if (int e = residency_.rebind(sci, old_words, touched)) return e;
+	const PoolBook::Pool& pool = residency_.book().pool(sci);
 	for (int j = 0; j < kCellsPerSupercell; ++j) {
 		if (!touched[j]) continue;
 		const uint32_t ow = old_words[j], nw = c.indices[j];
-		{
-			const int gx = sx * kSupercell + (j & 15), gy = sy * kSupercell + ((j >> 4) & 15);
-			FieldChange& ch = b.change;
-			ch.touch_lo[0] = std::min(ch.touch_lo[0], gx); ch.touch_hi[0] = std::max(ch.touch_hi[0], gx);
-			ch.touch_lo[1] = std::min(ch.touch_lo[1], gy); ch.touch_hi[1] = std::max(ch.touch_hi[1], gy);
-		}
-		const uint16_t ods = ow ? old_dev[ow & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
-		if (ods != kNoDeviceSlot) {
-			if (nw) dev[nw & BM_BRICK_INDEX_BITS] = ods; // resident stays resident, rewritten in place
-			else { c.pool_free.push_back(ods); resident_bricks_--; }
-		} else if (nw && preloaded_) {
-			fresh_cells.push_back(j);
-		}
-		if ((ow != 0) != (nw != 0)) {
-			const int g[3] = {sx * kSupercell + (j & 15), sy * kSupercell + ((j >> 4) & 15), sz * kSupercell + (j >> 8)};
-			for (int k = 0; k < 3; ++k) { b.change.box_lo[k] = std::min(b.change.box_lo[k], g[k]); b.change.box_hi[k] = std::max(b.change.box_hi[k], g[k]); }
-		}
-	}
-	if (!fresh_cells.empty()) { // preloaded scene: new bricks get pool slots now, freed ones first
-		const uint32_t reuse = static_cast<uint32_t>(std::min(fresh_cells.size(), c.pool_free.size()));
-		const uint32_t appends = static_cast<uint32_t>(fresh_cells.size()) - reuse;
-		if (c.resident + appends > c.pool_capacity) {
-			uint32_t grown = kStartingPool;
-			while (grown < c.resident + appends || grown < 2 * c.pool_capacity) grown *= 2;
-			uint32_t fresh = 0;
-			if (int e = pool_region(grown, &fresh)) { failed_ = true; return e; }
-			b.moves.push_back(PoolMove{c.pool_capacity ? c.pool_base : fresh, fresh, c.pool_capacity ? c.resident : 0u, static_cast<uint32_t>(sci)});
-			if (c.pool_capacity > 0) arena_.region_free_deferred(c.pool_capacity, c.pool_base); // (a preloaded pool is an exact fit: only its largest power of two is handed out again)
-			c.pool_base = fresh;
-			c.pool_capacity = grown;
-		}
-		for (const int j : fresh_cells) {
-			uint32_t ds;
-			if (!c.pool_free.empty()) { ds = c.pool_free.back(); c.pool_free.pop_back(); }
-			else ds = c.resident++;
-			dev[c.indices[j] & BM_BRICK_INDEX_BITS] = static_cast<uint16_t>(ds);
-			resident_bricks_++;
-		}
-	}
-	c.dev_slot.swap(dev);
-	for (int j = 0; j < kCellsPerSupercell; ++j) {
-		if (!touched[j]) continue;
-		const uint32_t nw = c.indices[j];
-		const uint16_t ds = nw ? c.dev_slot[nw & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
+		const int g[3] = {sx * kSupercell + (j & 15), sy * kSupercell + ((j >> 4) & 15), sz * kSupercell + (j >> 8)};
+		FieldChange& ch = b.change;
+		for (int k = 0; k < 2; ++k) { ch.touch_lo[k] = std::min(ch.touch_lo[k], g[k]); ch.touch_hi[k] = std::max(ch.touch_hi[k], g[k]); }
+		if ((ow != 0) != (nw != 0))
+			for (int k = 0; k < 3; ++k) { ch.box_lo[k] = std::min(ch.box_lo[k], g[k]); ch.box_hi[k] = std::max(ch.box_hi[k], g[k]); }
+		const uint16_t ds = nw ? pool.dev_slot[nw & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
 		b.cells.push_back(static_cast<uint32_t>(sci) * kCellsPerSupercell + static_cast<uint32_t>(j));
-		if (!nw) b.words.push_back(0u);
-		else if (ds == kNoDeviceSlot) b.words.push_back(BM_BRICK_UNLOADED_BIT | (nw & BM_BRICK_LOD_BITS));
-		else b.words.push_back(ds | BM_BRICK_LOADED_BIT | (nw & BM_BRICK_LOD_BITS));
-		b.slots.push_back(ds == kNoDeviceSlot ? 0xFFFFFFFFu : c.pool_base + ds);
+		b.words.push_back(PoolBook::device_word(nw, ds));
+		b.slots.push_back(ds == kNoDeviceSlot ? 0xFFFFFFFFu : pool.base + ds);
 		b.bricks.push_back(nw ? c.bricks[nw & BM_BRICK_INDEX_BITS] : Brick{});
 	}
 	return 0;
@@ -810,13 +444,14 @@ int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const 
 int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, hipEvent_t* marks) {
 	const uint32_t n = static_cast<uint32_t>(b.cells.size());
 	if (n == 0) { // nothing inside the world changed a brick (e.g. clearing empty space)
-		arena_.commit_freed_regions();
+		residency_.commit_batch();
 		return 0;
 	}
+	const std::vector<PoolMove>& moves = residency_.moves();
 
 	// ---- staging: [pool moves][cells][words][slots][bricks], 64-byte aligned sections
 	auto up = [](size_t v) { return (v + 63) / 64 * 64; };
-	const size_t o_cells = up(b.moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
+	const size_t o_cells = up(moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
 				 o_bricks = o_slots + up(n * 4ull), bytes = o_bricks + n * sizeof(Brick);
 	auto stage = [&]() -> int {
 		if (bytes > d_edit_.bytes()) { // (the two grow together: h_edit_ is as large as d_edit_)
@@ -826,7 +461,7 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, hipEvent_t* marks) {
 			if (int e = d_edit_.reserve(cap)) return e;
 		}
 		if (int e = fields_.prepare_update(b.change, load_stream_)) return e;
-		if (!b.moves.empty()) std::memcpy(h_edit_, b.moves.data(), b.moves.size() * sizeof(PoolMove));
+		if (!moves.empty()) std::memcpy(h_edit_, moves.data(), moves.size() * sizeof(PoolMove));
 		std::memcpy(h_edit_ + o_cells, b.cells.data(), n * 4ull);
 		std::memcpy(h_edit_ + o_words, b.words.data(), n * 4ull);
 		std::memcpy(h_edit_ + o_slots, b.slots.data(), n * 4ull);
@@ -839,24 +474,24 @@ int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, hipEvent_t* marks) {
 		BM_HIP(hipMemcpyAsync(d_edit_, h_edit_, bytes, hipMemcpyHostToDevice, load_stream_));
 		if (int e = edit_staging_.pass(load_stream_)) return e; // the pinned staging is free again from here on
 		BM_HIP(hipEventRecord(marks[0], load_stream_));
-		if (!b.moves.empty()) {
-			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_.get()), static_cast<uint32_t>(b.moves.size()), arena_.base(), d_pool_base_, load_stream_);
+		if (!moves.empty()) {
+			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_.get()), static_cast<uint32_t>(moves.size()), residency_.arena_base(), residency_.pool_base(), load_stream_);
 			BM_HIP(hipGetLastError());
 		}
 		launch_edit_scatter(reinterpret_cast<const uint32_t*>(d_edit_ + o_cells), reinterpret_cast<const uint32_t*>(d_edit_ + o_words),
-							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, d_index_grid_, arena_.base(),
+							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, residency_.index_grid(), residency_.arena_base(),
 							load_stream_);
 		BM_HIP(hipGetLastError());
 		BM_HIP(hipEventRecord(marks[1], load_stream_));
 		// the field and the escape heights where some cell's occupancy changed; what that makes stale is rebuilt before the next frame that reads it
-		if (int e = fields_.update(d_index_grid_, b.change, true, load_stream_)) return e;
+		if (int e = fields_.update(residency_.index_grid(), b.change, true, load_stream_)) return e;
 		BM_HIP(hipEventRecord(marks[2], load_stream_));
 		return 0;
 	};
 	int e = stage();
 	if (!e) e = order_.publish_behind_frames(queue);
-	if (e) { failed_ = true; return e; } // the host world is ahead of the device: refuse to go on
-	arena_.commit_freed_regions();
+	if (residency_.report(e)) return e; // the host world is ahead of the device: refuse to go on
+	residency_.commit_batch();
 	return 0;
 }
 
@@ -982,6 +617,7 @@ int Scene::write_region(const bm_region* region, int op, const uint8_t* voxels, 
 		for (auto& t : pool) t.join();
 	}
 	DeviceBatch batch;
+	residency_.begin_batch();
 	for (size_t i = 0; i < reached.size(); ++i)
 		if (int e = stage_touched(reached[i], old_words[i], touched[i].data(), batch)) return e;
 	region_clocked_ = kClockedCall | (where == BM_VOXELS_DEVICE ? kClockedPack : 0u);
@@ -1008,13 +644,14 @@ int Scene::stage_absent_bricks(bool inside, const int lo[3], const int hi[3], si
 	const WorldDims& d = world.dims;
 	std::vector<int> cells;
 	std::vector<Brick> bricks;
-	if (inside && !preloaded_)
+	if (inside && !residency_.book().preloaded())
 		for (int cz = lo[2] >> 3; cz <= (hi[2] - 1) >> 3; ++cz)
 			for (int cy = lo[1] >> 3; cy <= (hi[1] - 1) >> 3; ++cy)
 				for (int cx = lo[0] >> 3; cx <= (hi[0] - 1) >> 3; ++cx) {
-					const HostSupercell& c = world.supercells[d.supercell_id(cx / kSupercell, cy / kSupercell, cz / kSupercell)];
+					const int sci = d.supercell_id(cx / kSupercell, cy / kSupercell, cz / kSupercell);
+					const HostSupercell& c = world.supercells[sci];
 					const uint32_t word = c.indices[cell_local_index(cx, cy, cz)];
-					if (word == 0 || c.dev_slot[word & BM_BRICK_INDEX_BITS] != kNoDeviceSlot) continue;
+					if (!residency_.book().absent(sci, word)) continue;
 					cells.insert(cells.end(), {cx, cy, cz});
 					bricks.push_back(c.bricks[word & BM_BRICK_INDEX_BITS]);
 				}
@@ -1237,14 +874,14 @@ int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* l
 // ---- the sun plane and the view plane (walk_fields.h; field_book.h decides): each is built on the load stream by the production launch that is
 // about to read it, unless it stands.  *usable: the launch's frames with the book's key may read the plane.
 int Scene::ensure_sun_plane(const FrameConstants& fc, bool* usable) {
-	FieldBook::SunStep s = fields_.book().sun_launch(fc.cone_dir, fc.cone_extent, preloaded_);
+	FieldBook::SunStep s = fields_.book().sun_launch(fc.cone_dir, fc.cone_extent, residency_.book().preloaded());
 	*usable = s.step == FieldBook::kStands;
 	if (s.step != FieldBook::kBuildSlice && s.step != FieldBook::kBuildPlane) return 0;
 	bool ready = false;
 	if (int e = fields_.prepare(&s, load_stream_, &ready)) return e;
 	if (!ready) return 0;
 	// behind every frame in flight (their shadow rays read the plane) and, on the load stream, behind the field and escape updates it reads
-	if (int e = order_.publish_behind_frames([&] { return fields_.build(s, d_index_grid_, d_pool_base_, arena_.base(), load_stream_); })) return e;
+	if (int e = order_.publish_behind_frames([&] { return fields_.build(s, residency_.index_grid(), residency_.pool_base(), residency_.arena_base(), load_stream_); })) return e;
 	*usable = true;
 	return 0;
 }

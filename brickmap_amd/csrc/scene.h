@@ -1,4 +1,4 @@
-// scene.h -- device-resident brickmap scene for one GPU: residency, streaming, frame launch.
+// scene.h -- device-resident brickmap scene for one GPU: the world on the device, what changes it, what reads it, frame launch.
 // Mirrors the device half of the reference's Scene (src/Scene.cpp:29-36,152-194,200-258) and the
 // host orchestration of launch_kernels (src/kernel.cu:366-439).
 #pragma once
@@ -8,7 +8,6 @@
 #include <vector>
 
 #include "../../include/brickmap.h"
-#include "arena.h"
 #include "device_ops.h"
 #include "device_types.h"
 #include "error.h"
@@ -17,6 +16,7 @@
 #include "hip_owned.h"
 #include "kernels.h"
 #include "launch_book.h"
+#include "residency.h"
 #include "walk_fields.h"
 #include "world.h"
 
@@ -24,7 +24,7 @@ namespace bm {
 
 class Scene {
 public:
-	explicit Scene(int device) : device_(device), fields_(device) {}
+	explicit Scene(int device) : device_(device), fields_(device), residency_(device, &world) {}
 	~Scene();
 
 	int init(int grid_size, int grid_height); // Scene::Scene: streams + pinned staging
@@ -88,7 +88,6 @@ public:
 
 private:
 	int allocate_device();
-	int alloc_index_grid();   // the pieces of allocate_device that the device route of load_voxels shares with it
 	int ensure_sun_plane(const FrameConstants& fc, bool* usable); // builds the sun plane for the frame's cone unless it stands; *usable: shadow rays of that cone may read it
 	int ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usable); // builds the view plane for the first frame's origin if the camera rests there; *usable: the plane stands for that origin
 	void set_view_dims();
@@ -96,8 +95,7 @@ private:
 	// the device half of a change of the host world (scene.cpp "voxel edits"): the touched cells of every changed supercell are staged, then submitted
 	struct DeviceBatch {
 		std::vector<uint32_t> cells, words, slots;
-		std::vector<Brick> bricks;
-		std::vector<PoolMove> moves;
+		std::vector<Brick> bricks; // (the batch's pool moves: Residency::moves)
 		FieldChange change;
 		unsigned clocked() const { return cells.empty() ? 0u : change.occupancy() ? kClockedScatter | kClockedField : kClockedScatter; } // the stages submit_batch records for it
 	};
@@ -111,14 +109,9 @@ private:
 	// what the three label calls refuse about their box, before anything is launched; *d gets the box's dimensions
 	int check_label_box(const char* who, const int32_t lo[3], const int32_t hi[3], LabelDims* d, bool* empty);
 	void free_device();
-	int alloc_queue();
-	int service_ring(int ring, uint32_t count, uint32_t* serviced);
 	int require_on_device() const;  // BM_ESTATE + message unless the world is on the device
 	int require_not_failed() const; // BM_ESTATE + message once a streaming batch has failed
-	void use_ring(int ring);                // the request ring that frames issued from now on append to
-	void residency_rebuilt(bool preloaded); // the host state that goes with a freshly written index grid: ring 0, nothing pending, nothing failed, statistics from zero
-	int arena_fit(uint64_t bricks);         // empty the arena and size it for a known residency
-	int pool_region(uint32_t bricks, uint32_t* offset); // BrickArena::region_alloc, with the device view following the arena's base
+	void residency_rebuilt(); // residency_ has written a new index grid: the fields and the ordering hear of it
 
 	int device_;
 	bool on_device_ = false;
@@ -127,22 +120,16 @@ private:
 	// Who waits for whom.  Frames and the queries issued like them, on any stream, against what rewrites the world on the load stream: order_
 	// (frame_order.h) owns those events and every decision about them.  The entries of the frame ring and the clocks of the launches:
 	// frame_ring_ (launch_book.h) says which entries a launch takes and which earlier launches it waits for; the events stand here, indexed by
-	// its clock slots.  A scratch or staging buffer that one call at a time may use: a Turn (hip_owned.h) beside the buffer.
+	// its clock slots.  A scratch or staging buffer that one call at a time may use: a Turn (hip_owned.h) beside the buffer.  Which brick is
+	// resident where, the request rings and the upload batches: residency_ (residency.h; pool_book.h takes the decisions, the failed flag among them).
 	FrameOrder order_;
 	static constexpr int kTimingRing = 256; // hipEvent pairs around the most recent render launches
 	Event ev_start_[kTimingRing], ev_stop_[kTimingRing];
-	bool failed_ = false; // a streaming batch could not be completed (allocation failure): residency state is undefined until reset
 
-	// device memory (DeviceScene view)
-	DeviceBuffer<uint32_t> d_index_grid_, d_pool_base_;
 	// what the walk reads instead of index words: the cube field with the sun and the view plane, the escape table with the shadow heights, their
 	// scratch and the book of which derived plane stands and what makes it stale (walk_fields.h; every flag is explained in field_book.h)
 	WalkFields fields_;
-	// two request rings: the blocking (reference-order) mode only uses ring 0; the overlapped mode alternates them so
-	// that a frame can raise requests while the previous frame's ring is being copied out and serviced
-	DeviceBuffer<int> d_load_queue_[2];
-	DeviceBuffer<uint32_t> d_load_count_[2];
-	DeviceBuffer<uint32_t> d_bricks_queue_, d_indices_queue_;
+	Residency residency_;
 	DeviceBuffer<DeviceCounters> d_counters_;
 	// the frame ring: constants and ticket counters of the frames in flight -- a launch takes as many consecutive entries as it has frames
 	static constexpr int kFrameRing = 1024; // (a launch takes at most kMaxFramesPerLaunch, frame_plan.h)
@@ -151,22 +138,6 @@ private:
 	DeviceBuffer<uint32_t> d_work_counter_; // chunk counters of the persistent trace kernel: kFrameRing blocks of kWorkCounterBytes, zeroed before the launch that uses them
 	FrameRing<kFrameRing, kTimingRing, kMaxFramesPerLaunch> frame_ring_;
 	int compute_units_ = 0, blocks_per_cu_[2] = {0, 0};
-	// pinned staging (Scene.cpp:30-32)
-	PinnedBuffer<int> h_positions_[2];
-	PinnedBuffer<uint32_t> h_bricks_, h_indices_;
-	PinnedBuffer<uint32_t> h_count_[2];
-	bool overlapped_ = false;
-	int ring_cur_ = 0, ring_snapshot_ = 0;
-	Turn snapshot_; // pending: ring_snapshot_ is being copied out on the load stream
-
-	BrickArena arena_; // every supercell's pool (arena.h); view_.brick_arena follows its base
-	static constexpr uint32_t kStartingPool = BrickArena::kStartingPool;
-	uint64_t stream_batches_ = 0, stream_host_ns_ = 0;    // upload batches since the last residency reset / host time staging them
-	PinnedBuffer<PoolMove> h_moves_;             // pinned staging of one batch's pool moves
-	DeviceBuffer<PoolMove> d_moves_;
-	uint64_t resident_bricks_ = 0;               // resident non-empty bricks
-	bool preloaded_ = false;                     // bm_scene_preload_all: an edit uploads new bricks at once (no requests are serviced)
-	DeviceBuffer<int> d_positions_;              // a ring's entries without the stale ones, when service_ring skips some
 	// edits: pinned + device staging of one batch (pool moves, dirty cells, their words, arena slots and bricks), grown on demand;
 	// the pinned staging is the batch's until its copy has run (edit_staging_)
 	PinnedBuffer<char> h_edit_;
@@ -201,7 +172,6 @@ private:
 	// one after another, each waits for the one before it
 	DeviceBuffer<uint64_t> d_label_tmp_;
 	Turn label_;
-	int queue_cap_ = 1024;                       // variables.h:35
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27
 	DeviceScene view_{};
 };

@@ -119,7 +119,6 @@ void World::build_supercell(int sx, int sy, int sz, const float* heights) {
 	cell.indices.assign(kCellsPerSupercell, 0u);
 	cell.bricks.clear();
 	cell.free_slots.clear();
-	cell.resident = 0;
 
 	// per brick column: lowest / highest terrain height under its 8x8 footprint
 	float lo[kSupercell * kSupercell], hi[kSupercell * kSupercell];

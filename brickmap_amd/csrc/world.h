@@ -26,17 +26,7 @@ struct HostSupercell {               // Scene::Supercell, Scene.h:21-29 (host pa
 	std::vector<uint32_t> indices;   // 4096 words: slot | loaded | lod<<12, 0 = empty brick
 	std::vector<Brick> bricks;       // bricks in generation order; slots in free_slots are empty and unused
 	std::vector<uint32_t> free_slots; // host slots emptied by edits, reused (last first) before bricks grows
-	uint32_t resident = 0;           // gpu_index_highest: next free slot of this supercell's pool
-	// device residency of the host bricks, kept by Scene: host slot -> slot in the device pool (kNoDeviceSlot = not resident),
-	// and the device slots that edits have freed (reused before the pool's high-water mark `resident` moves)
-	std::vector<uint16_t> dev_slot;
-	std::vector<uint32_t> pool_free;
-	// device pool of this supercell (Scene::Supercell gpu_count / gpu_index_highest, Scene.h:24-27), kept by Scene
-	uint32_t pool_capacity = 0;      // bricks the pool can hold (0 = no pool yet)
-	uint32_t pool_base = 0;          // first arena slot of the pool
 };
-
-constexpr uint16_t kNoDeviceSlot = 0xFFFF;
 
 struct WorldDims {
 	int grid_size = 0, grid_height = 0;         // voxels

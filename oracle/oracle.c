@@ -457,7 +457,7 @@ ORC_API uint32_t orc_process_load_queue(orc_world* w) {
 	return count;
 }
 
-/* Overlapped servicing -- the product's two-ring mode (brickmap_amd/csrc/scene.cpp Scene::process_load_queue): the host
+/* Overlapped servicing -- the product's two-ring mode (brickmap_amd/csrc/residency.cpp Residency::process_load_queue): the host
  * never waits for the frame it has just launched.  One call, made after frame k,
  *   (1) stages and uploads the ring that the PREVIOUS call copied out (the requests of frame k-1): they are resident
  *       from frame k+1 on -- one frame later than in the reference's order, where process_load_queue after frame k-1
