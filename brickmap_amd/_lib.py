@@ -113,6 +113,20 @@ class bm_mesh_result(C.Structure):
     _fields_ = [("quads", C.c_uint64), ("faces", C.c_uint64)]
 
 
+BM_DISTANCE_TO_EMPTY = 1
+BM_DISTANCE_OUTSIDE = 2
+BM_DISTANCE_MASK_ABOVE = 1
+BM_DISTANCE_NONE = 0x7FFFFFFF
+
+
+class bm_distance_params(C.Structure):
+    _fields_ = [("extent", C.c_int32 * 3), ("row_pitch", C.c_int64), ("slice_pitch", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class bm_distance_result(C.Structure):
+    _fields_ = [("sources", C.c_uint64), ("max_sq", C.c_uint32), ("reserved0", C.c_uint32), ("max_at", C.c_uint64), ("reserved1", C.c_uint64)]
+
+
 class bm_volume(C.Structure):
     _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
 
@@ -208,6 +222,12 @@ SIGNATURES = {
     "bm_mesh_triangles": (_i, [_vp, _vp, C.c_int64, _vp, _vp]),
     "bm_host_mesh_quads": (_i, [C.POINTER(bm_mesh_params), _vp, _vp, C.c_uint64, C.POINTER(bm_mesh_result)]),
     "bm_host_mesh_triangles": (_i, [_vp, C.c_int64, _vp]),
+    "bm_distance_workspace_bytes": (_i, [C.POINTER(bm_distance_params), C.POINTER(C.c_size_t)]),
+    "bm_distance_field": (_i, [_vp, C.POINTER(bm_distance_params), _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bm_debug_distance_times": (_i, [_vp, C.POINTER(bm_distance_params), _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.POINTER(C.c_float)]),
+    "bm_distance_mask": (_i, [_vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "bm_host_distance_field": (_i, [C.POINTER(bm_distance_params), _vp, _vp, C.POINTER(bm_distance_result)]),
+    "bm_host_distance_mask": (_i, [C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

@@ -10,6 +10,7 @@
 #include "camera_rays.h"
 #include "denoise.h"
 #include "kernels.h"
+#include "distance.h"
 #include "mesh.h"
 #include "reproject.h"
 #include "scene.h"
@@ -281,6 +282,33 @@ int bm_debug_mesh_times(bm_scene* scene, const bm_mesh_params* params, const uin
 int bm_mesh_triangles(bm_scene* scene, const bm_quad* quads_dev, int64_t n, float* triangles_dev, void* hip_stream) {
 	BM_NEED(scene);
 	return bm::mesh_triangles(scene->impl.gpu(), quads_dev, n, triangles_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+// (bm_host_distance_field and bm_host_distance_mask are csrc/distance_host.cpp: host code that needs nothing of the library)
+int bm_distance_workspace_bytes(const bm_distance_params* params, size_t* bytes) {
+	if (!params || !bytes) { set_error("bm_distance_workspace_bytes: null argument"); return BM_EINVAL; }
+	const bm::DistanceParamsView pv = bm::distance_params_view(*params);
+	if (const char* why = bm::distance_params_problem(pv)) { set_error(std::string("bm_distance_workspace_bytes: ") + why); return BM_EINVAL; }
+	*bytes = bm::distance_workspace_bytes(bm::distance_dims(pv));
+	return 0;
+}
+
+int bm_distance_field(bm_scene* scene, const bm_distance_params* params, const uint8_t* volume_dev, uint32_t* dist_dev, bm_distance_result* result_dev, void* workspace_dev,
+					  size_t workspace_bytes, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::distance_field(scene->impl.gpu(), params, volume_dev, dist_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_distance_times(bm_scene* scene, const bm_distance_params* params, const uint8_t* volume_dev, uint32_t* dist_dev, bm_distance_result* result_dev,
+							void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms) {
+	BM_NEED(scene);
+	if (!kernel_ms) { set_error("bm_debug_distance_times: null argument"); return BM_EINVAL; }
+	return bm::distance_field(scene->impl.gpu(), params, volume_dev, dist_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), kernel_ms);
+}
+
+int bm_distance_mask(bm_scene* scene, uint64_t count, const uint32_t* dist_dev, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::distance_mask(scene->impl.gpu(), count, dist_dev, limit_sq, flags, volume_out_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)

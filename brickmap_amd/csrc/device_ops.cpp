@@ -7,6 +7,7 @@
 #include "buffer_checks.h"
 #include "camera_rays.h"
 #include "denoise.h"
+#include "distance.h"
 #include "error.h"
 #include "hip_owned.h"
 #include "kernels.h"
@@ -150,6 +151,58 @@ int mesh_triangles(const Gpu& gpu, const bm_quad* quads, int64_t n, float* trian
 		return BM_EINVAL;
 	}
 	launch_mesh_triangles(quads, static_cast<uint64_t>(n), triangles, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- voxels -> distances (bm_distance_field, bm_distance_mask): kernels on the caller's stream over the caller's buffers; nothing of the world is read
+int distance_field(const Gpu& gpu, const bm_distance_params* params, const uint8_t* volume, uint32_t* dist, bm_distance_result* result, void* workspace,
+				   size_t workspace_bytes, hipStream_t stream, float* kernel_ms) {
+	if (!params) { set_error("bm_distance_field: null params"); return BM_EINVAL; }
+	const DistanceParamsView pv = distance_params_view(*params);
+	if (const char* why = distance_params_problem(pv)) { set_error(std::string("bm_distance_field: ") + why); return BM_EINVAL; }
+	if (!volume || !dist || !result || !workspace) { set_error("bm_distance_field: null volume, field, result or workspace"); return BM_EINVAL; }
+	const DistanceDims d = distance_dims(pv);
+	const size_t need = distance_workspace_bytes(d);
+	if (workspace_bytes < need) { set_error("bm_distance_field: the workspace is smaller than bm_distance_workspace_bytes"); return BM_EINVAL; }
+	if (!aligned(dist, 4) || !aligned(result, 8) || !aligned(workspace, 16)) {
+		set_error("bm_distance_field: the field must be 4-byte, the result 8-byte and the workspace 16-byte aligned");
+		return BM_EINVAL;
+	}
+	const size_t span = static_cast<size_t>(distance_span(d)), field_bytes = static_cast<size_t>(d.voxels) * sizeof(uint32_t);
+	const Span ws = span_of(workspace, need), field = span_of(dist, field_bytes);
+	BM_HIP(hipSetDevice(gpu.device));
+	// (a volume whose pitches carry it past its allocation has no extent to overlap anything with, see mesh_quads)
+	const bool volume_ok = device_span_ok(gpu.device, volume, span);
+	if ((volume_ok && spans_overlap(span_of(volume, span), ws)) || spans_overlap(field, ws) || spans_overlap(span_of(result, sizeof(bm_distance_result)), ws)) {
+		set_error("bm_distance_field: the workspace overlaps the volume, the field or the result");
+		return BM_EINVAL;
+	}
+	if ((volume_ok && spans_overlap(span_of(volume, span), field)) || spans_overlap(span_of(result, sizeof(bm_distance_result)), field)) {
+		set_error("bm_distance_field: the field overlaps the volume or the result");
+		return BM_EINVAL;
+	}
+	if (!volume_ok || !device_span_ok(gpu.device, workspace, need) || !device_span_ok(gpu.device, dist, field_bytes) ||
+		!device_span_ok(gpu.device, result, sizeof(bm_distance_result))) {
+		set_error("bm_distance_field: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	return launch_staged<4>(3, kernel_ms, [&](hipEvent_t* marks) { launch_distance_field(d, volume, dist, result, workspace, stream, marks); });
+}
+
+int distance_mask(const Gpu& gpu, uint64_t count, const uint32_t* dist, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out, hipStream_t stream) {
+	if (count == 0 || count > static_cast<uint64_t>(kDistanceMaxVoxels)) { set_error("bm_distance_mask: a count of 0 or above 2^31 - 2"); return BM_EINVAL; }
+	if (flags & ~kDistanceMaskAbove) { set_error("bm_distance_mask: unknown flag"); return BM_EINVAL; }
+	if (!dist || !volume_out) { set_error("bm_distance_mask: null buffer"); return BM_EINVAL; }
+	if (!aligned(dist, 4)) { set_error("bm_distance_mask: the field must be 4-byte aligned"); return BM_EINVAL; }
+	const size_t field_bytes = static_cast<size_t>(count) * sizeof(uint32_t);
+	if (spans_overlap(span_of(dist, field_bytes), span_of(volume_out, static_cast<size_t>(count)))) { set_error("bm_distance_mask: the output overlaps the field"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, dist, field_bytes) || !device_span_ok(gpu.device, volume_out, static_cast<size_t>(count))) {
+		set_error("bm_distance_mask: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	launch_distance_mask(dist, count, limit_sq, flags & kDistanceMaskAbove, volume_out, stream);
 	BM_HIP(hipGetLastError());
 	return 0;
 }

@@ -32,6 +32,11 @@ int voxelize(const Gpu& gpu, const bm_voxelize_params* params, int64_t n, const 
 int mesh_quads(const Gpu& gpu, const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result, void* workspace,
 			   size_t workspace_bytes, hipStream_t stream, float* kernel_ms = nullptr);
 int mesh_triangles(const Gpu& gpu, const bm_quad* quads, int64_t n, float* triangles, hipStream_t stream);
+// voxels -> their squared distance to the nearest source (distance.hip): like mesh_quads, the buffers and the workspace are the caller's
+// kernel_ms: null, or 3 durations -- the x pass, the y pass, the z pass + finish (the call then waits; bm_debug_distance_times)
+int distance_field(const Gpu& gpu, const bm_distance_params* params, const uint8_t* volume, uint32_t* dist, bm_distance_result* result, void* workspace,
+				   size_t workspace_bytes, hipStream_t stream, float* kernel_ms = nullptr);
+int distance_mask(const Gpu& gpu, uint64_t count, const uint32_t* dist, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out, hipStream_t stream);
 // pixel-centre rays of a frame, written on the device (denoise.hip)
 int pixel_rays(const Gpu& gpu, const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
 // temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers

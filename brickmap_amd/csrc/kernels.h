@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -176,6 +176,15 @@ void launch_mesh_quads(const MeshDims& d, const uint8_t* volume, void* quads, ui
 					   hipEvent_t* marks = nullptr);
 // n quads -> 2 n triangles of 9 floats
 void launch_mesh_triangles(const void* quads, uint64_t n, float* triangles, hipStream_t stream);
+
+// voxels -> their squared distance to the nearest source (distance.hip; distance.h has the rules and DistanceDims): the tight field of
+// d.voxels words and the 32 bytes of `result`.  workspace: distance_workspace_bytes() bytes, 16-byte aligned, that no other launch uses
+// until this one has finished (its tail is zeroed here).  marks: null, or 4 events around the x pass, the y pass and the z pass + finish.
+struct DistanceDims;
+void launch_distance_field(const DistanceDims& d, const uint8_t* volume, uint32_t* field, void* result, void* workspace, hipStream_t stream,
+						   hipEvent_t* marks = nullptr);
+// out[i] = field[i] <= limit_sq (above: the opposite), i < n; out at any address
+void launch_distance_mask(const uint32_t* field, uint64_t n, uint32_t limit_sq, uint32_t above, uint8_t* out, hipStream_t stream);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

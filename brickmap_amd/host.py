@@ -556,6 +556,116 @@ class Quads:
         return tri
 
 
+# ---- voxels -> distances (bm_distance_field / bm_host_distance_field)
+DISTANCE_NONE = _lib.BM_DISTANCE_NONE
+DISTANCE_RESULT_DTYPE = np.dtype([("sources", "<u8"), ("max_sq", "<u4"), ("reserved0", "<u4"), ("max_at", "<u8"), ("reserved1", "<u8")])  # bm_distance_result, 32 bytes
+
+
+def _distance_flags(to, outside):
+    if to not in ("solid", "empty"):
+        raise ValueError(f"distance_field: to 'solid' or 'empty' expected, got {to!r}")
+    return (_lib.BM_DISTANCE_TO_EMPTY if to == "empty" else 0) | (_lib.BM_DISTANCE_OUTSIDE if outside else 0)
+
+
+def _distance_params(volume, to, outside, name="volume"):
+    """(bm_distance_params, data pointer, is_cuda) of `volume` ([z, y, x], laid out as region_of takes it)"""
+    flags = _distance_flags(to, outside)
+    r, ptr, cuda = region_of((0, 0, 0), volume, name)
+    nz, ny, nx = volume.shape
+    par = _lib.bm_distance_params()
+    par.extent[:] = [nx, ny, nz]
+    par.row_pitch, par.slice_pitch = r.row_pitch, r.slice_pitch
+    par.flags = flags
+    return par, ptr, cuda
+
+
+def distance_workspace_bytes(shape):
+    """bm_distance_workspace_bytes: device memory bm_distance_field needs beside its buffers for a volume of shape (nz, ny, nx)."""
+    par = _lib.bm_distance_params()
+    par.extent[:] = [int(shape[2]), int(shape[1]), int(shape[0])]
+    out = C.c_size_t(0)
+    check(_lib.load().bm_distance_workspace_bytes(C.byref(par), C.byref(out)))
+    return int(out.value)
+
+
+def host_distance_field(volume, to="solid", outside=False):
+    """bm_host_distance_field (host only, no device): the exact squared Euclidean distance of every voxel of a dense volume [z, y, x]
+    (uint8 or bool numpy array, non-zero = solid; a slice of a larger array works as long as x is contiguous) to the nearest source, as
+    plain loops.  to="solid": the solid voxels are the sources; to="empty": the empty ones; outside=True: every voxel outside the volume
+    is a source too.  Returns (field, record): an int32 array [z, y, x] (DISTANCE_NONE where there is no source) and a
+    DISTANCE_RESULT_DTYPE record (sources, max_sq, max_at)."""
+    par, ptr, cuda = _distance_params(volume, to, outside)
+    assert not cuda
+    if min(volume.shape) == 0:
+        raise ValueError(f"host_distance_field: a volume with positive extents expected, got shape {tuple(volume.shape)}")
+    field = np.zeros(tuple(volume.shape), np.int32)
+    res = _lib.bm_distance_result()
+    check(_lib.load().bm_host_distance_field(C.byref(par), C.c_void_p(ptr), C.c_void_p(field.ctypes.data), C.byref(res)))
+    rec = np.zeros((), DISTANCE_RESULT_DTYPE)
+    rec["sources"], rec["max_sq"], rec["max_at"] = res.sources, res.max_sq, res.max_at
+    return field, rec
+
+
+def host_distance_mask(field, limit_sq, above=False):
+    """bm_host_distance_mask (host only): the uint8 volume field <= limit_sq (above=True: the opposite) of an int32 / uint32 field, in its
+    shape; DISTANCE_NONE is above every limit."""
+    field = np.ascontiguousarray(field)
+    if field.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)):
+        raise ValueError(f"host_distance_mask: an int32 or uint32 field expected, got {field.dtype}")
+    out = np.zeros(field.shape, np.uint8)
+    check(_lib.load().bm_host_distance_mask(field.size, C.c_void_p(field.ctypes.data), int(limit_sq), _lib.BM_DISTANCE_MASK_ABOVE if above else 0, C.c_void_p(out.ctypes.data)))
+    return out
+
+
+class DistanceField:
+    """The field of a Scene.distance_field: `field` is the int32 tensor [z, y, x] on the device (DISTANCE_NONE where there is no source)
+    and `result` the bm_distance_result there (four int64 words).  record (a DISTANCE_RESULT_DTYPE scalar) and largest() copy the result
+    to the host, which waits for the call; mask() stays on the device."""
+
+    def __init__(self, scene, field, result):
+        self.scene, self.field, self.result = scene, field, result
+        self._record = None
+
+    @property
+    def record(self):
+        if self._record is None:
+            self._record = self.result.cpu().numpy().view(DISTANCE_RESULT_DTYPE).reshape(())
+        return self._record
+
+    sources = property(lambda self: int(self.record["sources"]))
+
+    def largest(self):
+        """((x, y, z), radius_sq) of the largest ball of non-sources: the lowest-indexed voxel with the largest finite distance, in the
+        volume's own coordinates; None when no distance is finite."""
+        rec = self.record
+        if int(rec["max_sq"]) == DISTANCE_NONE:
+            return None
+        nz, ny, nx = self.field.shape
+        at = int(rec["max_at"])
+        return (at % nx, at // nx % ny, at // (nx * ny)), int(rec["max_sq"])
+
+    def mask(self, radius_sq, above=False, out=None, stream=None):
+        """bm_distance_mask: a uint8 tensor of the field's shape, 1 where the distance is <= radius_sq (above=True: where it is not) --
+        what write_region takes.  out: a contiguous uint8 tensor of that many voxels to fill (any base address).  The host does not wait."""
+        import torch
+        if not 0 <= int(radius_sq) <= 0xFFFFFFFF:
+            raise ValueError(f"mask: radius_sq in 0 ... 2^32 - 1 expected, got {radius_sq}")
+        current, target = self.scene._volume_stream(self.field, stream)
+        with torch.cuda.stream(target):
+            if out is None:
+                out = torch.empty(tuple(self.field.shape), dtype=torch.uint8, device=self.field.device)
+        if not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != self.field.numel():
+            raise ValueError("mask: out must be a contiguous uint8 tensor of the field's size on the scene's GPU")
+        if target.cuda_stream != current.cuda_stream:
+            self.field.record_stream(target)
+            out.record_stream(target)
+        check(self.scene._L.bm_distance_mask(self.scene.gpuScene, self.field.numel(), C.c_void_p(self.field.data_ptr()), int(radius_sq),
+                                             _lib.BM_DISTANCE_MASK_ABOVE if above else 0, C.c_void_p(out.data_ptr()), C.c_void_p(target.cuda_stream)))
+        if target.cuda_stream != current.cuda_stream:
+            current.wait_stream(target)
+        return out
+
+
 # ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmax", "<f4"), ("reserved", "<u4")])   # bm_ray
 RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("voxel", "<i4", 3), ("level", "<i4")])  # bm_ray_hit
@@ -1282,6 +1392,95 @@ class Scene:
             lo, hi = [v - 1 for v in lo], [v + 1 for v in hi]
         volume = self.read_region(lo, hi, device=True, stream=stream)
         return self.mesh_quads(volume, lo, halo=not closed, unit=unit, stream=stream)
+
+    # ---- voxels -> distances (bm_distance_field): the scene only names the GPU; nothing of the world is read
+    def _distance_field(self, volume, to, outside, out, stream, times):
+        import torch
+        if not hasattr(volume, "is_cuda") or not volume.is_cuda:
+            raise ValueError("distance_field: volume must be a uint8 or bool tensor [z, y, x] on the scene's GPU")
+        par, ptr, _ = _distance_params(volume, to, outside)
+        if min(volume.shape) == 0:
+            raise ValueError(f"distance_field: a volume with positive extents expected, got shape {tuple(volume.shape)}")
+        dev = volume.device
+        shape = tuple(int(v) for v in volume.shape)
+        if out is not None and (not hasattr(out, "is_cuda") or not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"distance_field: out must be a contiguous int32 tensor of shape {shape} on the scene's GPU")
+        current, target = self._volume_stream(volume, stream)
+        with torch.cuda.stream(target):
+            if out is None:
+                out = torch.empty(shape, dtype=torch.int32, device=dev)
+            ws = torch.empty(distance_workspace_bytes(shape), dtype=torch.uint8, device=dev)
+            result = torch.empty(4, dtype=torch.int64, device=dev)
+        if target.cuda_stream != current.cuda_stream:
+            volume.record_stream(target)
+            out.record_stream(target)
+        args = (self.gpuScene, C.byref(par), C.c_void_p(ptr), C.c_void_p(out.data_ptr()), C.c_void_p(result.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                C.c_void_p(target.cuda_stream))
+        ms = None
+        if times:
+            ms = (C.c_float * 3)()
+            check(self._L.bm_debug_distance_times(*args, ms))
+        else:
+            check(self._L.bm_distance_field(*args))
+        if target.cuda_stream != current.cuda_stream:
+            current.wait_stream(target)
+        return DistanceField(self, out, result), ([float(v) for v in ms] if times else None)
+
+    def distance_field(self, volume, to="solid", outside=False, out=None, stream=None):
+        """bm_distance_field: the exact squared Euclidean distance of every voxel of a dense volume [z, y, x] -- a uint8 or
+        bool tensor on the scene's GPU, non-zero = solid, strides as in write_region -- to the nearest source: the nearest solid voxel
+        (to="solid") or the nearest empty one (to="empty"); outside=True counts every voxel outside the volume as a source too.  out: a
+        contiguous int32 tensor of the volume's shape to fill.  Returns a DistanceField: .field (int32 [z, y, x], DISTANCE_NONE where there
+        is no source), .record, .largest() and .mask(radius_sq, above=False); only .record and .largest() wait.  Stream handling as in
+        write_region; the workspace (8 bytes per voxel) comes from torch's pool."""
+        return self._distance_field(volume, to, outside, out, stream, False)[0]
+
+    def distance_field_times(self, volume, to="solid", outside=False, out=None, stream=None):
+        """bm_debug_distance_times: Scene.distance_field with a hipEvent between its stages; waits.  Returns (DistanceField, [ms of the x
+        pass, the y pass, the z pass with the finishing thread])."""
+        return self._distance_field(volume, to, outside, out, stream, True)
+
+    def clearance(self, lo, hi, stream=None):
+        """How far every voxel of the box lo <= v < hi (x, y, z) of the live scene is from the nearest solid voxel of the box:
+        read_region(lo, hi, device=True), then distance_field(to="solid").  .largest() is the centre (relative to lo) and the squared
+        radius of the largest empty ball."""
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if any(h <= l for l, h in zip(lo, hi)):
+            raise ValueError(f"clearance: an empty box ({lo} ... {hi})")
+        return self.distance_field(self.read_region(lo, hi, device=True, stream=stream), stream=stream)
+
+    def _morph(self, name, lo, hi, radius_sq, to, op, stream):
+        import math
+        radius_sq = int(radius_sq)
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if radius_sq < 1 or radius_sq > 3 * 16383 * 16383:
+            raise ValueError(f"{name}: radius_sq, an integer in 1 ... 3 * 16383^2, expected, got {radius_sq}")
+        if any(h <= l for l, h in zip(lo, hi)):
+            raise ValueError(f"{name}: an empty box ({lo} ... {hi})")
+        m = math.isqrt(radius_sq - 1) + 1  # ceil(sqrt(radius_sq))
+        volume = self.read_region([v - m for v in lo], [v + m for v in hi], device=True, stream=stream)
+        inner = (slice(m, -m),) * 3
+        mask = self.distance_field(volume, to=to, stream=stream).mask(radius_sq, stream=stream)[inner]
+        before = volume[inner] != 0
+        changed = (mask != 0) & (before if op == "clear" else ~before)
+        self.write_region(lo, mask, op=op, stream=stream)
+        return int(changed.sum().item())
+
+    def grow(self, lo, hi, radius_sq, stream=None):
+        """Dilate the live scene inside the box lo <= v < hi (x, y, z) with a Euclidean ball of squared radius radius_sq (an integer >= 1):
+        every voxel of the box within that distance of a solid voxel becomes solid.  The box enlarged by ceil(sqrt(radius_sq)) on every
+        side is read (read_region gives 0 outside the world), its distance to solid is taken, and the mask D <= radius_sq of the box is
+        written with op "set".  Because the margin covers the radius, the result inside the box equals the morphological operation on
+        the whole world restricted to the box; beyond the world's border counts as empty.  Returns the number of voxels changed (read
+        with torch: the host waits)."""
+        return self._morph("grow", lo, hi, radius_sq, "solid", "set", stream)
+
+    def shrink(self, lo, hi, radius_sq, stream=None):
+        """Erode the live scene inside the box lo <= v < hi with a Euclidean ball of squared radius radius_sq (an integer >= 1): every
+        voxel of the box within that distance of an empty voxel becomes empty -- the distance to empty of the enlarged box, the mask
+        D <= radius_sq, write_region with op "clear".  As for grow the margin covers the radius, and beyond the world's border counts as
+        empty, so solid voxels at the border erode.  Returns the number of voxels changed."""
+        return self._morph("shrink", lo, hi, radius_sq, "empty", "clear", stream)
 
     # ---- ray queries (bm_scene_cast_rays): issued like a frame -- after every edit and upload issued before, asynchronous to the host
     def cast_rays_raw(self, n, rays_ptr, hits_ptr, flags=0, lod_origin=None, stream=None):

@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -13,7 +13,10 @@
 // of the world, closed at the box's sides, is extracted on the GPU as quads merged inside the 8^3 cells (Scene::extract_mesh) and written
 // to FILE as triangles in the raw format --mesh reads; prints the counts of quads, faces and triangles.
 // --dig carves a sphere of radius r voxels around voxel (x, y, z) out of the world before the first frame (Scene::carve_sphere).
-// --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig: the pieces of that box that hang on nothing -- connected components by faces,
+// --grow x0,y0,z0:x1,y1,z1=r2 and --shrink x0,y0,z0:x1,y1,z1=r2, applied after --dig (grow first): the world inside that box is dilated or
+// eroded with a Euclidean ball of squared radius r2 -- the exact distance field of the box and a margin on the GPU, thresholded and written
+// back (Scene::grow, Scene::shrink); prints how many voxels changed.
+// --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig and --shrink: the pieces of that box that hang on nothing -- connected components by faces,
 // inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
 // and voxels went.
 // --dig-at picks the voxel under pixel (px, py) of the first frame's camera (Scene::pick) and carves a sphere of radius r there; the
@@ -49,6 +52,8 @@ int main(int argc_in, char** argv_in) {
 	int drop_lo[3] = {0, 0, 0}, drop_hi[3] = {0, 0, 0};
 	bool drop = false;
 	int ground[2] = {-1, -1};
+	int morph_lo[2][3] = {{0, 0, 0}, {0, 0, 0}}, morph_hi[2][3] = {{0, 0, 0}, {0, 0, 0}}; // [0]: --grow, [1]: --shrink
+	int morph_r2[2] = {0, 0};
 	const char* voxels_path = nullptr;
 	bool denoise = false, temporal = false;
 	std::string paste_path;
@@ -127,6 +132,17 @@ int main(int argc_in, char** argv_in) {
 			drop = true;
 			continue;
 		}
+		if ((std::string(argv_in[i]) == "--grow" || std::string(argv_in[i]) == "--shrink") && i + 1 < argc_in) {
+			const int k = std::string(argv_in[i]) == "--shrink" ? 1 : 0;
+			int* lo = morph_lo[k];
+			int* hi = morph_hi[k];
+			if (std::sscanf(argv_in[++i], "%d,%d,%d:%d,%d,%d=%d", &lo[0], &lo[1], &lo[2], &hi[0], &hi[1], &hi[2], &morph_r2[k]) != 7 || hi[0] <= lo[0] || hi[1] <= lo[1] ||
+				hi[2] <= lo[2] || morph_r2[k] < 1) {
+				std::cerr << (k ? "--shrink" : "--grow") << " wants x0,y0,z0:x1,y1,z1=r2 (a box that is not empty, r2 >= 1)\n";
+				return 2;
+			}
+			continue;
+		}
 		if (std::string(argv_in[i]) == "--dig" && i + 1 < argc_in) {
 			if (std::sscanf(argv_in[++i], "%d,%d,%d,%d", &dig[0], &dig[1], &dig[2], &dig[3]) != 4 || dig[3] < 0) {
 				std::cerr << "--dig wants x,y,z,r (r >= 0)\n";
@@ -187,6 +203,8 @@ int main(int argc_in, char** argv_in) {
 					static_cast<unsigned long long>(r.open_columns));
 	}
 	if (dig[3] >= 0) scene.carve_sphere(dig, dig[3]);
+	if (morph_r2[0] > 0) std::printf("grew %llu voxels\n", static_cast<unsigned long long>(scene.grow(morph_lo[0], morph_hi[0], static_cast<uint32_t>(morph_r2[0]))));
+	if (morph_r2[1] > 0) std::printf("shrank %llu voxels\n", static_cast<unsigned long long>(scene.shrink(morph_lo[1], morph_hi[1], static_cast<uint32_t>(morph_r2[1]))));
 	if (drop) {
 		const Scene::Removed gone = scene.remove_floating(drop_lo, drop_hi);
 		std::printf("dropped %llu floating pieces, %llu voxels\n", static_cast<unsigned long long>(gone.pieces), static_cast<unsigned long long>(gone.voxels));

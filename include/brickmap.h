@@ -672,6 +672,62 @@ BM_API int bm_debug_mesh_times(bm_scene* scene, const bm_mesh_params* params, co
 BM_API int bm_host_mesh_quads(const bm_mesh_params* params, const uint8_t* volume, bm_quad* quads, uint64_t capacity, bm_mesh_result* result);
 BM_API int bm_host_mesh_triangles(const bm_quad* quads, int64_t n, float* triangles);
 
+/* ---- voxels -> their exact squared distance to the nearest source (no reference counterpart).  A dense byte volume V[z][y][x] in device
+ * memory (any non-zero byte is solid; x contiguous, rows and slices at the given pitches, 0 = tight; any base alignment; extents and voxel
+ * limit those of bm_mesh_params: 1 ... 16384 per axis, at most 2^31 - 2 voxels) gives a tight uint32_t field D[z][y][x], 4-byte aligned.
+ * All integers, a minimum and therefore unique: the same bytes on every run, and bm_distance_field == bm_host_distance_field byte for
+ * byte (csrc/distance.h holds the rules once).
+ *  - D(p) = the minimum over all sources q of (px - qx)^2 + (py - qy)^2 + (pz - qz)^2, or BM_DISTANCE_NONE = 0x7FFFFFFF when there is no
+ *    source.  The largest finite value is 3 * 16383^2 < 2^30: the field reads as non-negative int32.  A source has D = 0.
+ *  - Sources.  Without flags the solid voxels of the volume; with BM_DISTANCE_TO_EMPTY its empty voxels.  With BM_DISTANCE_OUTSIDE every
+ *    voxel outside the volume is a source too: the nearest of those is always axis-aligned, so the flag is D = min(D, m^2) with m = the
+ *    minimum over the three axes of min(i + 1, n - i), i the voxel's index and n the extent on that axis.
+ *  - Result (32 bytes on the device, 8-byte aligned): sources = how many voxels of the volume are sources; max_sq = the largest finite D
+ *    (0 when every voxel is a source, BM_DISTANCE_NONE when no value is finite); max_at = the linear index (z ny + y) nx + x of the
+ *    lowest-indexed voxel that has that value (0 when there is none); the rest 0.  max_at and max_sq are the centre and the squared
+ *    radius of the largest ball of non-sources in the box.
+ *  - Mask.  bm_distance_mask writes the tight byte volume out[i] = (D[i] <= limit_sq) ? 1 : 0 -- what bm_scene_write_region takes -- and
+ *    with BM_DISTANCE_MASK_ABOVE the opposite.  BM_DISTANCE_NONE is above every limit.  out may begin at any address.
+ *  - Refusals, BM_EINVAL with nothing launched and nothing written: an extent below 1 or above 16384; more than 2^31 - 2 voxels; a pitch
+ *    below the extent it spans or a volume spanning more than 2^46 bytes; a span ((nz - 1) slice_pitch + (ny - 1) row_pitch + nx bytes) or
+ *    any other buffer that does not lie inside one allocation of the scene's device; an unknown flag bit or a non-zero `reserved`; a null
+ *    pointer; a field not 4-byte, a result not 8-byte or a workspace not 16-byte aligned; a workspace below bm_distance_workspace_bytes; a
+ *    workspace that overlaps the volume, the field or the result; a field that overlaps the volume.  For the mask: a count of 0 or above
+ *    2^31 - 2, an unknown flag, a null pointer, a field not 4-byte aligned, an output that overlaps the field. */
+#define BM_DISTANCE_TO_EMPTY 1u
+#define BM_DISTANCE_OUTSIDE 2u
+#define BM_DISTANCE_MASK_ABOVE 1u
+#define BM_DISTANCE_NONE 0x7FFFFFFFu
+typedef struct bm_distance_params {
+	int32_t extent[3];   /* nx, ny, nz: 1 ... 16384 (four bytes of padding follow) */
+	int64_t row_pitch;   /* bytes from one x-row to the next y; 0 = tight (nx) */
+	int64_t slice_pitch; /* bytes from one z-slice to the next; 0 = tight (row_pitch * ny) */
+	uint32_t flags;      /* BM_DISTANCE_TO_EMPTY | BM_DISTANCE_OUTSIDE */
+	uint32_t reserved;   /* 0 */
+} bm_distance_params;
+typedef struct bm_distance_result {
+	uint64_t sources;
+	uint32_t max_sq, reserved0;
+	uint64_t max_at;
+	uint64_t reserved1;
+} bm_distance_result;
+/* bytes of device memory bm_distance_field needs beside its buffers: 4 bytes per voxel for the plane between the line passes and 4 bytes
+ * per voxel for the lanes' stacks, each rounded up to 16, plus 32 */
+BM_API int bm_distance_workspace_bytes(const bm_distance_params* params, size_t* bytes);
+/* the buffers and the workspace are the caller's and the scene keeps no state (the scene names the device): calls on different streams
+ * with workspaces of their own are independent.  Asynchronous on hip_stream.  Nothing of the world is read. */
+BM_API int bm_distance_field(bm_scene* scene, const bm_distance_params* params, const uint8_t* volume_dev, uint32_t* dist_dev, bm_distance_result* result_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+/* count voxels of a field -> count bytes */
+BM_API int bm_distance_mask(bm_scene* scene, uint64_t count, const uint32_t* dist_dev, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out_dev, void* hip_stream);
+/* measuring door: bm_distance_field with a hipEvent between its stages; waits, then kernel_ms[0 ... 2] = the durations in ms of the x
+ * pass, the y pass and the z pass with the finishing thread */
+BM_API int bm_debug_distance_times(bm_scene* scene, const bm_distance_params* params, const uint8_t* volume_dev, uint32_t* dist_dev, bm_distance_result* result_dev,
+                                   void* workspace_dev, size_t workspace_bytes, void* hip_stream, float* kernel_ms);
+/* the same on host memory, as plain loops (csrc/distance_host.cpp; no device needed); the refusals that concern params and null pointers */
+BM_API int bm_host_distance_field(const bm_distance_params* params, const uint8_t* volume, uint32_t* dist, bm_distance_result* result);
+BM_API int bm_host_distance_mask(uint64_t count, const uint32_t* dist, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

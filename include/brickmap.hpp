@@ -420,7 +420,107 @@ public:
 		return out;
 	}
 
+	// voxels -> their exact squared distance to the nearest source (no counterpart in the reference; bm_distance_field): the byte volume of
+	// `params` in device memory gives the tight field dist_dev and the record result_dev; workspace_dev: distance_workspace_bytes() bytes of
+	// the caller's
+	static size_t distance_workspace_bytes(const bm_distance_params& params) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_distance_workspace_bytes(&params, &bytes));
+		return bytes;
+	}
+	void distance_field(const bm_distance_params& params, const uint8_t* volume_dev, uint32_t* dist_dev, bm_distance_result* result_dev, void* workspace_dev,
+						size_t workspace_bytes, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_distance_field(gpuScene.handle, &params, volume_dev, dist_dev, result_dev, workspace_dev, workspace_bytes, hip_stream));
+	}
+	// count voxels of a field -> the byte volume (dist <= limit_sq) ? 1 : 0 (BM_DISTANCE_MASK_ABOVE: the opposite): what write_region takes
+	void distance_mask(uint64_t count, const uint32_t* dist_dev, uint32_t limit_sq, uint8_t* volume_out_dev, uint32_t flags = 0, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_distance_mask(gpuScene.handle, count, dist_dev, limit_sq, flags, volume_out_dev, hip_stream));
+	}
+	// How far the voxels of `region` (its lo and hi; the pitches are not used) of the live scene are from the nearest solid voxel of the
+	// box: the record (max_at and max_sq: the centre, as an index into the box, and the squared radius of the largest empty ball) and, when
+	// `field` is given, the distances in HOST memory.  The box is read on the device (read_region); the host waits.
+	bm_distance_result clearance(const Region& region, std::vector<uint32_t>* field = nullptr) {
+		bm_distance_result out{};
+		bm_distance_params p{};
+		for (int a = 0; a < 3; ++a) p.extent[a] = region.hi[a] - region.lo[a];
+		const size_t voxels = Region(region.lo, region.hi).voxels(), ws_bytes = distance_workspace_bytes(p);
+		const size_t at_ws = 32, at_field = at_ws + ws_bytes, at_vol = at_field + voxels * 4;
+		void* buf = nullptr; // the result, the workspace, the field, then the volume
+		BM_CHECKED(bm_buffer_alloc(device_, at_vol + voxels, &buf));
+		char* base = static_cast<char*>(buf);
+		try {
+			read_region(Region(region.lo, region.hi), reinterpret_cast<uint8_t*>(base + at_vol), BM_VOXELS_DEVICE);
+			distance_field(p, reinterpret_cast<const uint8_t*>(base + at_vol), reinterpret_cast<uint32_t*>(base + at_field), reinterpret_cast<bm_distance_result*>(base),
+						   base + at_ws, ws_bytes);
+			BM_CHECKED(bm_buffer_read(device_, &out, base, sizeof out)); // (waits for the device)
+			if (field) {
+				field->resize(voxels);
+				BM_CHECKED(bm_buffer_read(device_, field->data(), base + at_field, voxels * 4));
+			}
+		} catch (...) {
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return out;
+	}
+	// Dilate (grow) or erode (shrink) the live scene inside the box lo <= v < hi with a Euclidean ball of squared radius radius_sq >= 1.
+	// The box enlarged by m = ceil(sqrt(radius_sq)) on every side is read (read_region gives 0 outside the world); grow takes its distance
+	// to solid and sets the voxels of the box with D <= radius_sq, shrink takes its distance to empty and clears them.  Because the margin
+	// covers the radius, the result inside the box is that of the operation on the whole world; beyond the world's border counts as
+	// empty.  Returns the number of voxels changed.  The host waits.
+	uint64_t grow(const int lo[3], const int hi[3], uint32_t radius_sq) { return morph(lo, hi, radius_sq, false); }
+	uint64_t shrink(const int lo[3], const int hi[3], uint32_t radius_sq) { return morph(lo, hi, radius_sq, true); }
+
 private:
+	uint64_t morph(const int lo[3], const int hi[3], uint32_t radius_sq, bool erode) {
+		bool bad = radius_sq < 1 || radius_sq > 3u * 16383u * 16383u;
+		for (int a = 0; a < 3; ++a) bad = bad || hi[a] <= lo[a];
+		if (bad) { // (as bm_assert reports a refused call)
+			std::fprintf(stderr, "hip_assert: grow / shrink: a box that is not empty and radius_sq in 1 ... 3 * 16383^2 expected %s %d\n", __FILE__, __LINE__);
+			std::exit(BM_EINVAL);
+		}
+		int m = 1;
+		while (static_cast<uint32_t>(m) * static_cast<uint32_t>(m) < radius_sq) ++m;
+		int big_lo[3], big_hi[3];
+		bm_distance_params p{};
+		for (int a = 0; a < 3; ++a) {
+			big_lo[a] = lo[a] - m;
+			big_hi[a] = hi[a] + m;
+			p.extent[a] = big_hi[a] - big_lo[a];
+		}
+		p.flags = erode ? BM_DISTANCE_TO_EMPTY : 0u;
+		const size_t voxels = Region(big_lo, big_hi).voxels(), ws_bytes = distance_workspace_bytes(p);
+		const size_t at_ws = 32, at_field = at_ws + ws_bytes, at_vol = at_field + voxels * 4, at_mask = at_vol + voxels;
+		void* buf = nullptr; // the result, the workspace, the field, the volume, then the mask
+		BM_CHECKED(bm_buffer_alloc(device_, at_mask + voxels, &buf));
+		char* base = static_cast<char*>(buf);
+		uint64_t changed = 0;
+		try {
+			read_region(Region(big_lo, big_hi), reinterpret_cast<uint8_t*>(base + at_vol), BM_VOXELS_DEVICE);
+			distance_field(p, reinterpret_cast<const uint8_t*>(base + at_vol), reinterpret_cast<uint32_t*>(base + at_field), reinterpret_cast<bm_distance_result*>(base),
+						   base + at_ws, ws_bytes);
+			distance_mask(voxels, reinterpret_cast<const uint32_t*>(base + at_field), radius_sq, reinterpret_cast<uint8_t*>(base + at_mask));
+			// the box is the enlarged volume's inside: the same bytes at the enlarged volume's pitches
+			const int64_t row = p.extent[0], slice = row * p.extent[1];
+			const size_t inner = static_cast<size_t>(m) * static_cast<size_t>(slice + row + 1);
+			write_region(Region(lo, hi, row, slice), reinterpret_cast<const uint8_t*>(base + at_mask + inner), erode ? BM_EDIT_CLEAR : BM_EDIT_SET, BM_VOXELS_DEVICE);
+			std::vector<uint8_t> host(2 * voxels); // the volume as it was, then the mask
+			BM_CHECKED(bm_buffer_read(device_, host.data(), base + at_vol, 2 * voxels)); // (waits for the device)
+			for (int z = 0; z < hi[2] - lo[2]; ++z)
+				for (int y = 0; y < hi[1] - lo[1]; ++y)
+					for (int x = 0; x < hi[0] - lo[0]; ++x) {
+						const size_t i = inner + static_cast<size_t>(z) * slice + static_cast<size_t>(y) * row + x;
+						if (host[voxels + i] && (host[i] != 0) == erode) ++changed;
+					}
+		} catch (...) {
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return changed;
+	}
+
 	int device_;
 };
 
