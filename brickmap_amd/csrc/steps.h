@@ -74,10 +74,34 @@ enum : int { ST_NEED = 0, ST_OUTER = 1, ST_CAND = 2, ST_JUMP = 3 };
 #define BM_JUMP_MIN 4 // smallest cube edge worth a jump (a jump costs about four single steps)
 #endif
 constexpr uint32_t kCubeNoJump = 0x100u; // RayState::cube flag: tmax is outside the range of jump.h, take single moves
-BM_JHD int field_state(uint32_t v, bool possible, uint32_t& cube) {
+
+// Is a jump WORTH it here -- which is not "is it valid here" (jump_possible, jump.h).  A jump never looks past the end of the binade
+// [2^e, 2^(e+1)) of the smallest tmax, a binade is 2^e long and tdelta is at least one cell: below t = 2^BM_JUMP_WORTH_EXP a jump (about
+// six single moves' worth of instructions) buys a few cells at most.  Every ray climbs through those binades first, and the primary
+// rays of a refill do it together.  The rule is a floor on that exponent (rule (a) of profiles/r17_jump_room.txt; 3 won the sweep of
+// 0 ... 4).  tdelta is in the signature for a rule that weighs the room left in the binade against it: rule (b) of the same file, which
+// lost and is tools/variants/jump_worth_ride_room.patch.
+// A lane that is not worth a jump is ST_OUTER WITHOUT kCubeNoJump: it takes single moves in a single-move pass, and in a jump pass that
+// other lanes asked for it jumps as before (valid: jump_worth implies jump_possible) -- the rule only keeps it from asking for one.
+// Single moves and jumps land on the same tmax bits, so the rule changes no result; tests/jump_worth_check.cpp.
+#ifndef BM_JUMP_WORTH_EXP
+#define BM_JUMP_WORTH_EXP 3
+#endif
+static_assert(BM_JUMP_WORTH_EXP >= BM_JUMP_TMIN_EXP && BM_JUMP_WORTH_EXP < 19, "jump_worth must imply jump_possible");
+constexpr uint32_t kJumpWorthBits = static_cast<uint32_t>(127 + BM_JUMP_WORTH_EXP) << 23;
+// (the test itself, on the bit pattern of the smallest tmax: the lookup of traverse.h has that minimum already, for jump_possible)
+BM_JHD bool jump_worth_bits(uint32_t min_tmax_bits) { return min_tmax_bits - kJumpWorthBits < kJumpMaxBits - kJumpWorthBits; }
+BM_JHD bool jump_worth(float tx, float ty, float tz, float dx, float dy, float dz) {
+	(void)dx; (void)dy; (void)dz;
+	float m = tx < ty ? tx : ty;
+	m = m < tz ? m : tz;
+	return jump_worth_bits(jump_bits(m));
+}
+
+BM_JHD int field_state(uint32_t v, bool possible, uint32_t& cube, bool worth = true) {
 	// select-style, no short-circuit: a branchy version costs its full instruction count in a divergent wave anyway
 	cube = possible ? v : (v | kCubeNoJump); // remembered for the walk pass, which may be several scheduler rounds away
-	const int jump = static_cast<int>(v >= static_cast<uint32_t>(BM_JUMP_MIN)) & static_cast<int>(possible);
+	const int jump = static_cast<int>(v >= static_cast<uint32_t>(BM_JUMP_MIN)) & static_cast<int>(possible) & static_cast<int>(worth);
 	int st = jump ? ST_JUMP : ST_OUTER;
 	st = v == 0u ? ST_CAND : st;
 	st = v == 255u ? ST_NEED : st; // left the grid (voxel.cuh:256): a miss

@@ -725,7 +725,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 				}
 				const f3 dir = shadow ? r.d : bdir;
 				// the plane this ray walks instead of its octant's: the sun plane for a shadow ray, the view plane for a primary ray, 0 = none
-				const int st = ray_setup<DBG, kEscape, kView>(sc, hitp, dir, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u,
+				const int st = ray_setup<DBG, kEscape, kView, true>(sc, hitp, dir, r, tally, &esc, kSun && shadow ? fc.shadow_field_off : 0u,
 															  kView && !shadow && bounces == 0 ? fc.view_field_off : 0u);
 				state = (st == ST_NEED && shadow) ? ST_CONN : st;
 			}
@@ -777,6 +777,9 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 			// ST_OUTER lanes are close to the surface.  With enough jumpers in the wave every walking lane takes the jump
 			// pass (a cube of edge 1-3 is crossed just the same, and a jump with n = 1 is exactly one move, valid in any
 			// cell); otherwise the lanes near the surface make a few single moves and the jumpers wait for company.
+			// A lane with a cube ahead but no room for a jump in the binade of its tmax (steps.h jump_worth: below t = 8 cells) is on
+			// the ST_OUTER side of that test -- the primary rays of a refill climb the low binades together, by single moves -- and
+			// jumps like the others when they take a jump pass.
 			if (BM_PRIO) __builtin_amdgcn_s_setprio(BM_PRIO_A);
 			const int nO = nA - nJ;
 			BM_REGION("A.jump");
@@ -787,8 +790,8 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 					if (BM_TIMED) { runsJ++; lanesJ += walkers; }
 					if (state == ST_JUMP || state == ST_OUTER) {
 						int st;
-						if (!(r.cube & kCubeNoJump)) st = field_jump<DBG, true, kEscape>(sc, r, tally, esc);
-						else st = field_step<DBG>(sc, r, tally); // tmax outside the range jump.h handles (first move of a ray that starts on a cell face)
+						if (!(r.cube & kCubeNoJump)) st = field_jump<DBG, true, kEscape, true>(sc, r, tally, esc);
+						else st = field_step<DBG, true>(sc, r, tally); // tmax outside the range jump.h handles (first move of a ray that starts on a cell face)
 						state = (st == ST_NEED && pstate != P_EXT_DONE) ? ST_CONN : st;
 					}
 					if (BM_JUMP_PASSES > 1) { // another pass right away while most of the walkers are still walking (saves a scheduler round)
@@ -803,7 +806,7 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 				for (int k = 0; k < BM_STEPS_PER_ROUND; ++k) {
 					if (BM_TIMED) { runsA++; lanesA += __popcll(__ballot(state == ST_OUTER)); }
 					if (state == ST_OUTER) {
-						const int st = field_step<DBG>(sc, r, tally);
+						const int st = field_step<DBG, true>(sc, r, tally);
 						state = (st == ST_NEED && pstate != P_EXT_DONE) ? ST_CONN : st;
 					}
 				}

@@ -274,14 +274,17 @@ __device__ __forceinline__ int move_axis(const DeviceScene& sc, int last_step) {
 __device__ __forceinline__ uint32_t field_index(const DeviceScene& sc, const RayState& r) {
 	return r.p; // the cell IS its entry's offset (cell_offset)
 }
-__device__ __forceinline__ bool field_jump_possible(const RayState& r) { // jump_possible(): tmax in the range jump.h handles
-	const float m = fminf(fminf(r.tx, r.ty), r.tz);
-	return __float_as_uint(m) - kJumpMinBits < kJumpMaxBits - kJumpMinBits;
-}
-// field_state(byte, possible, cube): steps.h
+// field_state(byte, possible, cube, worth): steps.h
+// WORTH: the lookup applies jump_worth (steps.h) -- the fused kernel's.  The queue kernels (wavefront.hip) and the ray queries
+// (query.hip) share this code and keep the rule off: their rays do not start together from one origin, and their walks were not
+// measured with it (profiles/r17_jump_room.txt section 7).
+template <bool WORTH = false>
 __device__ __forceinline__ int field_lookup(const DeviceScene& sc, RayState& r) {
 	const uint32_t v = sc.cube_field[field_index(sc, r)];
-	return field_state(v, field_jump_possible(r), r.cube);
+	const uint32_t m = __float_as_uint(fminf(fminf(r.tx, r.ty), r.tz)); // jump_possible() / jump_worth(): one minimum, two range tests
+	const bool possible = m - kJumpMinBits < kJumpMaxBits - kJumpMinBits;
+	const bool worth = !(WORTH && kJumpWorthBits != kJumpMinBits) || jump_worth_bits(m);
+	return field_state(v, possible, r.cube, worth);
 }
 
 // voxel.cuh:249-258: one Amanatides-Woo move to the next cell.  Select-style (no per-axis branches); `t += mask ? delta : 0` is
@@ -298,10 +301,10 @@ __device__ __forceinline__ void step_advance(RayState& r) {
 	r.tz = step_add(tz, r.dz, m.z);
 }
 // ... then the new cell's byte
-template <bool DBG>
+template <bool DBG, bool WORTH = false>
 __device__ __forceinline__ int field_step(const DeviceScene& sc, RayState& r, Tally& tally) {
 	step_advance(r);
-	const int st = field_lookup(sc, r);
+	const int st = field_lookup<WORTH>(sc, r);
 	if (DBG && st != ST_NEED) tally.index_loads++;
 	return st;
 }
@@ -331,10 +334,10 @@ __device__ __forceinline__ uint32_t jump_advance(RayState& r) {
 }
 // ESC: the landing is tested against the ray's escape threshold `esc` (escape.h; read once by ray_setup) -- a ray that has left the
 // occupied part of its octant's box is what a border byte would make it, a miss, without walking to the border.
-template <bool DBG, bool DIR = true, bool ESC = false>
+template <bool DBG, bool DIR = true, bool ESC = false, bool WORTH = false>
 __device__ __forceinline__ int field_jump(const DeviceScene& sc, RayState& r, Tally& tally, uint32_t esc = 0u) {
 	const uint32_t cells = jump_advance<DIR>(r);
-	int st = field_lookup(sc, r);
+	int st = field_lookup<WORTH>(sc, r);
 	if (ESC) st = escape_reached(r.p, esc, r.stepz) ? ST_NEED : st;
 	if (DBG) tally.index_loads += cells - (st == ST_NEED ? 1u : 0u); // the cells the reference would have loaded: all but a final one outside the grid
 	return st;
@@ -399,7 +402,7 @@ __device__ __forceinline__ int walk_round(const DeviceScene& sc, RayState& r, in
 // between the two planes, so that escape_reached compares offsets of one plane; the plane's own 255 stamps come on top.
 // (Shadow heights, shadowheight.h: a shadow ray that starts in a dark cell never gets here -- the shade block of trace.hip tests the
 // origin's cell with shadow_origin, which computes the very cell of this function, and does not draw the ray.)
-template <bool DBG, bool ESC = false, bool VIEW = false>
+template <bool DBG, bool ESC = false, bool VIEW = false, bool WORTH = false>
 __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const f3 dir, RayState& r, Tally& tally, uint32_t* esc = nullptr, uint32_t sun_plane = 0u, uint32_t view_plane = 0u) {
 	r.hit = false;
 	r.d = dir;
@@ -459,7 +462,7 @@ __device__ __forceinline__ int ray_setup(const DeviceScene& sc, f3 origin, const
 	r.dx = static_cast<float>(sx) * rx; r.dy = static_cast<float>(sy) * ry; r.dz = static_cast<float>(sz) * rz;
 	r.last_step = 0;
 	if (DBG) tally.index_loads++; // one per visited cell = the reference's index loads (algorithmic count)
-	const int st = field_lookup(sc, r); // inside the grid: never a border cell
+	const int st = field_lookup<WORTH>(sc, r); // inside the grid: never a border cell
 	return ESC && escape_reached(r.p, *esc, r.stepz) ? ST_NEED : st;
 }
 
