@@ -81,6 +81,16 @@ struct PoolMove {
 	uint32_t src, dst, count, supercell;
 };
 
+// A dense region (region.hip; change_book.h region_dims fills it in): [lo, hi) = the box clipped to the world (world voxels, not empty);
+// org = the world voxel of V[0][0][0] (the unclipped lo); c0 / nc = the brick cells the clipped box overlaps (first cell, count per axis);
+// g0 = c0[0] >> 4, the first run of 16 cells along x
+struct RegionDims {
+	int lo[3], hi[3], org[3];
+	int c0[3], nc[3], g0;
+	uint32_t sg_xy, sg_xy2;
+	int64_t row_pitch, slice_pitch;
+};
+
 // Per-launch constants computed on the host (launch_kernels:371-403 and the view-independent
 // part of the sky model, sunsky.cu:34-44,66-67).
 struct FrameConstants {

@@ -106,15 +106,7 @@ void launch_load_classify(const uint8_t* voxels, uint32_t* index_grid, const Loa
 void launch_load_number(uint32_t* index_grid, uint32_t* counts, uint32_t* pool_base, uint32_t* total, const LoadDims& d, hipStream_t stream);
 void launch_load_pack(const uint8_t* voxels, const uint32_t* index_grid, const uint32_t* pool_base, uint32_t* arena, const LoadDims& d, hipStream_t stream);
 
-// dense regions (region.hip): a box of voxels as a volume V[z][y][x] in device memory, x contiguous.  [lo, hi) = the box clipped to the
-// world (world voxels, not empty); org = the world voxel of V[0][0][0] (the unclipped lo); c0 / nc = the brick cells the clipped box
-// overlaps (first cell, count per axis); g0 = c0[0] >> 4, the first run of 16 cells along x
-struct RegionDims {
-	int lo[3], hi[3], org[3];
-	int c0[3], nc[3], g0;
-	uint32_t sg_xy, sg_xy2;
-	int64_t row_pitch, slice_pitch;
-};
+// dense regions (region.hip): a box of voxels as a volume V[z][y][x] in device memory, x contiguous (RegionDims: device_types.h)
 // bricks[16 i ...] = the box's part of its cell i (cells in x-fastest order over c0 ... c0 + nc), bits outside the box 0
 void launch_region_pack(const uint8_t* voxels, uint32_t* bricks, const RegionDims& d, hipStream_t stream);
 // the box's voxels as bytes 0 / 1 from the device world: 0 where a cell is empty or its brick is not resident

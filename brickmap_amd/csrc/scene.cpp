@@ -1,15 +1,13 @@
-// scene.cpp -- one GPU's scene: the world on the device, edits, regions, labels, queries and frame launch (residency and streaming: residency.cpp).
+// scene.cpp -- one GPU's scene: the world on the device, region reads, labels, queries and frame launch (residency and streaming: residency.cpp; edits and region writes: world_changes.cpp).
 #include "scene.h"
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 
 #include "buffer_checks.h"
 #include "label.h"
@@ -66,7 +64,7 @@ int Scene::init(int grid_size, int grid_height) {
 		if (int e = ev_stop_[i].create()) return e;
 	}
 	if (int e = order_.init(load_stream_)) return e;
-	if (int e = edit_marks_.create()) return e;
+	if (int e = changes_.init()) return e;
 	if (int e = residency_.init(&view_)) return e;
 	if (int e = d_counters_.alloc(sizeof(DeviceCounters))) return e;
 	BM_HIP(hipMemset(d_counters_, 0, sizeof(DeviceCounters)));
@@ -236,7 +234,7 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	uint32_t* d_total = counts + d.supercells;
 	// the field comes from the update of edit.hip with the box = every cell, into the field the allocation set to 255
 	const FieldChange all = FieldChange::whole(d);
-	if (int e = fields_.prepare_update(all, nullptr)) return e; // (load_voxels has synchronised the device: no stream to wait for, unlike submit_batch)
+	if (int e = fields_.prepare_update(all, nullptr)) return e; // (load_voxels has synchronised the device: no stream to wait for, unlike a change batch)
 	if (int e = order_.load_behind_caller(stream)) return e; // the volume is whatever the caller's stream has written by now
 	// ---- classify + number
 	uint32_t* const index_grid = residency_.index_grid();
@@ -274,23 +272,14 @@ int Scene::load_voxels_device(const uint8_t* voxels, hipStream_t stream) {
 	world.supercells.clear();
 	world.supercells.resize(d.supercells);
 	residency_.begin_adopt();
-	std::atomic<int> next{0};
-	auto fill = [&]() {
-		for (int i = next.fetch_add(1); i < d.supercells; i = next.fetch_add(1)) {
-			HostSupercell& c = world.supercells[i];
-			const uint32_t* w = &words[static_cast<size_t>(i) * kCellsPerSupercell];
-			const uint64_t end = i + 1 < d.supercells ? bases[i + 1] : total;
-			c.indices.assign(w, w + kCellsPerSupercell);
-			c.bricks.assign(bricks.begin() + bases[i], bricks.begin() + static_cast<ptrdiff_t>(end));
-			residency_.adopt(i, bases[i]);
-		}
-	};
-	{
-		std::vector<std::thread> pool;
-		for (int t = 1; t < std::min(16, d.supercells); ++t) pool.emplace_back(fill);
-		fill();
-		for (auto& t : pool) t.join();
-	}
+	parallel_for(d.supercells, 16, [&](int i) {
+		HostSupercell& c = world.supercells[i];
+		const uint32_t* w = &words[static_cast<size_t>(i) * kCellsPerSupercell];
+		const uint64_t end = i + 1 < d.supercells ? bases[i + 1] : total;
+		c.indices.assign(w, w + kCellsPerSupercell);
+		c.bricks.assign(bricks.begin() + bases[i], bricks.begin() + static_cast<ptrdiff_t>(end));
+		residency_.adopt(i, bases[i]);
+	});
 	world.generated = true;
 	residency_.adopted(total);
 	on_device_ = true;
@@ -361,150 +350,16 @@ int Scene::device_brick(int supercell, uint32_t device_slot, uint32_t* out16) {
 	return residency_.device_brick(supercell, device_slot, out16);
 }
 
-// ---------------------------------------------------------------- voxel edits
-// The host world first (World::edit_supercell on every supercell the batch reaches: bits, LoD masks, words, host slots), then the
-// device: per dirty cell its new device word -- slot | loaded | lod for a resident brick, which keeps its pool slot and gets its new
-// content; unloaded | lod for a brick that is not resident (requested bit clear: asked for again); 0 for an empty cell, whose pool
-// slot goes on the pool's free list.  A preloaded scene services no requests, so a new brick gets a pool slot at once (a freed one
-// first, else the pool grows through region_alloc and the move kernel).  On the load stream, behind every frame in flight: one copy
-// of the staged batch, the pool moves, one scatter kernel, and -- when some cell's occupancy changed -- the cube-field update
-// (edit.hip); recorded as an upload batch, so every frame issued later waits for it.
+// ---------------------------------------------------------------- voxel edits and region writes: world_changes.cpp
 int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 	std::string why;
 	if (!World::validate_edits(edits, count, &why)) { set_error("bm_scene_edit: " + why); return BM_EINVAL; }
 	if (!on_device_) { set_error("bm_scene_edit: scene not generated"); return BM_ESTATE; }
 	if (int e = require_not_failed()) return e;
-	const WorldDims& d = world.dims;
-	std::vector<int> reached;
-	{
-		std::vector<uint8_t> seen(static_cast<size_t>(d.supercells), 0);
-		for (int i = 0; i < count; ++i) {
-			int lo[3], hi[3];
-			if (!World::edit_bounds(d, edits[i], lo, hi)) continue;
-			for (int sz = lo[2] / kColumnSpan; sz <= (hi[2] - 1) / kColumnSpan; ++sz)
-				for (int sy = lo[1] / kColumnSpan; sy <= (hi[1] - 1) / kColumnSpan; ++sy)
-					for (int sx = lo[0] / kColumnSpan; sx <= (hi[0] - 1) / kColumnSpan; ++sx) {
-						const int sc = d.supercell_id(sx, sy, sz);
-						if (!seen[sc]) { seen[sc] = 1; reached.push_back(sc); }
-					}
-		}
-	}
-	if (reached.empty()) return 0;
-	std::sort(reached.begin(), reached.end());
-	BM_HIP(hipSetDevice(device_));
-	if (int e = edit_staging_.wait()) return e; // the staging of the previous batch has been copied
-
-	// ---- host world, supercell by supercell (voxels of different supercells are independent: batch order is kept within each)
-	DeviceBatch batch;
-	residency_.begin_batch();
-	std::vector<uint32_t> old_words;
-	std::vector<uint8_t> touched;
-	for (const int sci : reached) {
-		HostSupercell& c = world.supercells[sci];
-		const int sx = sci % d.supergrid_xy, sy = (sci / d.supergrid_xy) % d.supergrid_xy, sz = sci / (d.supergrid_xy * d.supergrid_xy);
-		old_words = c.indices;
-		touched.assign(kCellsPerSupercell, 0);
-		World::edit_supercell(d, c, sx, sy, sz, edits, count, touched.data());
-		if (int e = stage_touched(sci, old_words, touched.data(), batch)) return e;
-	}
-	if (int e = submit_batch(batch, stream, edit_marks_.marks())) return e;
-	if (batch.clocked()) edit_clocked_ = batch.clocked(); // (a batch that scatters nothing leaves the last one's times readable)
-	return 0;
+	return changes_.edit(count, edits, stream);
 }
 
-// The device half of a change of the host world, shared by edits and region writes.  stage_touched: the touched cells of one supercell
-// whose host world has just changed (old_words = its index words before) get their device slots by the residency rule above
-// (PoolBook::rebind) and join the batch.
-int Scene::stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b) {
-	const WorldDims& d = world.dims;
-	const HostSupercell& c = world.supercells[sci];
-	const int sx = sci % d.supergrid_xy, sy = (sci / d.supergrid_xy) % d.supergrid_xy, sz = sci / (d.supergrid_xy * d.supergrid_xy);
-	if (int e = residency_.rebind(sci, old_words, touched)) return e;
-	const PoolBook::Pool& pool = residency_.book().pool(sci);
-	for (int j = 0; j < kCellsPerSupercell; ++j) {
-		if (!touched[j]) continue;
-		const uint32_t ow = old_words[j], nw = c.indices[j];
-		const int g[3] = {sx * kSupercell + (j & 15), sy * kSupercell + ((j >> 4) & 15), sz * kSupercell + (j >> 8)};
-		FieldChange& ch = b.change;
-		for (int k = 0; k < 2; ++k) { ch.touch_lo[k] = std::min(ch.touch_lo[k], g[k]); ch.touch_hi[k] = std::max(ch.touch_hi[k], g[k]); }
-		if ((ow != 0) != (nw != 0))
-			for (int k = 0; k < 3; ++k) { ch.box_lo[k] = std::min(ch.box_lo[k], g[k]); ch.box_hi[k] = std::max(ch.box_hi[k], g[k]); }
-		const uint16_t ds = nw ? pool.dev_slot[nw & BM_BRICK_INDEX_BITS] : kNoDeviceSlot;
-		b.cells.push_back(static_cast<uint32_t>(sci) * kCellsPerSupercell + static_cast<uint32_t>(j));
-		b.words.push_back(PoolBook::device_word(nw, ds));
-		b.slots.push_back(ds == kNoDeviceSlot ? 0xFFFFFFFFu : pool.base + ds);
-		b.bricks.push_back(nw ? c.bricks[nw & BM_BRICK_INDEX_BITS] : Brick{});
-	}
-	return 0;
-}
-
-// submit_batch: the staged cells go to the device on the load stream -- one copy, the pool moves, the scatter and, when some cell's
-// occupancy changed, the cube-field update -- as an upload batch.  marks[0 ... 2] are recorded around the scatter and the field update
-// (DeviceBatch::clocked says which of the two a batch has).
-int Scene::submit_batch(DeviceBatch& b, hipStream_t stream, hipEvent_t* marks) {
-	const uint32_t n = static_cast<uint32_t>(b.cells.size());
-	if (n == 0) { // nothing inside the world changed a brick (e.g. clearing empty space)
-		residency_.commit_batch();
-		return 0;
-	}
-	const std::vector<PoolMove>& moves = residency_.moves();
-
-	// ---- staging: [pool moves][cells][words][slots][bricks], 64-byte aligned sections
-	auto up = [](size_t v) { return (v + 63) / 64 * 64; };
-	const size_t o_cells = up(moves.size() * sizeof(PoolMove)), o_words = o_cells + up(n * 4ull), o_slots = o_words + up(n * 4ull),
-				 o_bricks = o_slots + up(n * 4ull), bytes = o_bricks + n * sizeof(Brick);
-	auto stage = [&]() -> int {
-		if (bytes > d_edit_.bytes()) { // (the two grow together: h_edit_ is as large as d_edit_)
-			BM_HIP(hipStreamSynchronize(load_stream_)); // the previous batch's kernels may still read the device staging
-			const size_t cap = std::max<size_t>(bytes * 2, 1 << 16);
-			if (int e = h_edit_.reserve(cap)) return e;
-			if (int e = d_edit_.reserve(cap)) return e;
-		}
-		if (int e = fields_.prepare_update(b.change, load_stream_)) return e;
-		if (!moves.empty()) std::memcpy(h_edit_, moves.data(), moves.size() * sizeof(PoolMove));
-		std::memcpy(h_edit_ + o_cells, b.cells.data(), n * 4ull);
-		std::memcpy(h_edit_ + o_words, b.words.data(), n * 4ull);
-		std::memcpy(h_edit_ + o_slots, b.slots.data(), n * 4ull);
-		std::memcpy(h_edit_ + o_bricks, b.bricks.data(), n * sizeof(Brick));
-		return 0;
-	};
-	// behind every frame in flight (they read the words, pool bases, bricks and field this rewrites) and the caller's queued work
-	auto queue = [&]() -> int {
-		if (int e = order_.load_behind_caller(stream)) return e;
-		BM_HIP(hipMemcpyAsync(d_edit_, h_edit_, bytes, hipMemcpyHostToDevice, load_stream_));
-		if (int e = edit_staging_.pass(load_stream_)) return e; // the pinned staging is free again from here on
-		BM_HIP(hipEventRecord(marks[0], load_stream_));
-		if (!moves.empty()) {
-			launch_pool_moves(reinterpret_cast<const PoolMove*>(d_edit_.get()), static_cast<uint32_t>(moves.size()), residency_.arena_base(), residency_.pool_base(), load_stream_);
-			BM_HIP(hipGetLastError());
-		}
-		launch_edit_scatter(reinterpret_cast<const uint32_t*>(d_edit_ + o_cells), reinterpret_cast<const uint32_t*>(d_edit_ + o_words),
-							reinterpret_cast<const uint32_t*>(d_edit_ + o_slots), reinterpret_cast<const uint32_t*>(d_edit_ + o_bricks), n, residency_.index_grid(), residency_.arena_base(),
-							load_stream_);
-		BM_HIP(hipGetLastError());
-		BM_HIP(hipEventRecord(marks[1], load_stream_));
-		// the field and the escape heights where some cell's occupancy changed; what that makes stale is rebuilt before the next frame that reads it
-		if (int e = fields_.update(residency_.index_grid(), b.change, true, load_stream_)) return e;
-		BM_HIP(hipEventRecord(marks[2], load_stream_));
-		return 0;
-	};
-	int e = stage();
-	if (!e) e = order_.publish_behind_frames(queue);
-	if (residency_.report(e)) return e; // the host world is ahead of the device: refuse to go on
-	residency_.commit_batch();
-	return 0;
-}
-
-int Scene::last_edit_ms(float* scatter_ms, float* field_ms) {
-	if (!scatter_ms || !field_ms) { set_error("null argument"); return BM_EINVAL; }
-	if (!edit_clocked_) { set_error("no edit has changed the scene yet"); return BM_ESTATE; }
-	BM_HIP(hipSetDevice(device_));
-	float ms[2];
-	if (int e = edit_marks_.read(2, ms)) return e;
-	*scatter_ms = ms[0];
-	*field_ms = (edit_clocked_ & kClockedField) ? ms[1] : 0.0f;
-	return 0;
-}
+int Scene::last_edit_ms(float* scatter_ms, float* field_ms) { return changes_.last_edit_ms(scatter_ms, field_ms); }
 
 // ---------------------------------------------------------------- dense regions (bm_scene_write_region / bm_scene_read_region)
 namespace {
@@ -539,106 +394,15 @@ int Scene::check_region(const char* who, const bm_region* region, const void* vo
 	return 0;
 }
 
-RegionDims Scene::region_dims(const bm_region& r, const int lo[3], const int hi[3]) const {
-	RegionDims rd{};
-	for (int k = 0; k < 3; ++k) {
-		rd.lo[k] = lo[k]; rd.hi[k] = hi[k]; rd.org[k] = r.lo[k];
-		rd.c0[k] = lo[k] >> 3;
-		rd.nc[k] = ((hi[k] - 1) >> 3) - rd.c0[k] + 1;
-	}
-	rd.g0 = rd.c0[0] >> 4;
-	rd.sg_xy = static_cast<uint32_t>(world.dims.supergrid_xy);
-	rd.sg_xy2 = rd.sg_xy * rd.sg_xy;
-	rd.row_pitch = r.row_pitch;
-	rd.slice_pitch = r.slice_pitch;
-	return rd;
-}
-
-// The host world first, by World::write_region_supercell on every supercell the clipped box reaches (on CPU threads: supercells are
-// independent), then the touched cells go to the device as an edit's do (stage_touched / submit_batch).  A volume in device memory is
-// packed into one brick per covered cell on the load stream (region.hip), behind the work queued on the caller's stream, and those
-// bricks are copied to pinned memory: the call's one round trip -- the host world is authoritative and hands out the slots.
 int Scene::write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream) {
 	bm_region r;
 	uint64_t span = 0;
 	if (op != BM_REGION_REPLACE && op != BM_EDIT_SET && op != BM_EDIT_CLEAR) { set_error("bm_scene_write_region: unknown op"); return BM_EINVAL; }
 	if (int e = check_region("bm_scene_write_region", region, voxels, where, &r, &span)) return e;
-	const WorldDims& d = world.dims;
-	int lo[3], hi[3];
-	if (!World::region_bounds(d, r, lo, hi)) return 0;
-	if (int e = edit_staging_.wait()) return e;
-	if (int e = region_marks_.create()) return e;
-	hipEvent_t* const marks = region_marks_.marks();
-	const RegionDims rd = region_dims(r, lo, hi);
-	World::RegionSource src;
-	for (int k = 0; k < 3; ++k) { src.c0[k] = rd.c0[k]; src.nc[k] = rd.nc[k]; src.origin[k] = r.lo[k]; }
-	if (where == BM_VOXELS_DEVICE) {
-		const size_t bytes = static_cast<size_t>(rd.nc[0]) * rd.nc[1] * rd.nc[2] * sizeof(Brick);
-		if (bytes > d_region_.bytes()) { // (no earlier write still uses them: each waits for its copy)
-			if (int e = d_region_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
-			if (int e = h_region_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
-		}
-		if (int e = order_.load_behind_caller(stream)) return e; // the volume is whatever the caller's stream has written by now
-		BM_HIP(hipEventRecord(marks[0], load_stream_));
-		launch_region_pack(voxels, reinterpret_cast<uint32_t*>(d_region_.get()), rd, load_stream_);
-		BM_HIP(hipGetLastError());
-		BM_HIP(hipEventRecord(marks[1], load_stream_));
-		BM_HIP(hipMemcpyAsync(h_region_, d_region_, bytes, hipMemcpyDeviceToHost, load_stream_));
-		BM_HIP(hipEventRecord(marks[2], load_stream_));
-		BM_HIP(hipStreamSynchronize(load_stream_));
-		src.packed = h_region_;
-	} else {
-		src.voxels = voxels;
-		src.row_pitch = r.row_pitch;
-		src.slice_pitch = r.slice_pitch;
-	}
-	// ---- merge
-	std::vector<int> reached;
-	for (int sz = lo[2] / kColumnSpan; sz <= (hi[2] - 1) / kColumnSpan; ++sz)
-		for (int sy = lo[1] / kColumnSpan; sy <= (hi[1] - 1) / kColumnSpan; ++sy)
-			for (int sx = lo[0] / kColumnSpan; sx <= (hi[0] - 1) / kColumnSpan; ++sx) reached.push_back(d.supercell_id(sx, sy, sz));
-	std::vector<std::vector<uint32_t>> old_words(reached.size());
-	std::vector<std::vector<uint8_t>> touched(reached.size());
-	{
-		std::atomic<size_t> next{0};
-		auto merge = [&]() {
-			for (size_t i = next.fetch_add(1); i < reached.size(); i = next.fetch_add(1)) {
-				const int sci = reached[i];
-				HostSupercell& c = world.supercells[sci];
-				old_words[i] = c.indices;
-				touched[i].assign(kCellsPerSupercell, 0);
-				World::write_region_supercell(d, c, sci % d.supergrid_xy, (sci / d.supergrid_xy) % d.supergrid_xy, sci / (d.supergrid_xy * d.supergrid_xy), lo, hi, op, src,
-											  touched[i].data());
-			}
-		};
-		std::vector<std::thread> pool;
-		for (size_t t = 1; t < std::min<size_t>(16, reached.size()); ++t) pool.emplace_back(merge);
-		merge();
-		for (auto& t : pool) t.join();
-	}
-	DeviceBatch batch;
-	residency_.begin_batch();
-	for (size_t i = 0; i < reached.size(); ++i)
-		if (int e = stage_touched(reached[i], old_words[i], touched[i].data(), batch)) return e;
-	region_clocked_ = kClockedCall | (where == BM_VOXELS_DEVICE ? kClockedPack : 0u);
-	if (int e = submit_batch(batch, stream, marks + 3)) return e;
-	region_clocked_ |= batch.clocked();
-	return 0;
+	return changes_.write_region(r, op, voxels, where, stream);
 }
 
-int Scene::last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms) {
-	if (!pack_ms || !copy_ms || !scatter_ms || !field_ms) { set_error("null argument"); return BM_EINVAL; }
-	if (!region_clocked_) { set_error("no region has been written yet"); return BM_ESTATE; }
-	BM_HIP(hipSetDevice(device_));
-	float ms[4] = {0.f, 0.f, 0.f, 0.f};
-	if (region_clocked_ & kClockedPack) { if (int e = region_marks_.read(2, ms)) return e; }
-	if (region_clocked_ & kClockedScatter) { if (int e = region_marks_.read(2, ms + 2, 3)) return e; }
-	*pack_ms = ms[0];
-	*copy_ms = ms[1];
-	*scatter_ms = ms[2];
-	*field_ms = (region_clocked_ & kClockedField) ? ms[3] : 0.0f;
-	return 0;
-}
+int Scene::last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms) { return changes_.last_region_ms(pack_ms, copy_ms, scatter_ms, field_ms); }
 
 int Scene::stage_absent_bricks(bool inside, const int lo[3], const int hi[3], size_t* count, size_t* bricks_at, size_t* total) {
 	const WorldDims& d = world.dims;
@@ -695,7 +459,7 @@ int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipS
 		launch_region_zero(voxels + region_offset(r, x0, y0, z0), r.row_pitch, r.slice_pitch, x1 - x0, y1 - y0, z1 - z0, stream);
 	});
 	if (inside) {
-		const RegionDims rd = region_dims(r, lo, hi);
+		const RegionDims rd = region_dims(d, r, lo, hi);
 		launch_region_unpack(voxels, view.index_grid, view.pool_base, view.brick_arena, rd, stream);
 		if (n > 0) {
 			BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));

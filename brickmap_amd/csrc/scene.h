@@ -19,12 +19,13 @@
 #include "residency.h"
 #include "walk_fields.h"
 #include "world.h"
+#include "world_changes.h"
 
 namespace bm {
 
 class Scene {
 public:
-	explicit Scene(int device) : device_(device), fields_(device), residency_(device, &world) {}
+	explicit Scene(int device) : device_(device), fields_(device), residency_(device, &world), changes_(device, &world, &residency_, &fields_, &order_, &load_stream_) {}
 	~Scene();
 
 	int init(int grid_size, int grid_height); // Scene::Scene: streams + pinned staging
@@ -40,14 +41,14 @@ public:
 	int info(bm_scene_info* out);
 	int device_indices(int supercell, uint32_t* out4096);
 	int device_brick(int supercell, uint32_t device_slot, uint32_t* out16);
-	// voxel edits (edit.hip / scene.cpp "voxel edits"): host world first, then one scatter + the cube-field update on the load stream
+	// voxel edits (edit.hip / world_changes.h): host world first, then one scatter + the cube-field update on the load stream
 	int edit(int count, const bm_edit* edits, hipStream_t stream);
 	int host_cube_field(uint8_t* dst, size_t capacity, size_t* bytes);
 	int last_edit_ms(float* scatter_ms, float* field_ms); // device time of the last batch that changed something
 	// the cube field, the escape table and the planes derived from them: walk_fields.h has their readbacks and build statistics
 	WalkFields& fields() { return fields_; }
 	WalkFields* fields_on_device() { return require_on_device() ? nullptr : &fields_; } // null + message unless the world is on the device
-	// dense regions (region.hip / scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
+	// dense regions (region.hip / world_changes.h, scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
 	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
 	int read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream);
 	int last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms);
@@ -92,17 +93,7 @@ private:
 	int ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usable); // builds the view plane for the first frame's origin if the camera rests there; *usable: the plane stands for that origin
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
-	// the device half of a change of the host world (scene.cpp "voxel edits"): the touched cells of every changed supercell are staged, then submitted
-	struct DeviceBatch {
-		std::vector<uint32_t> cells, words, slots;
-		std::vector<Brick> bricks; // (the batch's pool moves: Residency::moves)
-		FieldChange change;
-		unsigned clocked() const { return cells.empty() ? 0u : change.occupancy() ? kClockedScatter | kClockedField : kClockedScatter; } // the stages submit_batch records for it
-	};
-	int stage_touched(int sci, const std::vector<uint32_t>& old_words, const uint8_t* touched, DeviceBatch& b);
-	int submit_batch(DeviceBatch& b, hipStream_t stream, hipEvent_t* marks); // marks[0 ... 2]: around the scatter and the field update
 	int check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span);
-	RegionDims region_dims(const bm_region& r, const int lo[3], const int hi[3]) const;
 	// the bricks of the clipped box [lo, hi) that the device does not hold, from the host world into h_patch_ / d_patch_'s layout: *n of them,
 	// the bricks from byte *o_bricks on, *bytes in all (a preloaded scene, or inside == false: none)
 	int stage_absent_bricks(bool inside, const int lo[3], const int hi[3], size_t* n, size_t* o_bricks, size_t* bytes);
@@ -122,6 +113,7 @@ private:
 	// frame_ring_ (launch_book.h) says which entries a launch takes and which earlier launches it waits for; the events stand here, indexed by
 	// its clock slots.  A scratch or staging buffer that one call at a time may use: a Turn (hip_owned.h) beside the buffer.  Which brick is
 	// resident where, the request rings and the upload batches: residency_ (residency.h; pool_book.h takes the decisions, the failed flag among them).
+	// The device half of an edit or a region write, its staging and its stage clocks: changes_ (world_changes.h; change_book.h takes the decisions).
 	FrameOrder order_;
 	static constexpr int kTimingRing = 256; // hipEvent pairs around the most recent render launches
 	Event ev_start_[kTimingRing], ev_stop_[kTimingRing];
@@ -130,6 +122,7 @@ private:
 	// scratch and the book of which derived plane stands and what makes it stale (walk_fields.h; every flag is explained in field_book.h)
 	WalkFields fields_;
 	Residency residency_;
+	WorldChanges changes_;
 	DeviceBuffer<DeviceCounters> d_counters_;
 	// the frame ring: constants and ticket counters of the frames in flight -- a launch takes as many consecutive entries as it has frames
 	static constexpr int kFrameRing = 1024; // (a launch takes at most kMaxFramesPerLaunch, frame_plan.h)
@@ -138,26 +131,16 @@ private:
 	DeviceBuffer<uint32_t> d_work_counter_; // chunk counters of the persistent trace kernel: kFrameRing blocks of kWorkCounterBytes, zeroed before the launch that uses them
 	FrameRing<kFrameRing, kTimingRing, kMaxFramesPerLaunch> frame_ring_;
 	int compute_units_ = 0, blocks_per_cu_[2] = {0, 0};
-	// edits: pinned + device staging of one batch (pool moves, dirty cells, their words, arena slots and bricks), grown on demand;
-	// the pinned staging is the batch's until its copy has run (edit_staging_)
-	PinnedBuffer<char> h_edit_;
-	DeviceBuffer<char> d_edit_;
-	Turn edit_staging_;
-	// region writes: the packed bricks of a device volume (64 bytes per covered cell, device + pinned, grown on demand);
 	// region reads: the list of non-resident bricks (pinned + device), the read's until its launch has used it (region_read_)
-	DeviceBuffer<char> d_region_, d_patch_;
-	PinnedBuffer<Brick> h_region_;
+	DeviceBuffer<char> d_patch_;
 	PinnedBuffer<char> h_patch_;
 	Turn region_read_;
-	// Stage clocks of the calls that report device times (StageMarks, made on first use), each with the stages its last call recorded.
-	// Edits: marks 0 ... 2 around scatter and field, of the last batch that scattered something.  Region writes: 0 ... 2 around pack and copy
-	// (a device volume), 3 ... 5 around scatter and field.  Loads from device memory: 0, 1 around classify + number, 2 ... 5 around pack,
-	// field and mirror (the host's round trip lies between 1 and 2).  label_region: 0 ... 3 around local, merge and flatten.
-	enum : unsigned { kClockedCall = 1, kClockedPack = 2, kClockedScatter = 4, kClockedField = 8 };
-	StageMarks<3> edit_marks_;
-	StageMarks<6> region_marks_, load_marks_;
+	// Stage clocks of the calls that report device times here (StageMarks, made on first use), each with the stages its last call recorded (kClocked*,
+	// change_book.h: 0 = nothing to report).  Loads from device memory: 0, 1 around classify + number, 2 ... 5 around pack, field and mirror (the
+	// host's round trip lies between 1 and 2).  label_region: 0 ... 3 around local, merge and flatten.
+	StageMarks<6> load_marks_;
 	StageMarks<4> label_marks_;
-	unsigned edit_clocked_ = 0, region_clocked_ = 0, load_clocked_ = 0, label_clocked_ = 0; // kClocked*: 0 = the call has nothing to report
+	unsigned load_clocked_ = 0, label_clocked_ = 0;
 	// ray queries: a ring of slot counters (one 128-byte line each); a query that reuses an entry waits for the one that used it last
 	static constexpr int kQueryRing = 64;
 	DeviceBuffer<uint32_t> d_query_tickets_;

@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "change_book.h" // FieldChange: what a change of the world tells the fields
 #include "device_types.h"
 #include "error.h"
 #include "field_book.h"
@@ -15,19 +16,6 @@
 #include "world.h"
 
 namespace bm {
-
-// the cells a change of the world touched, collected while it is staged
-struct FieldChange {
-	int box_lo[3] = {1 << 30, 1 << 30, 1 << 30}, box_hi[3] = {-1, -1, -1}; // cells whose occupancy changed (unbordered, inclusive)
-	int touch_lo[2] = {1 << 30, 1 << 30}, touch_hi[2] = {-1, -1};          // columns of every touched cell (x, y): what the shadow heights scan again
-	bool occupancy() const { return box_hi[0] >= 0; }
-	static FieldChange whole(const WorldDims& d) { // a new world
-		FieldChange c;
-		for (int k = 0; k < 3; ++k) { c.box_lo[k] = 0; c.box_hi[k] = (k == 2 ? d.cells_height : d.cells) - 1; }
-		for (int k = 0; k < 2; ++k) { c.touch_lo[k] = 0; c.touch_hi[k] = d.cells - 1; }
-		return c;
-	}
-};
 
 // the device time of a plane's last build
 class BuildClock {

@@ -9,10 +9,8 @@
 #include "voxel_bits.h"
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cstring>
-#include <thread>
 
 namespace bm {
 
@@ -178,22 +176,12 @@ void World::generate(int threads) {
 	supercells.clear();
 	supercells.resize(dims.supercells);
 	const int columns = dims.supergrid_xy * dims.supergrid_xy;
-	threads = std::max(1, std::min(threads, columns));
-	std::atomic<int> next{0};
-	auto work = [&]() {
+	parallel_for(columns, threads, [&](int c) {
 		std::vector<float> heights(kColumnSpan * kColumnSpan);
-		for (;;) {
-			const int c = next.fetch_add(1);
-			if (c >= columns) return;
-			const int sx = c % dims.supergrid_xy, sy = c / dims.supergrid_xy;
-			column_heights(sx, sy, heights.data());
-			for (int sz = 0; sz < dims.supergrid_z; ++sz) build_supercell(sx, sy, sz, heights.data());
-		}
-	};
-	std::vector<std::thread> pool;
-	for (int i = 1; i < threads; ++i) pool.emplace_back(work);
-	work();
-	for (auto& t : pool) t.join();
+		const int sx = c % dims.supergrid_xy, sy = c / dims.supergrid_xy;
+		column_heights(sx, sy, heights.data());
+		for (int sz = 0; sz < dims.supergrid_z; ++sz) build_supercell(sx, sy, sz, heights.data());
+	});
 	generated = true;
 }
 
@@ -204,21 +192,6 @@ uint64_t World::total_bricks() const {
 }
 
 // ---------------------------------------------------------------- dense voxels -> bricks
-namespace {
-// run work(i) for i in [0, n) on up to `threads` threads
-template <class F> void parallel_for(int n, int threads, F work) {
-	threads = std::max(1, std::min(threads, n));
-	std::atomic<int> next{0};
-	auto loop = [&]() {
-		for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) work(i);
-	};
-	std::vector<std::thread> pool;
-	for (int i = 1; i < threads; ++i) pool.emplace_back(loop);
-	loop();
-	for (auto& t : pool) t.join();
-}
-} // namespace
-
 void World::load_supercell(const WorldDims& dims, HostSupercell& cell, int sx, int sy, int sz, const uint8_t* voxels) {
 	cell = HostSupercell{};
 	cell.indices.assign(kCellsPerSupercell, 0u);
@@ -253,7 +226,9 @@ void World::load_voxels(const uint8_t* voxels, int threads) {
 	supercells.clear();
 	supercells.resize(dims.supercells);
 	parallel_for(dims.supercells, threads, [&](int sc) {
-		load_supercell(dims, supercells[sc], sc % dims.supergrid_xy, (sc / dims.supergrid_xy) % dims.supergrid_xy, sc / (dims.supergrid_xy * dims.supergrid_xy), voxels);
+		int sx, sy, sz;
+		dims.supercell_coords(sc, &sx, &sy, &sz);
+		load_supercell(dims, supercells[sc], sx, sy, sz, voxels);
 	});
 	generated = true;
 }
@@ -262,7 +237,8 @@ void World::store_voxels(uint8_t* voxels, int threads) const {
 	const size_t g = static_cast<size_t>(dims.grid_size);
 	parallel_for(dims.supercells, threads, [&](int sc) {
 		const HostSupercell& c = supercells[sc];
-		const int sx = sc % dims.supergrid_xy, sy = (sc / dims.supergrid_xy) % dims.supergrid_xy, sz = sc / (dims.supergrid_xy * dims.supergrid_xy);
+		int sx, sy, sz;
+		dims.supercell_coords(sc, &sx, &sy, &sz);
 		for (int cell = 0; cell < kCellsPerSupercell; ++cell) {
 			const uint32_t word = c.indices.empty() ? 0u : c.indices[cell];
 			const uint8_t* bits = word ? reinterpret_cast<const uint8_t*>(c.bricks[word & BM_BRICK_INDEX_BITS].data) : nullptr;
@@ -549,7 +525,8 @@ void World::build_cube_field(std::vector<uint8_t>& field, int threads) const {
 	std::vector<uint8_t> occupied(plane, 1); // border counts as occupied
 	for (int sc = 0; sc < dims.supercells; ++sc) {
 		const HostSupercell& c = supercells[sc];
-		const int sx = sc % dims.supergrid_xy, sy = (sc / dims.supergrid_xy) % dims.supergrid_xy, sz = sc / (dims.supergrid_xy * dims.supergrid_xy);
+		int sx, sy, sz;
+		dims.supercell_coords(sc, &sx, &sy, &sz);
 		for (int lz = 0; lz < kSupercell; ++lz)
 			for (int ly = 0; ly < kSupercell; ++ly) {
 				uint8_t* row = &occupied[(static_cast<size_t>(sz * kSupercell + lz + 1) * X + (sy * kSupercell + ly + 1)) * X + sx * kSupercell + 1];
@@ -585,14 +562,7 @@ void World::build_cube_field(std::vector<uint8_t>& field, int threads) const {
 				else row[0] = row[X - 1] = 255;
 			}
 	};
-	const int n_threads = std::max(1, std::min(threads, 8));
-	std::vector<std::thread> pool;
-	std::atomic<int> next{0};
-	for (int t = 0; t < n_threads; ++t)
-		pool.emplace_back([&] {
-			for (int oct = next.fetch_add(1); oct < 8; oct = next.fetch_add(1)) sweep(oct);
-		});
-	for (auto& th : pool) th.join();
+	parallel_for(8, std::min(threads, 8), sweep);
 }
 
 } // namespace bm

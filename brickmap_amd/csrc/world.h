@@ -2,8 +2,11 @@
 // Product code (not the oracle).  Mirrors the host half of the reference's Scene
 // (src/Scene.h:3-44, src/Scene.cpp:44-147), with the world dimensions made runtime.
 #pragma once
+#include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/brickmap.h"
@@ -35,8 +38,26 @@ struct WorldDims {
 	int supercells = 0;
 	bool set(int grid_size_, int grid_height_);
 	int supercell_id(int sx, int sy, int sz) const { return sx + sy * supergrid_xy + sz * supergrid_xy * supergrid_xy; }
+	void supercell_coords(int sci, int* sx, int* sy, int* sz) const { // the inverse
+		*sx = sci % supergrid_xy;
+		*sy = (sci / supergrid_xy) % supergrid_xy;
+		*sz = sci / (supergrid_xy * supergrid_xy);
+	}
 };
 static_assert(kIndexBits == BM_BRICK_INDEX_BITS && kLoadedBit == BM_BRICK_LOADED_BIT, "device_types.h and brickmap.h name one index word");
+
+// run work(i) for i in [0, n) on up to `threads` threads, the caller's among them: THE worker pool of the host code
+template <class F> void parallel_for(int n, int threads, F work) {
+	threads = std::max(1, std::min(threads, n));
+	std::atomic<int> next{0};
+	auto loop = [&]() {
+		for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) work(i);
+	};
+	std::vector<std::thread> pool;
+	for (int i = 1; i < threads; ++i) pool.emplace_back(loop);
+	loop();
+	for (auto& t : pool) t.join();
+}
 
 // 2-D simplex noise + fBm exactly as the reference's terrain uses it (SimplexNoise.cpp:216-292,
 // 435-450 with SimplexNoise(1,1,2,0.5), Scene.cpp:45,53).  Pure fp32, no contraction.

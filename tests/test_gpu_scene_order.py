@@ -1,6 +1,6 @@
 """Who waits for whom in a scene, on the MI355X (csrc/frame_order.h, csrc/launch_book.h, Turn and StageMarks of csrc/hip_owned.h): the stage
 clocks of edits, region writes and loads -- what each reports, and when it reports nothing --, more frame streams than the stream table
-holds with edits between the frames, a query ring that wraps, and a scratch buffer that has to grow while the call before still uses it.
+holds with edits between the frames, a query ring that wraps, and a scratch or staging buffer that has to grow while the call before still uses it.
 Every result is compared with the same calls made one by one, each waited for.  Nothing here depends on how the library decides the
 ordering, only on what it computes: the file passes on a library built before the ordering had one owner as well.
 
@@ -225,3 +225,41 @@ def test_label_scratch_grows_behind_a_call_in_flight(bm, torch_cuda, volume):
         assert torch.equal(labels, want.labels), f"box {lo} ... {hi}: labels differ from the call made alone"
         assert torch.equal(table[:n], want._table[:n]), f"box {lo} ... {hi}: the component table differs from the call made alone"
     s.close()
+
+
+def _device_world(scene):
+    """the index words of the world's one supercell, the brick the device holds for every cell that names one, and the device's cube field"""
+    words = scene.device_indices(0)
+    bricks = {int(j): scene.device_brick(0, int(words[j]) & 0xFFF) for j in np.flatnonzero(words & np.uint32(0x80000000))}
+    return words, bricks, scene.device_cube_field()
+
+
+def test_edit_staging_grows_behind_a_batch_in_flight(bm, torch_cuda, volume):
+    torch = torch_cuda
+    # a batch is staged in 76 bytes a cell (cell, word, arena slot, brick) and the staging starts at 64 KiB: one cell fits; the 2048 cells of eight
+    # layers of the world (155 648 bytes, and a pool move: the exact-fit pool of a loaded world grows) do not, so the staging grows while the
+    # batch before may still be running; the region write of the same box then packs 2048 bricks (128 KiB), more than its 64 KiB as well
+    lo, hi = (0, 0, 56), (G, G, 120)
+    z, y, x = np.indices((64, G, G))
+    pattern = (((x // 4 + y // 4 + z // 4) & 1) == 0).astype(np.uint8)  # every brick of the box gets a checkerboard of 4-voxel blocks
+    dev = torch.from_numpy(pattern).to("cuda:0")
+    worlds = []
+    for wait in (False, True):
+        s = bm.Scene.from_voxels(volume)
+        torch.cuda.synchronize()
+        for call in (lambda: s.fill_box(*AIR), lambda: s.fill_box(lo, hi), lambda: s.write_region(lo, dev)):
+            call()
+            if wait:
+                s.synchronize()
+                torch.cuda.synchronize()
+        s.synchronize()
+        worlds.append(_device_world(s))
+        want = volume.copy()
+        want[56:120] = pattern
+        assert np.array_equal(s.voxels(), want.astype(bool))
+        s.close()
+    (words, bricks, field), (words_1, bricks_1, field_1) = worlds
+    assert len(bricks_1) >= 2048 + 512, "the floor and the eight layers"
+    assert np.array_equal(words, words_1), "index words differ from the calls made one by one"
+    assert bricks.keys() == bricks_1.keys() and all(np.array_equal(bricks[j], bricks_1[j]) for j in bricks), "bricks differ from the calls made one by one"
+    assert np.array_equal(field, field_1), "the cube field differs from the calls made one by one"
