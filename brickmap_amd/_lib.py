@@ -127,6 +127,17 @@ class bm_distance_result(C.Structure):
     _fields_ = [("sources", C.c_uint64), ("max_sq", C.c_uint32), ("reserved0", C.c_uint32), ("max_at", C.c_uint64), ("reserved1", C.c_uint64)]
 
 
+BM_TRAVEL_NONE = 0x7FFFFFFF
+
+
+class bm_travel_params(C.Structure):
+    _fields_ = [("extent", C.c_int32 * 3), ("max_steps", C.c_uint32), ("row_pitch", C.c_int64), ("slice_pitch", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class bm_travel_result(C.Structure):
+    _fields_ = [("reached", C.c_uint64), ("farthest", C.c_uint32), ("seeds_rejected", C.c_uint32), ("farthest_at", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 class bm_volume(C.Structure):
     _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
 
@@ -228,6 +239,12 @@ SIGNATURES = {
     "bm_distance_mask": (_i, [_vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "bm_host_distance_field": (_i, [C.POINTER(bm_distance_params), _vp, _vp, C.POINTER(bm_distance_result)]),
     "bm_host_distance_mask": (_i, [C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "bm_travel_workspace_bytes": (_i, [C.POINTER(bm_travel_params), C.POINTER(C.c_size_t)]),
+    "bm_travel_field": (_i, [_vp, C.POINTER(bm_travel_params), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bm_debug_travel_times": (_i, [_vp, C.POINTER(bm_travel_params), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "bm_travel_paths": (_i, [_vp, C.POINTER(C.c_int32), _vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
+    "bm_host_travel_field": (_i, [C.POINTER(bm_travel_params), _vp, _vp, C.c_int64, _vp, C.POINTER(bm_travel_result)]),
+    "bm_host_travel_paths": (_i, [C.POINTER(C.c_int32), _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

@@ -14,6 +14,7 @@
 #include "mesh.h"
 #include "reproject.h"
 #include "scene.h"
+#include "travel.h"
 #include "voxelize.h"
 #include "wavefront.h"
 
@@ -309,6 +310,35 @@ int bm_debug_distance_times(bm_scene* scene, const bm_distance_params* params, c
 int bm_distance_mask(bm_scene* scene, uint64_t count, const uint32_t* dist_dev, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out_dev, void* hip_stream) {
 	BM_NEED(scene);
 	return bm::distance_mask(scene->impl.gpu(), count, dist_dev, limit_sq, flags, volume_out_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+// (bm_host_travel_field and bm_host_travel_paths are csrc/travel_host.cpp: host code that needs nothing of the library)
+int bm_travel_workspace_bytes(const bm_travel_params* params, size_t* bytes) {
+	if (!params || !bytes) { set_error("bm_travel_workspace_bytes: null argument"); return BM_EINVAL; }
+	const bm::TravelParamsView pv = bm::travel_params_view(*params);
+	if (const char* why = bm::travel_params_problem(pv)) { set_error(std::string("bm_travel_workspace_bytes: ") + why); return BM_EINVAL; }
+	*bytes = bm::travel_workspace_bytes(bm::travel_dims(pv));
+	return 0;
+}
+
+int bm_travel_field(bm_scene* scene, const bm_travel_params* params, const uint8_t* volume_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev,
+					bm_travel_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::travel_field(scene->impl.gpu(), params, volume_dev, seeds_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_travel_times(bm_scene* scene, const bm_travel_params* params, const uint8_t* volume_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev,
+						  bm_travel_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, uint32_t batch, float* stage_ms, uint32_t* counts) {
+	BM_NEED(scene);
+	if (!stage_ms || !counts) { set_error("bm_debug_travel_times: null argument"); return BM_EINVAL; }
+	return bm::travel_field(scene->impl.gpu(), params, volume_dev, seeds_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), batch,
+							stage_ms, counts);
+}
+
+int bm_travel_paths(bm_scene* scene, const int32_t extent[3], const uint32_t* field_dev, const int32_t* starts_dev, int64_t n, int32_t capacity, int32_t* path_dev,
+					int32_t* lengths_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::travel_paths(scene->impl.gpu(), extent, field_dev, starts_dev, n, capacity, path_dev, lengths_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)

@@ -12,6 +12,7 @@
 #include "hip_owned.h"
 #include "kernels.h"
 #include "mesh.h"
+#include "travel.h"
 #include "voxelize.h"
 
 namespace bm {
@@ -203,6 +204,107 @@ int distance_mask(const Gpu& gpu, uint64_t count, const uint32_t* dist, uint32_t
 		return BM_EINVAL;
 	}
 	launch_distance_mask(dist, count, limit_sq, flags & kDistanceMaskAbove, volume_out, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- voxels + seeds -> shortest face-step distances (bm_travel_field, bm_travel_paths): kernels on the caller's stream over the caller's
+// buffers; nothing of the world is read.  The host loop of the rounds is here: batches of rounds, and between them one word read back.
+int travel_field(const Gpu& gpu, const bm_travel_params* params, const uint8_t* volume, const int32_t* seeds, int64_t n, uint32_t* field, bm_travel_result* result,
+				 void* workspace, size_t workspace_bytes, hipStream_t stream, uint32_t batch, float* stage_ms, uint32_t* counts) {
+	if (!params) { set_error("bm_travel_field: null params"); return BM_EINVAL; }
+	const TravelParamsView pv = travel_params_view(*params);
+	if (const char* why = travel_params_problem(pv)) { set_error(std::string("bm_travel_field: ") + why); return BM_EINVAL; }
+	if (n < 0 || n > 0x7FFFFFFF) { set_error("bm_travel_field: a negative number of seeds, or more than 2^31 - 1"); return BM_EINVAL; }
+	if (!volume || !field || !result || !workspace || (n > 0 && !seeds)) { set_error("bm_travel_field: null volume, seeds, field, result or workspace"); return BM_EINVAL; }
+	const TravelDims d = travel_dims(pv);
+	const size_t need = travel_workspace_bytes(d);
+	if (workspace_bytes < need) { set_error("bm_travel_field: the workspace is smaller than bm_travel_workspace_bytes"); return BM_EINVAL; }
+	if (!aligned(field, 4) || !aligned(seeds, 4) || !aligned(result, 8) || !aligned(workspace, 16)) {
+		set_error("bm_travel_field: the field and the seeds must be 4-byte, the result 8-byte and the workspace 16-byte aligned");
+		return BM_EINVAL;
+	}
+	const size_t span = static_cast<size_t>(travel_span(d)), field_bytes = static_cast<size_t>(d.voxels) * sizeof(uint32_t), seed_bytes = static_cast<size_t>(n) * 12;
+	const Span ws = span_of(workspace, need), fs = span_of(field, field_bytes), ss = span_of(seeds, seed_bytes), rs = span_of(result, sizeof(bm_travel_result));
+	BM_HIP(hipSetDevice(gpu.device));
+	// (a volume whose pitches carry it past its allocation has no extent to overlap anything with, see mesh_quads)
+	const bool volume_ok = device_span_ok(gpu.device, volume, span);
+	if ((volume_ok && spans_overlap(span_of(volume, span), ws)) || spans_overlap(fs, ws) || spans_overlap(ss, ws) || spans_overlap(rs, ws)) {
+		set_error("bm_travel_field: the workspace overlaps the volume, the seeds, the field or the result");
+		return BM_EINVAL;
+	}
+	if ((volume_ok && spans_overlap(span_of(volume, span), fs)) || spans_overlap(ss, fs) || spans_overlap(rs, fs)) {
+		set_error("bm_travel_field: the field overlaps the volume, the seeds or the result");
+		return BM_EINVAL;
+	}
+	if (!volume_ok || !device_span_ok(gpu.device, workspace, need) || !device_span_ok(gpu.device, field, field_bytes) || (n > 0 && !device_span_ok(gpu.device, seeds, seed_bytes)) ||
+		!device_span_ok(gpu.device, result, sizeof(bm_travel_result))) {
+		set_error("bm_travel_field: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (batch == 0) batch = kTravelBatch;
+	StageMarks<4> marks;
+	if (stage_ms) {
+		if (int e = marks.create(4)) return e;
+	}
+	auto stamp = [&](int i) { if (stage_ms) (void)hipEventRecord(marks.marks()[i], stream); };
+	stamp(0);
+	launch_travel_setup(d, volume, seeds, static_cast<uint32_t>(n), field, workspace, stream);
+	stamp(1);
+	// Round k settles every voxel whose shortest path crosses at most k - 1 tile faces (travel.h), a path of s steps crosses at most s,
+	// and no path is longer than the limit or has more steps than the volume has voxels: the list is empty after that many rounds + 2.
+	const uint64_t cap = static_cast<uint64_t>(pv.max_steps != 0 && pv.max_steps < d.voxels ? pv.max_steps : d.voxels) + 2;
+	const uint8_t* tail = static_cast<const uint8_t*>(workspace) + travel_tail_offset(d);
+	uint64_t done = 0;
+	uint32_t looks = 0, listed = n > 0 ? 1u : 0u; // (without seeds no list ever holds a tile)
+	while (listed != 0) {
+		if (done >= cap) { set_error("bm_travel_field: internal error: tiles are still listed after every round the field can need"); return BM_ESTATE; }
+		const uint32_t rounds = static_cast<uint32_t>(cap - done < batch ? cap - done : batch);
+		launch_travel_rounds(d, field, workspace, static_cast<uint32_t>(done) + 1u, rounds, stream);
+		done += rounds;
+		// the next list's count: what round done + 1 would read
+		BM_HIP(hipMemcpyAsync(&listed, tail + 4 * (kTravelTailCountWord + (done + 1) % 3), 4, hipMemcpyDeviceToHost, stream));
+		BM_HIP(hipStreamSynchronize(stream));
+		++looks;
+	}
+	stamp(2);
+	launch_travel_finish(d, field, result, workspace, stream);
+	stamp(3);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipStreamSynchronize(stream)); // the call returns when the field and the record stand
+	if (counts) {
+		counts[0] = static_cast<uint32_t>(done);
+		counts[1] = looks;
+	}
+	if (stage_ms) return marks.read(3, stage_ms);
+	return 0;
+}
+
+int travel_paths(const Gpu& gpu, const int32_t extent[3], const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path, int32_t* lengths,
+				 hipStream_t stream) {
+	if (!extent) { set_error("bm_travel_paths: null extent"); return BM_EINVAL; }
+	if (const char* why = travel_extent_problem(extent)) { set_error(std::string("bm_travel_paths: ") + why); return BM_EINVAL; }
+	if (n < 0 || n > 0x7FFFFFFF) { set_error("bm_travel_paths: a negative number of starts, or more than 2^31 - 1"); return BM_EINVAL; }
+	if (capacity < 1) { set_error("bm_travel_paths: a capacity below 1"); return BM_EINVAL; }
+	if (!field || (n > 0 && (!starts || !path || !lengths))) { set_error("bm_travel_paths: null field, starts, path or lengths"); return BM_EINVAL; }
+	if (!all_aligned(4, field, starts, path, lengths)) { set_error("bm_travel_paths: the field, the starts, the path and the lengths must be 4-byte aligned"); return BM_EINVAL; }
+	if (static_cast<uint64_t>(n) * static_cast<uint64_t>(capacity) > (uint64_t{1} << 40)) { set_error("bm_travel_paths: more than 2^40 path voxels"); return BM_EINVAL; }
+	const TravelDims d = travel_field_dims(extent);
+	const size_t field_bytes = static_cast<size_t>(d.voxels) * sizeof(uint32_t), start_bytes = static_cast<size_t>(n) * 12, path_bytes = start_bytes * static_cast<size_t>(capacity),
+				 length_bytes = static_cast<size_t>(n) * 4;
+	const Span fs = span_of(field, field_bytes), ss = span_of(starts, start_bytes), ps = span_of(path, path_bytes), ls = span_of(lengths, length_bytes);
+	if (spans_overlap(ps, fs) || spans_overlap(ps, ss) || spans_overlap(ls, fs) || spans_overlap(ls, ss) || spans_overlap(ps, ls)) {
+		set_error("bm_travel_paths: the path or the lengths buffer overlaps the field, the starts or the other of the two");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, field, field_bytes) ||
+		(n > 0 && (!device_span_ok(gpu.device, starts, start_bytes) || !device_span_ok(gpu.device, path, path_bytes) || !device_span_ok(gpu.device, lengths, length_bytes)))) {
+		set_error("bm_travel_paths: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (n == 0) return 0;
+	launch_travel_paths(d, field, starts, static_cast<uint32_t>(n), capacity, path, lengths, stream);
 	BM_HIP(hipGetLastError());
 	return 0;
 }

@@ -37,6 +37,13 @@ int mesh_triangles(const Gpu& gpu, const bm_quad* quads, int64_t n, float* trian
 int distance_field(const Gpu& gpu, const bm_distance_params* params, const uint8_t* volume, uint32_t* dist, bm_distance_result* result, void* workspace,
 				   size_t workspace_bytes, hipStream_t stream, float* kernel_ms = nullptr);
 int distance_mask(const Gpu& gpu, uint64_t count, const uint32_t* dist, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out, hipStream_t stream);
+// voxels + seeds -> shortest face-step distances (travel.hip): the buffers and the workspace are the caller's.  Unlike its siblings the
+// call returns when the field stands: it waits on `stream` between batches of `batch` rounds (0 = kTravelBatch).  stage_ms: null, or 3
+// durations -- set-up, rounds, finish; counts: null, or the rounds enqueued and the looks of the host (bm_debug_travel_times)
+int travel_field(const Gpu& gpu, const bm_travel_params* params, const uint8_t* volume, const int32_t* seeds, int64_t n, uint32_t* field, bm_travel_result* result,
+				 void* workspace, size_t workspace_bytes, hipStream_t stream, uint32_t batch = 0, float* stage_ms = nullptr, uint32_t* counts = nullptr);
+int travel_paths(const Gpu& gpu, const int32_t extent[3], const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path, int32_t* lengths,
+				 hipStream_t stream);
 // pixel-centre rays of a frame, written on the device (denoise.hip)
 int pixel_rays(const Gpu& gpu, const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
 // temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers

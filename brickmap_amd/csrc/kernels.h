@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, travel.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -177,6 +177,17 @@ void launch_distance_field(const DistanceDims& d, const uint8_t* volume, uint32_
 						   hipEvent_t* marks = nullptr);
 // out[i] = field[i] <= limit_sq (above: the opposite), i < n; out at any address
 void launch_distance_mask(const uint32_t* field, uint64_t n, uint32_t limit_sq, uint32_t above, uint8_t* out, hipStream_t stream);
+
+// voxels + seeds -> shortest face-step distances (travel.hip; travel.h has the rules, TravelDims and the workspace's layout).  The caller
+// (device_ops.cpp) enqueues the set-up, then rounds in batches -- between batches it reads the next list's count from the tail and stops
+// at 0 -- then the finish.  workspace: travel_workspace_bytes() bytes, 16-byte aligned, that no other launch uses until the finish has
+// run (its stamps and tail are zeroed by the set-up).  Rounds count from 1.
+struct TravelDims;
+void launch_travel_setup(const TravelDims& d, const uint8_t* volume, const int32_t* seeds, uint32_t n, uint32_t* field, void* workspace, hipStream_t stream);
+void launch_travel_rounds(const TravelDims& d, uint32_t* field, void* workspace, uint32_t first_round, uint32_t rounds, hipStream_t stream);
+void launch_travel_finish(const TravelDims& d, const uint32_t* field, void* result, void* workspace, hipStream_t stream);
+// n starts -> n paths of at most `capacity` voxels down the field, and their lengths
+void launch_travel_paths(const TravelDims& d, const uint32_t* field, const int32_t* starts, uint32_t n, int32_t capacity, int32_t* path, int32_t* lengths, hipStream_t stream);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

@@ -666,6 +666,145 @@ class DistanceField:
         return out
 
 
+# ---- voxels + seeds -> shortest face-step distances and paths (bm_travel_field / bm_host_travel_field)
+TRAVEL_NONE = _lib.BM_TRAVEL_NONE
+TRAVEL_RESULT_DTYPE = np.dtype([("reached", "<u8"), ("farthest", "<u4"), ("seeds_rejected", "<u4"), ("farthest_at", "<u8"), ("reserved", "<u8")])  # bm_travel_result, 32 bytes
+
+
+def _travel_params(volume, max_steps, name="volume"):
+    """(bm_travel_params, data pointer, is_cuda) of `volume` ([z, y, x], laid out as region_of takes it)"""
+    if not 0 <= int(max_steps) <= 0xFFFFFFFF:
+        raise ValueError(f"travel_field: max_steps in 0 ... 2^32 - 1 expected (0 = no limit), got {max_steps}")
+    r, ptr, cuda = region_of((0, 0, 0), volume, name)
+    nz, ny, nx = volume.shape
+    par = _lib.bm_travel_params()
+    par.extent[:] = [nx, ny, nz]
+    par.max_steps = int(max_steps)
+    par.row_pitch, par.slice_pitch = r.row_pitch, r.slice_pitch
+    return par, ptr, cuda
+
+
+def _points(points, name):
+    """an int32 numpy array [n, 3] of (x, y, z) from a list or an array ([3] is one point)"""
+    a = np.asarray(points)
+    if a.size == 0:
+        return np.zeros((0, 3), np.int32)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{name}: integer coordinates expected, got {a.dtype}")
+    if a.ndim == 1 and a.shape[0] == 3:
+        a = a.reshape(1, 3)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"{name}: an array [n, 3] of (x, y, z) expected, got shape {a.shape}")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def travel_workspace_bytes(shape):
+    """bm_travel_workspace_bytes: device memory bm_travel_field needs beside its buffers for a volume of shape (nz, ny, nx)."""
+    par = _lib.bm_travel_params()
+    par.extent[:] = [int(shape[2]), int(shape[1]), int(shape[0])]
+    out = C.c_size_t(0)
+    check(_lib.load().bm_travel_workspace_bytes(C.byref(par), C.byref(out)))
+    return int(out.value)
+
+
+def host_travel_field(volume, seeds, max_steps=0):
+    """bm_host_travel_field (host only, no device): the least number of face steps from any accepted seed to every voxel of a dense volume
+    [z, y, x] (uint8 or bool numpy array, non-zero = blocked; a slice of a larger array works as long as x is contiguous) through voxels
+    that are not blocked, as a plain breadth-first search.  seeds: [n, 3] of (x, y, z); max_steps: 0 = no limit.  Returns (field, record):
+    an int32 array [z, y, x] (TRAVEL_NONE where blocked, unreachable or beyond max_steps) and a TRAVEL_RESULT_DTYPE record."""
+    par, ptr, cuda = _travel_params(volume, max_steps)
+    assert not cuda
+    if min(volume.shape) == 0:
+        raise ValueError(f"host_travel_field: a volume with positive extents expected, got shape {tuple(volume.shape)}")
+    pts = _points(seeds, "host_travel_field")
+    field = np.zeros(tuple(volume.shape), np.int32)
+    res = _lib.bm_travel_result()
+    check(_lib.load().bm_host_travel_field(C.byref(par), C.c_void_p(ptr), C.c_void_p(pts.ctypes.data if len(pts) else None), len(pts), C.c_void_p(field.ctypes.data), C.byref(res)))
+    rec = np.zeros((), TRAVEL_RESULT_DTYPE)
+    rec["reached"], rec["farthest"], rec["seeds_rejected"], rec["farthest_at"] = res.reached, res.farthest, res.seeds_rejected, res.farthest_at
+    return field, rec
+
+
+def host_travel_paths(field, starts, capacity):
+    """bm_host_travel_paths (host only): walks down an int32 / uint32 field [z, y, x] from every start ([n, 3] of (x, y, z)).  Returns
+    (path, lengths): int32 [n, capacity, 3], of which the first min(length, capacity) voxels of every path are written (the rest is -1),
+    and int32 [n]: T(start) + 1, 0 for a start outside the volume or without a finite value, -1 where the field is not a travel field."""
+    field = np.ascontiguousarray(field)
+    if field.dtype not in (np.dtype(np.int32), np.dtype(np.uint32)) or field.ndim != 3:
+        raise ValueError(f"host_travel_paths: an int32 or uint32 field [z, y, x] expected, got {field.dtype} {field.shape}")
+    pts = _points(starts, "host_travel_paths")
+    capacity = int(capacity)
+    path = np.full((len(pts), max(capacity, 0), 3), -1, np.int32)
+    lengths = np.zeros(len(pts), np.int32)
+    extent = (C.c_int32 * 3)(field.shape[2], field.shape[1], field.shape[0])
+    check(_lib.load().bm_host_travel_paths(extent, C.c_void_p(field.ctypes.data), C.c_void_p(pts.ctypes.data if len(pts) else None), len(pts), capacity,
+                                           C.c_void_p(path.ctypes.data if path.size else None), C.c_void_p(lengths.ctypes.data if len(pts) else None)))
+    return path, lengths
+
+
+class TravelField:
+    """The field of a Scene.travel_field: `field` is the int32 tensor [z, y, x] on the device (TRAVEL_NONE where blocked, unreachable or
+    beyond max_steps) and `result` the bm_travel_result there (four int64 words).  The field stands when travel_field returns.  record (a
+    TRAVEL_RESULT_DTYPE scalar) and path() copy to the host, which waits; paths() stays on the device."""
+
+    def __init__(self, scene, field, result):
+        self.scene, self.field, self.result = scene, field, result
+        self._record = None
+
+    @property
+    def record(self):
+        if self._record is None:
+            self._record = self.result.cpu().numpy().view(TRAVEL_RESULT_DTYPE).reshape(())
+        return self._record
+
+    reached = property(lambda self: int(self.record["reached"]))
+
+    def paths(self, starts, capacity, stream=None):
+        """bm_travel_paths: from every start ([n, 3] of (x, y, z) in the volume's coordinates; a list, a numpy array or an int32 tensor on
+        the scene's GPU) down the field.  Returns (path, lengths), int32 tensors [n, capacity, 3] and [n] on the device: the first
+        min(length, capacity) voxels of every path, the start first (the rest is -1); lengths as in host_travel_paths.  The host does not
+        wait."""
+        import torch
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError(f"paths: a capacity of at least 1 expected, got {capacity}")
+        dev = self.field.device
+        if not (hasattr(starts, "is_cuda") and starts.is_cuda):
+            starts = torch.from_numpy(_points(starts, "paths")).to(dev)
+        if starts.dtype != torch.int32 or starts.dim() != 2 or starts.shape[1] != 3 or not starts.is_contiguous():
+            raise ValueError("paths: starts must be a contiguous int32 tensor [n, 3]")
+        n = int(starts.shape[0])
+        current, target = self.scene._volume_stream(self.field, stream)
+        with torch.cuda.stream(target):
+            path = torch.full((n, capacity, 3), -1, dtype=torch.int32, device=dev)
+            lengths = torch.zeros(n, dtype=torch.int32, device=dev)
+        if target.cuda_stream != current.cuda_stream:
+            for t in (self.field, starts, path, lengths):
+                t.record_stream(target)
+        nz, ny, nx = self.field.shape
+        extent = (C.c_int32 * 3)(nx, ny, nz)
+        check(self.scene._L.bm_travel_paths(self.scene.gpuScene, extent, C.c_void_p(self.field.data_ptr()), C.c_void_p(starts.data_ptr() if n else None), n, capacity,
+                                            C.c_void_p(path.data_ptr() if n else None), C.c_void_p(lengths.data_ptr() if n else None), C.c_void_p(target.cuda_stream)))
+        if target.cuda_stream != current.cuda_stream:
+            current.wait_stream(target)
+        return path, lengths
+
+    def path(self, start):
+        """The whole path from `start` (x, y, z) down to a seed: an int32 numpy array [length, 3], the start first; None when the start is
+        outside the volume or has no finite value.  Waits: the start's value is read first, and gives the capacity."""
+        x, y, z = (int(v) for v in start)
+        nz, ny, nx = self.field.shape
+        if not (0 <= x < nx and 0 <= y < ny and 0 <= z < nz):
+            return None
+        t = int(self.field[z, y, x].item())
+        if t == TRAVEL_NONE:
+            return None
+        path, lengths = self.paths([(x, y, z)], t + 1)
+        if int(lengths[0].item()) != t + 1:
+            raise RuntimeError("path: the field is not a travel field")
+        return path[0].cpu().numpy()
+
+
 # ---- ray queries (bm_scene_cast_rays): packed records, 32 bytes each
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("tmax", "<f4"), ("reserved", "<u4")])   # bm_ray
 RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("normal", "<f4", 3), ("voxel", "<i4", 3), ("level", "<i4")])  # bm_ray_hit
@@ -1481,6 +1620,101 @@ class Scene:
         D <= radius_sq, write_region with op "clear".  As for grow the margin covers the radius, and beyond the world's border counts as
         empty, so solid voxels at the border erode.  Returns the number of voxels changed."""
         return self._morph("shrink", lo, hi, radius_sq, "empty", "clear", stream)
+
+    # ---- voxels + seeds -> shortest face-step distances (bm_travel_field): the scene only names the GPU; nothing of the world is read
+    def _travel_field(self, volume, seeds, max_steps, out, stream, times, batch=0):
+        import torch
+        if not hasattr(volume, "is_cuda") or not volume.is_cuda:
+            raise ValueError("travel_field: volume must be a uint8 or bool tensor [z, y, x] on the scene's GPU")
+        par, ptr, _ = _travel_params(volume, max_steps)
+        if min(volume.shape) == 0:
+            raise ValueError(f"travel_field: a volume with positive extents expected, got shape {tuple(volume.shape)}")
+        dev = volume.device
+        shape = tuple(int(v) for v in volume.shape)
+        if out is not None and (not hasattr(out, "is_cuda") or not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"travel_field: out must be a contiguous int32 tensor of shape {shape} on the scene's GPU")
+        current, target = self._volume_stream(volume, stream)
+        with torch.cuda.stream(target):
+            if not (hasattr(seeds, "is_cuda") and seeds.is_cuda):
+                seeds = torch.from_numpy(_points(seeds, "travel_field")).to(dev)
+            if seeds.dtype != torch.int32 or seeds.dim() != 2 or seeds.shape[1] != 3 or not seeds.is_contiguous():
+                raise ValueError("travel_field: seeds must be a contiguous int32 tensor [n, 3]")
+            if out is None:
+                out = torch.empty(shape, dtype=torch.int32, device=dev)
+            ws = torch.empty(travel_workspace_bytes(shape), dtype=torch.uint8, device=dev)
+            result = torch.empty(4, dtype=torch.int64, device=dev)
+        n = int(seeds.shape[0])
+        if target.cuda_stream != current.cuda_stream:
+            for t in (volume, seeds, out):
+                t.record_stream(target)
+        args = (self.gpuScene, C.byref(par), C.c_void_p(ptr), C.c_void_p(seeds.data_ptr() if n else None), n, C.c_void_p(out.data_ptr()), C.c_void_p(result.data_ptr()),
+                C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(target.cuda_stream))
+        info = None
+        if times:
+            ms, counts = (C.c_float * 3)(), (C.c_uint32 * 2)()
+            check(self._L.bm_debug_travel_times(*args, int(batch), ms, counts))
+            info = ([float(v) for v in ms], int(counts[0]), int(counts[1]))
+        else:
+            check(self._L.bm_travel_field(*args))
+        if target.cuda_stream != current.cuda_stream:
+            current.wait_stream(target)
+        return TravelField(self, out, result), info
+
+    def travel_field(self, volume, seeds, max_steps=0, out=None, stream=None):
+        """bm_travel_field: the least number of face steps from any accepted seed to every voxel of a dense volume
+        [z, y, x] -- a uint8 or bool tensor on the scene's GPU, non-zero = blocked, strides as in write_region -- through voxels that are
+        not blocked.  seeds: [n, 3] of (x, y, z) in the volume's coordinates (a list, a numpy array or an int32 tensor on the GPU); a seed
+        outside the volume or on a blocked voxel is counted and ignored.  max_steps: 0 = no limit.  out: a contiguous int32 tensor of the
+        volume's shape to fill.  Returns a TravelField: .field (int32 [z, y, x], TRAVEL_NONE where there is no value), .record,
+        .paths(starts, capacity) and .path(start).  Unlike its siblings the call returns when the field stands: it waits on the stream
+        between batches of rounds.  Stream handling as in write_region; the workspace (76 bytes per 8^3 tile) comes from torch's pool."""
+        return self._travel_field(volume, seeds, max_steps, out, stream, False)[0]
+
+    def travel_field_times(self, volume, seeds, max_steps=0, out=None, stream=None, batch=0):
+        """bm_debug_travel_times: Scene.travel_field with a hipEvent between its stages and `batch` rounds between two looks of the host
+        (0 = the default).  Returns (TravelField, ([ms of the set-up, the rounds, the finish], rounds, looks))."""
+        return self._travel_field(volume, seeds, max_steps, out, stream, True, batch)
+
+    def _blocked_box(self, name, lo, hi, clearance_sq, stream):
+        import math
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        clearance_sq = int(clearance_sq)
+        if any(h <= l for l, h in zip(lo, hi)):
+            raise ValueError(f"{name}: an empty box ({lo} ... {hi})")
+        if clearance_sq < 0 or clearance_sq > 3 * 16383 * 16383:
+            raise ValueError(f"{name}: clearance_sq, an integer in 0 ... 3 * 16383^2, expected, got {clearance_sq}")
+        if clearance_sq == 0:
+            return self.read_region(lo, hi, device=True, stream=stream)
+        m = math.isqrt(clearance_sq - 1) + 1  # ceil(sqrt(clearance_sq))
+        volume = self.read_region([v - m for v in lo], [v + m for v in hi], device=True, stream=stream)
+        return self.distance_field(volume, to="solid", stream=stream).mask(clearance_sq - 1, stream=stream)[(slice(m, -m),) * 3]
+
+    def reach(self, lo, hi, seeds, clearance_sq=0, max_steps=0, stream=None):
+        """How many face steps every voxel of the box lo <= v < hi (x, y, z) of the live scene is from the nearest of `seeds` ([n, 3] WORLD
+        voxels) without leaving the box: read_region(lo, hi, device=True), then travel_field.  With clearance_sq >= 1 a voxel is blocked
+        when a solid voxel lies closer than that squared distance -- where an agent of that squared radius does not fit: the distance to
+        solid of the box enlarged by ceil(sqrt(clearance_sq)) (read_region gives 0 outside the world, as for grow), masked at
+        clearance_sq - 1 and cut back to the box.  Returns a TravelField in the box's coordinates (voxel - lo)."""
+        blocked = self._blocked_box("reach", lo, hi, clearance_sq, stream)
+        pts = _points(seeds, "reach") - np.asarray([int(v) for v in lo], np.int32)
+        return self.travel_field(blocked, pts, max_steps=max_steps, stream=stream)
+
+    def find_path(self, start, goal, lo=None, hi=None, clearance_sq=0, max_steps=0, stream=None):
+        """A shortest face-step path from world voxel `start` to world voxel `goal` inside the box lo <= v < hi (default: the bounding box
+        of the two enlarged by 32 and clipped to the world): reach() seeded at the goal, then the walk down from the start.  Returns an
+        int32 numpy array [length, 3] of world voxels, the start first and the goal last, or None when there is no path (within
+        max_steps).  Ordered like a query: it sees every edit issued before.  The host waits."""
+        start, goal = [int(v) for v in start], [int(v) for v in goal]
+        world = (self.grid_size, self.grid_size, self.grid_height)
+        if lo is None:
+            lo = [max(min(s, g) - 32, 0) for s, g in zip(start, goal)]
+        if hi is None:
+            hi = [min(max(s, g) + 33, w) for s, g, w in zip(start, goal, world)]
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        if any(h <= l for l, h in zip(lo, hi)):
+            return None
+        path = self.reach(lo, hi, [goal], clearance_sq, max_steps, stream).path([s - l for s, l in zip(start, lo)])
+        return None if path is None else path + np.asarray(lo, np.int32)
 
     # ---- ray queries (bm_scene_cast_rays): issued like a frame -- after every edit and upload issued before, asynchronous to the host
     def cast_rays_raw(self, n, rays_ptr, hits_ptr, flags=0, lod_origin=None, stream=None):

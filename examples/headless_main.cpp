@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--path x0,y0,z0:x1,y1,z1] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -16,6 +16,9 @@
 // --grow x0,y0,z0:x1,y1,z1=r2 and --shrink x0,y0,z0:x1,y1,z1=r2, applied after --dig (grow first): the world inside that box is dilated or
 // eroded with a Euclidean ball of squared radius r2 -- the exact distance field of the box and a margin on the GPU, thresholded and written
 // back (Scene::grow, Scene::shrink); prints how many voxels changed.
+// --path x0,y0,z0:x1,y1,z1, applied after --dig, --grow and --shrink: a shortest face-step path through the empty voxels from the first
+// voxel to the second, by the exact travel field of their surroundings on the GPU (Scene::find_path); prints "path of N voxels:" and the
+// voxels, or "no path".
 // --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig and --shrink: the pieces of that box that hang on nothing -- connected components by faces,
 // inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
 // and voxels went.
@@ -54,6 +57,8 @@ int main(int argc_in, char** argv_in) {
 	int ground[2] = {-1, -1};
 	int morph_lo[2][3] = {{0, 0, 0}, {0, 0, 0}}, morph_hi[2][3] = {{0, 0, 0}, {0, 0, 0}}; // [0]: --grow, [1]: --shrink
 	int morph_r2[2] = {0, 0};
+	int path_ends[2][3] = {{0, 0, 0}, {0, 0, 0}};
+	bool path = false;
 	const char* voxels_path = nullptr;
 	bool denoise = false, temporal = false;
 	std::string paste_path;
@@ -132,6 +137,14 @@ int main(int argc_in, char** argv_in) {
 			drop = true;
 			continue;
 		}
+		if (std::string(argv_in[i]) == "--path" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d,%d:%d,%d,%d", &path_ends[0][0], &path_ends[0][1], &path_ends[0][2], &path_ends[1][0], &path_ends[1][1], &path_ends[1][2]) != 6) {
+				std::cerr << "--path wants x0,y0,z0:x1,y1,z1\n";
+				return 2;
+			}
+			path = true;
+			continue;
+		}
 		if ((std::string(argv_in[i]) == "--grow" || std::string(argv_in[i]) == "--shrink") && i + 1 < argc_in) {
 			const int k = std::string(argv_in[i]) == "--shrink" ? 1 : 0;
 			int* lo = morph_lo[k];
@@ -205,6 +218,15 @@ int main(int argc_in, char** argv_in) {
 	if (dig[3] >= 0) scene.carve_sphere(dig, dig[3]);
 	if (morph_r2[0] > 0) std::printf("grew %llu voxels\n", static_cast<unsigned long long>(scene.grow(morph_lo[0], morph_hi[0], static_cast<uint32_t>(morph_r2[0]))));
 	if (morph_r2[1] > 0) std::printf("shrank %llu voxels\n", static_cast<unsigned long long>(scene.shrink(morph_lo[1], morph_hi[1], static_cast<uint32_t>(morph_r2[1]))));
+	if (path) {
+		const auto voxels = scene.find_path(path_ends[0], path_ends[1]);
+		if (voxels.empty()) std::printf("no path\n");
+		else {
+			std::printf("path of %zu voxels:", voxels.size());
+			for (const auto& v : voxels) std::printf(" %d,%d,%d", v[0], v[1], v[2]);
+			std::printf("\n");
+		}
+	}
 	if (drop) {
 		const Scene::Removed gone = scene.remove_floating(drop_lo, drop_hi);
 		std::printf("dropped %llu floating pieces, %llu voxels\n", static_cast<unsigned long long>(gone.pieces), static_cast<unsigned long long>(gone.voxels));

@@ -728,6 +728,69 @@ BM_API int bm_debug_distance_times(bm_scene* scene, const bm_distance_params* pa
 BM_API int bm_host_distance_field(const bm_distance_params* params, const uint8_t* volume, uint32_t* dist, bm_distance_result* result);
 BM_API int bm_host_distance_mask(uint64_t count, const uint32_t* dist, uint32_t limit_sq, uint32_t flags, uint8_t* volume_out);
 
+/* ---- voxels + seeds -> exact shortest face-step distances and paths (no reference counterpart).  A dense byte volume V[z][y][x] in device
+ * memory (any non-zero byte is blocked; x contiguous, rows and slices at the given pitches, 0 = tight; any base alignment; extents and
+ * voxel limit those of bm_distance_params) and n >= 0 seeds, int32 seeds[n][3] = (x, y, z) in device memory (the pointer may be null when
+ * n is 0), give a tight uint32_t field T[z][y][x], 4-byte aligned.  All integers, and a breadth-first distance is unique: the same bytes
+ * on every run whatever order anything ran in, and bm_travel_field == bm_host_travel_field byte for byte (csrc/travel.h holds the rules
+ * once).
+ *  - T(p) = the least number of face steps (6-neighbourhood, inside the volume only) from any accepted seed to p through voxels that are
+ *    not blocked, or BM_TRAVEL_NONE = 0x7FFFFFFF when p is blocked or unreachable -- and, with max_steps != 0, when p is farther than
+ *    max_steps.  max_steps == 0 means no limit.  Every finite value is below 2^31 - 2: the field reads as non-negative int32.
+ *  - Seeds.  A seed is accepted when it lies inside the volume on a voxel that is not blocked; the others are counted.  Duplicates are
+ *    fine.  An accepted seed has T = 0.
+ *  - Result (32 bytes on the device, 8-byte aligned): reached = the voxels with a finite value; farthest = the largest finite value,
+ *    BM_TRAVEL_NONE when none is finite; seeds_rejected; farthest_at = the lowest linear index (z ny + y) nx + x that holds `farthest`, 0
+ *    when there is none; the rest 0.
+ *  - Waiting.  Unlike the other operators bm_travel_field RETURNS WHEN THE FIELD STANDS: it enqueues rounds of relaxation in batches on
+ *    hip_stream and between batches waits on that stream for one word, the number of tiles still listed.  It therefore cannot be captured
+ *    into a graph.  bm_travel_paths is asynchronous on hip_stream like everything else.
+ *  - Paths.  bm_travel_paths takes a field, n >= 0 starts (int32 starts[n][3]), a per-path capacity >= 1, int32 path[n][capacity][3] and
+ *    int32 lengths[n].  lengths[q] = T(start) + 1, the voxels of the path with both ends, or 0 when the start is outside the volume or has
+ *    no finite value.  The first min(length, capacity) voxels are written: they begin at the start and descend -- from p the next voxel is
+ *    the first neighbour in the order -x, +x, -y, +y, -z, +z that lies inside the volume and holds T(p) - 1 -- so a truncated path still
+ *    gives an agent its next steps, and a full one ends on a seed.  If no neighbour qualifies the field was not made by bm_travel_field:
+ *    the walk stops and lengths[q] = -1.  The loop is bounded by T(start) and by capacity.
+ *  - Refusals, BM_EINVAL with nothing launched and nothing written: an extent below 1 or above 16384; more than 2^31 - 2 voxels; a pitch
+ *    below the extent it spans or a volume spanning more than 2^46 bytes; a span or any other buffer that does not lie inside one
+ *    allocation of the scene's device; a null pointer; a field, seeds, starts, path or lengths not 4-byte, a result not 8-byte or a
+ *    workspace not 16-byte aligned; a workspace below bm_travel_workspace_bytes; a workspace that overlaps the volume, the seeds, the field
+ *    or the result; a field that overlaps the volume, the seeds or the result; an unknown flag bit (none is defined) or a non-zero
+ *    `reserved`; a negative n or one above 2^31 - 1; a capacity below 1; more than 2^40 path voxels (n * capacity); a path or lengths buffer that overlaps the field or the starts. */
+#define BM_TRAVEL_NONE 0x7FFFFFFFu
+typedef struct bm_travel_params {
+	int32_t extent[3];   /* nx, ny, nz: 1 ... 16384 */
+	uint32_t max_steps;  /* 0 = no limit */
+	int64_t row_pitch;   /* bytes from one x-row to the next y; 0 = tight (nx) */
+	int64_t slice_pitch; /* bytes from one z-slice to the next; 0 = tight (row_pitch * ny) */
+	uint32_t flags;      /* 0 */
+	uint32_t reserved;   /* 0 */
+} bm_travel_params;
+typedef struct bm_travel_result {
+	uint64_t reached;
+	uint32_t farthest, seeds_rejected;
+	uint64_t farthest_at;
+	uint64_t reserved;
+} bm_travel_result;
+/* bytes of device memory bm_travel_field needs beside its buffers: per 8^3 tile 64 bytes of blocked bits, a round stamp and two work-list
+ * entries (each part rounded up to 16), plus 64 */
+BM_API int bm_travel_workspace_bytes(const bm_travel_params* params, size_t* bytes);
+/* the buffers and the workspace are the caller's, nothing is allocated on the device and the scene keeps no state (the scene names the
+ * device).  Nothing of the world is read.  Returns when the field and the result stand (see Waiting). */
+BM_API int bm_travel_field(bm_scene* scene, const bm_travel_params* params, const uint8_t* volume_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev,
+                           bm_travel_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+BM_API int bm_travel_paths(bm_scene* scene, const int32_t extent[3], const uint32_t* field_dev, const int32_t* starts_dev, int64_t n, int32_t capacity, int32_t* path_dev,
+                           int32_t* lengths_dev, void* hip_stream);
+/* measuring door: bm_travel_field with a hipEvent between its stages and `batch` rounds between two looks of the host (0 = the default);
+ * stage_ms[0 ... 2] = the durations in ms of the set-up (fill, bit bricks, seeds), the rounds and the finish; counts[0] = the rounds
+ * enqueued, counts[1] = the looks of the host */
+BM_API int bm_debug_travel_times(bm_scene* scene, const bm_travel_params* params, const uint8_t* volume_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev,
+                                 bm_travel_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, uint32_t batch, float* stage_ms,
+                                 uint32_t* counts);
+/* the same on host memory, as plain loops (csrc/travel_host.cpp; no device needed); the refusals that concern params, n, capacity and null pointers */
+BM_API int bm_host_travel_field(const bm_travel_params* params, const uint8_t* volume, const int32_t* seeds, int64_t n, uint32_t* field, bm_travel_result* result);
+BM_API int bm_host_travel_paths(const int32_t extent[3], const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path, int32_t* lengths);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

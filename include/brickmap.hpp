@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <thread>
+#include <array>
 #include <vector>
 
 #include "brickmap.h"
@@ -471,6 +472,80 @@ public:
 	// empty.  Returns the number of voxels changed.  The host waits.
 	uint64_t grow(const int lo[3], const int hi[3], uint32_t radius_sq) { return morph(lo, hi, radius_sq, false); }
 	uint64_t shrink(const int lo[3], const int hi[3], uint32_t radius_sq) { return morph(lo, hi, radius_sq, true); }
+
+	// voxels + seeds -> exact shortest face-step distances (no counterpart in the reference; bm_travel_field): the byte volume of `params` in
+	// device memory (non-zero = blocked) and n seeds (x, y, z) there give the tight field field_dev and the record result_dev;
+	// workspace_dev: travel_workspace_bytes() bytes of the caller's.  Returns when the field stands.
+	static size_t travel_workspace_bytes(const bm_travel_params& params) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_travel_workspace_bytes(&params, &bytes));
+		return bytes;
+	}
+	void travel_field(const bm_travel_params& params, const uint8_t* volume_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev, bm_travel_result* result_dev,
+					  void* workspace_dev, size_t workspace_bytes, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_travel_field(gpuScene.handle, &params, volume_dev, seeds_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, hip_stream));
+	}
+	// n starts -> the first `capacity` voxels of every path down the field and the paths' lengths (bm_travel_paths); asynchronous
+	void travel_paths(const int32_t extent[3], const uint32_t* field_dev, const int32_t* starts_dev, int64_t n, int32_t capacity, int32_t* path_dev, int32_t* lengths_dev,
+					  void* hip_stream = nullptr) {
+		BM_CHECKED(bm_travel_paths(gpuScene.handle, extent, field_dev, starts_dev, n, capacity, path_dev, lengths_dev, hip_stream));
+	}
+	// A shortest face-step path through the empty voxels of the live scene from world voxel `start` to world voxel `goal`, inside the
+	// bounding box of the two enlarged by 32 and clipped to the world: the box is read on the device (read_region), the travel field is
+	// seeded at the goal, and the walk goes down from the start.  Returns the path's world voxels (x, y, z), the start first and the goal
+	// last; empty when there is no path (within max_steps, 0 = no limit).  The host waits.
+	std::vector<std::array<int, 3>> find_path(const int start[3], const int goal[3], uint32_t max_steps = 0) {
+		std::vector<std::array<int, 3>> out;
+		bm_scene_info info;
+		BM_CHECKED(bm_scene_get_info(gpuScene.handle, &info));
+		const int world[3] = {info.grid_size, info.grid_size, info.grid_height};
+		int lo[3], hi[3];
+		int32_t ends[6]; // the goal (the seed), then the start, in the box's coordinates
+		bm_travel_params p{};
+		for (int a = 0; a < 3; ++a) {
+			const int mn = start[a] < goal[a] ? start[a] : goal[a], mx = start[a] < goal[a] ? goal[a] : start[a];
+			lo[a] = mn - 32 > 0 ? mn - 32 : 0;
+			hi[a] = mx + 33 < world[a] ? mx + 33 : world[a];
+			if (hi[a] <= lo[a]) return out;
+			p.extent[a] = hi[a] - lo[a];
+			ends[a] = goal[a] - lo[a];
+			ends[3 + a] = start[a] - lo[a];
+		}
+		p.max_steps = max_steps;
+		const size_t voxels = Region(lo, hi).voxels(), ws_bytes = travel_workspace_bytes(p);
+		const size_t at_ends = 32, at_len = at_ends + 32, at_ws = at_len + 16, at_field = at_ws + ws_bytes, at_vol = at_field + voxels * 4;
+		void* buf = nullptr; // the result, the two ends, the path's length, the workspace, the field, then the volume
+		BM_CHECKED(bm_buffer_alloc(device_, at_vol + voxels, &buf));
+		char* base = static_cast<char*>(buf);
+		void* path_buf = nullptr;
+		try {
+			BM_CHECKED(bm_buffer_write(device_, base + at_ends, ends, sizeof ends));
+			read_region(Region(lo, hi), reinterpret_cast<uint8_t*>(base + at_vol), BM_VOXELS_DEVICE);
+			uint32_t* field = reinterpret_cast<uint32_t*>(base + at_field);
+			travel_field(p, reinterpret_cast<const uint8_t*>(base + at_vol), reinterpret_cast<const int32_t*>(base + at_ends), 1, field, reinterpret_cast<bm_travel_result*>(base),
+						 base + at_ws, ws_bytes);
+			const bool inside = ends[3] >= 0 && ends[4] >= 0 && ends[5] >= 0 && ends[3] < p.extent[0] && ends[4] < p.extent[1] && ends[5] < p.extent[2];
+			uint32_t t = BM_TRAVEL_NONE;
+			if (inside) BM_CHECKED(bm_buffer_read(device_, &t, field + (static_cast<size_t>(ends[5]) * p.extent[1] + ends[4]) * p.extent[0] + ends[3], sizeof t));
+			if (t != BM_TRAVEL_NONE) {
+				const int32_t capacity = static_cast<int32_t>(t) + 1;
+				BM_CHECKED(bm_buffer_alloc(device_, static_cast<size_t>(capacity) * 12, &path_buf));
+				travel_paths(p.extent, field, reinterpret_cast<const int32_t*>(base + at_ends) + 3, 1, capacity, static_cast<int32_t*>(path_buf),
+							 reinterpret_cast<int32_t*>(base + at_len));
+				std::vector<int32_t> host(static_cast<size_t>(capacity) * 3);
+				BM_CHECKED(bm_buffer_read(device_, host.data(), path_buf, host.size() * 4)); // (waits for the device)
+				out.resize(static_cast<size_t>(capacity));
+				for (size_t k = 0; k < out.size(); ++k) out[k] = {host[3 * k] + lo[0], host[3 * k + 1] + lo[1], host[3 * k + 2] + lo[2]};
+			}
+		} catch (...) {
+			if (path_buf) (void)bm_buffer_free(device_, path_buf);
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		if (path_buf) BM_CHECKED(bm_buffer_free(device_, path_buf));
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return out;
+	}
 
 private:
 	uint64_t morph(const int lo[3], const int hi[3], uint32_t radius_sq, bool erode) {
