@@ -29,6 +29,46 @@ BM_JHD int step_pick(const StepAxis& m, int sx, int sy, int sz) { return m.x ? s
 // `t += mask ? delta : 0` is the reference's `tmax += mask * tdelta` for finite deltas
 BM_JHD float step_add(float t, float d, bool mask) { return t + (mask ? d : 0.f); }
 
+// ---- the pair move: two single moves whose cube-field bytes are in flight together.  Where a walk goes depends on tmax and tdelta alone;
+// the byte of a cell decides whether the lane stops there, not where the next cell is.  So the address of the cell after next is known
+// before the first byte is back, and one wait serves both loads:
+//     step_pair_ahead    move 1 in full (the arithmetic of one plain move) and, from the new tmax, move 2's axis, increment and cell
+//     (the caller loads the bytes of `p` and of `StepAhead::p`, and reads the first: field_state)
+//     step_pair_commit   for a lane that move 1 left ST_OUTER (go): move 2 becomes the lane's state, by the plain move's own operations
+// A lane that stops at cell 1 drops the second byte and nothing of it needs rolling back: move 2 lives in the StepAhead until committed.
+// The same cells in the same order, the same tmax bits and the same last_step as two plain moves, for any fp32 input
+// (tests/step_pair_check.cpp); the cell looked at and not committed may lie one increment outside the planes (field_layout.h).
+struct StepAhead {
+	StepAxis m;  // move 2's axis
+	int step;    // ... its increment
+	uint32_t p;  // ... and the cell it reaches
+};
+BM_JHD StepAhead step_pair_ahead(float& tx, float& ty, float& tz, float dx, float dy, float dz, uint32_t& p, int& last_step, int sx, int sy, int sz) {
+	const StepAxis m = step_choose(tx, ty, tz);
+	const int step = step_pick(m, sx, sy, sz);
+	p += static_cast<uint32_t>(step);
+	last_step = step;
+	tx = step_add(tx, dx, m.x);
+	ty = step_add(ty, dy, m.y);
+	tz = step_add(tz, dz, m.z);
+	StepAhead a;
+	a.m = step_choose(tx, ty, tz);
+	a.step = step_pick(a.m, sx, sy, sz);
+	a.p = p + static_cast<uint32_t>(a.step);
+	return a;
+}
+// go: the lane commits (false: nothing changes).  Cell and increment by select, written in place; tmax only where the lane goes on -- a lane
+// that stops keeps the very bits move 1 left it (`t + 0` is not the identity for every fp32 value).
+BM_JHD void step_pair_commit(float& tx, float& ty, float& tz, float dx, float dy, float dz, uint32_t& p, int& last_step, const StepAhead& a, bool go) {
+	p = go ? a.p : p;
+	last_step = go ? a.step : last_step;
+	if (go) {
+		tx = step_add(tx, dx, a.m.x);
+		ty = step_add(ty, dy, a.m.y);
+		tz = step_add(tz, dz, a.m.z);
+	}
+}
+
 // ---- the cell of the brick walk (N = 8: the 8^3 bitmask of a brick; N = 2: the 2^3 LoD mask of the index word), ONE register:
 //     bits 5 ...        the voxel's linear index  v = x + N*y + N*N*z  (9 bits for N = 8, 3 for N = 2)
 //     bits 15-19, 20-24, 25-29   guard copies of the coordinates, each as (coordinate + 8)

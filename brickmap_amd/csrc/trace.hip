@@ -139,6 +139,12 @@ enum : int { ST_IDLE = 4, ST_CONN = 5 };
 #ifndef BM_STEPS_PER_ROUND
 #define BM_STEPS_PER_ROUND 4
 #endif
+// moves per iteration of a single-move round: 1 = a move, its byte, a wait, four times over; 2 = two pair moves (steps.h step_pair_ahead),
+// each with the bytes of both its cells in flight during one wait.  The queue kernels and the ray queries keep 1 (traverse.h walk_round).
+#ifndef BM_STEP_AHEAD
+#define BM_STEP_AHEAD 2
+#endif
+static_assert(BM_STEPS_PER_ROUND % BM_STEP_AHEAD == 0, "a round is a whole number of pair moves");
 // -DBM_PHASE_TIMING: profiling build in which the plain kernel also reports the scheduler statistics
 // -DBM_ISA_MARKERS: comment lines in the compiler's .s output at the boundaries of the scheduler's passes (tools/isa_passes.py
 // turns them into the per-pass instruction table of profiles/); a listing aid only -- the product is built without them
@@ -802,13 +808,16 @@ __global__ __launch_bounds__(256, DBG ? 2 : BM_WAVES_PER_SIMD) void trace_paths(
 				}
 			} else {
 				BM_REGION("A.single");
+				// BM_STEP_AHEAD moves per iteration (2: the pair move of steps.h -- the second cell's byte is loaded with the first's, one wait
+				// for both); runsA / lanesA keep counting moves and the lanes that made them
 #pragma unroll 1
-				for (int k = 0; k < BM_STEPS_PER_ROUND; ++k) {
-					if (BM_TIMED) { runsA++; lanesA += __popcll(__ballot(state == ST_OUTER)); }
+				for (int k = 0; k < BM_STEPS_PER_ROUND; k += BM_STEP_AHEAD) {
+					int moves = 0;
 					if (state == ST_OUTER) {
-						const int st = field_step<DBG, true>(sc, r, tally);
+						const int st = field_step<DBG, true, BM_STEP_AHEAD>(sc, r, tally, BM_TIMED ? &moves : nullptr);
 						state = (st == ST_NEED && pstate != P_EXT_DONE) ? ST_CONN : st;
 					}
+					if (BM_TIMED) { runsA += BM_STEP_AHEAD; lanesA += __popcll(__ballot(moves >= 1)) + __popcll(__ballot(moves >= 2)); }
 				}
 			}
 		}

@@ -278,13 +278,18 @@ __device__ __forceinline__ uint32_t field_index(const DeviceScene& sc, const Ray
 // WORTH: the lookup applies jump_worth (steps.h) -- the fused kernel's.  The queue kernels (wavefront.hip) and the ray queries
 // (query.hip) share this code and keep the rule off: their rays do not start together from one origin, and their walks were not
 // measured with it (profiles/r17_jump_room.txt section 7).
+// (field_byte_state: what the byte `v` of the current cell means at the current tmax)
 template <bool WORTH = false>
-__device__ __forceinline__ int field_lookup(const DeviceScene& sc, RayState& r) {
-	const uint32_t v = sc.cube_field[field_index(sc, r)];
+__device__ __forceinline__ int field_byte_state(uint32_t v, RayState& r) {
 	const uint32_t m = __float_as_uint(fminf(fminf(r.tx, r.ty), r.tz)); // jump_possible() / jump_worth(): one minimum, two range tests
 	const bool possible = m - kJumpMinBits < kJumpMaxBits - kJumpMinBits;
 	const bool worth = !(WORTH && kJumpWorthBits != kJumpMinBits) || jump_worth_bits(m);
 	return field_state(v, possible, r.cube, worth);
+}
+template <bool WORTH = false>
+__device__ __forceinline__ int field_lookup(const DeviceScene& sc, RayState& r) {
+	const uint32_t v = sc.cube_field[field_index(sc, r)];
+	return field_byte_state<WORTH>(v, r);
 }
 
 // voxel.cuh:249-258: one Amanatides-Woo move to the next cell.  Select-style (no per-axis branches); `t += mask ? delta : 0` is
@@ -301,11 +306,35 @@ __device__ __forceinline__ void step_advance(RayState& r) {
 	r.tz = step_add(tz, r.dz, m.z);
 }
 // ... then the new cell's byte
-template <bool DBG, bool WORTH = false>
-__device__ __forceinline__ int field_step(const DeviceScene& sc, RayState& r, Tally& tally) {
-	step_advance(r);
-	const int st = field_lookup<WORTH>(sc, r);
+// AHEAD = 2: the pair move (steps.h) -- up to two moves, the bytes of both cells loaded before the one wait; the second is committed only
+// by a lane the first left ST_OUTER, which is the lane that would have taken it in the next iteration of the caller's loop.  *moves (where
+// asked for): how many the lane made.  The byte looked at and not used may lie in the guard bytes round the planes (field_layout.h).
+template <bool DBG, bool WORTH = false, int AHEAD = 1>
+__device__ __forceinline__ int field_step(const DeviceScene& sc, RayState& r, Tally& tally, int* moves = nullptr) {
+	static_assert(AHEAD == 1 || AHEAD == 2, "one move, or a pair");
+	if (AHEAD == 1) {
+		step_advance(r);
+		const int st = field_lookup<WORTH>(sc, r);
+		if (DBG && st != ST_NEED) tally.index_loads++;
+		if (moves) *moves = 1;
+		return st;
+	}
+	const int step_x = r.sx, step_y = r.stepy, step_z = r.stepz; // scalar copies, see step_advance
+	const StepAhead a = step_pair_ahead(r.tx, r.ty, r.tz, r.dx, r.dy, r.dz, r.p, r.last_step, step_x, step_y, step_z);
+	uint32_t v1 = sc.cube_field[r.p], v2 = sc.cube_field[a.p];
+	// both bytes are waited for HERE: left alone, the compiler moves the second load and everything it needs into the branch below, behind the
+	// wait for the first -- two plain moves again (an empty statement, no instruction)
+	asm volatile("" : "+v"(v1), "+v"(v2));
+	int st = field_byte_state<WORTH>(v1, r);
 	if (DBG && st != ST_NEED) tally.index_loads++;
+	if (moves) *moves = 1;
+	const bool go = st == ST_OUTER;
+	step_pair_commit(r.tx, r.ty, r.tz, r.dx, r.dy, r.dz, r.p, r.last_step, a, go);
+	if (go) {
+		st = field_byte_state<WORTH>(v2, r);
+		if (DBG && st != ST_NEED) tally.index_loads++; // committed cells only
+		if (moves) *moves = 2;
+	}
 	return st;
 }
 

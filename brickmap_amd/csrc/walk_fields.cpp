@@ -22,40 +22,29 @@ int BuildClock::stats(int device, uint64_t count, uint64_t* builds, float* last_
 	return 0;
 }
 
-WalkFields::Layout WalkFields::layout(const WorldDims& d) {
-	int shift = 2;
-	while ((1 << shift) < d.cells + 2) ++shift;
-	Layout l{};
-	l.shift = shift;
-	l.pxy = static_cast<uint64_t>(d.cells + 2) << shift;
-	l.plane = l.pxy * static_cast<uint64_t>(d.cells_height + 2);
-	l.fits = l.pxy < (1ull << 23) && l.plane * 8 < (1ull << 32);
-	l.ninth = BM_SUNFIELD != 0 && l.fits && l.plane * 9 < (1ull << 32);
-	l.tenth = BM_VIEWFIELD != 0 && l.ninth && l.plane * 10 < (1ull << 32);
-	return l;
-}
-
 int WalkFields::allocate(const WorldDims& d, DeviceScene* view) {
 	const Layout l = layout(d);
+	const size_t guard = field_guard_bytes(l); // before the first plane and behind the last: field_layout.h
 	if (!l.fits) { set_error("world too large for the 32-bit cube-field offsets of the walk"); return BM_EINVAL; }
 	// a ninth plane behind the eight is the sun plane of shadow rays and a tenth the view plane of primary rays, where they can be had: a scene
 	// without them renders as before, so doing without is no error -- neither HIP's slot nor ours keeps it
 	int planes = 8;
 	for (const int want : {l.tenth ? 10 : 0, l.ninth ? 9 : 0}) {
 		if (planes > 8 || !want) continue;
-		if (d_cube_field_.alloc(l.plane * want) == 0) planes = want;
+		if (d_field_alloc_.alloc(2 * guard + l.plane * want) == 0) planes = want;
 		else { (void)hipGetLastError(); set_error(""); }
 	}
-	if (planes == 8) { if (int e = d_cube_field_.alloc(l.plane * 8)) return e; }
+	if (planes == 8) { if (int e = d_field_alloc_.alloc(2 * guard + l.plane * 8)) return e; }
 	l_ = l;
+	guard_ = guard;
 	cells_ = d.cells; cells_height_ = d.cells_height; sg_xy_ = d.supergrid_xy;
 	book_.allocated(planes >= 9, planes == 10, d.cells, d.cells_height);
-	BM_HIP(hipMemset(d_cube_field_, 255, d_cube_field_.bytes()));
+	BM_HIP(hipMemset(d_field_alloc_, 255, d_field_alloc_.bytes())); // the guards too
 	view->cf_shift = l.shift;
 	view->cf_pxy = static_cast<uint32_t>(l.pxy);
 	view->cf_plane = static_cast<uint32_t>(l.plane);
 	division_magic(view->cf_pxy, &view->cf_magic, &view->cf_magic_shift);
-	view->cube_field = d_cube_field_;
+	view->cube_field = plane0(); // behind the head guard: every offset of the planes is what it was
 	// ... and the escape heights that go with it, with the slice of the shadow heights behind the octants' eight: zero = no dark cell
 	if (int e = d_escape_.alloc((escape_entries(view->cf_pxy) + (BM_SHADOWHEIGHT != 0 ? view->cf_pxy : 0u)) * sizeof(uint32_t))) return e;
 	BM_HIP(hipMemset(d_escape_, 0, d_escape_.bytes())); // (border and padding entries: never read, never written)
@@ -65,7 +54,7 @@ int WalkFields::allocate(const WorldDims& d, DeviceScene* view) {
 }
 
 void WalkFields::release() {
-	(void)d_cube_field_.release();
+	(void)d_field_alloc_.release();
 	book_.released();
 	(void)d_escape_.release();
 	(void)d_escape_cols_.release();
@@ -75,7 +64,7 @@ int WalkFields::upload(const uint8_t* field) {
 	const size_t X = static_cast<size_t>(cells_) + 2, Z = static_cast<size_t>(cells_height_) + 2;
 	// 8 planes x Z slices, each X rows of X bytes -> rows of 2^shift bytes (the padding is never read)
 	for (size_t o = 0; o < 8; ++o)
-		BM_HIP(hipMemcpy2D(d_cube_field_ + o * l_.plane, static_cast<size_t>(1) << l_.shift, field + o * X * X * Z, X, X, X * Z, hipMemcpyHostToDevice));
+		BM_HIP(hipMemcpy2D(plane0() + o * l_.plane, static_cast<size_t>(1) << l_.shift, field + o * X * X * Z, X, X, X * Z, hipMemcpyHostToDevice));
 	return 0;
 }
 
@@ -116,7 +105,7 @@ int WalkFields::update(const uint32_t* index_grid, const FieldChange& c, bool fi
 	book_.bits_changed(c.touch_lo, c.touch_hi);
 	if (!c.occupancy()) return 0;
 	if (field_pass) {
-		launch_field_update(index_grid, d_cube_field_, d_cf_tmp_, field_update_box(c.box_lo, c.box_hi), stream);
+		launch_field_update(index_grid, plane0(), d_cf_tmp_, field_update_box(c.box_lo, c.box_hi), stream);
 		BM_HIP(hipGetLastError());
 	}
 	// the columns of the cells whose occupancy changed, then the quadrant passes over the whole table
@@ -157,7 +146,7 @@ int WalkFields::prepare(FieldBook::SunStep* s, hipStream_t stream, bool* ready) 
 
 int WalkFields::build(const FieldBook::SunStep& s, const uint32_t* index_grid, const uint32_t* pool_base, const uint32_t* arena, hipStream_t stream) {
 	BM_HIP(hipEventRecord(sun_clock_[0], stream));
-	launch_sun_build(index_grid, pool_base, arena, d_escape_cols_, d_escape_, d_cube_field_, d_sun_tmp_, d_shadow_tmp_, sun_build(s), s.step == FieldBook::kBuildPlane, stream);
+	launch_sun_build(index_grid, pool_base, arena, d_escape_cols_, d_escape_, plane0(), d_sun_tmp_, d_shadow_tmp_, sun_build(s), s.step == FieldBook::kBuildPlane, stream);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(sun_clock_[1], stream));
 	book_.built(s);
@@ -169,7 +158,7 @@ int WalkFields::build(const FieldBook::ViewStep& v, hipStream_t stream) {
 	ViewBuild u = geometry<ViewBuild>();
 	u.plan = v.plan;
 	BM_HIP(hipEventRecord(view_clock_[0], stream));
-	launch_view_build(d_escape_, d_cube_field_, u, stream);
+	launch_view_build(d_escape_, plane0(), u, stream);
 	BM_HIP(hipGetLastError());
 	BM_HIP(hipEventRecord(view_clock_[1], stream));
 	book_.built(v);
@@ -184,7 +173,7 @@ int WalkFields::read_planes(const char* what, bool have, int first, int count, u
 	if (capacity < need) { set_error(std::string(what) + " buffer too small"); return BM_EINVAL; }
 	BM_HIP(hipSetDevice(device_));
 	BM_HIP(hipDeviceSynchronize());
-	BM_HIP(hipMemcpy2D(dst, X, d_cube_field_ + first * l_.plane, static_cast<size_t>(1) << l_.shift, X, count * X * Z, hipMemcpyDeviceToHost));
+	BM_HIP(hipMemcpy2D(dst, X, plane0() + first * l_.plane, static_cast<size_t>(1) << l_.shift, X, count * X * Z, hipMemcpyDeviceToHost));
 	return 0;
 }
 

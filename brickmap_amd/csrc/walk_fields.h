@@ -11,6 +11,7 @@
 #include "device_types.h"
 #include "error.h"
 #include "field_book.h"
+#include "field_layout.h"
 #include "hip_owned.h"
 #include "kernels.h"
 #include "world.h"
@@ -32,17 +33,13 @@ class WalkFields {
 public:
 	explicit WalkFields(int device) : device_(device) {}
 
-	// Device layout of the cube field: rows padded to a power of two (1 << shift bytes), pxy = bytes of a slice, plane = bytes of one plane.  The walk
-	// keeps a ray's cell as ONE 32-bit byte offset into the planes and steps slices with 23-bit immediates (traverse.h cell_offset).
-	struct Layout {
-		int shift;
-		uint64_t pxy, plane;
-		bool fits, ninth, tenth; // the eight octant planes' offsets fit / the sun plane's as well / and the view plane's, behind it
-	};
-	static Layout layout(const WorldDims& d);
+	// Device layout of the cube field and the guard bytes round it: field_layout.h (host only)
+	typedef FieldLayout Layout;
+	static Layout layout(const WorldDims& d) { return field_layout(d.cells, d.cells_height); }
 	static size_t tight_plane_bytes(const WorldDims& d) { return (static_cast<size_t>(d.cells) + 2) * (d.cells + 2) * (d.cells_height + 2); } // a plane with its border, rows not padded
 
-	// Allocated and set to 255 everywhere (the row padding reads as border cells: a stray offset ends a walk); the interior is the caller's -- a
+	// Allocated, with guard bytes before and behind the planes (field_guard_bytes: the pair move looks one cell past a border), and set to 255
+	// everywhere (the row padding reads as border cells: a stray offset ends a walk); the interior is the caller's -- a
 	// host build copied up (upload), or the passes of edit.hip (update).  Writes the cf_*, cube_field and escape members of *view.
 	int allocate(const WorldDims& d, DeviceScene* view);
 	void release();
@@ -96,7 +93,9 @@ private:
 	int device_;
 	int cells_ = 0, cells_height_ = 0, sg_xy_ = 0;
 	Layout l_{};
-	DeviceBuffer<uint8_t> d_cube_field_;
+	size_t guard_ = 0;                    // field_guard_bytes(l_)
+	DeviceBuffer<uint8_t> d_field_alloc_; // head guard, the planes, tail guard
+	uint8_t* plane0() const { return d_field_alloc_ + guard_; } // DeviceScene::cube_field: what every builder, edit pass and readback addresses
 	// escape heights: the table the walk reads (a ninth slice behind the octants' eight holds the shadow heights), and every column's top and
 	// bottom, kept for the updates.  Valid and rebuilt wherever the cube field is, on the same stream right behind it.
 	DeviceBuffer<uint32_t> d_escape_;

@@ -21,4 +21,6 @@ for K in (1, 20):
     for k, name in (("jump", "J"), ("step", "S"), ("candidate", "B"), ("shade", "C")):
         r, l = s[k + "_runs"] / K, s[k + "_lanes"] / K
         print(f"   {name}: {r/1e6:.3f} M passes at {l/max(r,1):.1f} lanes")
+        if k == "step":  # S counts MOVES: a round is BM_STEPS_PER_ROUND = 4 of them, a pair iteration (BM_STEP_AHEAD = 2, csrc/trace.hip) two -- one wait each
+            print(f"      = {r/4e6:.3f} M single-move rounds, {r/2e6:.3f} M pair iterations (waits) at {2*l/max(r,1):.1f} lane-moves each; {l/1e6:.3f} M lane-moves")
     print(f"   connect lanes {s['connect_lanes']/K/1e6:.3f} M in {s['connect_runs']/K/1e6:.3f} M passes; rays {(c['extend_rays']+c['shadow_rays'])/K/1e6:.3f} M; drain share {100*s['drain_cycles']/max(s['total_cycles'],1):.1f} %")
