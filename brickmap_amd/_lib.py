@@ -8,6 +8,8 @@ torch.distributed).
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbrickmap_hip.so")
 
@@ -88,6 +90,10 @@ class bm_denoise_params(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("sigma_l", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class bm_component(C.Structure):
+    _fields_ = [("label", C.c_int32), ("faces", C.c_uint32), ("voxels", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+
 BM_VOXELIZE_SURFACE = 1
 BM_VOXELIZE_SOLID = 2
 BM_VOXELIZE_KEEP = 1
@@ -107,6 +113,10 @@ BM_MESH_UNIT_FACES = 2
 
 class bm_mesh_params(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("extent", C.c_int32 * 3), ("row_pitch", C.c_int64), ("slice_pitch", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class bm_quad(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32), ("shape", C.c_uint32)]
 
 
 class bm_mesh_result(C.Structure):
@@ -176,6 +186,18 @@ SCHED_NAMES = ("step_runs", "step_lanes", "candidate_runs", "candidate_lanes", "
 class bm_sched_stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in SCHED_NAMES]
 
+
+# The records as numpy sees them, each derived from its structure above (tests/test_binding_surface.py keeps an independent second copy)
+RAY_DTYPE, RAY_HIT_DTYPE = np.dtype(bm_ray), np.dtype(bm_ray_hit)                                   # 32 bytes each
+VOLUME_DTYPE, VOLUME_RESULT_DTYPE = np.dtype(bm_volume), np.dtype(bm_volume_result)                 # 48 bytes in, 40 bytes out
+COMPONENT_DTYPE = np.dtype(bm_component)                                                            # 40 bytes
+VOXELIZE_RESULT_DTYPE = np.dtype(bm_voxelize_result)                                                # 16 bytes
+QUAD_DTYPE, MESH_RESULT_DTYPE = np.dtype(bm_quad), np.dtype(bm_mesh_result)                         # 16 bytes each; a quad's shape = d | w << 4 | h << 8
+DISTANCE_RESULT_DTYPE, TRAVEL_RESULT_DTYPE = np.dtype(bm_distance_result), np.dtype(bm_travel_result)  # 32 bytes each
+# the queue records (variables.h:43-52 RayQueue, :54-59 ShadowQueue), which the header does not declare
+RAY_QUEUE_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("throughput", "<f4", 3), ("normal", "<f4", 3),
+                            ("distance", "<f4"), ("identifier", "<i4"), ("bounces", "<i4"), ("pixel_index", "<u4")])
+SHADOW_QUEUE_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("color", "<f4", 3), ("pixel_index", "<u4")])
 
 # every symbol include/brickmap.h declares: name -> (restype, argtypes)
 _vp, _i, _u32p = C.c_void_p, C.c_int, C.POINTER(C.c_uint32)
@@ -338,3 +360,20 @@ def check(code):
     if code != 0:
         msg = load().bm_last_error_string()
         raise BrickmapError(f"brickmap error {code}: {msg.decode() if msg else ''}")
+
+
+def size_call(name, *args):
+    """the size_t that the library's `name`(*args, &size) reports"""
+    out = C.c_size_t(0)
+    check(getattr(load(), name)(*args, C.byref(out)))
+    return int(out.value)
+
+
+def stage_call(plain, timed, args, stages=None, before=(), after=()):
+    """Issue an operator: plain(*args), or with `stages` its stage-timing twin timed(*args, *before, ms, *after), where ms is a float array
+    of that many stages.  Returns the stage times in ms as a list, or None for the plain call."""
+    if stages is None:
+        return check(plain(*args))
+    ms = (C.c_float * stages)()
+    check(timed(*args, *before, ms, *after))
+    return [float(v) for v in ms]

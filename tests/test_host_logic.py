@@ -114,7 +114,9 @@ def test_product_never_touches_the_oracle():
 
 def test_no_reference_reads_at_runtime():
     """/root/reference does not exist on the GPU box: product, bench and smoke never open it."""
-    for rel in ["bench.py", "__graft_entry__.py", "brickmap_amd/_lib.py", "brickmap_amd/host.py", "brickmap_amd/dist.py"]:
+    package = sorted(os.path.relpath(os.path.join(d, f), ROOT) for d, _, files in os.walk(os.path.join(ROOT, "brickmap_amd")) for f in files if f.endswith(".py"))
+    assert {"brickmap_amd/_lib.py", "brickmap_amd/host.py", "brickmap_amd/dist.py"} <= set(package)
+    for rel in ["bench.py", "__graft_entry__.py"] + package:
         assert "/root/reference" not in open(os.path.join(ROOT, rel)).read(), rel
 
 
