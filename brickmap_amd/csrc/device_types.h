@@ -91,6 +91,16 @@ struct RegionDims {
 	int64_t row_pitch, slice_pitch;
 };
 
+// A label box (label.hip; read_book.h check_label_box and label_clip fill it in): the label volume L[z][y][x] of the box [org, org + (nx, ny, nz))
+// is tight, one int32 per voxel.  [lo, hi) = the box clipped to the world (lo == hi == 0 when nothing is left: then c0 / nc are not used),
+// c0 / nc = the brick cells it overlaps
+struct LabelDims {
+	int lo[3], hi[3], org[3];
+	uint32_t nx, ny, nz;
+	int c0[3], nc[3];
+	uint32_t sg_xy, sg_xy2;
+};
+
 // Per-launch constants computed on the host (launch_kernels:371-403 and the view-independent
 // part of the sky model, sunsky.cu:34-44,66-67).
 struct FrameConstants {

@@ -127,15 +127,7 @@ int volume_blocks_per_cu(bool any);
 size_t volume_tmp_bytes(uint32_t n);
 void launch_volume_query(const DeviceScene& sc, const void* volumes, void* results, uint32_t n, bool any, uint64_t* tmp, int resident_blocks, hipStream_t stream);
 
-// connected components (label.hip; label.h has the rules): the label volume L[z][y][x] of the box [org, org + (nx, ny, nz)) is tight, one
-// int32 per voxel.  [lo, hi) = the box clipped to the world (lo == hi == 0 when nothing is left: then c0 / nc are not used), c0 / nc = the
-// brick cells it overlaps
-struct LabelDims {
-	int lo[3], hi[3], org[3];
-	uint32_t nx, ny, nz;
-	int c0[3], nc[3];
-	uint32_t sg_xy, sg_xy2;
-};
+// connected components (label.hip; label.h has the rules, device_types.h LabelDims)
 // local, merge, flatten over the clipped box (not empty; the voxels outside the world are zeroed by the caller): labels as the contract
 // of bm_scene_label_region has them, and the number of components added to *count.  patch_cells / patch_bricks: `patches` listed cells
 // (as launch_region_patch takes them) whose bricks the device does not hold.  marks: null, or 4 events around local, merge and flatten.

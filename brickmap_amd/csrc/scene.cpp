@@ -1,16 +1,11 @@
-// scene.cpp -- one GPU's scene: the world on the device, region reads, labels, queries and frame launch (residency and streaming: residency.cpp; edits and region writes: world_changes.cpp).
+// scene.cpp -- one GPU's scene: lifetime, the world on the device, loads and frame launch (residency and streaming: residency.cpp; edits and region writes: world_changes.cpp; region reads, labels and queries: world_reads.cpp).
 #include "scene.h"
 
 #include <algorithm>
-#include <climits>
-#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-
-#include "buffer_checks.h"
-#include "label.h"
 
 namespace bm {
 
@@ -39,6 +34,13 @@ int Scene::require_on_device() const {
 
 int Scene::require_not_failed() const {
 	if (residency_.book().failed()) { set_error(PoolBook::kFailedWhy); return BM_ESTATE; }
+	return 0;
+}
+
+int Scene::ready() const {
+	if (int e = require_on_device()) return e;
+	if (int e = require_not_failed()) return e;
+	BM_HIP(hipSetDevice(device_));
 	return 0;
 }
 
@@ -315,9 +317,7 @@ int Scene::host_voxels(uint8_t* dst, size_t capacity, size_t* bytes) {
 // ---------------------------------------------------------------- streaming and readbacks: residency.cpp
 int Scene::process_load_queue(uint32_t* serviced) {
 	if (serviced) *serviced = 0;
-	if (int e = require_on_device()) return e;
-	if (int e = require_not_failed()) return e;
-	BM_HIP(hipSetDevice(device_));
+	if (int e = ready()) return e;
 	return residency_.process_load_queue(order_, load_stream_, serviced);
 }
 
@@ -362,20 +362,6 @@ int Scene::edit(int count, const bm_edit* edits, hipStream_t stream) {
 int Scene::last_edit_ms(float* scatter_ms, float* field_ms) { return changes_.last_edit_ms(scatter_ms, field_ms); }
 
 // ---------------------------------------------------------------- dense regions (bm_scene_write_region / bm_scene_read_region)
-namespace {
-// the parts of the box [blo, bhi) that lie outside its clipped part [lo, hi) (all of it when `inside` is false), as up to six boxes
-template <class F> void for_outside_slabs(const int32_t blo[3], const int32_t bhi[3], bool inside, const int lo[3], const int hi[3], F f) {
-	if (!inside) { f(blo[0], bhi[0], blo[1], bhi[1], blo[2], bhi[2]); return; }
-	if (blo[2] < lo[2]) f(blo[0], bhi[0], blo[1], bhi[1], blo[2], lo[2]);
-	if (hi[2] < bhi[2]) f(blo[0], bhi[0], blo[1], bhi[1], hi[2], bhi[2]);
-	if (blo[1] < lo[1]) f(blo[0], bhi[0], blo[1], lo[1], lo[2], hi[2]);
-	if (hi[1] < bhi[1]) f(blo[0], bhi[0], hi[1], bhi[1], lo[2], hi[2]);
-	if (blo[0] < lo[0]) f(blo[0], lo[0], lo[1], hi[1], lo[2], hi[2]);
-	if (hi[0] < bhi[0]) f(hi[0], bhi[0], lo[1], hi[1], lo[2], hi[2]);
-}
-int64_t region_offset(const bm_region& r, int64_t x, int64_t y, int64_t z) { return (z - r.lo[2]) * r.slice_pitch + (y - r.lo[1]) * r.row_pitch + (x - r.lo[0]); }
-} // namespace
-
 // what write_region and read_region refuse, before anything changes; *r gets its pitches filled in, *span the bytes of the volume
 int Scene::check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span) {
 	const std::string at = std::string(who) + ": ";
@@ -404,236 +390,31 @@ int Scene::write_region(const bm_region* region, int op, const uint8_t* voxels, 
 
 int Scene::last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms) { return changes_.last_region_ms(pack_ms, copy_ms, scatter_ms, field_ms); }
 
-int Scene::stage_absent_bricks(bool inside, const int lo[3], const int hi[3], size_t* count, size_t* bricks_at, size_t* total) {
-	const WorldDims& d = world.dims;
-	std::vector<int> cells;
-	std::vector<Brick> bricks;
-	if (inside && !residency_.book().preloaded())
-		for (int cz = lo[2] >> 3; cz <= (hi[2] - 1) >> 3; ++cz)
-			for (int cy = lo[1] >> 3; cy <= (hi[1] - 1) >> 3; ++cy)
-				for (int cx = lo[0] >> 3; cx <= (hi[0] - 1) >> 3; ++cx) {
-					const int sci = d.supercell_id(cx / kSupercell, cy / kSupercell, cz / kSupercell);
-					const HostSupercell& c = world.supercells[sci];
-					const uint32_t word = c.indices[cell_local_index(cx, cy, cz)];
-					if (!residency_.book().absent(sci, word)) continue;
-					cells.insert(cells.end(), {cx, cy, cz});
-					bricks.push_back(c.bricks[word & BM_BRICK_INDEX_BITS]);
-				}
-	const size_t n = bricks.size(), o_bricks = (n * 3 * sizeof(int) + 63) / 64 * 64, bytes = o_bricks + n * sizeof(Brick);
-	if (n > 0) {
-		if (int e = region_read_.wait()) return e; // the previous read's list has been used
-		if (int e = h_patch_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
-		if (int e = d_patch_.reserve(std::max<size_t>(bytes, 1 << 16))) return e;
-		std::memcpy(h_patch_, cells.data(), n * 3 * sizeof(int));
-		std::memcpy(h_patch_ + o_bricks, bricks.data(), n * sizeof(Brick));
-	}
-	*count = n; *bricks_at = o_bricks; *total = bytes;
-	return 0;
-}
-
-// The host world is authoritative, so a host read is World::store_region.  A device read is issued like a query: the unpack kernel reads
-// the device words and bricks; bricks that are not resident (a streaming scene) are staged from the host world and written by a second
-// small launch; what lies outside the world is zeroed.
+// ---------------------------------------------------------------- what only reads the world: world_reads.cpp
 int Scene::read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream) {
 	bm_region r;
 	uint64_t span = 0;
 	if (int e = check_region("bm_scene_read_region", region, voxels, where, &r, &span)) return e;
 	if (span == 0) return 0;
-	const WorldDims& d = world.dims;
-	int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-	const bool inside = World::region_bounds(d, r, lo, hi);
-	if (where == BM_VOXELS_HOST) {
-		for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
-			for (int64_t z = z0; z < z1; ++z)
-				for (int64_t y = y0; y < y1; ++y) std::memset(voxels + region_offset(r, x0, y, z), 0, static_cast<size_t>(x1 - x0));
-		});
-		if (inside) world.store_region(lo, hi, r.lo, voxels, r.row_pitch, r.slice_pitch, 16);
-		return 0;
-	}
-	size_t n = 0, o_bricks = 0, bytes = 0;
-	if (int e = stage_absent_bricks(inside, lo, hi, &n, &o_bricks, &bytes)) return e;
-	DeviceScene view;
-	if (int e = begin_frame(stream, &view, nullptr)) return e;
-	FrameOrder::Ending frame(order_, stream);
-	for_outside_slabs(r.lo, r.hi, inside, lo, hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
-		launch_region_zero(voxels + region_offset(r, x0, y0, z0), r.row_pitch, r.slice_pitch, x1 - x0, y1 - y0, z1 - z0, stream);
-	});
-	if (inside) {
-		const RegionDims rd = region_dims(d, r, lo, hi);
-		launch_region_unpack(voxels, view.index_grid, view.pool_base, view.brick_arena, rd, stream);
-		if (n > 0) {
-			BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));
-			launch_region_patch(voxels, reinterpret_cast<const int*>(d_patch_.get()), reinterpret_cast<const uint32_t*>(d_patch_ + o_bricks), static_cast<uint32_t>(n), rd, stream);
-			if (int e = region_read_.pass(stream)) return e;
-		}
-	}
-	BM_HIP(hipGetLastError());
-	(void)frame.end();
-	return 0;
+	return reads_.read_region(r, voxels, where, stream);
 }
 
-// ---------------------------------------------------------------- connected components (bm_scene_label_region / _components / _mask)
-int Scene::check_label_box(const char* who, const int32_t lo[3], const int32_t hi[3], LabelDims* d, bool* empty) {
-	const std::string at = std::string(who) + ": ";
-	if (!lo || !hi) { set_error(at + "null box"); return BM_EINVAL; }
-	int64_t n[3];
-	for (int k = 0; k < 3; ++k) {
-		n[k] = static_cast<int64_t>(hi[k]) - lo[k];
-		if (n[k] < 0) { set_error(at + "hi < lo"); return BM_EINVAL; }
-	}
-	*empty = n[0] == 0 || n[1] == 0 || n[2] == 0;
-	// (64 bits: each factor is below 2^32, so the first product is below 2^63 once n[0] has passed, and the second is formed only below 2^31 * 2^32)
-	if (!*empty && (n[0] > kLabelMaxVoxels || n[0] * n[1] > kLabelMaxVoxels || n[0] * n[1] * n[2] > kLabelMaxVoxels)) { set_error(at + "the box holds more than 2^31 - 2 voxels"); return BM_EINVAL; }
-	*d = LabelDims{};
-	for (int k = 0; k < 3; ++k) d->org[k] = lo[k];
-	d->nx = static_cast<uint32_t>(n[0]); d->ny = static_cast<uint32_t>(n[1]); d->nz = static_cast<uint32_t>(n[2]);
-	d->sg_xy = static_cast<uint32_t>(world.dims.supergrid_xy);
-	d->sg_xy2 = d->sg_xy * d->sg_xy;
-	return 0;
-}
+int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags, int32_t* labels, uint64_t* count, hipStream_t stream) { return reads_.label_region(lo, hi, flags, labels, count, stream); }
 
-namespace {
-// the box clipped to the world, as World::region_bounds gives it, and the cells it overlaps
-bool label_clip(const WorldDims& wd, const int32_t lo[3], const int32_t hi[3], LabelDims* d) {
-	bm_region r{};
-	for (int k = 0; k < 3; ++k) { r.lo[k] = lo[k]; r.hi[k] = hi[k]; }
-	int clo[3] = {0, 0, 0}, chi[3] = {0, 0, 0};
-	const bool inside = World::region_bounds(wd, r, clo, chi);
-	for (int k = 0; k < 3; ++k) {
-		d->lo[k] = inside ? clo[k] : 0;
-		d->hi[k] = inside ? chi[k] : 0;
-		d->c0[k] = inside ? clo[k] >> 3 : 0;
-		d->nc[k] = inside ? ((chi[k] - 1) >> 3) - d->c0[k] + 1 : 0;
-	}
-	return inside;
-}
-} // namespace
+int Scene::last_label_ms(float* local_ms, float* merge_ms, float* flatten_ms) { return reads_.last_label_ms(local_ms, merge_ms, flatten_ms); }
 
-// Issued like a device read of the same box (read_region): zero what lies outside the world, label the cells the device holds and then
-// the staged ones, merge across cell faces, flatten and count.  Only the caller's volume is written.
-int Scene::label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags, int32_t* labels, uint64_t* count, hipStream_t stream) {
-	const char* who = "bm_scene_label_region";
-	LabelDims ld;
-	bool empty = false;
-	if (flags != 0) { set_error("bm_scene_label_region: unknown flags (must be 0)"); return BM_EINVAL; }
-	if (int e = check_label_box(who, lo, hi, &ld, &empty)) return e;
-	if (!count || (!empty && !labels)) { set_error("bm_scene_label_region: null label volume or count"); return BM_EINVAL; }
-	if (!aligned(count, 8) || (!empty && !aligned(labels, 4))) {
-		set_error("bm_scene_label_region: labels must be 4-byte aligned, count 8-byte aligned");
-		return BM_EINVAL;
-	}
-	if (int e = require_on_device()) return e;
-	if (int e = require_not_failed()) return e;
-	BM_HIP(hipSetDevice(device_));
-	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
-	if (!device_span_ok(device_, count, sizeof(uint64_t)) ||
-		(!empty && !device_span_ok(device_, labels, voxels * sizeof(int32_t)))) {
-		set_error("bm_scene_label_region: the label volume's whole span and the count must lie inside one allocation each of the scene's device");
-		return BM_EINVAL;
-	}
-	const bool inside = !empty && label_clip(world.dims, lo, hi, &ld);
-	size_t n = 0, o_bricks = 0, bytes = 0;
-	if (int e = stage_absent_bricks(inside, ld.lo, ld.hi, &n, &o_bricks, &bytes)) return e;
-	if (int e = label_marks_.create()) return e;
-	DeviceScene view;
-	if (int e = begin_frame(stream, &view, nullptr)) return e;
-	FrameOrder::Ending frame(order_, stream);
-	if (int e = label_.order(stream)) return e;
-	BM_HIP(hipMemsetAsync(count, 0, sizeof(uint64_t), stream));
-	label_clocked_ = 0;
-	if (!empty) {
-		uint8_t* bytes_out = reinterpret_cast<uint8_t*>(labels);
-		const int64_t row = static_cast<int64_t>(ld.nx) * 4, slice = row * ld.ny;
-		for_outside_slabs(lo, hi, inside, ld.lo, ld.hi, [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1, int64_t z0, int64_t z1) {
-			launch_region_zero(bytes_out + (z0 - lo[2]) * slice + (y0 - lo[1]) * row + (x0 - lo[0]) * 4, row, slice, (x1 - x0) * 4, y1 - y0, z1 - z0, stream);
-		});
-		if (inside) {
-			if (n > 0) BM_HIP(hipMemcpyAsync(d_patch_, h_patch_, bytes, hipMemcpyHostToDevice, stream));
-			launch_label_region(view, reinterpret_cast<uint32_t*>(labels), count, ld, reinterpret_cast<const int*>(d_patch_.get()),
-								reinterpret_cast<const uint32_t*>(d_patch_.get() + o_bricks), static_cast<uint32_t>(n), stream, label_marks_.marks());
-			label_clocked_ = kClockedCall;
-			if (n > 0) { if (int e = region_read_.pass(stream)) return e; }
-		}
-	}
-	BM_HIP(hipGetLastError());
-	if (int e = label_.pass(stream)) return e;
-	(void)frame.end();
-	return 0;
-}
-
-int Scene::last_label_ms(float* local_ms, float* merge_ms, float* flatten_ms) {
-	if (!local_ms || !merge_ms || !flatten_ms) { set_error("null argument"); return BM_EINVAL; }
-	if (!label_clocked_) { set_error("the last bm_scene_label_region launched nothing, or there was none"); return BM_ESTATE; }
-	BM_HIP(hipSetDevice(device_));
-	float ms[3];
-	if (int e = label_marks_.read(3, ms)) return e;
-	*local_ms = ms[0]; *merge_ms = ms[1]; *flatten_ms = ms[2];
-	return 0;
-}
-
-// Reads the label volume alone, so it is not a frame: ordered on its stream, and behind the label call before it (the root counts are
-// one buffer, which grows only once that call has finished).
 int Scene::label_components(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, bm_component* comps, int64_t capacity, hipStream_t stream) {
-	const char* who = "bm_scene_label_components";
-	LabelDims ld;
-	bool empty = false;
-	if (int e = check_label_box(who, lo, hi, &ld, &empty)) return e;
-	if (capacity < 0) { set_error("bm_scene_label_components: negative capacity"); return BM_EINVAL; }
-	if (empty || capacity == 0) return 0;
-	if (!labels || !comps) { set_error("bm_scene_label_components: null label volume or table"); return BM_EINVAL; }
-	if (!aligned(labels, 4) || !aligned(comps, 8)) {
-		set_error("bm_scene_label_components: labels must be 4-byte aligned, the table 8-byte aligned");
-		return BM_EINVAL;
-	}
-	if (int e = require_on_device()) return e;
-	if (int e = require_not_failed()) return e;
-	BM_HIP(hipSetDevice(device_));
-	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
-	const size_t records = static_cast<size_t>(std::min<int64_t>(capacity, static_cast<int64_t>(voxels))); // (no more components than voxels)
-	if (!device_span_ok(device_, labels, voxels * sizeof(int32_t)) ||
-		!device_span_ok(device_, comps, records * sizeof(bm_component))) {
-		set_error("bm_scene_label_components: the label volume and min(capacity, voxels) records must lie inside one allocation each of the scene's device");
-		return BM_EINVAL;
-	}
-	label_clip(world.dims, lo, hi, &ld);
-	const size_t need = label_tmp_bytes(static_cast<uint32_t>(voxels));
-	if (d_label_tmp_.bytes() < need) {
-		if (int e = label_.wait()) return e;
-		if (int e = d_label_tmp_.reserve(std::max<size_t>(need, 1 << 16))) return e;
-	}
-	if (int e = label_.order(stream)) return e;
-	launch_label_components(reinterpret_cast<const uint32_t*>(labels), comps, static_cast<uint64_t>(capacity), ld, d_label_tmp_, stream);
-	BM_HIP(hipGetLastError());
-	return label_.pass(stream);
+	return reads_.label_components(lo, hi, labels, comps, capacity, stream);
 }
 
 int Scene::label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* mask,
 					  hipStream_t stream) {
-	const char* who = "bm_scene_label_mask";
-	LabelDims ld;
-	bool empty = false;
-	if (int e = check_label_box(who, lo, hi, &ld, &empty)) return e;
-	if (n < 0) { set_error("bm_scene_label_mask: negative record count"); return BM_EINVAL; }
-	if (empty) return 0;
-	if (!labels || !mask || (n > 0 && (!comps || !chosen))) { set_error("bm_scene_label_mask: null buffer"); return BM_EINVAL; }
-	if (!aligned(labels, 4) || !aligned(comps, 8)) {
-		set_error("bm_scene_label_mask: labels must be 4-byte aligned, the table 8-byte aligned");
-		return BM_EINVAL;
-	}
-	if (int e = require_on_device()) return e;
-	if (int e = require_not_failed()) return e;
-	BM_HIP(hipSetDevice(device_));
-	const size_t voxels = static_cast<size_t>(ld.nx) * ld.ny * ld.nz;
-	if (!device_span_ok(device_, labels, voxels * sizeof(int32_t)) || !device_span_ok(device_, mask, voxels) ||
-		(n > 0 && (!device_span_ok(device_, comps, static_cast<size_t>(n) * sizeof(bm_component)) || !device_span_ok(device_, chosen, static_cast<size_t>(n))))) {
-		set_error("bm_scene_label_mask: every buffer's whole span must lie inside one allocation of the scene's device");
-		return BM_EINVAL;
-	}
-	if (int e = label_.order(stream)) return e;
-	launch_label_mask(reinterpret_cast<const uint32_t*>(labels), static_cast<uint32_t>(voxels), comps, static_cast<uint64_t>(n), chosen, mask, stream);
-	BM_HIP(hipGetLastError());
-	return label_.pass(stream);
+	return reads_.label_mask(lo, hi, labels, comps, n, chosen, mask, stream);
 }
+
+int Scene::cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream) { return reads_.cast_rays(n, rays, hits, flags, lod_origin, stream); }
+
+int Scene::query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* results, uint32_t flags, hipStream_t stream) { return reads_.query_volumes(n, volumes, results, flags, stream); }
 
 // ---- the sun plane and the view plane (walk_fields.h; field_book.h decides): each is built on the load stream by the production launch that is
 // about to read it, unless it stands.  *usable: the launch's frames with the book's key may read the plane.
@@ -737,83 +518,6 @@ int Scene::render_frames(int count, const bm_camera* cams, const bm_frame_params
 		return e;
 	}
 	frame_ring_.issued(ring);
-	return 0;
-}
-
-// ---- ray queries (bm_scene_cast_rays).  Issued through the frames' bookkeeping: the stream is ordered behind pending uploads and
-// edits (begin_frame), and process_load_queue orders itself behind the query (end_frame).  The kernel only reads the world, apart
-// from the request atomics, so it may run beside frames.
-int Scene::cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream) {
-	if (flags & ~(BM_QUERY_LOD | BM_QUERY_NO_REQUESTS)) { set_error("bm_scene_cast_rays: unknown flag"); return BM_EINVAL; }
-	if (n < 0 || n > (int64_t{1} << 28)) { set_error("bm_scene_cast_rays: n must be 0 ... 2^28"); return BM_EINVAL; }
-	if (n == 0) return 0;
-	if (!rays || !hits) { set_error("bm_scene_cast_rays: null ray or hit buffer"); return BM_EINVAL; }
-	int campos[3] = {0, 0, 0};
-	if (flags & BM_QUERY_LOD) {
-		if (!lod_origin) { set_error("bm_scene_cast_rays: BM_QUERY_LOD needs lod_origin"); return BM_EINVAL; }
-		for (int i = 0; i < 3; ++i) {
-			if (!(std::fabs(lod_origin[i]) < 16777216.f)) { set_error("bm_scene_cast_rays: lod_origin must be finite and below 2^24"); return BM_EINVAL; }
-			campos[i] = static_cast<int>(lod_origin[i] / 8.f); // as fill_frame_constants: ivec3(camera.position / 8.f)
-		}
-	}
-	if (int e = require_on_device()) return e;
-	if (int e = require_not_failed()) return e;
-	BM_HIP(hipSetDevice(device_));
-	if (!d_query_tickets_) {
-		if (int e = d_query_tickets_.alloc(kQueryRing * 128)) return e;
-		for (Event& ev : ev_query_) if (int e = ev.create(hipEventDisableTiming)) return e;
-		query_blocks_per_cu_[0] = query_blocks_per_cu(false);
-		query_blocks_per_cu_[1] = query_blocks_per_cu(true);
-	}
-	const bool request = !(flags & BM_QUERY_NO_REQUESTS);
-	DeviceScene view;
-	if (int e = begin_frame(stream, &view, nullptr)) return e;
-	FrameOrder::Ending frame(order_, stream);
-	if (!(flags & BM_QUERY_LOD)) view.lod_distance_8x8x8 = view.lod_distance_2x2x2 = INT_MAX; // exact: every brick at voxel level
-	const int slot = query_ring_.slot();
-	uint32_t* ticket = d_query_tickets_ + slot * 32;
-	if (query_ring_.reused()) BM_HIP(hipStreamWaitEvent(stream, ev_query_[slot], 0));
-	BM_HIP(hipMemsetAsync(ticket, 0, sizeof(uint32_t), stream));
-	launch_query(view, campos, rays, hits, static_cast<uint32_t>(n), ticket, query_blocks_per_cu_[request ? 1 : 0] * compute_units_, request, stream);
-	BM_HIP(hipGetLastError());
-	BM_HIP(hipEventRecord(ev_query_[slot], stream));
-	query_ring_.issued();
-	(void)frame.end();
-	return 0;
-}
-
-// ---- volume queries (bm_scene_query_volumes).  Issued like a ray query; the kernels only read the world.  The item offsets are one
-// buffer, so a query is ordered behind the previous one (on whatever stream that ran), and the buffer grows only once that has finished.
-int Scene::query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* results, uint32_t flags, hipStream_t stream) {
-	if (flags & ~BM_VOLUME_ANY) { set_error("bm_scene_query_volumes: unknown flag"); return BM_EINVAL; }
-	if (n < 0 || n > (int64_t{1} << 24)) { set_error("bm_scene_query_volumes: n must be 0 ... 2^24"); return BM_EINVAL; }
-	if (n == 0) return 0;
-	if (!volumes || !results) { set_error("bm_scene_query_volumes: null volume or result buffer"); return BM_EINVAL; }
-	if (!aligned(volumes, 4) || !aligned(results, 8)) {
-		set_error("bm_scene_query_volumes: volumes must be 4-byte aligned, results 8-byte aligned");
-		return BM_EINVAL;
-	}
-	if (int e = require_on_device()) return e;
-	if (int e = require_not_failed()) return e;
-	BM_HIP(hipSetDevice(device_));
-	if (!volume_blocks_per_cu_[0]) {
-		volume_blocks_per_cu_[0] = volume_blocks_per_cu(false);
-		volume_blocks_per_cu_[1] = volume_blocks_per_cu(true);
-	}
-	const size_t need = volume_tmp_bytes(static_cast<uint32_t>(n));
-	if (d_volume_tmp_.bytes() < need) {
-		if (int e = volume_.wait()) return e;
-		if (int e = d_volume_tmp_.reserve(std::max<size_t>(need, 1 << 16))) return e;
-	}
-	const bool any = (flags & BM_VOLUME_ANY) != 0;
-	DeviceScene view;
-	if (int e = begin_frame(stream, &view, nullptr)) return e;
-	FrameOrder::Ending frame(order_, stream);
-	if (int e = volume_.order(stream)) return e;
-	launch_volume_query(view, volumes, results, static_cast<uint32_t>(n), any, d_volume_tmp_, volume_blocks_per_cu_[any ? 1 : 0] * compute_units_, stream);
-	BM_HIP(hipGetLastError());
-	if (int e = volume_.pass(stream)) return e;
-	(void)frame.end();
 	return 0;
 }
 

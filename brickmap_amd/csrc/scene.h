@@ -1,4 +1,5 @@
-// scene.h -- device-resident brickmap scene for one GPU: the world on the device, what changes it, what reads it, frame launch.
+// scene.h -- device-resident brickmap scene for one GPU: lifetime, the world on the device, loads and frame launch; what else changes the world
+// (world_changes.h) and what only reads it (world_reads.h) it holds as members and forwards to.
 // Mirrors the device half of the reference's Scene (src/Scene.cpp:29-36,152-194,200-258) and the
 // host orchestration of launch_kernels (src/kernel.cu:366-439).
 #pragma once
@@ -20,12 +21,15 @@
 #include "walk_fields.h"
 #include "world.h"
 #include "world_changes.h"
+#include "world_reads.h"
 
 namespace bm {
 
 class Scene {
 public:
-	explicit Scene(int device) : device_(device), fields_(device), residency_(device, &world), changes_(device, &world, &residency_, &fields_, &order_, &load_stream_) {}
+	explicit Scene(int device)
+		: device_(device), fields_(device), residency_(device, &world), changes_(device, &world, &residency_, &fields_, &order_, &load_stream_),
+		  reads_(device, &world, &residency_, &order_, &view_, &compute_units_, [this] { return ready(); }) {}
 	~Scene();
 
 	int init(int grid_size, int grid_height); // Scene::Scene: streams + pinned staging
@@ -48,7 +52,7 @@ public:
 	// the cube field, the escape table and the planes derived from them: walk_fields.h has their readbacks and build statistics
 	WalkFields& fields() { return fields_; }
 	WalkFields* fields_on_device() { return require_on_device() ? nullptr : &fields_; } // null + message unless the world is on the device
-	// dense regions (region.hip / world_changes.h, scene.cpp "dense regions"): a box of voxels written into / read out of the live scene
+	// dense regions (region.hip; world_changes.h writes, world_reads.h reads): a box of voxels written into / read out of the live scene
 	int write_region(const bm_region* region, int op, const uint8_t* voxels, int where, hipStream_t stream);
 	int read_region(const bm_region* region, uint8_t* voxels, int where, hipStream_t stream);
 	int last_region_ms(float* pack_ms, float* copy_ms, float* scatter_ms, float* field_ms);
@@ -56,11 +60,10 @@ public:
 	int load_voxels(const uint8_t* voxels, size_t bytes, int where, hipStream_t stream);
 	int host_voxels(uint8_t* dst, size_t capacity, size_t* bytes);
 	int last_load_ms(float* pack_ms, float* field_ms, float* mirror_ms); // device time of the last load from device memory
-	// ray queries (query.hip): issued like a frame (begin_frame / end_frame), asynchronous to the host
+	// what only reads the world (world_reads.h): ray queries (query.hip), volume queries (volume.hip) and connected components (label.hip), issued
+	// like a frame and asynchronous to the host; label_components and label_mask only read the caller's label volume
 	int cast_rays(int64_t n, const bm_ray* rays, bm_ray_hit* hits, uint32_t flags, const float* lod_origin, hipStream_t stream);
-	// volume queries (volume.hip): issued like a ray query
 	int query_volumes(int64_t n, const bm_volume* volumes, bm_volume_result* results, uint32_t flags, hipStream_t stream);
-	// connected components (label.hip): label_region is issued like a query; the other two only read the caller's label volume
 	int label_region(const int32_t lo[3], const int32_t hi[3], uint32_t flags, int32_t* labels, uint64_t* count, hipStream_t stream);
 	int label_components(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, bm_component* comps, int64_t capacity, hipStream_t stream);
 	int label_mask(const int32_t lo[3], const int32_t hi[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* mask,
@@ -93,15 +96,11 @@ private:
 	int ensure_view_plane(const std::vector<FrameConstants>& fcs, bool* usable); // builds the view plane for the first frame's origin if the camera rests there; *usable: the plane stands for that origin
 	void set_view_dims();
 	int load_voxels_device(const uint8_t* voxels, hipStream_t stream);
-	int check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span);
-	// the bricks of the clipped box [lo, hi) that the device does not hold, from the host world into h_patch_ / d_patch_'s layout: *n of them,
-	// the bricks from byte *o_bricks on, *bytes in all (a preloaded scene, or inside == false: none)
-	int stage_absent_bricks(bool inside, const int lo[3], const int hi[3], size_t* n, size_t* o_bricks, size_t* bytes);
-	// what the three label calls refuse about their box, before anything is launched; *d gets the box's dimensions
-	int check_label_box(const char* who, const int32_t lo[3], const int32_t hi[3], LabelDims* d, bool* empty);
+	int check_region(const char* who, const bm_region* region, const void* voxels, int where, bm_region* r, uint64_t* span); // what write_region and read_region refuse
 	void free_device();
 	int require_on_device() const;  // BM_ESTATE + message unless the world is on the device
 	int require_not_failed() const; // BM_ESTATE + message once a streaming batch has failed
+	int ready() const;              // both, in this order, then the scene's device is the current one: what a call that is about to use the device asks first
 	void residency_rebuilt(); // residency_ has written a new index grid: the fields and the ordering hear of it
 
 	int device_;
@@ -114,6 +113,8 @@ private:
 	// its clock slots.  A scratch or staging buffer that one call at a time may use: a Turn (hip_owned.h) beside the buffer.  Which brick is
 	// resident where, the request rings and the upload batches: residency_ (residency.h; pool_book.h takes the decisions, the failed flag among them).
 	// The device half of an edit or a region write, its staging and its stage clocks: changes_ (world_changes.h; change_book.h takes the decisions).
+	// The calls that only read the world -- region reads, labels, ray and volume queries --, their scratch and the Turns beside it: reads_
+	// (world_reads.h; read_book.h takes the decisions).
 	FrameOrder order_;
 	static constexpr int kTimingRing = 256; // hipEvent pairs around the most recent render launches
 	Event ev_start_[kTimingRing], ev_stop_[kTimingRing];
@@ -123,6 +124,7 @@ private:
 	WalkFields fields_;
 	Residency residency_;
 	WorldChanges changes_;
+	WorldReads reads_;
 	DeviceBuffer<DeviceCounters> d_counters_;
 	// the frame ring: constants and ticket counters of the frames in flight -- a launch takes as many consecutive entries as it has frames
 	static constexpr int kFrameRing = 1024; // (a launch takes at most kMaxFramesPerLaunch, frame_plan.h)
@@ -131,30 +133,10 @@ private:
 	DeviceBuffer<uint32_t> d_work_counter_; // chunk counters of the persistent trace kernel: kFrameRing blocks of kWorkCounterBytes, zeroed before the launch that uses them
 	FrameRing<kFrameRing, kTimingRing, kMaxFramesPerLaunch> frame_ring_;
 	int compute_units_ = 0, blocks_per_cu_[2] = {0, 0};
-	// region reads: the list of non-resident bricks (pinned + device), the read's until its launch has used it (region_read_)
-	DeviceBuffer<char> d_patch_;
-	PinnedBuffer<char> h_patch_;
-	Turn region_read_;
-	// Stage clocks of the calls that report device times here (StageMarks, made on first use), each with the stages its last call recorded (kClocked*,
-	// change_book.h: 0 = nothing to report).  Loads from device memory: 0, 1 around classify + number, 2 ... 5 around pack, field and mirror (the
-	// host's round trip lies between 1 and 2).  label_region: 0 ... 3 around local, merge and flatten.
+	// The stage clock of a load from device memory (StageMarks, made on first use) with the stages the last load recorded (kClocked*, change_book.h:
+	// 0 = nothing to report): marks 0, 1 around classify + number, 2 ... 5 around pack, field and mirror (the host's round trip lies between 1 and 2).
 	StageMarks<6> load_marks_;
-	StageMarks<4> label_marks_;
-	unsigned load_clocked_ = 0, label_clocked_ = 0;
-	// ray queries: a ring of slot counters (one 128-byte line each); a query that reuses an entry waits for the one that used it last
-	static constexpr int kQueryRing = 64;
-	DeviceBuffer<uint32_t> d_query_tickets_;
-	Event ev_query_[kQueryRing];
-	ClockRing<kQueryRing> query_ring_;
-	int query_blocks_per_cu_[2] = {0, 0};
-	// volume queries: the item offsets of one launch (volume_tmp_bytes, grown on demand); a query waits for the one before it, which used them
-	DeviceBuffer<uint64_t> d_volume_tmp_;
-	Turn volume_;
-	int volume_blocks_per_cu_[2] = {0, 0};
-	// connected components: the root counts of one bm_scene_label_components (label_tmp_bytes, grown on demand); label calls of a scene run
-	// one after another, each waits for the one before it
-	DeviceBuffer<uint64_t> d_label_tmp_;
-	Turn label_;
+	unsigned load_clocked_ = 0;
 	int lod8_ = 600000, lod2_ = 100000;          // variables.h:24-27
 	DeviceScene view_{};
 };

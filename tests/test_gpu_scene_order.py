@@ -263,3 +263,38 @@ def test_edit_staging_grows_behind_a_batch_in_flight(bm, torch_cuda, volume):
     assert np.array_equal(words, words_1), "index words differ from the calls made one by one"
     assert bricks.keys() == bricks_1.keys() and all(np.array_equal(bricks[j], bricks_1[j]) for j in bricks), "bricks differ from the calls made one by one"
     assert np.array_equal(field, field_1), "the cube field differs from the calls made one by one"
+
+
+def test_patch_list_grows_behind_a_read_in_flight(bm, torch_cuda):
+    torch = torch_cuda
+    # a device read of a streaming scene lists the bricks the device does not hold in 12 bytes a cell + 64 a brick (the bricks on a 64-byte
+    # line), and the list starts at 64 KiB: 862 bricks fit.  Four layers of cells are 16 x 16 x 4 = 1024 bricks (77 824 bytes), so the list
+    # grows while the read before may still use it -- and label_region of the same box then takes the same list
+    vox = np.zeros((G, G, G), np.uint8)
+    vox[:32] = 1
+    s = bm.Scene.from_voxels(vox).reset_residency()  # streaming, nothing resident: every brick of a box is listed
+    assert s.info()["resident_bricks"] == 0
+    cell, whole = ((0, 0, 0), (8, 8, 8)), ((0, 0, 0), (G, G, G))
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    s.synchronize()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(a):
+        small = s.read_region(*cell, device=True)
+    with torch.cuda.stream(b):
+        large = s.read_region(*whole, device=True)
+    with torch.cuda.stream(a):
+        labels, count = s.label_region(*whole)
+    torch.cuda.synchronize()
+    assert s.info()["resident_bricks"] == 0, "a read asks for no bricks"
+    for got, box in ((small, cell), (large, whole)):
+        want = s.read_region(*box, device=True)
+        torch.cuda.synchronize()
+        assert torch.equal(got, want), f"box {box}: the read in flight differs from the read made alone"
+        assert np.array_equal(got.cpu().numpy(), vox[tuple(slice(l, h) for l, h in zip(box[0][::-1], box[1][::-1]))])
+    assert int(small.min()) == 1, "a cell of the solid layers"
+    want_labels, want_count = s.label_region(*whole)
+    torch.cuda.synchronize()
+    assert int(count.item()) == int(want_count.item()) == 1, "the four layers are one piece"
+    assert torch.equal(labels, want_labels), "labels differ from the call made alone"
+    assert np.array_equal(labels.cpu().numpy() != 0, vox != 0)
+    s.close()
