@@ -148,6 +148,11 @@ class bm_travel_result(C.Structure):
     _fields_ = [("reached", C.c_uint64), ("farthest", C.c_uint32), ("seeds_rejected", C.c_uint32), ("farthest_at", C.c_uint64), ("reserved", C.c_uint64)]
 
 
+class bm_settle_result(C.Structure):
+    _fields_ = [("moved_voxels", C.c_uint64), ("chosen_pieces", C.c_uint32), ("moved_pieces", C.c_uint32), ("largest_drop", C.c_uint32), ("reserved", C.c_uint32),
+                ("contacts", C.c_uint64)]
+
+
 class bm_volume(C.Structure):
     _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
 
@@ -194,6 +199,7 @@ COMPONENT_DTYPE = np.dtype(bm_component)                                        
 VOXELIZE_RESULT_DTYPE = np.dtype(bm_voxelize_result)                                                # 16 bytes
 QUAD_DTYPE, MESH_RESULT_DTYPE = np.dtype(bm_quad), np.dtype(bm_mesh_result)                         # 16 bytes each; a quad's shape = d | w << 4 | h << 8
 DISTANCE_RESULT_DTYPE, TRAVEL_RESULT_DTYPE = np.dtype(bm_distance_result), np.dtype(bm_travel_result)  # 32 bytes each
+SETTLE_RESULT_DTYPE = np.dtype(bm_settle_result)                                                    # 32 bytes
 # the queue records (variables.h:43-52 RayQueue, :54-59 ShadowQueue), which the header does not declare
 RAY_QUEUE_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("throughput", "<f4", 3), ("normal", "<f4", 3),
                             ("distance", "<f4"), ("identifier", "<i4"), ("bounces", "<i4"), ("pixel_index", "<u4")])
@@ -267,6 +273,11 @@ SIGNATURES = {
     "bm_travel_paths": (_i, [_vp, C.POINTER(C.c_int32), _vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "bm_host_travel_field": (_i, [C.POINTER(bm_travel_params), _vp, _vp, C.c_int64, _vp, C.POINTER(bm_travel_result)]),
     "bm_host_travel_paths": (_i, [C.POINTER(C.c_int32), _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
+    "bm_settle_workspace_bytes": (_i, [C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_size_t)]),
+    "bm_settle": (_i, [_vp, C.POINTER(C.c_int32), _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp]),
+    "bm_debug_settle_times": (_i, [_vp, C.POINTER(C.c_int32), _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_float),
+                                   C.POINTER(C.c_uint32)]),
+    "bm_host_settle": (_i, [C.POINTER(C.c_int32), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.POINTER(bm_settle_result)]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

@@ -14,6 +14,7 @@
 #include "mesh.h"
 #include "reproject.h"
 #include "scene.h"
+#include "settle.h"
 #include "travel.h"
 #include "voxelize.h"
 #include "wavefront.h"
@@ -339,6 +340,31 @@ int bm_travel_paths(bm_scene* scene, const int32_t extent[3], const uint32_t* fi
 					int32_t* lengths_dev, void* hip_stream) {
 	BM_NEED(scene);
 	return bm::travel_paths(scene->impl.gpu(), extent, field_dev, starts_dev, n, capacity, path_dev, lengths_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+// (bm_host_settle is csrc/settle_host.cpp: host code that needs nothing of the library)
+int bm_settle_workspace_bytes(const int32_t extent[3], int64_t n, size_t* bytes) {
+	if (!extent || !bytes) { set_error("bm_settle_workspace_bytes: null argument"); return BM_EINVAL; }
+	if (const char* why = bm::settle_extent_problem(extent)) { set_error(std::string("bm_settle_workspace_bytes: ") + why); return BM_EINVAL; }
+	if (n < 0 || n > bm::kSettleMaxVoxels) { set_error("bm_settle_workspace_bytes: a negative number of records, or more than 2^31 - 2"); return BM_EINVAL; }
+	*bytes = bm::settle_workspace_bytes(bm::settle_dims(extent, n));
+	return 0;
+}
+
+int bm_settle(bm_scene* scene, const int32_t extent[3], const int32_t* labels_dev, const bm_component* comps_dev, int64_t n, const uint8_t* chosen_dev, uint8_t* out_dev,
+			  int32_t* drops_dev, bm_settle_result* result_dev, void* workspace_dev, size_t workspace_bytes, uint32_t flags, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::settle(scene->impl.gpu(), extent, labels_dev, comps_dev, n, chosen_dev, out_dev, drops_dev, result_dev, workspace_dev, workspace_bytes, flags,
+					  static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_settle_times(bm_scene* scene, const int32_t extent[3], const int32_t* labels_dev, const bm_component* comps_dev, int64_t n, const uint8_t* chosen_dev,
+						  uint8_t* out_dev, int32_t* drops_dev, bm_settle_result* result_dev, void* workspace_dev, size_t workspace_bytes, uint32_t flags, void* hip_stream,
+						  uint32_t batch, float* stage_ms, uint32_t* counts) {
+	BM_NEED(scene);
+	if (!stage_ms || !counts) { set_error("bm_debug_settle_times: null argument"); return BM_EINVAL; }
+	return bm::settle(scene->impl.gpu(), extent, labels_dev, comps_dev, n, chosen_dev, out_dev, drops_dev, result_dev, workspace_dev, workspace_bytes, flags,
+					  static_cast<hipStream_t>(hip_stream), batch, stage_ms, counts);
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)

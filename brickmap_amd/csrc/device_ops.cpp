@@ -12,6 +12,7 @@
 #include "hip_owned.h"
 #include "kernels.h"
 #include "mesh.h"
+#include "settle.h"
 #include "travel.h"
 #include "voxelize.h"
 
@@ -306,6 +307,80 @@ int travel_paths(const Gpu& gpu, const int32_t extent[3], const uint32_t* field,
 	if (n == 0) return 0;
 	launch_travel_paths(d, field, starts, static_cast<uint32_t>(n), capacity, path, lengths, stream);
 	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- labels + chosen records -> the settled volume (bm_settle): kernels on the caller's stream over the caller's buffers; nothing of the
+// world is read.  The host loop of the rounds is here: batches of rounds, and between them one small copy read back.
+int settle(const Gpu& gpu, const int32_t extent[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* out, int32_t* drops,
+		   bm_settle_result* result, void* workspace, size_t workspace_bytes, uint32_t flags, hipStream_t stream, uint32_t batch, float* stage_ms, uint32_t* counts) {
+	if (!extent) { set_error("bm_settle: null extent"); return BM_EINVAL; }
+	if (const char* why = settle_extent_problem(extent)) { set_error(std::string("bm_settle: ") + why); return BM_EINVAL; }
+	if (flags != 0) { set_error("bm_settle: unknown flag"); return BM_EINVAL; }
+	if (n < 0 || n > kSettleMaxVoxels) { set_error("bm_settle: a negative number of records, or more than 2^31 - 2"); return BM_EINVAL; }
+	if (!labels || !out || !result || !workspace || (n > 0 && (!comps || !chosen || !drops))) {
+		set_error("bm_settle: null labels, records, chosen, out, drops, result or workspace");
+		return BM_EINVAL;
+	}
+	const SettleDims d = settle_dims(extent, n);
+	const size_t need = settle_workspace_bytes(d);
+	if (workspace_bytes < need) { set_error("bm_settle: the workspace is smaller than bm_settle_workspace_bytes"); return BM_EINVAL; }
+	if (!aligned(labels, 4) || !aligned(workspace, 4) || !aligned(result, 8) || (n > 0 && (!aligned(drops, 4) || !aligned(comps, 8)))) {
+		set_error("bm_settle: labels, drops and workspace must be 4-byte, the records and the result 8-byte aligned");
+		return BM_EINVAL;
+	}
+	const size_t label_bytes = static_cast<size_t>(d.voxels) * 4, out_bytes = d.voxels, comp_bytes = static_cast<size_t>(n) * sizeof(bm_component),
+				 chosen_bytes = static_cast<size_t>(n), drop_bytes = static_cast<size_t>(n) * 4;
+	const Span ws = span_of(workspace, need), ls = span_of(labels, label_bytes), os = span_of(out, out_bytes), rs = span_of(result, sizeof(bm_settle_result));
+	const Span cs = span_of(comps, comp_bytes), hs = span_of(chosen, chosen_bytes), ds = span_of(drops, drop_bytes);
+	if (spans_overlap(os, ls)) { set_error("bm_settle: out overlaps labels"); return BM_EINVAL; }
+	if (spans_overlap(ls, ws) || spans_overlap(os, ws) || spans_overlap(rs, ws) || (n > 0 && (spans_overlap(cs, ws) || spans_overlap(hs, ws) || spans_overlap(ds, ws)))) {
+		set_error("bm_settle: the workspace overlaps labels, the records, chosen, out, the drops or the result");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, labels, label_bytes) || !device_span_ok(gpu.device, out, out_bytes) || !device_span_ok(gpu.device, result, sizeof(bm_settle_result)) ||
+		!device_span_ok(gpu.device, workspace, need) ||
+		(n > 0 && (!device_span_ok(gpu.device, comps, comp_bytes) || !device_span_ok(gpu.device, chosen, chosen_bytes) || !device_span_ok(gpu.device, drops, drop_bytes)))) {
+		set_error("bm_settle: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (batch == 0) batch = kSettleBatch;
+	StageMarks<4> marks;
+	if (stage_ms) {
+		if (int e = marks.create(4)) return e;
+	}
+	auto stamp = [&](int i) { if (stage_ms) (void)hipEventRecord(marks.marks()[i], stream); };
+	stamp(0);
+	launch_settle_setup(d, chosen, workspace, stream);
+	stamp(1);
+	// After round r every piece whose shortest chain has at most r contacts is final, a chain has at most as many contacts as there are
+	// chosen records, and the round after the last change counts none: chosen + 1 rounds at most, and one to spare.  Until the first
+	// look has brought the number of chosen records, n stands in for it.
+	const uint8_t* tail = reinterpret_cast<const uint8_t*>(settle_tail_at(d, workspace));
+	uint64_t done = 0, cap = static_cast<uint64_t>(n) + 2;
+	uint32_t looks = 0, seen[4] = {0, 0, 0, 0}, changes = 1; // seen: the tail's three counts and `chosen`
+	while (changes != 0) {
+		if (done >= cap) { set_error("bm_settle: internal error: drops still fall after every round the pieces can need"); return BM_ESTATE; }
+		const uint32_t rounds = static_cast<uint32_t>(cap - done < batch ? cap - done : batch);
+		launch_settle_rounds(d, labels, comps, chosen, workspace, static_cast<uint32_t>(done) + 1u, rounds, stream);
+		done += rounds;
+		BM_HIP(hipMemcpyAsync(seen, tail + 4 * kSettleTailCountWord, sizeof(seen), hipMemcpyDeviceToHost, stream));
+		BM_HIP(hipStreamSynchronize(stream));
+		++looks;
+		changes = seen[done % 3]; // what round `done` counted
+		cap = static_cast<uint64_t>(seen[3]) + 2;
+	}
+	stamp(2);
+	launch_settle_move(d, labels, comps, chosen, out, drops, result, workspace, stream);
+	stamp(3);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipStreamSynchronize(stream)); // the call returns when out, the drops and the record stand
+	if (counts) {
+		counts[0] = static_cast<uint32_t>(done);
+		counts[1] = looks;
+	}
+	if (stage_ms) return marks.read(3, stage_ms);
 	return 0;
 }
 

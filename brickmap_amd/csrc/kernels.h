@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, travel.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, travel.hip, settle.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -180,6 +180,17 @@ void launch_travel_rounds(const TravelDims& d, uint32_t* field, void* workspace,
 void launch_travel_finish(const TravelDims& d, const uint32_t* field, void* result, void* workspace, hipStream_t stream);
 // n starts -> n paths of at most `capacity` voxels down the field, and their lengths
 void launch_travel_paths(const TravelDims& d, const uint32_t* field, const int32_t* starts, uint32_t n, int32_t capacity, int32_t* path, int32_t* lengths, hipStream_t stream);
+
+// labels + chosen records -> the settled volume (settle.hip; settle.h has the rules, SettleDims and the workspace's layout).  The caller
+// (device_ops.cpp) enqueues the set-up, then rounds in batches -- between batches it reads the last round's count of changes from the
+// tail and stops at 0 -- then the move with the finish.  workspace: settle_workspace_bytes() bytes, 4-byte aligned, that no other launch
+// uses until the move has run (its tail is zeroed by the set-up).  Rounds count from 1.  records, chosen, drops: unused when d.n is 0.
+struct SettleDims;
+void launch_settle_setup(const SettleDims& d, const uint8_t* chosen, void* workspace, hipStream_t stream);
+void launch_settle_rounds(const SettleDims& d, const int32_t* labels, const void* records, const uint8_t* chosen, void* workspace, uint32_t first_round, uint32_t rounds,
+						  hipStream_t stream);
+void launch_settle_move(const SettleDims& d, const int32_t* labels, const void* records, const uint8_t* chosen, uint8_t* out, int32_t* drops, void* result, void* workspace,
+						hipStream_t stream);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

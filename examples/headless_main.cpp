@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--path x0,y0,z0:x1,y1,z1] [--drop-floating x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--path x0,y0,z0:x1,y1,z1] [--drop-floating x0,y0,z0:x1,y1,z1] [--settle x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -22,6 +22,9 @@
 // --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig and --shrink: the pieces of that box that hang on nothing -- connected components by faces,
 // inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
 // and voxels went.
+// --settle x0,y0,z0:x1,y1,z1, applied where --drop-floating is (after it, if both are given): the same pieces fall instead -- straight down, each as
+// one rigid body, until they rest on the box's bottom, on something that did not move or on each other (Scene::settle_floating); prints
+// how many pieces and voxels moved and the largest drop.  The floor is the bottom of the box: take z0 down to the ground.
 // --dig-at picks the voxel under pixel (px, py) of the first frame's camera (Scene::pick) and carves a sphere of radius r there; the
 // world streams, so while the pick lands on a brick that is not resident yet (level 3) the load queue is serviced and the pick repeated
 // (at most 8 times).  Prints `picked voxel x,y,z level L`; after the carve, what the same pixel sees now.  A pick that stays
@@ -54,6 +57,8 @@ int main(int argc_in, char** argv_in) {
 	int dig_at[3] = {0, 0, -1};
 	int drop_lo[3] = {0, 0, 0}, drop_hi[3] = {0, 0, 0};
 	bool drop = false;
+	int settle_lo[3] = {0, 0, 0}, settle_hi[3] = {0, 0, 0};
+	bool settle = false;
 	int ground[2] = {-1, -1};
 	int morph_lo[2][3] = {{0, 0, 0}, {0, 0, 0}}, morph_hi[2][3] = {{0, 0, 0}, {0, 0, 0}}; // [0]: --grow, [1]: --shrink
 	int morph_r2[2] = {0, 0};
@@ -135,6 +140,14 @@ int main(int argc_in, char** argv_in) {
 				return 2;
 			}
 			drop = true;
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--settle" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d,%d:%d,%d,%d", &settle_lo[0], &settle_lo[1], &settle_lo[2], &settle_hi[0], &settle_hi[1], &settle_hi[2]) != 6) {
+				std::cerr << "--settle wants x0,y0,z0:x1,y1,z1\n";
+				return 2;
+			}
+			settle = true;
 			continue;
 		}
 		if (std::string(argv_in[i]) == "--path" && i + 1 < argc_in) {
@@ -230,6 +243,11 @@ int main(int argc_in, char** argv_in) {
 	if (drop) {
 		const Scene::Removed gone = scene.remove_floating(drop_lo, drop_hi);
 		std::printf("dropped %llu floating pieces, %llu voxels\n", static_cast<unsigned long long>(gone.pieces), static_cast<unsigned long long>(gone.voxels));
+	}
+	if (settle) {
+		const Scene::Settled fell = scene.settle_floating(settle_lo, settle_hi);
+		std::printf("settled %llu floating pieces, %llu voxels, largest drop %u\n", static_cast<unsigned long long>(fell.pieces), static_cast<unsigned long long>(fell.voxels),
+					fell.largest_drop);
 	}
 	camera.position = {grid_size / 2.f, grid_size / 8.f, 0.8f * grid_height};
 	camera.horizontal_angle = 0.8;

@@ -791,6 +791,64 @@ BM_API int bm_debug_travel_times(bm_scene* scene, const bm_travel_params* params
 BM_API int bm_host_travel_field(const bm_travel_params* params, const uint8_t* volume, const int32_t* seeds, int64_t n, uint32_t* field, bm_travel_result* result);
 BM_API int bm_host_travel_paths(const int32_t extent[3], const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path, int32_t* lengths);
 
+/* ---- rigid settling: floating pieces fall and land (no reference counterpart).  The step between bm_scene_label_components and
+ * bm_scene_write_region: the pieces the caller chooses fall straight down, each as one rigid body, until they rest on the floor, on
+ * something that does not move, or on each other.  All integers; the answer is unique and does not depend on any order, so the same
+ * bytes on every run, and bm_settle == bm_host_settle byte for byte (csrc/settle.h holds the rules once).
+ *  - Inputs.  labels_dev: a tight int32 volume L[z][y][x] in device memory, 0 = empty, equal non-zero values = one rigid piece (what
+ *    bm_scene_label_region writes, but nothing relies on that).  comps_dev: n >= 0 bm_component records in ascending label, as
+ *    bm_scene_label_components writes them (only `label` is read).  chosen_dev: one byte per record.  With n == 0 the three pointers
+ *    comps_dev, chosen_dev and drops_dev may be null.  extent = (nx, ny, nz), 1 ... 16384 each, at most 2^31 - 2 voxels.  z is up.
+ *  - Who moves.  A solid voxel is MOVING when a binary search of the table (the lower bound of its label, then one comparison) finds
+ *    its label at a slot with chosen[slot] != 0.  Every other solid voxel is STATIC, also one whose label is not in the table.  Every
+ *    kernel and the host routine use the same search, so a malformed table still gives every label one answer and nothing can fault.
+ *  - Contacts.  In a column (x, y), a moving voxel at height z whose nearest solid voxel below lies at z' and carries a different label
+ *    -- if there is none, the floor at z' = -1 -- is a contact with gap g = z - z' - 1.  A pair with the same label is no contact: a
+ *    piece is rigid.
+ *  - Drops.  Every moving piece gets a drop >= 0; static pieces and the floor have drop 0.  The drops are the greatest values with
+ *    drop(upper) <= drop(lower) + g for every contact.  That greatest solution exists and is unique: it is the shortest-path distance from
+ *    "ground" in the contact graph, whose weights are not negative.  It is finite, at most nz: the voxel under a piece's lowest voxel
+ *    belongs to the floor, to a static piece or to a piece that reaches lower.  Interlocked pieces (a hook through a ring) come out with
+ *    the drops that keep them apart, a stack comes down as a stack.  No rotation, no sideways motion, no toppling, no friction.
+ *    A chosen record at which no voxel's search arrives (a label without voxels, the second of two equal labels) has drop 0.
+ *  - THE FLOOR IS THE BOTTOM OF THE VOLUME, wherever the caller took it from: a box that ends above the world's ground lets pieces land
+ *    in mid-air at its lowest slice.  Take the box down to the ground.
+ *  - Outputs.  out_dev[z][y][x], a tight uint8 volume (what bm_scene_write_region's replace takes): zeroed, then every solid voxel at z
+ *    writes out[z - drop] = 1 when its drop is 0, 2 when it arrived by falling.  The order within a column is kept and the new gaps are
+ *    g + drop(lower) - drop(upper) >= 0: no two voxels land on one and none lands below 0.  drops_dev[n]: int32 per record, 0 for records
+ *    not chosen.  result_dev: the 32 bytes of a bm_settle_result.  `contacts` counts the contacts as defined above (one per such pair of
+ *    voxels): a fact of the geometry, the same on every run.  The number of rounds is not in the record: it may differ between runs.
+ *  - Waiting.  Like bm_travel_field the call RETURNS WHEN THE RESULT STANDS: it enqueues rounds of relaxation in batches on hip_stream
+ *    and between batches waits on that stream for one small copy.  It cannot be captured into a graph.
+ *  - Refusals, BM_EINVAL with nothing launched and nothing written: an extent below 1 or above 16384; more than 2^31 - 2 voxels; a
+ *    negative n or one above 2^31 - 2; a null pointer (but see n == 0); labels, drops or workspace not 4-byte aligned, records or result
+ *    not 8-byte aligned; a buffer that does not lie inside one allocation of the scene's device; a workspace below
+ *    bm_settle_workspace_bytes; flags other than 0; out overlapping labels; a workspace overlapping anything else. */
+typedef struct bm_settle_result {   /* 32 bytes */
+	uint64_t moved_voxels;          /* the 2s of out */
+	uint32_t chosen_pieces;         /* records with chosen != 0 */
+	uint32_t moved_pieces;          /* of those, with drop > 0 */
+	uint32_t largest_drop;
+	uint32_t reserved;              /* 0 */
+	uint64_t contacts;
+} bm_settle_result;
+/* bytes of device memory bm_settle needs beside its buffers: 4 per record, 4 per 64 columns (x, y) (each part rounded up to 16), plus 72.
+ * Bytes per piece and per column group, none per voxel. */
+BM_API int bm_settle_workspace_bytes(const int32_t extent[3], int64_t n, size_t* bytes);
+/* the buffers and the workspace are the caller's, nothing is allocated on the device and the scene keeps no state (the scene names the
+ * device).  Nothing of the world is read.  Returns when out, the drops and the result stand (see Waiting). */
+BM_API int bm_settle(bm_scene* scene, const int32_t extent[3], const int32_t* labels_dev, const bm_component* comps_dev, int64_t n, const uint8_t* chosen_dev,
+                     uint8_t* out_dev, int32_t* drops_dev, bm_settle_result* result_dev, void* workspace_dev, size_t workspace_bytes, uint32_t flags, void* hip_stream);
+/* measuring door: bm_settle with a hipEvent between its stages and `batch` rounds between two looks of the host (0 = the default);
+ * stage_ms[0 ... 2] = the durations in ms of the set-up, the rounds and the move (with the finish); counts[0] = the rounds enqueued,
+ * counts[1] = the looks of the host */
+BM_API int bm_debug_settle_times(bm_scene* scene, const int32_t extent[3], const int32_t* labels_dev, const bm_component* comps_dev, int64_t n, const uint8_t* chosen_dev,
+                                 uint8_t* out_dev, int32_t* drops_dev, bm_settle_result* result_dev, void* workspace_dev, size_t workspace_bytes, uint32_t flags,
+                                 void* hip_stream, uint32_t batch, float* stage_ms, uint32_t* counts);
+/* the same on host memory, as plain loops (csrc/settle_host.cpp; no device needed); the refusals that concern the extents, n and null pointers */
+BM_API int bm_host_settle(const int32_t extent[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* out, int32_t* drops,
+                          bm_settle_result* result);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

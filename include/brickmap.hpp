@@ -299,6 +299,71 @@ public:
 		return out;
 	}
 
+	// rigid settling (no counterpart in the reference; bm_settle): the chosen pieces of a tight int32 label volume of `extent` in device memory
+	// fall straight down and land; out_dev (uint8: 0 empty, 1 stayed, 2 fell), drops_dev (int32 per record) and result_dev receive the
+	// outcome; workspace_dev: settle_workspace_bytes() bytes of the caller's.  Returns when the result stands.
+	static size_t settle_workspace_bytes(const int32_t extent[3], int64_t n) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_settle_workspace_bytes(extent, n, &bytes));
+		return bytes;
+	}
+	void settle(const int32_t extent[3], const int32_t* labels_dev, const bm_component* comps_dev, int64_t n, const uint8_t* chosen_dev, uint8_t* out_dev, int32_t* drops_dev,
+				bm_settle_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_settle(gpuScene.handle, extent, labels_dev, comps_dev, n, chosen_dev, out_dev, drops_dev, result_dev, workspace_dev, workspace_bytes, 0u, hip_stream));
+	}
+	// Let the floating pieces of the box fall: the components of the box, those without a voxel on one of the `anchor` faces (bits as
+	// bm_component::faces) are chosen, settle, write_region with replace.  A piece that touches an anchor face does not move, and the floor
+	// is the bottom of the box: take lo[2] down to the ground.  Returns what moved.  The host waits.
+	struct Settled { uint64_t pieces, voxels; uint32_t largest_drop; };
+	Settled settle_floating(const int lo[3], const int hi[3], uint32_t anchor = 0x1Fu) {
+		Settled out{0, 0, 0};
+		const size_t voxels = Region(lo, hi).voxels();
+		if (voxels == 0) return out;
+		const int32_t extent[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+		void* buf = nullptr; // the result, the count, the labels, then out
+		BM_CHECKED(bm_buffer_alloc(device_, 40 + voxels * 5, &buf));
+		bm_settle_result* d_result = static_cast<bm_settle_result*>(buf);
+		uint64_t* d_count = reinterpret_cast<uint64_t*>(static_cast<char*>(buf) + 32);
+		int32_t* d_labels = reinterpret_cast<int32_t*>(static_cast<char*>(buf) + 40);
+		uint8_t* d_out = reinterpret_cast<uint8_t*>(d_labels + voxels);
+		void* table = nullptr;
+		try {
+			label_region(lo, hi, d_labels, d_count);
+			uint64_t count = 0;
+			BM_CHECKED(bm_buffer_read(device_, &count, d_count, sizeof count)); // (waits for the device)
+			if (count > 0) {
+				const size_t ws_bytes = settle_workspace_bytes(extent, static_cast<int64_t>(count));
+				const size_t at_drops = count * sizeof(bm_component), at_ws = at_drops + count * 4, at_chosen = at_ws + ((ws_bytes + 3) & ~size_t{3});
+				BM_CHECKED(bm_buffer_alloc(device_, at_chosen + count, &table)); // the records, the drops, the workspace, then chosen
+				char* base = static_cast<char*>(table);
+				bm_component* d_comps = static_cast<bm_component*>(table);
+				label_components(lo, hi, d_labels, d_comps, static_cast<int64_t>(count));
+				std::vector<bm_component> comps(count);
+				BM_CHECKED(bm_buffer_read(device_, comps.data(), d_comps, count * sizeof(bm_component)));
+				std::vector<uint8_t> chosen(count);
+				bool any = false;
+				for (uint64_t i = 0; i < count; ++i)
+					if ((comps[i].faces & anchor) == 0) { chosen[i] = 1; any = true; }
+				if (any) {
+					BM_CHECKED(bm_buffer_write(device_, base + at_chosen, chosen.data(), count));
+					settle(extent, d_labels, d_comps, static_cast<int64_t>(count), reinterpret_cast<const uint8_t*>(base + at_chosen), d_out, reinterpret_cast<int32_t*>(base + at_drops),
+						   d_result, base + at_ws, ws_bytes);
+					bm_settle_result result{};
+					BM_CHECKED(bm_buffer_read(device_, &result, d_result, sizeof result));
+					out = {result.moved_pieces, result.moved_voxels, result.largest_drop};
+					if (result.moved_voxels > 0) write_region(Region(lo, hi), d_out, BM_REGION_REPLACE, BM_VOXELS_DEVICE);
+				}
+			}
+		} catch (...) {
+			if (table) (void)bm_buffer_free(device_, table);
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		if (table) BM_CHECKED(bm_buffer_free(device_, table));
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return out;
+	}
+
 	// triangle meshes -> voxels (no counterpart in the reference; bm_voxelize): n triangles of 9 floats in device memory fill the byte volume
 	// of `params` with 0 / 1; result_dev: null, or a bm_voxelize_result there; workspace_dev: voxelize_workspace_bytes() bytes of the caller's
 	static size_t voxelize_workspace_bytes(const bm_voxelize_params& params, int64_t n) {
