@@ -153,6 +153,17 @@ class bm_settle_result(C.Structure):
                 ("contacts", C.c_uint64)]
 
 
+BM_FOOT_NONE, BM_FOOT_TOWARD, BM_FOOT_NO_FLOOR = 0x7FFFFFFF, 1, 2
+
+
+class bm_foot_params(C.Structure):  # begins with the fields of bm_travel_params: dense_layout fills that part unchanged
+    _fields_ = bm_travel_params._fields_ + [("height", C.c_int32), ("climb", C.c_int32), ("drop", C.c_int32), ("reserved2", C.c_int32)]
+
+
+class bm_foot_result(C.Structure):
+    _fields_ = [("reached", C.c_uint64), ("farthest", C.c_uint32), ("seeds_rejected", C.c_uint32), ("farthest_at", C.c_uint64), ("standable", C.c_uint64)]
+
+
 class bm_volume(C.Structure):
     _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
 
@@ -200,6 +211,7 @@ VOXELIZE_RESULT_DTYPE = np.dtype(bm_voxelize_result)                            
 QUAD_DTYPE, MESH_RESULT_DTYPE = np.dtype(bm_quad), np.dtype(bm_mesh_result)                         # 16 bytes each; a quad's shape = d | w << 4 | h << 8
 DISTANCE_RESULT_DTYPE, TRAVEL_RESULT_DTYPE = np.dtype(bm_distance_result), np.dtype(bm_travel_result)  # 32 bytes each
 SETTLE_RESULT_DTYPE = np.dtype(bm_settle_result)                                                    # 32 bytes
+FOOT_RESULT_DTYPE = np.dtype(bm_foot_result)                                                        # 32 bytes
 # the queue records (variables.h:43-52 RayQueue, :54-59 ShadowQueue), which the header does not declare
 RAY_QUEUE_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("throughput", "<f4", 3), ("normal", "<f4", 3),
                             ("distance", "<f4"), ("identifier", "<i4"), ("bounces", "<i4"), ("pixel_index", "<u4")])
@@ -278,6 +290,14 @@ SIGNATURES = {
     "bm_debug_settle_times": (_i, [_vp, C.POINTER(C.c_int32), _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_uint32, _vp, C.c_uint32, C.POINTER(C.c_float),
                                    C.POINTER(C.c_uint32)]),
     "bm_host_settle": (_i, [C.POINTER(C.c_int32), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.POINTER(bm_settle_result)]),
+    "bm_foot_workspace_bytes": (_i, [C.POINTER(bm_foot_params), C.POINTER(C.c_size_t)]),
+    "bm_foot_room": (_i, [_vp, C.POINTER(bm_foot_params), _vp, _vp, _vp]),
+    "bm_foot_field": (_i, [_vp, C.POINTER(bm_foot_params), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bm_debug_foot_times": (_i, [_vp, C.POINTER(bm_foot_params), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "bm_foot_paths": (_i, [_vp, C.POINTER(bm_foot_params), _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
+    "bm_host_foot_room": (_i, [C.POINTER(bm_foot_params), _vp, _vp]),
+    "bm_host_foot_field": (_i, [C.POINTER(bm_foot_params), _vp, _vp, C.c_int64, _vp, C.POINTER(bm_foot_result)]),
+    "bm_host_foot_paths": (_i, [C.POINTER(bm_foot_params), _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

@@ -11,6 +11,7 @@
 #include "denoise.h"
 #include "kernels.h"
 #include "distance.h"
+#include "foot.h"
 #include "mesh.h"
 #include "reproject.h"
 #include "scene.h"
@@ -365,6 +366,40 @@ int bm_debug_settle_times(bm_scene* scene, const int32_t extent[3], const int32_
 	if (!stage_ms || !counts) { set_error("bm_debug_settle_times: null argument"); return BM_EINVAL; }
 	return bm::settle(scene->impl.gpu(), extent, labels_dev, comps_dev, n, chosen_dev, out_dev, drops_dev, result_dev, workspace_dev, workspace_bytes, flags,
 					  static_cast<hipStream_t>(hip_stream), batch, stage_ms, counts);
+}
+
+// (bm_host_foot_room, bm_host_foot_field and bm_host_foot_paths are csrc/foot_host.cpp: host code that needs nothing of the library)
+int bm_foot_workspace_bytes(const bm_foot_params* params, size_t* bytes) {
+	if (!params || !bytes) { set_error("bm_foot_workspace_bytes: null argument"); return BM_EINVAL; }
+	const bm::FootParamsView pv = bm::foot_params_view(*params);
+	if (const char* why = bm::foot_params_problem(pv)) { set_error(std::string("bm_foot_workspace_bytes: ") + why); return BM_EINVAL; }
+	*bytes = bm::foot_workspace_bytes(bm::foot_dims(pv));
+	return 0;
+}
+
+int bm_foot_room(bm_scene* scene, const bm_foot_params* params, const uint8_t* volume_dev, uint8_t* room_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::foot_room(scene->impl.gpu(), params, volume_dev, room_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_foot_field(bm_scene* scene, const bm_foot_params* params, const uint8_t* room_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev, bm_foot_result* result_dev,
+				  void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::foot_field(scene->impl.gpu(), params, room_dev, seeds_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_foot_times(bm_scene* scene, const bm_foot_params* params, const uint8_t* room_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev,
+						bm_foot_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, uint32_t batch, float* stage_ms, uint32_t* counts) {
+	BM_NEED(scene);
+	if (!stage_ms || !counts) { set_error("bm_debug_foot_times: null argument"); return BM_EINVAL; }
+	return bm::foot_field(scene->impl.gpu(), params, room_dev, seeds_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), batch,
+						  stage_ms, counts);
+}
+
+int bm_foot_paths(bm_scene* scene, const bm_foot_params* params, const uint8_t* room_dev, const uint32_t* field_dev, const int32_t* starts_dev, int64_t n, int32_t capacity,
+				  int32_t* path_dev, int32_t* lengths_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::foot_paths(scene->impl.gpu(), params, room_dev, field_dev, starts_dev, n, capacity, path_dev, lengths_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)

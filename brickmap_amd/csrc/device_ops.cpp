@@ -9,6 +9,7 @@
 #include "denoise.h"
 #include "distance.h"
 #include "error.h"
+#include "foot.h"
 #include "hip_owned.h"
 #include "kernels.h"
 #include "mesh.h"
@@ -381,6 +382,130 @@ int settle(const Gpu& gpu, const int32_t extent[3], const int32_t* labels, const
 		counts[1] = looks;
 	}
 	if (stage_ms) return marks.read(3, stage_ms);
+	return 0;
+}
+
+// ---- ground navigation (bm_foot_room, bm_foot_field, bm_foot_paths): kernels on the caller's stream over the caller's buffers; nothing of
+// the world is read.  The host loop of the rounds is that of travel_field: batches of rounds, and between them one word read back.
+int foot_room(const Gpu& gpu, const bm_foot_params* params, const uint8_t* volume, uint8_t* room, hipStream_t stream) {
+	if (!params) { set_error("bm_foot_room: null params"); return BM_EINVAL; }
+	const FootParamsView pv = foot_params_view(*params);
+	if (const char* why = foot_params_problem(pv)) { set_error(std::string("bm_foot_room: ") + why); return BM_EINVAL; }
+	if (!volume || !room) { set_error("bm_foot_room: null volume or room"); return BM_EINVAL; }
+	const FootDims d = foot_dims(pv);
+	const size_t span = static_cast<size_t>(foot_span(d));
+	BM_HIP(hipSetDevice(gpu.device));
+	// (a volume whose pitches carry it past its allocation has no extent to overlap anything with, see mesh_quads)
+	const bool volume_ok = device_span_ok(gpu.device, volume, span);
+	if (volume_ok && spans_overlap(span_of(volume, span), span_of(room, d.voxels))) { set_error("bm_foot_room: the room volume overlaps the byte volume"); return BM_EINVAL; }
+	if (!volume_ok || !device_span_ok(gpu.device, room, d.voxels)) {
+		set_error("bm_foot_room: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	launch_foot_room(d, volume, room, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+int foot_field(const Gpu& gpu, const bm_foot_params* params, const uint8_t* room, const int32_t* seeds, int64_t n, uint32_t* field, bm_foot_result* result, void* workspace,
+			   size_t workspace_bytes, hipStream_t stream, uint32_t batch, float* stage_ms, uint32_t* counts) {
+	if (!params) { set_error("bm_foot_field: null params"); return BM_EINVAL; }
+	const FootParamsView pv = foot_params_view(*params);
+	if (const char* why = foot_params_problem(pv)) { set_error(std::string("bm_foot_field: ") + why); return BM_EINVAL; }
+	if (n < 0 || n > 0x7FFFFFFF) { set_error("bm_foot_field: a negative number of seeds, or more than 2^31 - 1"); return BM_EINVAL; }
+	if (!room || !field || !result || !workspace || (n > 0 && !seeds)) { set_error("bm_foot_field: null room, seeds, field, result or workspace"); return BM_EINVAL; }
+	const FootDims d = foot_dims(pv);
+	const size_t need = foot_workspace_bytes(d);
+	if (workspace_bytes < need) { set_error("bm_foot_field: the workspace is smaller than bm_foot_workspace_bytes"); return BM_EINVAL; }
+	if (!aligned(field, 4) || !aligned(seeds, 4) || !aligned(result, 8) || !aligned(workspace, 16)) {
+		set_error("bm_foot_field: the field and the seeds must be 4-byte, the result 8-byte and the workspace 16-byte aligned");
+		return BM_EINVAL;
+	}
+	const size_t room_bytes = d.voxels, field_bytes = static_cast<size_t>(d.voxels) * sizeof(uint32_t), seed_bytes = static_cast<size_t>(n) * 12;
+	const Span ws = span_of(workspace, need), fs = span_of(field, field_bytes), ss = span_of(seeds, seed_bytes), rs = span_of(result, sizeof(bm_foot_result)),
+			   os = span_of(room, room_bytes);
+	if (spans_overlap(fs, ws) || spans_overlap(ss, ws) || spans_overlap(rs, ws)) {
+		set_error("bm_foot_field: the workspace overlaps the seeds, the field or the result");
+		return BM_EINVAL;
+	}
+	if (spans_overlap(ss, fs) || spans_overlap(rs, fs)) { set_error("bm_foot_field: the field overlaps the seeds or the result"); return BM_EINVAL; }
+	if (spans_overlap(os, fs) || spans_overlap(os, ws) || spans_overlap(os, rs)) {
+		set_error("bm_foot_field: the room volume overlaps the field, the workspace or the result");
+		return BM_EINVAL;
+	}
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, room, room_bytes) || !device_span_ok(gpu.device, workspace, need) || !device_span_ok(gpu.device, field, field_bytes) ||
+		(n > 0 && !device_span_ok(gpu.device, seeds, seed_bytes)) || !device_span_ok(gpu.device, result, sizeof(bm_foot_result))) {
+		set_error("bm_foot_field: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (batch == 0) batch = kFootBatch;
+	StageMarks<4> marks;
+	if (stage_ms) {
+		if (int e = marks.create(4)) return e;
+	}
+	auto stamp = [&](int i) { if (stage_ms) (void)hipEventRecord(marks.marks()[i], stream); };
+	stamp(0);
+	launch_foot_setup(d, room, seeds, static_cast<uint32_t>(n), field, workspace, stream);
+	stamp(1);
+	// Round k gives the value k, every round but the last appends a stand that was not in the queue, and no value is above the limit:
+	// the front is empty after that many rounds + 2.
+	const uint64_t cap = static_cast<uint64_t>(pv.max_steps != 0 && pv.max_steps < d.queue ? pv.max_steps : d.queue) + 2;
+	const uint8_t* tail = static_cast<const uint8_t*>(workspace) + foot_tail_offset(d);
+	uint64_t done = 0;
+	uint32_t looks = 0, front = n > 0 ? 1u : 0u; // (without seeds no level ever holds a stand)
+	while (front != 0) {
+		if (done >= cap) { set_error("bm_foot_field: internal error: the front is not empty after every round the field can need"); return BM_ESTATE; }
+		const uint32_t rounds = static_cast<uint32_t>(cap - done < batch ? cap - done : batch);
+		launch_foot_rounds(d, room, field, workspace, static_cast<uint32_t>(done) + 1u, rounds, stream);
+		done += rounds;
+		// the size of the next front, level `done`: what round done + 1 would read
+		BM_HIP(hipMemcpyAsync(&front, tail + 4 * (kFootTailCountWord + done % 3), 4, hipMemcpyDeviceToHost, stream));
+		BM_HIP(hipStreamSynchronize(stream));
+		++looks;
+	}
+	stamp(2);
+	launch_foot_finish(d, field, result, workspace, static_cast<uint32_t>(done), stream);
+	stamp(3);
+	BM_HIP(hipGetLastError());
+	BM_HIP(hipStreamSynchronize(stream)); // the call returns when the field and the record stand
+	if (counts) {
+		counts[0] = static_cast<uint32_t>(done);
+		counts[1] = looks;
+	}
+	if (stage_ms) return marks.read(3, stage_ms);
+	return 0;
+}
+
+int foot_paths(const Gpu& gpu, const bm_foot_params* params, const uint8_t* room, const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path,
+			   int32_t* lengths, hipStream_t stream) {
+	if (!params) { set_error("bm_foot_paths: null params"); return BM_EINVAL; }
+	const FootParamsView pv = foot_params_view(*params);
+	if (const char* why = foot_params_problem(pv)) { set_error(std::string("bm_foot_paths: ") + why); return BM_EINVAL; }
+	if (n < 0 || n > 0x7FFFFFFF) { set_error("bm_foot_paths: a negative number of starts, or more than 2^31 - 1"); return BM_EINVAL; }
+	if (capacity < 1) { set_error("bm_foot_paths: a capacity below 1"); return BM_EINVAL; }
+	if (!room || !field || (n > 0 && (!starts || !path || !lengths))) { set_error("bm_foot_paths: null room, field, starts, path or lengths"); return BM_EINVAL; }
+	if (!all_aligned(4, field, starts, path, lengths)) { set_error("bm_foot_paths: the field, the starts, the path and the lengths must be 4-byte aligned"); return BM_EINVAL; }
+	if (static_cast<uint64_t>(n) * static_cast<uint64_t>(capacity) > (uint64_t{1} << 40)) { set_error("bm_foot_paths: more than 2^40 path voxels"); return BM_EINVAL; }
+	const FootDims d = foot_dims(pv);
+	const size_t room_bytes = d.voxels, field_bytes = static_cast<size_t>(d.voxels) * sizeof(uint32_t), start_bytes = static_cast<size_t>(n) * 12,
+				 path_bytes = start_bytes * static_cast<size_t>(capacity), length_bytes = static_cast<size_t>(n) * 4;
+	const Span os = span_of(room, room_bytes), fs = span_of(field, field_bytes), ss = span_of(starts, start_bytes), ps = span_of(path, path_bytes),
+			   ls = span_of(lengths, length_bytes);
+	if (spans_overlap(ps, fs) || spans_overlap(ps, ss) || spans_overlap(ls, fs) || spans_overlap(ls, ss) || spans_overlap(ps, ls)) {
+		set_error("bm_foot_paths: the path or the lengths buffer overlaps the field, the starts or the other of the two");
+		return BM_EINVAL;
+	}
+	if (spans_overlap(os, ps) || spans_overlap(os, ls)) { set_error("bm_foot_paths: the room volume overlaps the path or the lengths"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, room, room_bytes) || !device_span_ok(gpu.device, field, field_bytes) ||
+		(n > 0 && (!device_span_ok(gpu.device, starts, start_bytes) || !device_span_ok(gpu.device, path, path_bytes) || !device_span_ok(gpu.device, lengths, length_bytes)))) {
+		set_error("bm_foot_paths: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (n == 0) return 0;
+	launch_foot_paths(d, room, field, starts, static_cast<uint32_t>(n), capacity, path, lengths, stream);
+	BM_HIP(hipGetLastError());
 	return 0;
 }
 

@@ -51,6 +51,15 @@ int travel_paths(const Gpu& gpu, const int32_t extent[3], const uint32_t* field,
 int settle(const Gpu& gpu, const int32_t extent[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* out, int32_t* drops,
 		   bm_settle_result* result, void* workspace, size_t workspace_bytes, uint32_t flags, hipStream_t stream, uint32_t batch = 0, float* stage_ms = nullptr,
 		   uint32_t* counts = nullptr);
+// ground navigation (foot.hip): a byte volume -> room bytes; room bytes + seeds -> the walk field and the record; a field -> paths.  The
+// buffers and the workspace are the caller's.  foot_room and foot_paths are asynchronous; like travel_field, foot_field returns when the
+// field stands: it waits on `stream` between batches of `batch` rounds (0 = kFootBatch).  stage_ms: null, or 3 durations -- set-up,
+// rounds, finish; counts: null, or the rounds enqueued and the looks of the host (bm_debug_foot_times)
+int foot_room(const Gpu& gpu, const bm_foot_params* params, const uint8_t* volume, uint8_t* room, hipStream_t stream);
+int foot_field(const Gpu& gpu, const bm_foot_params* params, const uint8_t* room, const int32_t* seeds, int64_t n, uint32_t* field, bm_foot_result* result, void* workspace,
+			   size_t workspace_bytes, hipStream_t stream, uint32_t batch = 0, float* stage_ms = nullptr, uint32_t* counts = nullptr);
+int foot_paths(const Gpu& gpu, const bm_foot_params* params, const uint8_t* room, const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path,
+			   int32_t* lengths, hipStream_t stream);
 // pixel-centre rays of a frame, written on the device (denoise.hip)
 int pixel_rays(const Gpu& gpu, const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
 // temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, travel.hip, settle.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, travel.hip, settle.hip, foot.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -191,6 +191,18 @@ void launch_settle_rounds(const SettleDims& d, const int32_t* labels, const void
 						  hipStream_t stream);
 void launch_settle_move(const SettleDims& d, const int32_t* labels, const void* records, const uint8_t* chosen, uint8_t* out, int32_t* drops, void* result, void* workspace,
 						hipStream_t stream);
+
+// a byte volume -> room bytes, room bytes + seeds -> walk distances and paths (foot.hip; foot.h has the rules, FootDims and the workspace's
+// layout).  The caller (device_ops.cpp) enqueues the set-up, then rounds in batches -- between batches it reads the size of the next front
+// from the tail and stops at 0 -- then the finish with the number of rounds enqueued.  workspace: foot_workspace_bytes() bytes, 16-byte
+// aligned, that no other launch uses until the finish has run (its tail is zeroed by the set-up).  Rounds count from 1.
+struct FootDims;
+void launch_foot_room(const FootDims& d, const uint8_t* volume, uint8_t* room, hipStream_t stream);
+void launch_foot_setup(const FootDims& d, const uint8_t* room, const int32_t* seeds, uint32_t n, uint32_t* field, void* workspace, hipStream_t stream);
+void launch_foot_rounds(const FootDims& d, const uint8_t* room, uint32_t* field, void* workspace, uint32_t first_round, uint32_t rounds, hipStream_t stream);
+void launch_foot_finish(const FootDims& d, const uint32_t* field, void* result, void* workspace, uint32_t done, hipStream_t stream);
+void launch_foot_paths(const FootDims& d, const uint8_t* room, const uint32_t* field, const int32_t* starts, uint32_t n, int32_t capacity, int32_t* path, int32_t* lengths,
+					   hipStream_t stream);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--path x0,y0,z0:x1,y1,z1] [--drop-floating x0,y0,z0:x1,y1,z1] [--settle x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--path x0,y0,z0:x1,y1,z1] [--walk x0,y0,z0:x1,y1,z1] [--drop-floating x0,y0,z0:x1,y1,z1] [--settle x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -19,6 +19,9 @@
 // --path x0,y0,z0:x1,y1,z1, applied after --dig, --grow and --shrink: a shortest face-step path through the empty voxels from the first
 // voxel to the second, by the exact travel field of their surroundings on the GPU (Scene::find_path); prints "path of N voxels:" and the
 // voxels, or "no path".
+// --walk x0,y0,z0:x1,y1,z1, applied where --path is: a shortest walk on foot from the ground under the first voxel to the ground under the
+// second, for an agent two voxels tall that climbs one voxel and drops three per move, by the exact walk field of their surroundings on
+// the GPU (Scene::find_walk); prints "walk of N voxels:" and the voxels, or "no way on foot".
 // --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig and --shrink: the pieces of that box that hang on nothing -- connected components by faces,
 // inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
 // and voxels went.
@@ -64,6 +67,8 @@ int main(int argc_in, char** argv_in) {
 	int morph_r2[2] = {0, 0};
 	int path_ends[2][3] = {{0, 0, 0}, {0, 0, 0}};
 	bool path = false;
+	int walk_ends[2][3] = {{0, 0, 0}, {0, 0, 0}};
+	bool walk = false;
 	const char* voxels_path = nullptr;
 	bool denoise = false, temporal = false;
 	std::string paste_path;
@@ -148,6 +153,14 @@ int main(int argc_in, char** argv_in) {
 				return 2;
 			}
 			settle = true;
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--walk" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d,%d:%d,%d,%d", &walk_ends[0][0], &walk_ends[0][1], &walk_ends[0][2], &walk_ends[1][0], &walk_ends[1][1], &walk_ends[1][2]) != 6) {
+				std::cerr << "--walk wants x0,y0,z0:x1,y1,z1\n";
+				return 2;
+			}
+			walk = true;
 			continue;
 		}
 		if (std::string(argv_in[i]) == "--path" && i + 1 < argc_in) {
@@ -236,6 +249,15 @@ int main(int argc_in, char** argv_in) {
 		if (voxels.empty()) std::printf("no path\n");
 		else {
 			std::printf("path of %zu voxels:", voxels.size());
+			for (const auto& v : voxels) std::printf(" %d,%d,%d", v[0], v[1], v[2]);
+			std::printf("\n");
+		}
+	}
+	if (walk) {
+		const auto voxels = scene.find_walk(walk_ends[0], walk_ends[1]);
+		if (voxels.empty()) std::printf("no way on foot\n");
+		else {
+			std::printf("walk of %zu voxels:", voxels.size());
 			for (const auto& v : voxels) std::printf(" %d,%d,%d", v[0], v[1], v[2]);
 			std::printf("\n");
 		}

@@ -849,6 +849,90 @@ BM_API int bm_debug_settle_times(bm_scene* scene, const int32_t extent[3], const
 BM_API int bm_host_settle(const int32_t extent[3], const int32_t* labels, const bm_component* comps, int64_t n, const uint8_t* chosen, uint8_t* out, int32_t* drops,
                           bm_settle_result* result);
 
+/* ---- ground navigation: exact walk fields and paths for an agent on foot (no reference counterpart).  bm_travel_field answers "how do I
+ * get there" for something that flies; these three answer it for something that stands on solid ground, is taller than one voxel, climbs a
+ * step but not a wall, drops off a ledge it could never climb back, and bumps its head under a lintel.  All integers; every move costs 1, a
+ * breadth-first distance in a directed graph of unit moves is unique, so the same bytes on every run whatever order anything ran in, and
+ * bm_foot_* == bm_host_foot_* byte for byte (csrc/foot.h holds the rules once).
+ *  - Input.  A dense byte volume V[z][y][x] in device memory: any non-zero byte is blocked, z is up; x contiguous, rows and slices at
+ *    the given pitches, 0 = tight; any base alignment; extents and voxel limit those of bm_travel_params.  Only bm_foot_room reads it.
+ *  - Room byte.  bm_foot_room writes a tight byte volume room[z][y][x].  Low 7 bits R: 0 for a blocked voxel, otherwise the number of
+ *    consecutive free voxels from this one upwards, capped at 127.  Everything ABOVE the volume counts as free, so a free run that reaches
+ *    the top is 127.  Bit 7, supported: set when the voxel is free and the voxel below it is blocked; at z = 0 it is set when the voxel is
+ *    free, unless BM_FOOT_NO_FLOOR is given.  THE FLOOR IS THE BOTTOM OF THE BOX, as in bm_settle; the flag is for boxes that end above the
+ *    ground.  The byte does not depend on the agent (height, climb, drop, max_steps and BM_FOOT_TOWARD are validated and otherwise unused).
+ *  - Stand.  With height h in 1 ... 32 a voxel p is a STAND when it is supported and R(p) >= h.
+ *  - Move.  p -> q is legal when q lies in one of the four columns (x +- 1, y), (x, y +- 1) inside the volume, p and q are both stands,
+ *    -drop <= z(q) - z(p) <= climb with climb in 0 ... 32 and drop in 0 ... 64, and the LOWER of the two has R >= h + |dz|: the agent rises
+ *    or falls in the lower voxel's column through free voxels and crosses sideways at the upper height.  Every move costs 1.  No
+ *    diagonals.  Since h + 64 <= 96 < 127 the cap on R never decides a move.
+ *  - Field.  bm_foot_field takes the room volume and n >= 0 seeds, int32 seeds[n][3] = (x, y, z) (the pointer may be null when n is 0),
+ *    and gives a tight uint32_t field W[z][y][x], 4-byte aligned.  With flags 0, W(p) is the least number of moves of a walk from an
+ *    accepted seed to p; with BM_FOOT_TOWARD the least number of moves from p to a seed (the same search with climb and drop exchanged).
+ *    W(p) is BM_FOOT_NONE = 0x7FFFFFFF where p is no stand, where p is unreachable, and where p lies beyond max_steps (0 = no limit).  A
+ *    seed is accepted when it lies inside the volume on a stand; the others are counted.  Duplicates are fine.  BM_FOOT_NO_FLOOR is
+ *    ignored here: the room bytes carry it.
+ *  - Result (32 bytes on the device, 8-byte aligned): reached = the voxels with a finite value; farthest = the largest finite value,
+ *    BM_FOOT_NONE when none is finite; seeds_rejected; farthest_at = the lowest linear index (z ny + y) nx + x that holds `farthest`, 0
+ *    when there is none; standable = the number of stands.
+ *  - Paths.  bm_foot_paths takes the params, the room, a field, n >= 0 starts (int32 starts[n][3]), a per-path capacity >= 1,
+ *    int32 path[n][capacity][3] and int32 lengths[n].  lengths[q] = W(start) + 1, or 0 when the start is outside the volume or has no
+ *    finite value.  The first min(length, capacity) voxels are written, the start first: from p the next voxel is the first q that holds
+ *    W(p) - 1 and whose move is legal, the columns in the order -x, +x, -y, +y and inside a column in ascending z.  Legal means p -> q with
+ *    BM_FOOT_TOWARD and q -> p without it: without the flag the written path is the walk reversed.  If no q qualifies the walk stops and
+ *    lengths[q] = -1.  The walk is bounded by W(start) and capacity; a truncated path keeps its first voxels.
+ *  - Waiting.  bm_foot_room and bm_foot_paths are asynchronous on hip_stream like everything else.  Like bm_travel_field, bm_foot_field
+ *    RETURNS WHEN THE FIELD STANDS: it enqueues rounds in batches on hip_stream and between batches waits on that stream for one word, the
+ *    size of the next front.  It therefore cannot be captured into a graph.
+ *  - Refusals, BM_EINVAL with nothing launched and nothing written: those of bm_travel_field and bm_travel_paths (extents, voxels,
+ *    pitches, spans, null pointers, alignment -- field, seeds, starts, path, lengths 4-byte, result 8-byte, workspace 16-byte --, a workspace
+ *    below bm_foot_workspace_bytes, the overlaps, n, capacity, n * capacity); a height outside 1 ... 32, a climb outside 0 ... 32, a drop
+ *    outside 0 ... 64; a flag bit other than the two, a non-zero `reserved` or `reserved2`; a room volume that overlaps the byte volume,
+ *    the field, the workspace, the result, the path or the lengths. */
+#define BM_FOOT_NONE 0x7FFFFFFFu
+#define BM_FOOT_TOWARD 1u   /* bm_foot_field, bm_foot_paths: W counts the moves from p to a seed */
+#define BM_FOOT_NO_FLOOR 2u /* bm_foot_room: the bottom of the volume does not support */
+typedef struct bm_foot_params { /* begins with the 40 bytes of a bm_travel_params */
+	int32_t extent[3];   /* nx, ny, nz: 1 ... 16384 */
+	uint32_t max_steps;  /* 0 = no limit */
+	int64_t row_pitch;   /* of the byte volume: bytes from one x-row to the next y; 0 = tight (nx) */
+	int64_t slice_pitch; /* bytes from one z-slice to the next; 0 = tight (row_pitch * ny) */
+	uint32_t flags;      /* BM_FOOT_TOWARD | BM_FOOT_NO_FLOOR */
+	uint32_t reserved;   /* 0 */
+	int32_t height;      /* 1 ... 32 */
+	int32_t climb;       /* 0 ... 32 */
+	int32_t drop;        /* 0 ... 64 */
+	int32_t reserved2;   /* 0 */
+} bm_foot_params;
+typedef struct bm_foot_result {
+	uint64_t reached;
+	uint32_t farthest, seeds_rejected;
+	uint64_t farthest_at;
+	uint64_t standable;
+} bm_foot_result;
+/* bytes of device memory bm_foot_field needs beside its buffers: the queue, 4 bytes for each of ceil(nz / 2) * ny * nx entries -- a
+ * column holds at most that many stands, and a stand enters the queue once -- rounded up to 16, plus 64.  At most 2 bytes per voxel. */
+BM_API int bm_foot_workspace_bytes(const bm_foot_params* params, size_t* bytes);
+/* the buffers and the workspace are the caller's, nothing is allocated on the device and the scene keeps no state (the scene names the
+ * device).  Nothing of the world is read. */
+BM_API int bm_foot_room(bm_scene* scene, const bm_foot_params* params, const uint8_t* volume_dev, uint8_t* room_dev, void* hip_stream);
+/* returns when the field and the result stand (see Waiting) */
+BM_API int bm_foot_field(bm_scene* scene, const bm_foot_params* params, const uint8_t* room_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev,
+                         bm_foot_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+BM_API int bm_foot_paths(bm_scene* scene, const bm_foot_params* params, const uint8_t* room_dev, const uint32_t* field_dev, const int32_t* starts_dev, int64_t n,
+                         int32_t capacity, int32_t* path_dev, int32_t* lengths_dev, void* hip_stream);
+/* measuring door: bm_foot_field with a hipEvent between its stages and `batch` rounds between two looks of the host (0 = the default);
+ * stage_ms[0 ... 2] = the durations in ms of the set-up (fill, count of stands, seeds), the rounds and the finish; counts[0] = the rounds
+ * enqueued, counts[1] = the looks of the host */
+BM_API int bm_debug_foot_times(bm_scene* scene, const bm_foot_params* params, const uint8_t* room_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev,
+                               bm_foot_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, uint32_t batch, float* stage_ms,
+                               uint32_t* counts);
+/* the same on host memory, as plain loops (csrc/foot_host.cpp; no device needed); the refusals that concern params, n, capacity and null pointers */
+BM_API int bm_host_foot_room(const bm_foot_params* params, const uint8_t* volume, uint8_t* room);
+BM_API int bm_host_foot_field(const bm_foot_params* params, const uint8_t* room, const int32_t* seeds, int64_t n, uint32_t* field, bm_foot_result* result);
+BM_API int bm_host_foot_paths(const bm_foot_params* params, const uint8_t* room, const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path,
+                              int32_t* lengths);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

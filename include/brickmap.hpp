@@ -612,6 +612,105 @@ public:
 		return out;
 	}
 
+	// ground navigation (no counterpart in the reference; bm_foot_room, bm_foot_field, bm_foot_paths): the byte volume of `params` in device
+	// memory gives a tight room volume (one byte per voxel); the room bytes and n seeds give the tight uint32 walk field and the result;
+	// a field gives paths.  workspace_dev: foot_workspace_bytes() bytes of the caller's.  foot_field returns when the field stands, the
+	// other two are asynchronous.
+	static size_t foot_workspace_bytes(const bm_foot_params& params) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_foot_workspace_bytes(&params, &bytes));
+		return bytes;
+	}
+	void foot_room(const bm_foot_params& params, const uint8_t* volume_dev, uint8_t* room_dev, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_foot_room(gpuScene.handle, &params, volume_dev, room_dev, hip_stream));
+	}
+	void foot_field(const bm_foot_params& params, const uint8_t* room_dev, const int32_t* seeds_dev, int64_t n, uint32_t* field_dev, bm_foot_result* result_dev, void* workspace_dev,
+					size_t workspace_bytes, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_foot_field(gpuScene.handle, &params, room_dev, seeds_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, hip_stream));
+	}
+	void foot_paths(const bm_foot_params& params, const uint8_t* room_dev, const uint32_t* field_dev, const int32_t* starts_dev, int64_t n, int32_t capacity, int32_t* path_dev,
+					int32_t* lengths_dev, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_foot_paths(gpuScene.handle, &params, room_dev, field_dev, starts_dev, n, capacity, path_dev, lengths_dev, hip_stream));
+	}
+	// A shortest walk from world voxel `start` to world voxel `goal` for an agent `height` voxels tall that climbs `climb` and drops `drop`
+	// voxels per move, inside the box of find_path taken down by `drop`: the box is read on the device (read_region), the room bytes are
+	// made with the floor where the box stands on the world's bottom, both ends are snapped to the highest stand at or below them in
+	// their columns, the field is seeded at the goal with BM_FOOT_TOWARD, and the walk goes down from the start.  Returns the walk's world
+	// voxels, the start's ground first and the goal's last; empty when there is no way on foot.  The host waits.
+	std::vector<std::array<int, 3>> find_walk(const int start[3], const int goal[3], int height = 2, int climb = 1, int drop = 3) {
+		std::vector<std::array<int, 3>> out;
+		bm_scene_info info;
+		BM_CHECKED(bm_scene_get_info(gpuScene.handle, &info));
+		const int world[3] = {info.grid_size, info.grid_size, info.grid_height};
+		int lo[3], hi[3];
+		int32_t ends[6]; // the goal (the seed), then the start, in the box's coordinates
+		bm_foot_params p{};
+		for (int a = 0; a < 3; ++a) {
+			const int mn = start[a] < goal[a] ? start[a] : goal[a], mx = start[a] < goal[a] ? goal[a] : start[a], down = a == 2 ? 32 + drop : 32;
+			lo[a] = mn - down > 0 ? mn - down : 0;
+			hi[a] = mx + 33 < world[a] ? mx + 33 : world[a];
+			if (hi[a] <= lo[a]) return out;
+			p.extent[a] = hi[a] - lo[a];
+			ends[a] = goal[a] - lo[a];
+			ends[3 + a] = start[a] - lo[a];
+		}
+		p.height = height;
+		p.climb = climb;
+		p.drop = drop;
+		p.flags = BM_FOOT_TOWARD | (lo[2] == 0 ? 0u : BM_FOOT_NO_FLOOR);
+		const size_t voxels = Region(lo, hi).voxels(), ws_bytes = foot_workspace_bytes(p);
+		const size_t at_ends = 32, at_len = at_ends + 32, at_ws = at_len + 16, at_field = at_ws + ws_bytes, at_vol = at_field + voxels * 4, at_room = at_vol + voxels;
+		void* buf = nullptr; // the result, the two ends, the path's length, the workspace, the field, the volume, then the room bytes
+		BM_CHECKED(bm_buffer_alloc(device_, at_room + voxels, &buf));
+		char* base = static_cast<char*>(buf);
+		void* path_buf = nullptr;
+		try {
+			read_region(Region(lo, hi), reinterpret_cast<uint8_t*>(base + at_vol), BM_VOXELS_DEVICE);
+			const uint8_t* room = reinterpret_cast<const uint8_t*>(base + at_room);
+			foot_room(p, reinterpret_cast<const uint8_t*>(base + at_vol), reinterpret_cast<uint8_t*>(base + at_room));
+			std::vector<uint8_t> cells(voxels);
+			BM_CHECKED(bm_buffer_read(device_, cells.data(), room, voxels)); // (waits for the device)
+			bool grounded = true;
+			for (int e = 0; e < 2; ++e) { // the highest stand at or below each end
+				int32_t* at = ends + 3 * e;
+				bool found = false;
+				if (at[0] >= 0 && at[1] >= 0 && at[2] >= 0 && at[0] < p.extent[0] && at[1] < p.extent[1] && at[2] < p.extent[2])
+					for (int32_t z = at[2]; z >= 0 && !found; --z) {
+						const uint8_t cell = cells[(static_cast<size_t>(z) * p.extent[1] + at[1]) * p.extent[0] + at[0]];
+						if ((cell & 0x80u) && (cell & 0x7Fu) >= static_cast<unsigned>(height)) {
+							at[2] = z;
+							found = true;
+						}
+					}
+				grounded = grounded && found;
+			}
+			if (grounded) {
+				BM_CHECKED(bm_buffer_write(device_, base + at_ends, ends, sizeof ends));
+				uint32_t* field = reinterpret_cast<uint32_t*>(base + at_field);
+				foot_field(p, room, reinterpret_cast<const int32_t*>(base + at_ends), 1, field, reinterpret_cast<bm_foot_result*>(base), base + at_ws, ws_bytes);
+				uint32_t t = BM_FOOT_NONE;
+				BM_CHECKED(bm_buffer_read(device_, &t, field + (static_cast<size_t>(ends[5]) * p.extent[1] + ends[4]) * p.extent[0] + ends[3], sizeof t));
+				if (t != BM_FOOT_NONE) {
+					const int32_t capacity = static_cast<int32_t>(t) + 1;
+					BM_CHECKED(bm_buffer_alloc(device_, static_cast<size_t>(capacity) * 12, &path_buf));
+					foot_paths(p, room, field, reinterpret_cast<const int32_t*>(base + at_ends) + 3, 1, capacity, static_cast<int32_t*>(path_buf),
+							   reinterpret_cast<int32_t*>(base + at_len));
+					std::vector<int32_t> host(static_cast<size_t>(capacity) * 3);
+					BM_CHECKED(bm_buffer_read(device_, host.data(), path_buf, host.size() * 4)); // (waits for the device)
+					out.resize(static_cast<size_t>(capacity));
+					for (size_t k = 0; k < out.size(); ++k) out[k] = {host[3 * k] + lo[0], host[3 * k + 1] + lo[1], host[3 * k + 2] + lo[2]};
+				}
+			}
+		} catch (...) {
+			if (path_buf) (void)bm_buffer_free(device_, path_buf);
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		if (path_buf) BM_CHECKED(bm_buffer_free(device_, path_buf));
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return out;
+	}
+
 private:
 	uint64_t morph(const int lo[3], const int hi[3], uint32_t radius_sq, bool erode) {
 		bool bad = radius_sq < 1 || radius_sq > 3u * 16383u * 16383u;
