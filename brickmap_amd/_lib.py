@@ -164,6 +164,18 @@ class bm_foot_result(C.Structure):
     _fields_ = [("reached", C.c_uint64), ("farthest", C.c_uint32), ("seeds_rejected", C.c_uint32), ("farthest_at", C.c_uint64), ("standable", C.c_uint64)]
 
 
+BM_WATER_NONE = 0x7FFFFFFF
+BM_WATER_FACES = {"-x": 1, "+x": 2, "-y": 4, "+y": 8, "-z": 16, "+z": 32}   # the bits of bm_component.faces
+
+
+class bm_water_params(C.Structure):  # a bm_travel_params with sea_level where max_steps is: dense_layout fills the rest unchanged
+    _fields_ = [("extent", C.c_int32 * 3), ("sea_level", C.c_uint32), ("row_pitch", C.c_int64), ("slice_pitch", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class bm_water_result(C.Structure):
+    _fields_ = [("wet", C.c_uint64), ("deepest", C.c_uint32), ("drains_rejected", C.c_uint32), ("deepest_at", C.c_uint64), ("closed", C.c_uint64)]
+
+
 class bm_volume(C.Structure):
     _fields_ = [("shape", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("center", C.c_int32 * 3), ("radius", C.c_int32), ("reserved", C.c_uint32)]
 
@@ -212,6 +224,7 @@ QUAD_DTYPE, MESH_RESULT_DTYPE = np.dtype(bm_quad), np.dtype(bm_mesh_result)     
 DISTANCE_RESULT_DTYPE, TRAVEL_RESULT_DTYPE = np.dtype(bm_distance_result), np.dtype(bm_travel_result)  # 32 bytes each
 SETTLE_RESULT_DTYPE = np.dtype(bm_settle_result)                                                    # 32 bytes
 FOOT_RESULT_DTYPE = np.dtype(bm_foot_result)                                                        # 32 bytes
+WATER_RESULT_DTYPE = np.dtype(bm_water_result)                                                      # 32 bytes
 # the queue records (variables.h:43-52 RayQueue, :54-59 ShadowQueue), which the header does not declare
 RAY_QUEUE_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("throughput", "<f4", 3), ("normal", "<f4", 3),
                             ("distance", "<f4"), ("identifier", "<i4"), ("bounces", "<i4"), ("pixel_index", "<u4")])
@@ -298,6 +311,12 @@ SIGNATURES = {
     "bm_host_foot_room": (_i, [C.POINTER(bm_foot_params), _vp, _vp]),
     "bm_host_foot_field": (_i, [C.POINTER(bm_foot_params), _vp, _vp, C.c_int64, _vp, C.POINTER(bm_foot_result)]),
     "bm_host_foot_paths": (_i, [C.POINTER(bm_foot_params), _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp]),
+    "bm_water_workspace_bytes": (_i, [C.POINTER(bm_water_params), C.POINTER(C.c_size_t)]),
+    "bm_water_field": (_i, [_vp, C.POINTER(bm_water_params), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bm_debug_water_times": (_i, [_vp, C.POINTER(bm_water_params), _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_size_t, _vp, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "bm_water_mask": (_i, [_vp, C.POINTER(C.c_int32), _vp, C.c_uint32, _vp, _vp]),
+    "bm_host_water_field": (_i, [C.POINTER(bm_water_params), _vp, _vp, C.c_int64, _vp, C.POINTER(bm_water_result)]),
+    "bm_host_water_mask": (_i, [C.POINTER(C.c_int32), _vp, C.c_uint32, _vp]),
     "bm_camera_pixel_rays": (_i, [C.POINTER(bm_camera), _i, _i, C.c_int64, _vp, _vp, _vp]),
     "bm_camera_pixel_rays_device": (_i, [_vp, C.POINTER(bm_camera), _i, _i, _vp, _vp]),
     "bm_denoise_workspace_bytes": (_i, [_i, _i, C.POINTER(C.c_size_t)]),

@@ -18,6 +18,7 @@
 #include "settle.h"
 #include "travel.h"
 #include "voxelize.h"
+#include "water.h"
 #include "wavefront.h"
 
 struct bm_scene {
@@ -400,6 +401,34 @@ int bm_foot_paths(bm_scene* scene, const bm_foot_params* params, const uint8_t* 
 				  int32_t* path_dev, int32_t* lengths_dev, void* hip_stream) {
 	BM_NEED(scene);
 	return bm::foot_paths(scene->impl.gpu(), params, room_dev, field_dev, starts_dev, n, capacity, path_dev, lengths_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+// (bm_host_water_field and bm_host_water_mask are csrc/water_host.cpp: host code that needs nothing of the library)
+int bm_water_workspace_bytes(const bm_water_params* params, size_t* bytes) {
+	if (!params || !bytes) { set_error("bm_water_workspace_bytes: null argument"); return BM_EINVAL; }
+	const bm::TravelParamsView pv = bm::water_params_view(*params);
+	if (const char* why = bm::water_params_problem(pv)) { set_error(std::string("bm_water_workspace_bytes: ") + why); return BM_EINVAL; }
+	*bytes = bm::travel_workspace_bytes(bm::water_dims(pv));
+	return 0;
+}
+
+int bm_water_field(bm_scene* scene, const bm_water_params* params, const uint8_t* volume_dev, const int32_t* drains_dev, int64_t n, uint32_t* field_dev,
+				   bm_water_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::water_field(scene->impl.gpu(), params, volume_dev, drains_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+int bm_debug_water_times(bm_scene* scene, const bm_water_params* params, const uint8_t* volume_dev, const int32_t* drains_dev, int64_t n, uint32_t* field_dev,
+						 bm_water_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, uint32_t batch, float* stage_ms, uint32_t* counts) {
+	BM_NEED(scene);
+	if (!stage_ms || !counts) { set_error("bm_debug_water_times: null argument"); return BM_EINVAL; }
+	return bm::water_field(scene->impl.gpu(), params, volume_dev, drains_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, static_cast<hipStream_t>(hip_stream), batch,
+						   stage_ms, counts);
+}
+
+int bm_water_mask(bm_scene* scene, const int32_t extent[3], const uint32_t* field_dev, uint32_t min_depth, uint8_t* mask_dev, void* hip_stream) {
+	BM_NEED(scene);
+	return bm::water_mask(scene->impl.gpu(), extent, field_dev, min_depth, mask_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 // (bm_host_reproject is csrc/reproject_host.cpp: host code that needs nothing of the library)

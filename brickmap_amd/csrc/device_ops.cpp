@@ -16,6 +16,7 @@
 #include "settle.h"
 #include "travel.h"
 #include "voxelize.h"
+#include "water.h"
 
 namespace bm {
 
@@ -307,6 +308,101 @@ int travel_paths(const Gpu& gpu, const int32_t extent[3], const uint32_t* field,
 	}
 	if (n == 0) return 0;
 	launch_travel_paths(d, field, starts, static_cast<uint32_t>(n), capacity, path, lengths, stream);
+	BM_HIP(hipGetLastError());
+	return 0;
+}
+
+// ---- voxels + drains -> spill levels and pools (bm_water_field, bm_water_mask): kernels on the caller's stream over the caller's buffers;
+// nothing of the world is read.  The refusals and the host loop of the rounds are those of travel_field.
+int water_field(const Gpu& gpu, const bm_water_params* params, const uint8_t* volume, const int32_t* drains, int64_t n, uint32_t* field, bm_water_result* result,
+				void* workspace, size_t workspace_bytes, hipStream_t stream, uint32_t batch, float* stage_ms, uint32_t* counts) {
+	if (!params) { set_error("bm_water_field: null params"); return BM_EINVAL; }
+	const TravelParamsView pv = water_params_view(*params);
+	if (const char* why = water_params_problem(pv)) { set_error(std::string("bm_water_field: ") + why); return BM_EINVAL; }
+	if (n < 0 || n > 0x7FFFFFFF) { set_error("bm_water_field: a negative number of drains, or more than 2^31 - 1"); return BM_EINVAL; }
+	if (!volume || !field || !result || !workspace || (n > 0 && !drains)) { set_error("bm_water_field: null volume, drains, field, result or workspace"); return BM_EINVAL; }
+	const TravelDims d = water_dims(pv);
+	const size_t need = travel_workspace_bytes(d);
+	if (workspace_bytes < need) { set_error("bm_water_field: the workspace is smaller than bm_water_workspace_bytes"); return BM_EINVAL; }
+	if (!aligned(field, 4) || !aligned(drains, 4) || !aligned(result, 8) || !aligned(workspace, 16)) {
+		set_error("bm_water_field: the field and the drains must be 4-byte, the result 8-byte and the workspace 16-byte aligned");
+		return BM_EINVAL;
+	}
+	const size_t span = static_cast<size_t>(travel_span(d)), field_bytes = static_cast<size_t>(d.voxels) * sizeof(uint32_t), drain_bytes = static_cast<size_t>(n) * 12;
+	const Span ws = span_of(workspace, need), fs = span_of(field, field_bytes), ss = span_of(drains, drain_bytes), rs = span_of(result, sizeof(bm_water_result));
+	BM_HIP(hipSetDevice(gpu.device));
+	// (a volume whose pitches carry it past its allocation has no extent to overlap anything with, see mesh_quads)
+	const bool volume_ok = device_span_ok(gpu.device, volume, span);
+	if ((volume_ok && spans_overlap(span_of(volume, span), ws)) || spans_overlap(fs, ws) || spans_overlap(ss, ws) || spans_overlap(rs, ws)) {
+		set_error("bm_water_field: the workspace overlaps the volume, the drains, the field or the result");
+		return BM_EINVAL;
+	}
+	if ((volume_ok && spans_overlap(span_of(volume, span), fs)) || spans_overlap(ss, fs) || spans_overlap(rs, fs)) {
+		set_error("bm_water_field: the field overlaps the volume, the drains or the result");
+		return BM_EINVAL;
+	}
+	if (!volume_ok || !device_span_ok(gpu.device, workspace, need) || !device_span_ok(gpu.device, field, field_bytes) || (n > 0 && !device_span_ok(gpu.device, drains, drain_bytes)) ||
+		!device_span_ok(gpu.device, result, sizeof(bm_water_result))) {
+		set_error("bm_water_field: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	if (batch == 0) batch = kTravelBatch;
+	StageMarks<4> marks;
+	if (stage_ms) {
+		if (int e = marks.create(4)) return e;
+	}
+	auto stamp = [&](int i) { if (stage_ms) (void)hipEventRecord(marks.marks()[i], stream); };
+	stamp(0);
+	launch_water_setup(d, params->sea_level, params->flags & kWaterFaces, volume, drains, static_cast<uint32_t>(n), field, workspace, stream);
+	stamp(1);
+	// Round k settles every voxel whose best path crosses at most k - 1 tile faces (water.h), and a best path without a repeated voxel
+	// crosses fewer faces than the volume has voxels: the list is empty after that many rounds + 2.
+	const uint64_t cap = static_cast<uint64_t>(d.voxels) + 2;
+	const uint8_t* tail = static_cast<const uint8_t*>(workspace) + travel_tail_offset(d);
+	uint64_t done = 0;
+	uint32_t looks = 0, listed = 0;
+	// whether anything is an outlet is known on the device only: the first list's count, what round 1 would read
+	BM_HIP(hipMemcpyAsync(&listed, tail + 4 * (kTravelTailCountWord + 1), 4, hipMemcpyDeviceToHost, stream));
+	BM_HIP(hipStreamSynchronize(stream));
+	++looks;
+	while (listed != 0) {
+		if (done >= cap) { set_error("bm_water_field: internal error: tiles are still listed after every round the field can need"); return BM_ESTATE; }
+		const uint32_t rounds = static_cast<uint32_t>(cap - done < batch ? cap - done : batch);
+		launch_water_rounds(d, field, workspace, static_cast<uint32_t>(done) + 1u, rounds, stream);
+		done += rounds;
+		// the next list's count: what round done + 1 would read
+		BM_HIP(hipMemcpyAsync(&listed, tail + 4 * (kTravelTailCountWord + (done + 1) % 3), 4, hipMemcpyDeviceToHost, stream));
+		BM_HIP(hipStreamSynchronize(stream));
+		++looks;
+	}
+	stamp(2);
+	launch_water_finish(d, field, result, workspace, stream);
+	stamp(3);
+	BM_HIP(hipGetLastError());
+	if (counts) {
+		counts[0] = static_cast<uint32_t>(done);
+		counts[1] = looks;
+		BM_HIP(hipMemcpyAsync(&counts[2], tail + 4 * kWaterTailVisitsWord, 4, hipMemcpyDeviceToHost, stream));
+	}
+	BM_HIP(hipStreamSynchronize(stream)); // the call returns when the field and the record stand
+	if (stage_ms) return marks.read(3, stage_ms);
+	return 0;
+}
+
+int water_mask(const Gpu& gpu, const int32_t extent[3], const uint32_t* field, uint32_t min_depth, uint8_t* mask, hipStream_t stream) {
+	if (!extent) { set_error("bm_water_mask: null extent"); return BM_EINVAL; }
+	if (const char* why = travel_extent_problem(extent)) { set_error(std::string("bm_water_mask: ") + why); return BM_EINVAL; }
+	if (min_depth < 1) { set_error("bm_water_mask: a min_depth below 1"); return BM_EINVAL; }
+	if (!field || !mask) { set_error("bm_water_mask: null field or mask"); return BM_EINVAL; }
+	if (!aligned(field, 4)) { set_error("bm_water_mask: the field must be 4-byte aligned"); return BM_EINVAL; }
+	const size_t voxels = static_cast<size_t>(extent[0]) * static_cast<size_t>(extent[1]) * static_cast<size_t>(extent[2]);
+	if (spans_overlap(span_of(field, voxels * sizeof(uint32_t)), span_of(mask, voxels))) { set_error("bm_water_mask: the mask overlaps the field"); return BM_EINVAL; }
+	BM_HIP(hipSetDevice(gpu.device));
+	if (!device_span_ok(gpu.device, field, voxels * sizeof(uint32_t)) || !device_span_ok(gpu.device, mask, voxels)) {
+		set_error("bm_water_mask: a buffer does not lie inside one allocation of the scene's device");
+		return BM_EINVAL;
+	}
+	launch_water_mask(extent, field, min_depth, mask, stream);
 	BM_HIP(hipGetLastError());
 	return 0;
 }

@@ -60,6 +60,13 @@ int foot_field(const Gpu& gpu, const bm_foot_params* params, const uint8_t* room
 			   size_t workspace_bytes, hipStream_t stream, uint32_t batch = 0, float* stage_ms = nullptr, uint32_t* counts = nullptr);
 int foot_paths(const Gpu& gpu, const bm_foot_params* params, const uint8_t* room, const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path,
 			   int32_t* lengths, hipStream_t stream);
+// spill levels and pools (water.hip): a byte volume + drains -> the field and the record; a field -> the mask.  The buffers and the
+// workspace are the caller's.  Like travel_field, water_field returns when the field stands: it waits on `stream` between batches of
+// `batch` rounds (0 = kTravelBatch); water_mask is asynchronous.  stage_ms: null, or 3 durations -- set-up, rounds, finish; counts: null,
+// or the rounds enqueued, the looks of the host and the tile visits (bm_debug_water_times)
+int water_field(const Gpu& gpu, const bm_water_params* params, const uint8_t* volume, const int32_t* drains, int64_t n, uint32_t* field, bm_water_result* result,
+				void* workspace, size_t workspace_bytes, hipStream_t stream, uint32_t batch = 0, float* stage_ms = nullptr, uint32_t* counts = nullptr);
+int water_mask(const Gpu& gpu, const int32_t extent[3], const uint32_t* field, uint32_t min_depth, uint8_t* mask, hipStream_t stream);
 // pixel-centre rays of a frame, written on the device (denoise.hip)
 int pixel_rays(const Gpu& gpu, const bm_camera* cam, int width, int height, bm_ray* rays, hipStream_t stream);
 // temporal accumulation (reproject.hip): one kernel on the caller's stream over the caller's buffers

@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, travel.hip, settle.hip, foot.hip, denoise.hip, reproject.hip and wavefront.hip.
+// kernels.h -- host-callable launchers implemented in trace.hip, edit.hip, escape.hip, sunfield.hip, viewfield.hip, load.hip, region.hip, query.hip, volume.hip, label.hip, voxelize.hip, mesh.hip, distance.hip, travel.hip, settle.hip, foot.hip, water.hip, denoise.hip, reproject.hip and wavefront.hip.
 // What those kernel files share on the device side: device_types.h (argument blocks, the index word and a cell's place), global_mem.h
 // (plain global accesses), voxel_bits.h (voxel bytes <-> brick bits), brick_rows.h (a run of 16 bricks through LDS), traverse.h (the walk).
 #pragma once
@@ -203,6 +203,17 @@ void launch_foot_rounds(const FootDims& d, const uint8_t* room, uint32_t* field,
 void launch_foot_finish(const FootDims& d, const uint32_t* field, void* result, void* workspace, uint32_t done, hipStream_t stream);
 void launch_foot_paths(const FootDims& d, const uint8_t* room, const uint32_t* field, const int32_t* starts, uint32_t n, int32_t capacity, int32_t* path, int32_t* lengths,
 					   hipStream_t stream);
+
+// a byte volume + drains -> spill levels, and a field -> the mask of its pools (water.hip; water.h has the rules; the dims, the workspace
+// and the rounds are those of the travel field).  The caller (device_ops.cpp) enqueues the set-up, reads the first list's count, then
+// enqueues rounds in batches -- between batches it reads the next list's count from the tail and stops at 0 -- then the finish.
+// workspace: travel_workspace_bytes() bytes, 16-byte aligned, that no other launch uses until the finish has run.  Rounds count from 1.
+void launch_water_setup(const TravelDims& d, uint32_t sea, uint32_t faces, const uint8_t* volume, const int32_t* drains, uint32_t n, uint32_t* field, void* workspace,
+						hipStream_t stream);
+void launch_water_rounds(const TravelDims& d, uint32_t* field, void* workspace, uint32_t first_round, uint32_t rounds, hipStream_t stream);
+void launch_water_finish(const TravelDims& d, const uint32_t* field, void* result, void* workspace, hipStream_t stream);
+// mask[i] = the voxel is wet and at least min_depth deep; mask at any address
+void launch_water_mask(const int32_t extent[3], const uint32_t* field, uint32_t min_depth, uint8_t* mask, hipStream_t stream);
 
 // the a-trous filter (denoise.hip; denoise.h has the rules): accum and hits in, out = (c, 1) per pixel; workspace: denoise_workspace_bytes()
 // bytes that no other launch uses until this one has finished.  iterations 0 ... 8, every pointer 16-byte aligned; out may be accum.

@@ -1,7 +1,7 @@
 // examples/headless_main.cpp -- the reference's main loop (src/main.cpp:100-147) without the window:
 // State + Scene + generate(), then per frame launch_kernels -> process_load_queue, finally a PPM of the
 // resolved frame.  Build: see `make -C examples` (g++ on this file, linked against libbrickmap_hip.so).
-//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--path x0,y0,z0:x1,y1,z1] [--walk x0,y0,z0:x1,y1,z1] [--drop-floating x0,y0,z0:x1,y1,z1] [--settle x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
+//   usage: headless_main [--denoise] [--temporal] [--voxels FILE] [--paste FILE:nx,ny,nz@x,y,z] [--mesh FILE@x,y,z] [--mesh-out x0,y0,z0:x1,y1,z1=FILE] [--dig x,y,z,r] [--grow x0,y0,z0:x1,y1,z1=r2] [--shrink x0,y0,z0:x1,y1,z1=r2] [--path x0,y0,z0:x1,y1,z1] [--walk x0,y0,z0:x1,y1,z1] [--pools x0,y0,z0:x1,y1,z1] [--drop-floating x0,y0,z0:x1,y1,z1] [--settle x0,y0,z0:x1,y1,z1] [--dig-at px,py,r] [--ground x,y] [grid_size grid_height width height frames out.ppm [wavefront | ring]]
 // --voxels FILE: the world is FILE instead of the generated terrain -- raw bytes, one per voxel, [z][y][x] with x fastest,
 // grid_size * grid_size * grid_height of them, non-zero = solid (Scene::load_voxels; the scene is resident afterwards).
 // --paste FILE:nx,ny,nz@x,y,z writes the raw volume FILE (nx * ny * nz bytes, [z][y][x], non-zero = solid) into the world with its
@@ -22,6 +22,8 @@
 // --walk x0,y0,z0:x1,y1,z1, applied where --path is: a shortest walk on foot from the ground under the first voxel to the ground under the
 // second, for an agent two voxels tall that climbs one voxel and drops three per move, by the exact walk field of their surroundings on
 // the GPU (Scene::find_walk); prints "walk of N voxels:" and the voxels, or "no way on foot".
+// --pools x0,y0,z0:x1,y1,z1, applied where --path is: where water stands in that box with its four sides open, by the exact spill levels of
+// the box on the GPU (Scene::pools); prints "pools: W wet, C closed" and the deepest point with its depth, or "nothing is wet".
 // --drop-floating x0,y0,z0:x1,y1,z1, applied after --dig and --shrink: the pieces of that box that hang on nothing -- connected components by faces,
 // inside the box, without a voxel on the box's four sides or its bottom -- are removed (Scene::remove_floating); prints how many pieces
 // and voxels went.
@@ -69,6 +71,8 @@ int main(int argc_in, char** argv_in) {
 	bool path = false;
 	int walk_ends[2][3] = {{0, 0, 0}, {0, 0, 0}};
 	bool walk = false;
+	int pools_box[2][3] = {{0, 0, 0}, {0, 0, 0}};
+	bool pools = false;
 	const char* voxels_path = nullptr;
 	bool denoise = false, temporal = false;
 	std::string paste_path;
@@ -153,6 +157,15 @@ int main(int argc_in, char** argv_in) {
 				return 2;
 			}
 			settle = true;
+			continue;
+		}
+		if (std::string(argv_in[i]) == "--pools" && i + 1 < argc_in) {
+			if (std::sscanf(argv_in[++i], "%d,%d,%d:%d,%d,%d", &pools_box[0][0], &pools_box[0][1], &pools_box[0][2], &pools_box[1][0], &pools_box[1][1], &pools_box[1][2]) != 6 ||
+				pools_box[1][0] <= pools_box[0][0] || pools_box[1][1] <= pools_box[0][1] || pools_box[1][2] <= pools_box[0][2]) {
+				std::cerr << "--pools wants x0,y0,z0:x1,y1,z1, a box that is not empty\n";
+				return 2;
+			}
+			pools = true;
 			continue;
 		}
 		if (std::string(argv_in[i]) == "--walk" && i + 1 < argc_in) {
@@ -251,6 +264,16 @@ int main(int argc_in, char** argv_in) {
 			std::printf("path of %zu voxels:", voxels.size());
 			for (const auto& v : voxels) std::printf(" %d,%d,%d", v[0], v[1], v[2]);
 			std::printf("\n");
+		}
+	}
+	if (pools) {
+		const bm_water_result rec = scene.pools(pools_box[0], pools_box[1]);
+		std::printf("pools: %llu wet, %llu closed\n", static_cast<unsigned long long>(rec.wet), static_cast<unsigned long long>(rec.closed));
+		if (rec.deepest == 0) std::printf("nothing is wet\n");
+		else {
+			const unsigned long long nx = pools_box[1][0] - pools_box[0][0], ny = pools_box[1][1] - pools_box[0][1], at = rec.deepest_at;
+			std::printf("deepest: %u at %d,%d,%d\n", rec.deepest, pools_box[0][0] + static_cast<int>(at % nx), pools_box[0][1] + static_cast<int>(at / nx % ny),
+						pools_box[0][2] + static_cast<int>(at / (nx * ny)));
 		}
 	}
 	if (walk) {

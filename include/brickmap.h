@@ -933,6 +933,67 @@ BM_API int bm_host_foot_field(const bm_foot_params* params, const uint8_t* room,
 BM_API int bm_host_foot_paths(const bm_foot_params* params, const uint8_t* room, const uint32_t* field, const int32_t* starts, int64_t n, int32_t capacity, int32_t* path,
                               int32_t* lengths);
 
+/* ---- where water stands: exact spill levels and pools of a voxel volume (no reference counterpart).  WHAT THIS IS: water stands wherever
+ * it could not run off, if it were supplied.  The field does not model how much rain reaches a cave or whether trapped air stops it, nor
+ * finite amounts of water: every basin is full to its lowest rim.  All integers; a spill level is a minimum of integers and therefore
+ * unique, so the same bytes on every run whatever order anything ran in, and bm_water_field == bm_host_water_field byte for byte
+ * (csrc/water.h holds the rules once).
+ *  - Input.  A dense byte volume V[z][y][x] in device memory: any non-zero byte is solid, z is up; x contiguous, rows and slices at the
+ *    given pitches, 0 = tight; any base alignment; extents and voxel limit those of bm_travel_params.
+ *  - Outlets.  The free voxels that lie on the OPEN faces of the box: flags bit 0 ... 5 opens the -x, +x, -y, +y, -z, +z face (the bits of
+ *    bm_component.faces).  And the accepted DRAINS: n >= 0 drains, int32 drains[n][3] = (x, y, z) in device memory (the pointer may be
+ *    null when n is 0); a drain inside the volume on a free voxel is accepted, the others are counted.  Duplicates are fine.  With no open
+ *    face and no accepted drain nothing is an outlet.
+ *  - Field.  A tight uint32_t field L[z][y][x], 4-byte aligned.  For a free voxel p with a face-connected path of free voxels
+ *    (6-neighbourhood, inside the volume only) to an outlet, L(p) = max(sea_level, the least over all such paths of the largest z on the
+ *    path); p and the outlet both count as on the path.  sea_level is in box-local z, 0 = none.  L(p) = BM_WATER_NONE = 0x7FFFFFFF where p
+ *    is solid, or CLOSED: free, but with no path to an outlet.  Always L(p) >= z(p).  p is DRY when L(p) == z(p): water in it runs off
+ *    without rising.  p is WET when z(p) < L(p) < BM_WATER_NONE: the surface of its pool is the bottom of slice L(p), and L(p) - z(p) is
+ *    the depth.
+ *  - Result (32 bytes on the device, 8-byte aligned): wet = the wet voxels; deepest = the largest depth, 0 when nothing is wet;
+ *    drains_rejected; deepest_at = the lowest linear index (z ny + y) nx + x that holds `deepest`, 0 when nothing is wet; closed = the
+ *    closed voxels.
+ *  - Mask.  bm_water_mask takes a field and min_depth >= 1 and writes the tight byte volume that bm_scene_write_region and bm_mesh_quads
+ *    take: 1 where the voxel is wet and L - z >= min_depth, otherwise 0.  The mask may not overlap the field.  Asynchronous on hip_stream.
+ *  - Waiting.  Like bm_travel_field, bm_water_field RETURNS WHEN THE FIELD STANDS: it enqueues rounds of relaxation in batches on
+ *    hip_stream and between batches waits on that stream for one word, the number of tiles still listed.  It therefore cannot be captured
+ *    into a graph.
+ *  - Refusals, BM_EINVAL with nothing launched and nothing written: those of bm_travel_field (extents, voxels, pitches, a non-zero
+ *    `reserved`, spans, null pointers, alignment -- field and drains 4-byte, result 8-byte, workspace 16-byte --, a workspace below
+ *    bm_water_workspace_bytes, the overlaps among volume, drains, field, result and workspace, n); a flag bit other than the six; a
+ *    sea_level above extent[2]; a min_depth below 1; a mask that overlaps the field. */
+#define BM_WATER_NONE 0x7FFFFFFFu
+typedef struct bm_water_params { /* the 40 bytes of a bm_travel_params, with sea_level where max_steps is */
+	int32_t extent[3];   /* nx, ny, nz: 1 ... 16384 */
+	uint32_t sea_level;  /* box-local z, 0 ... nz; 0 = none */
+	int64_t row_pitch;   /* bytes from one x-row to the next y; 0 = tight (nx) */
+	int64_t slice_pitch; /* bytes from one z-slice to the next; 0 = tight (row_pitch * ny) */
+	uint32_t flags;      /* bit 0 ... 5: the -x, +x, -y, +y, -z, +z face of the box is open */
+	uint32_t reserved;   /* 0 */
+} bm_water_params;
+typedef struct bm_water_result {
+	uint64_t wet;
+	uint32_t deepest, drains_rejected;
+	uint64_t deepest_at;
+	uint64_t closed;
+} bm_water_result;
+/* bytes of device memory bm_water_field needs beside its buffers: what bm_travel_workspace_bytes gives for the same extents */
+BM_API int bm_water_workspace_bytes(const bm_water_params* params, size_t* bytes);
+/* the buffers and the workspace are the caller's, nothing is allocated on the device and the scene keeps no state (the scene names the
+ * device).  Nothing of the world is read.  Returns when the field and the result stand (see Waiting). */
+BM_API int bm_water_field(bm_scene* scene, const bm_water_params* params, const uint8_t* volume_dev, const int32_t* drains_dev, int64_t n, uint32_t* field_dev,
+                          bm_water_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+BM_API int bm_water_mask(bm_scene* scene, const int32_t extent[3], const uint32_t* field_dev, uint32_t min_depth, uint8_t* mask_dev, void* hip_stream);
+/* measuring door: bm_water_field with a hipEvent between its stages and `batch` rounds between two looks of the host (0 = the default);
+ * stage_ms[0 ... 2] = the durations in ms of the set-up (fill, bit bricks, outlets, drains), the rounds and the finish; counts[0] = the
+ * rounds enqueued, counts[1] = the looks of the host, counts[2] = the tile visits (the sum of the rounds' list lengths) */
+BM_API int bm_debug_water_times(bm_scene* scene, const bm_water_params* params, const uint8_t* volume_dev, const int32_t* drains_dev, int64_t n, uint32_t* field_dev,
+                                bm_water_result* result_dev, void* workspace_dev, size_t workspace_bytes, void* hip_stream, uint32_t batch, float* stage_ms,
+                                uint32_t* counts);
+/* the same on host memory, as a plain priority flood (csrc/water_host.cpp; no device needed); the refusals that concern params, n, min_depth and null pointers */
+BM_API int bm_host_water_field(const bm_water_params* params, const uint8_t* volume, const int32_t* drains, int64_t n, uint32_t* field, bm_water_result* result);
+BM_API int bm_host_water_mask(const int32_t extent[3], const uint32_t* field, uint32_t min_depth, uint8_t* mask);
+
 /* host-only world-build doors (no device needed): the terrain generator behind Scene::generate */
 BM_API int bm_host_column_heights(int grid_size, int grid_height, int sx, int sy, float* heights128x128);
 BM_API int bm_host_generate_supercell(int grid_size, int grid_height, int sx, int sy, int sz, uint32_t* indices4096,

@@ -711,6 +711,66 @@ public:
 		return out;
 	}
 
+	// where water stands (no counterpart in the reference; bm_water_field, bm_water_mask): the byte volume of `params` in device memory
+	// (non-zero = solid, z up), the open faces of its flags and n drains (x, y, z) there give the tight uint32 field of spill levels and the
+	// record; a field gives the byte mask of its pools.  workspace_dev: water_workspace_bytes() bytes of the caller's.  water_field returns
+	// when the field stands, water_mask is asynchronous.
+	static size_t water_workspace_bytes(const bm_water_params& params) {
+		size_t bytes = 0;
+		BM_CHECKED(bm_water_workspace_bytes(&params, &bytes));
+		return bytes;
+	}
+	void water_field(const bm_water_params& params, const uint8_t* volume_dev, const int32_t* drains_dev, int64_t n, uint32_t* field_dev, bm_water_result* result_dev,
+					 void* workspace_dev, size_t workspace_bytes, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_water_field(gpuScene.handle, &params, volume_dev, drains_dev, n, field_dev, result_dev, workspace_dev, workspace_bytes, hip_stream));
+	}
+	void water_mask(const int32_t extent[3], const uint32_t* field_dev, uint32_t min_depth, uint8_t* mask_dev, void* hip_stream = nullptr) {
+		BM_CHECKED(bm_water_mask(gpuScene.handle, extent, field_dev, min_depth, mask_dev, hip_stream));
+	}
+	// Where water stands in the box lo <= v < hi of the live scene: the box is read on the device (read_region) and its spill levels are
+	// taken with the given faces open (default: the four sides), the drains (world voxels) and the sea (a world z; below lo[2] = none,
+	// clamped into the box).  Returns the record; `field`, when given, gets the levels [z][y][x] in the box's coordinates (voxel - lo) and
+	// `mask`, when given, the bytes of bm_water_mask at min_depth.  The host waits.
+	bm_water_result pools(const int lo[3], const int hi[3], std::vector<uint32_t>* field = nullptr, std::vector<uint8_t>* mask = nullptr, uint32_t min_depth = 1,
+						  const std::vector<std::array<int, 3>>& drains = {}, int sea_level = -1, uint32_t open_faces = 15u) {
+		bm_water_params p{};
+		for (int a = 0; a < 3; ++a) p.extent[a] = hi[a] - lo[a];
+		const int sea = sea_level - lo[2];
+		p.sea_level = sea_level < 0 || sea < 0 ? 0u : static_cast<uint32_t>(sea < p.extent[2] ? sea : p.extent[2]);
+		p.flags = open_faces;
+		std::vector<int32_t> local;
+		for (const auto& d : drains)
+			for (int a = 0; a < 3; ++a) local.push_back(d[a] - lo[a]);
+		const size_t voxels = Region(lo, hi).voxels(), ws_bytes = water_workspace_bytes(p), drain_bytes = (local.size() * 4 + 15) & ~size_t{15};
+		const size_t at_drains = 32, at_ws = at_drains + drain_bytes, at_field = at_ws + ws_bytes, at_vol = at_field + voxels * 4, at_mask = at_vol + ((voxels + 15) & ~size_t{15});
+		void* buf = nullptr; // the result, the drains, the workspace, the field, the volume, then the mask
+		BM_CHECKED(bm_buffer_alloc(device_, at_mask + voxels, &buf));
+		char* base = static_cast<char*>(buf);
+		bm_water_result rec{};
+		try {
+			if (!local.empty()) BM_CHECKED(bm_buffer_write(device_, base + at_drains, local.data(), local.size() * 4));
+			read_region(Region(lo, hi), reinterpret_cast<uint8_t*>(base + at_vol), BM_VOXELS_DEVICE);
+			uint32_t* levels = reinterpret_cast<uint32_t*>(base + at_field);
+			water_field(p, reinterpret_cast<const uint8_t*>(base + at_vol), local.empty() ? nullptr : reinterpret_cast<const int32_t*>(base + at_drains),
+						static_cast<int64_t>(drains.size()), levels, reinterpret_cast<bm_water_result*>(base), base + at_ws, ws_bytes);
+			BM_CHECKED(bm_buffer_read(device_, &rec, base, sizeof rec));
+			if (field) {
+				field->resize(voxels);
+				BM_CHECKED(bm_buffer_read(device_, field->data(), levels, voxels * 4));
+			}
+			if (mask) {
+				water_mask(p.extent, levels, min_depth, reinterpret_cast<uint8_t*>(base + at_mask));
+				mask->resize(voxels);
+				BM_CHECKED(bm_buffer_read(device_, mask->data(), base + at_mask, voxels)); // (waits for the device)
+			}
+		} catch (...) {
+			(void)bm_buffer_free(device_, buf);
+			throw;
+		}
+		BM_CHECKED(bm_buffer_free(device_, buf));
+		return rec;
+	}
+
 private:
 	uint64_t morph(const int lo[3], const int hi[3], uint32_t radius_sq, bool erode) {
 		bool bad = radius_sq < 1 || radius_sq > 3u * 16383u * 16383u;
